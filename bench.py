@@ -3,7 +3,14 @@
 V views (forward + image loss (0.8 L1 + 0.2 (1-SSIM), or L1 with --loss l1) + backward to the six leaf-parameter gradients, + gradient
 all-reduce when N > 1), 300k articulated Gaussians, 1920x1080, 8 views, synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps once (no HIP events inside them) and prints the line:
+`value` = K / the time of those K steps, `ms_per_step` = that time / K.  --full adds everything else the
+benchmark measures or checks: the region timed REPEATS - 1 more times (median / min / max beside the headline)
+with HIP events around the dominant kernel (`roofline`), the depth-cut hints and trained-state figures, and the
+CPU oracle leg (`cpu_baseline`, `parity`).  --dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy (float32; a fixed, seeded sample of the rows / pixels of the large arrays).
 
 For N > 1 the driver launches it under torch.distributed.run (one rank per GPU, RCCL); the
 8 views are sharded across the ranks (strong scaling).  Rank 0 prints ONE JSON line.
@@ -26,7 +33,7 @@ import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (guides/MI355X_MICROARCH.md)
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc.json")  # rocprofv3 --pmc passes of this same command (tools/measure_round.sh)
-REPEATS = 5   # the --steps loop is timed this many times; the median goes into the line, min / max beside it
+REPEATS = 5   # --full: the --steps loop is timed this many times in all; median / min / max go beside the headline (the first)
 
 
 def pmc_counters(kernel, N, V, W, H):
@@ -314,6 +321,44 @@ def cpu_baseline_and_parity(scene_cpu, cams, targets_cpu, gpu, sample_views=2, n
     return cpu, par
 
 
+DUMP_ROWS = 1 << 16      # --dump-outputs: per-Gaussian arrays with more rows keep this fixed, seeded sample of them
+DUMP_PIXELS = 1 << 20    # ... and an image with more pixel positions (views x H x W) this many of them, all channels
+DUMP_SEED = 2024
+
+
+def dump_outputs(path, out, image):
+    """--dump-outputs: what the last timed step returned -- the step's dict (the six leaf gradients, grad2d, vis, radii, loss)
+    and the rendered image of the compute object -- as float32 `path/<name>.npy`.  Arrays along the N Gaussians are cut to
+    DUMP_ROWS rows and the image to DUMP_PIXELS pixel positions, both drawn with DUMP_SEED (the same sample for the same
+    arguments), so the files stay under 35 MB at the headline size."""
+    os.makedirs(path, exist_ok=True)
+    N = out["grad2d"].shape[0]
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = None
+    if N > DUMP_ROWS:
+        rows = torch.from_numpy(np.sort(rng.choice(N, DUMP_ROWS, replace=False))).to(out["grad2d"].device)
+
+    def save(name, t):
+        t = t.detach()
+        if rows is not None and t.dim() > 0:
+            axis = 0 if t.shape[0] == N else t.dim() - 1 if t.shape[-1] == N else None
+            if axis is not None:
+                t = t.index_select(axis, rows)
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+    for k, g in out["grads"].items():
+        save("grad" + k, g)
+    for k in ("grad2d", "vis", "radii"):
+        save(k, out[k])
+    save("loss", out["loss"].reshape(1))
+    img = image.detach()
+    V_, C_, H_, W_ = img.shape
+    if V_ * H_ * W_ > DUMP_PIXELS:   # (V, 3, H, W) -> (DUMP_PIXELS, 3): the colours of sampled (view, y, x) positions
+        px = torch.from_numpy(np.sort(rng.choice(V_ * H_ * W_, DUMP_PIXELS, replace=False))).to(img.device)
+        img = img.permute(0, 2, 3, 1).reshape(-1, C_).index_select(0, px)
+    np.save(os.path.join(path, "image.npy"), img.float().cpu().numpy())
+
+
 def dropin_main(args):
     """`--route dropin`: the zero-change route.  What an unmodified MANUS gets with only PYTHONPATH set is the two shim
     packages (`diff_gaussian_rasterization.GaussianRasterizer`, `simple_knn._C.distCUDA2`) under torch autograd, ONE
@@ -392,7 +437,8 @@ def dropin_main(args):
         rasterizer.set_sync_policy(False)
     dts, issue = [], []
     _lib.profile_enable(False)
-    for _ in range(REPEATS):
+    repeats = REPEATS if args.full else 1       # (the headline is the first region of exactly --steps steps; --full adds the spread)
+    for _ in range(repeats):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -400,40 +446,44 @@ def dropin_main(args):
         issue.append(time.perf_counter() - t0)      # (the host is done issuing; what is left is the device's backlog)
         torch.cuda.synchronize()
         dts.append(time.perf_counter() - t0)
-    dt = float(np.median(dts))
-    host_issue_ms = 1e3 * float(np.median(issue)) / args.steps
+    dt = dts[0]
+    host_issue_ms = 1e3 * issue[0] / args.steps
     if args.dropin_fenced:
         rasterizer.check_overflow()      # (raises if a forward of the timed loops ran out of pair capacity)
+    finite = all(bool(torch.isfinite(t.grad).all()) for t in P.values())
+    final_loss = float(loss.detach())
     # per-kernel breakdown of the library launches (HIP events around each: slows the step, taken in a separate loop)
-    _lib.profile_enable(True, only=None)
-    for _ in range(args.steps):
-        one_step()
-    prof = _lib.profile_report()
-    _lib.profile_enable(False)
-    tot = sum(v[1] for v in prof.values())
-    lib_ms = tot / args.steps
+    prof, lib_ms = {}, None
+    if args.full or args.profile_all:
+        _lib.profile_enable(True, only=None)
+        for _ in range(args.steps):
+            one_step()
+        prof = _lib.profile_report()
+        _lib.profile_enable(False)
+        tot = sum(v[1] for v in prof.values())
+        lib_ms = tot / args.steps
     if args.profile_all:
         for k, (c, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
             print("%-22s %6d launches %9.3f ms avg %8.4f ms  %5.1f%%" % (k, c, ms, ms / c, 100 * ms / tot), file=sys.stderr)
         print("library kernels %.3f ms/step of %.3f ms/step wall (the rest: torch glue kernels -- cat, sigmoid, permute, the loss's "
               "arithmetic, gradient accumulation -- and the host: ctypes calls; the pair count is read back for the first forwards only)"
               % (lib_ms, 1e3 * dt / args.steps), file=sys.stderr)
-    finite = all(bool(torch.isfinite(t.grad).all()) for t in P.values())
     dom = max(prof, key=lambda k_: prof[k_][1]) if prof else None
     line = {"metric": "train iters/sec (fwd+bwd), drop-in operator route: 1 view per step, %dk Gaussians @%dx%d "
                       "[not the headline configuration: GaussianRasterizer + reference-shaped modules under autograd]" % (N // 1000, W, H),
             "headline": False, "value": round(args.steps / dt, 4), "unit": "iters/s", "n_gpus": 1, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "repeats": REPEATS,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "repeats": repeats,
+            "ms_per_step_median": round(1e3 * float(np.median(dts)) / args.steps, 4),
             "ms_per_step_min": round(1e3 * min(dts) / args.steps, 4), "ms_per_step_max": round(1e3 * max(dts) / args.steps, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s, %d Gaussians, ONE view per step (cycling over %d cameras) at %dx%d, modules.hand_forward + "
                                    "render.render_gaussians + losses (0.8 L1 + 0.2 (1 - SSIM)) under torch autograd" % (args.kind, N, V, W, H),
                        "route": "dropin", "gaussians": N, "views_per_step": 1, "width": W, "height": H,
                        "host_syncs_per_step": 0 if (args.dropin_fenced or rasterizer.context(dev).auto_fenced > 0) else 1,
-                       "library_kernel_ms_per_step": round(lib_ms, 4),
+                       "library_kernel_ms_per_step": round(lib_ms, 4) if lib_ms is not None else None,
                        "host_issue_ms_per_step": round(host_issue_ms, 4),
                        "dominant_library_kernel": dom, "dominant_kernel_ms": round(prof[dom][1] / prof[dom][0], 4) if dom else None,
-                       "finite_grads": finite, "loss": float(loss.detach())},
+                       "finite_grads": finite, "loss": final_loss},
             "roofline": None, "cpu_baseline": None, "parity": None}
     print(json.dumps(line))
     sys.stdout.flush()
@@ -496,8 +546,15 @@ def main():
                          "steps leave; 0 = skip it)")
     ap.add_argument("--parity-views", type=int, default=2, help="views of the step run through the CPU oracle")
     ap.add_argument("--profile-all", action="store_true", help="print a per-kernel HIP-event breakdown to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: repeated timed regions, roofline, "
+                         "depth-cut hints, trained state, CPU baseline and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; a seeded sample of the large arrays, ~30 MB at the headline size)")
     args = ap.parse_args()
     if args.route == "dropin":
+        if args.dump_outputs:
+            ap.error("--dump-outputs is implemented for the fused route (the headline) only")
         return dropin_main(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -646,29 +703,36 @@ def main():
 
     # The dominant kernel is the one THIS run spends most of its time in (k_blend_bwd with eight views on the GPU, the
     # forward blend with one or two): three untimed steps with HIP events around every library kernel decide it, so that
-    # every line -- also the one-view-per-GPU shares of a multi-GPU run -- carries the roofline of its own dominant kernel.
-    _lib.profile_enable(True, only=None)
-    for _ in range(3):
-        step.step()
-    pre = _lib.profile_report()
-    _lib.profile_enable(False)
-    pre.pop("k_image_loss_list", None)      # (runs on the side stream next to the forward blend: its bracket spans the overlap)
-    DOMINANT = max(pre, key=lambda k_: pre[k_][1]) if pre else "k_blend_bwd"
-    if world > 1:   # every rank brackets the same kernel (rank 0's choice)
-        names = sorted(pre) if pre else ["k_blend_bwd"]
-        pick = torch.tensor([names.index(DOMINANT)], device=dev)
-        dist.broadcast(pick, src=0)
-        DOMINANT = names[int(pick.item())] if int(pick.item()) < len(names) else DOMINANT
+    # every line -- also the one-view-per-GPU shares of a multi-GPU run -- carries the roofline of its own dominant kernel
+    # (--full only).
+    DOMINANT = None
+    if args.full:
+        _lib.profile_enable(True, only=None)
+        for _ in range(3):
+            step.step()
+        pre = _lib.profile_report()
+        _lib.profile_enable(False)
+        pre.pop("k_image_loss_list", None)      # (runs on the side stream next to the forward blend: its bracket spans the overlap)
+        DOMINANT = max(pre, key=lambda k_: pre[k_][1]) if pre else "k_blend_bwd"
+        if world > 1:   # every rank brackets the same kernel (rank 0's choice)
+            names = sorted(pre) if pre else ["k_blend_bwd"]
+            pick = torch.tensor([names.index(DOMINANT)], device=dev)
+            dist.broadcast(pick, src=0)
+            DOMINANT = names[int(pick.item())] if int(pick.item()) < len(names) else DOMINANT
     # HIP events on the kernel's own stream: around the dominant kernel only (the roofline's duration), around every
     # library kernel with --profile-all (26 bracketed launches per step cost ~0.1 ms of the step).
-    # The loop of exactly --steps steps (barrier + synchronize on both sides, MAX over the ranks) is timed REPEATS times:
-    # the line carries the median, the spread beside it -- one hiccup in a 40 ms region no longer moves the headline.
+    # The loop of exactly --steps steps (barrier + synchronize on both sides, MAX over the ranks) is timed `repeats` times.
+    # The headline is ONE such region without events (every kernel bracketed under --profile-all); --full times it REPEATS - 1
+    # more times with the events around the dominant kernel and puts their median and spread beside the headline.
     # (the two events around a launch cost ~6 us of idle GPU each: the dominant kernel is bracketed on every fourth step of
-    # the timed region -- 5 x steps / 4 samples of its duration, all taken inside it)
-    def timed_region():
-        _lib.profile_enable(True, only=None if args.profile_all else DOMINANT, every=1 if args.profile_all else 4)
+    # those regions -- steps / 4 samples of its duration per region, all taken inside them)
+    def timed_region(repeats=REPEATS, events=True):
+        if args.profile_all:
+            _lib.profile_enable(True, only=None, every=1)
+        elif events:
+            _lib.profile_enable(True, only=DOMINANT, every=4)
         dts_ = []
-        for _ in range(REPEATS):
+        for _ in range(repeats):
             barrier()
             t0 = time.perf_counter()
             for _ in range(args.steps):
@@ -680,11 +744,13 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 d_ = float(tt.item())
             dts_.append(d_)
-        p_ = _lib.profile_report()
-        _lib.profile_enable(False)
+        p_ = {}
+        if args.profile_all or events:
+            p_ = _lib.profile_report()
+            _lib.profile_enable(False)
         return dts_, p_, o_
 
-    dts, prof, out = timed_region()
+    dts, prof, out = timed_region(1, events=False)
     # A flagged forward inside the timed region (depth-cut hints that did not fit: the model stands still in this loop, so none
     # is expected) would have left an incomplete step in the measurement: if that ever happens the region is measured again
     # without the depth cut, and the line says so.
@@ -700,23 +766,19 @@ def main():
         rasterizer.check_overflow()
         rasterizer.set_sync_policy(False)
         step.step()
-        dts, prof, out = timed_region()
+        dts, prof, out = timed_region(1, events=False)
         rasterizer.check_overflow()
         remeasured = True
     dt = float(np.median(dts))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, compute.last_image)
     # With the optimizer in the loop a Gaussian can walk out of the skin-weight grid; its weights are then 0/0 = NaN
     # exactly like the reference (gaussian_utils.py:193-195), which drops such rows when it loads a checkpoint.
     nonfinite = sum(int((~torch.isfinite(x)).sum()) for x in out["grads"].values())
     assert args.optimizer or nonfinite == 0 or (variant_bits & 1), "non-finite gradients"   # (only a knock-out build may produce them: tools/instr)
-    # list entries the blend actually consumed (sum over tiles of the deepest contributor): the units k_blend_fwd / _bwd process
-    consumed = None
-    import ctypes
-    ws = rasterizer.context(dev).last_ws
-    if ws is not None:
-        arr = (ctypes.c_size_t * 32)()
-        _lib.lib().mgr_raster_layout(V_local, N, W, H, ws.cap, arr, 32)
-        VT = V_local * ((W + 15) // 16) * ((H + 15) // 16)
-        consumed = int(ws.buf[int(arr[9]): int(arr[9]) + 4 * VT].view(torch.int32).sum().item())
+    # digest of the step's (reduced) leaf gradients: lets an N-rank line be compared with the one-rank line of the same size
+    digest = {k: [float(g.double().sum()), float(g.double().abs().sum())] for k, g in out["grads"].items()}
+    digest["loss"] = float(out["loss"])
 
     def keep(o_):
         return {k: ({n: g.clone() for n, g in v.items()} if isinstance(v, dict) else (v.clone() if torch.is_tensor(v) else v))
@@ -737,10 +799,26 @@ def main():
     # fwd+bwd loop -- so their figure is an extra key, `value_with_hints`, measured here on the same box and process.
     static_model = world == 1 and not args.optimizer
     timed_out = timed_img = None
-    if static_model:
+    if static_model and args.full:
         timed_out, timed_img = keep(out), compute.last_image.clone()
+    # --full: the spread of the region (REPEATS - 1 more timed regions, the dominant kernel bracketed: the roofline's duration)
+    # and the list entries the blend actually consumed (sum over tiles of the deepest contributor): the units k_blend_fwd /
+    # _bwd process
+    ms_spread = None
+    consumed = None
+    import ctypes
+    if args.full:
+        dts_more, prof, _ = timed_region(REPEATS - 1)
+        rasterizer.check_overflow()
+        ms_spread = [1e3 * d_ / args.steps for d_ in dts + dts_more]
+        ws = rasterizer.context(dev).last_ws
+        if ws is not None:
+            arr = (ctypes.c_size_t * 32)()
+            _lib.lib().mgr_raster_layout(V_local, N, W, H, ws.cap, arr, 32)
+            VT = V_local * ((W + 15) // 16) * ((H + 15) // 16)
+            consumed = int(ws.buf[int(arr[9]): int(arr[9]) + 4 * VT].view(torch.int32).sum().item())
     hints = None
-    if static_model and not compute.depth_cut and not args.no_hints_variant and compute.fused:
+    if args.full and static_model and not compute.depth_cut and not args.no_hints_variant and compute.fused:
         compute.depth_cut = os.environ.get("MANUS_DEPTH_CUT", "1") != "0"
         if compute.depth_cut:
             for _ in range(3):      # the first forward leaves the hints, the following ones bin against them
@@ -764,7 +842,7 @@ def main():
     # the walks (2.9 M -> ~4 M consumed list entries on this scene); the headline above is timed on the initial state.  Same
     # process, same compute object and mode; the parameters are put back bit for bit afterwards (the parity block follows).
     trained = None
-    if static_model and args.trained_steps > 0 and compute.fused:
+    if args.full and static_model and args.trained_steps > 0 and compute.fused:
         from manus_amd.optim import GaussianOptimizer
         saved = {k: v.detach().clone() for k, v in compute.params.items()}
         try:
@@ -820,9 +898,6 @@ def main():
     if world > 1:
         views_by_rank = [None] * world
         dist.all_gather_object(views_by_rank, [int(v) for v in step.local_views])
-    # digest of the step's (reduced) leaf gradients: lets an N-rank line be compared with the one-rank line of the same size
-    digest = {k: [float(g.double().sum()), float(g.double().abs().sum())] for k, g in out["grads"].items()}
-    digest["loss"] = float(out["loss"])
 
     if rank == 0:
         R_view = npairs_local / max(1, V_local)          # measured pairs per view (num_rendered)
@@ -881,10 +956,11 @@ def main():
             for k, (c, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
                 print("%-20s %6d launches %9.3f ms avg %8.4f ms  %5.1f%%" % (k, c, ms, ms / c, 100 * ms / tot),
                       file=sys.stderr)
-            print("library kernels %.3f ms/iter of %.3f ms/iter wall" % (tot / (args.steps * REPEATS), 1e3 * dt / args.steps),
+            prof_regions = REPEATS - 1 if args.full else 1       # (the regions `prof` was taken over)
+            print("library kernels %.3f ms/iter of %.3f ms/iter wall" % (tot / (args.steps * prof_regions), 1e3 * dt / args.steps),
                   file=sys.stderr)
         cpu = parity = None
-        if not args.no_cpu_baseline and world == 1 and args.kind == "hand" and not args.optimizer and args.sh_storage == "fp32" and not (variant_bits & 1):
+        if args.full and not args.no_cpu_baseline and world == 1 and args.kind == "hand" and not args.optimizer and args.sh_storage == "fp32" and not (variant_bits & 1):
             # The GPU step once more on the sampled views alone (same targets, same loss, same 1/V scale), ON THE TIMED
             # REGION'S compute object and IN ITS MODE (no host sync per forward: fenced; kept buffers; no depth cut) -- run
             # twice, so that the second one has the row- / tile-selective fills of the kept buffers in use like every timed
@@ -955,11 +1031,12 @@ def main():
                                                                           ", library variant '%s' (bits %d)" % (variant_name, variant_bits) if (variant_bits or variant_name) else "")
         kind_str = {"hand": "HAND_GAUSSIAN: %d Gaussians, 21-transform LBS" % N, "object": "OBJ_GAUSSIAN: %d static Gaussians" % N,
                     "composite": "COMPOSITE: %d Gaussians (hand, 21-transform LBS + static object)" % N}.get(args.kind, args.kind)
-        ms = [1e3 * d_ / args.steps for d_ in dts]
+        ms = ms_spread or [1e3 * d_ / args.steps for d_ in dts]      # (--full: the headline region and the REPEATS - 1 after it)
         line = {
             "metric": metric, "headline": bool(headline and args.gaussian_order == "given"),
             "value": round(args.steps / dt, 4), "unit": "iters/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "repeats": REPEATS,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "repeats": len(ms),
+            "ms_per_step_median": round(float(np.median(ms)), 4),
             "ms_per_step_min": round(min(ms), 4), "ms_per_step_max": round(max(ms), 4), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "value_with_hints": hints["value"] if hints else None,

@@ -341,7 +341,7 @@ def test_bench_dropin_route_runs(extra):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--route", "dropin", "--gaussians", "4000", "--views", "2", "--width", "160",
-           "--height", "96", "--steps", "2", "--warmup", "1"] + extra
+           "--height", "96", "--steps", "2", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -349,6 +349,6 @@ def test_bench_dropin_route_runs(extra):
     d = json.loads(lines[0])
     assert d["headline"] is False and d["value"] > 0 and d["config"]["route"] == "dropin" and d["config"]["finite_grads"] is True
     # (without the flag the context itself stops reading the pair count back after RasterContext.AUTO_FENCE_AFTER clean forwards:
-    #  this run has more than that many)
+    #  with --full -- five timed loops and the breakdown loop -- this run has more than that many)
     assert d["config"]["host_syncs_per_step"] == 0 and d["config"]["host_issue_ms_per_step"] > 0
     assert (d["config"]["width"], d["config"]["height"]) == (160, 96)

@@ -18,7 +18,7 @@ sys.argv = sys.argv[:1]
 import bench  # noqa: E402
 
 bench.REPEATS = 1
-ns = argparse.Namespace(views=8, gaussians=300000, width=1920, height=1080, kind="hand", warmup=12, steps=STEPS, dropin_fenced=False, profile_all=False)
+ns = argparse.Namespace(views=8, gaussians=300000, width=1920, height=1080, kind="hand", warmup=12, steps=STEPS, dropin_fenced=False, profile_all=False, full=True)
 pr = cProfile.Profile()
 pr.enable()
 bench.dropin_main(ns)

@@ -25,7 +25,7 @@ def main():
 
     # run bench.dropin_main's set-up by borrowing its step function: re-create it here (same code path as the bench)
     ns = argparse.Namespace(views=8, gaussians=300000, width=1920, height=1080, kind="hand", warmup=12, steps=STEPS, dropin_fenced=False,
-                            profile_all=False)
+                            profile_all=False, full=True)
     src = bench.dropin_main
     # the bench times inside dropin_main; for the op table the step function is needed: rebuild through a tiny hook
     import types

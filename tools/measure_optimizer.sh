@@ -14,9 +14,9 @@ rm -rf gpurun_out/prof_opt_$TAG
 cp $(find gpurun_out/prof_opt_$TAG -name "*kernel_stats.csv" | head -1) profiles/${RND}_${TAG}_optimizer_rocprofv3_kernel_stats.csv
 python tools/instr/step_timeline.py $(find gpurun_out/prof_opt_$TAG -name "*kernel_trace.csv" | head -1) > profiles/${RND}_${TAG}_optimizer_step_timeline.txt
 rm -f $(find gpurun_out/prof_opt_$TAG -name "*kernel_trace.csv")
-python bench.py --steps 50 --warmup 5 --no-cpu-baseline --optimizer $EXTRA > profiles/${RND}_${TAG}_optimizer_bench.json 2> gpurun_out/opt_$TAG.err0
+python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --optimizer $EXTRA > profiles/${RND}_${TAG}_optimizer_bench.json
 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --optimizer --profile-all $EXTRA 2>&1 >/dev/null | grep -v amdgpu.ids > profiles/${RND}_${TAG}_optimizer_kernel_breakdown.txt
-python bench.py --steps 50 --warmup 5 --no-cpu-baseline $EXTRA > profiles/${RND}_${TAG}_optimizer_ref_noopt.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline $EXTRA > profiles/${RND}_${TAG}_optimizer_ref_noopt.json 2>/dev/null
 cp profiles/${RND}_${TAG}_optimizer_* gpurun_out/
 cat profiles/${RND}_${TAG}_optimizer_step_timeline.txt
 cat profiles/${RND}_${TAG}_optimizer_kernel_breakdown.txt

@@ -18,13 +18,12 @@ rm -rf gpurun_out/prof_$TAG
 cp $(find gpurun_out/prof_$TAG -name "*kernel_stats.csv" | head -1) profiles/${RND}_${TAG}_rocprofv3_kernel_stats.csv
 python tools/instr/step_timeline.py $(find gpurun_out/prof_$TAG -name "*kernel_trace.csv" | head -1) > profiles/${RND}_${TAG}_step_timeline.txt
 rm -f $(find gpurun_out/prof_$TAG -name "*kernel_trace.csv")
-# the bench line as the driver runs it (events around the dominant kernel only), then the per-kernel breakdown
-# (--profile-all: events around all ~26 launches of a step, which costs ~0.1 ms per step)
-python bench.py --steps 50 --warmup 5 > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err0
+# the full bench line (--full: roofline with events around the dominant kernel, CPU oracle leg), then the per-kernel
+# breakdown (--profile-all: events around all ~26 launches of a step, which costs ~0.1 ms per step)
+python bench.py --full --steps 50 --warmup 5 > profiles/${RND}_${TAG}_bench.json
 python bench.py --steps 50 --warmup 5 --profile-all --no-cpu-baseline --no-hints-variant > gpurun_out/bench_${TAG}_all.json 2> gpurun_out/bench_$TAG.err
-cp gpurun_out/bench_$TAG.json profiles/${RND}_${TAG}_bench.json
 grep -v amdgpu.ids gpurun_out/bench_$TAG.err > profiles/${RND}_${TAG}_bench_kernel_breakdown.txt
 python tools/kernel_limits.py profiles/${RND}_pmc.json > profiles/${RND}_${TAG}_kernel_limits.txt
 mkdir -p gpurun_out/profiles_$TAG; cp profiles/${RND}_${TAG}_* profiles/${RND}_pmc.json gpurun_out/profiles_$TAG/
 cat profiles/${RND}_${TAG}_kernel_limits.txt; cat profiles/${RND}_${TAG}_step_timeline.txt
-tail -22 gpurun_out/bench_$TAG.err; cat gpurun_out/bench_$TAG.json; head -30 gpurun_out/pmc_${TAG}.txt
+tail -22 profiles/${RND}_${TAG}_bench_kernel_breakdown.txt; cat profiles/${RND}_${TAG}_bench.json; head -30 profiles/${RND}_${TAG}_pmc.txt

@@ -4,7 +4,7 @@
 RND=${1:-r06}
 OUT=profiles/${RND}_other_configs
 mkdir -p $OUT
-run() { name=$1; shift; python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-hints-variant --trained-steps 0 "$@" > $OUT/$name.json 2>/dev/null
+run() { name=$1; shift; python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-hints-variant --trained-steps 0 "$@" > $OUT/$name.json 2>/dev/null
         python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-hints-variant --trained-steps 0 --profile-all "$@" 2>&1 >/dev/null | grep -v amdgpu.ids > $OUT/${name}_breakdown.txt
         python -c "import json;d=json.load(open('$OUT/$name.json'));print('$name',d['value'],d['ms_per_step'])"; }
 run hand_v1 --views 1
