@@ -94,6 +94,9 @@ int mgr_version(void);
  * non-default MGR_BIN_BLOCK: results unchanged).  bench.py labels such a run and refuses to call it the headline; the parity
  * block does not run on a library that reports bit 0. */
 int mgr_build_variant(void);
+/* Tiles per view (ceil(W/16) * ceil(H/16)) up to which the depth cut's on-device repair (mgr_views_forward debug bit 2048) is
+ * used; on a larger grid a depth-cut tile that runs out flags the forward (MGR_ECUT) and the caller runs it again uncut. */
+int mgr_raster_repair_max_tiles(void);
 /* Thread-local text of the last error returned on this host thread. */
 const char* mgr_last_error(void);
 

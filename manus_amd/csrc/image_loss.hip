@@ -43,21 +43,25 @@ __global__ __launch_bounds__(IL_T) void k_image_loss(int H, int W, const float* 
                                                      float w_ssim, float grad_scale, float* __restrict__ dL_dpred,
                                                      float2* __restrict__ partial, const uint32_t* __restrict__ work_list,
                                                      const uint32_t* __restrict__ work_count, int gxb, int gyb,
-                                                     unsigned long long* __restrict__ acc_slots) {
+                                                     unsigned long long* __restrict__ acc_slots, uint32_t nb, float sum_lim,
+                                                     uint32_t* __restrict__ bad_flag) {
     // channel-mixed statistics (5 x 3 rows of positions) and, later, the channel-mixed derivative
     // maps (3 x 3); .x = image row h0, .y = image row h0 + 1
     __shared__ v2f s_mix[5][3][IL_NX];
     __shared__ float s_red[4];
     const int tid = threadIdx.x;
-    const uint32_t n_work = *work_count;
+    const uint32_t n_work = min(*work_count, nb);   // (a count beyond the list -- a stale list never finished -- reads no further)
     // The loss sums (round 6).  Thread 0 keeps the workgroup's sums of its spans as 64-bit FIXED-POINT integers (2^-32: integer
     // addition is associative, so the total does not depend on which workgroup took which span or on the order the atomics land
     // in -- the value is reproducible, as the fold over the per-span sums in index order was) and adds them to one of IL_ACC_SLOTS
     // slot triples at its end (no return value, no fence: the kernel boundary orders them); k_image_loss_fold adds the slots and
     // the spans the list pass finished (every pixel of those has SSIM 1 and no L1: all pixels minus the listed ones).  The fold
     // over 34 560 per-span sums took 12 us between this kernel and the backward blend; over 64 slots it is a minimal launch.
+    // The fixed-point total holds |sum| < 2^31.  A workgroup whose sum is not finite or exceeds sum_lim = 2^31 / (spans of the
+    // batch) raises bad_flag, and the fold then reports NaN: every total that is not flagged is in range, none wraps.
     long long acc_l1 = 0, acc_ss = 0;
     unsigned long long acc_px = 0;
+    bool bad = false;
   for (uint32_t wi = blockIdx.x; wi < n_work; wi += gridDim.x) {   // the workgroups k_image_loss_scan found different
     const uint32_t bid = work_list[wi];
     const int bxi = (int)(bid % (uint32_t)gxb), byi = (int)((bid / (uint32_t)gxb) % (uint32_t)gyb), v = (int)(bid / (uint32_t)(gxb * gyb));
@@ -213,6 +217,7 @@ __global__ __launch_bounds__(IL_T) void k_image_loss(int H, int W, const float* 
     if (tid == 0) {
         const float pa = s_red[0] + s_red[1], pb = s_red[2] + s_red[3];
         partial[bid] = make_float2(pa, pb);
+        bad |= !(fabsf(pa) <= sum_lim && fabsf(pb) <= sum_lim);     // (NaN fails the comparison)
         acc_l1 += __double2ll_rn((double)pa * 4294967296.0);
         acc_ss += __double2ll_rn((double)pb * 4294967296.0);
         acc_px += (unsigned long long)((min((bxi + 1) * IL_W, W) - bxi * IL_W) * 3 * (row1 ? 2 : 1));
@@ -223,6 +228,7 @@ __global__ __launch_bounds__(IL_T) void k_image_loss(int H, int W, const float* 
         atomicAdd(sl, (unsigned long long)acc_l1);
         atomicAdd(sl + 1, (unsigned long long)acc_ss);
         atomicAdd(sl + 2, acc_px);
+        if (bad) atomicOr(bad_flag, 1u);
     }
 }
 
@@ -432,7 +438,8 @@ __global__ __launch_bounds__(ILS_T) void k_image_loss_list_mapped(IlListArgs a) 
 }
 
 // the loss from the slot sums of k_image_loss: sums[0] = sum |pred - target|, sums[1] = sum of the SSIM map (the spans the list
-// pass finished contribute one per pixel and channel: total_px3 minus the listed ones), sums[2] = the caller's loss value
+// pass finished contribute one per pixel and channel: total_px3 minus the listed ones), sums[2] = the caller's loss value;
+// all three NaN when k_image_loss flagged a sum that is not finite or beyond the fixed-point range (work_count[1])
 __global__ __launch_bounds__(IL_ACC_SLOTS) void k_image_loss_fold(unsigned long long* __restrict__ acc_slots, long long total_px3,
                                                                   float* __restrict__ sums, float ca, float cb, float cc,
                                                                   uint32_t* __restrict__ work_count) {
@@ -454,15 +461,19 @@ __global__ __launch_bounds__(IL_ACC_SLOTS) void k_image_loss_fold(unsigned long 
         }
         const double ta = (double)t_l1 * (1.0 / 4294967296.0);
         const double tb = (double)t_ss * (1.0 / 4294967296.0) + (double)((unsigned long long)total_px3 - t_px);
-        sums[0] = (float)ta;
-        sums[1] = (float)tb;
-        sums[2] = (float)((double)ca * ta + (double)cb * tb + (double)cc);  // the caller's loss value, no host-side arithmetic
-        *work_count = 0u;   // the list is consumed: a caller that keeps the workspace builds the next one without a memset
+        const bool bad = work_count[1] != 0u;
+        const float qnan = __int_as_float(0x7FC00000);
+        sums[0] = bad ? qnan : (float)ta;
+        sums[1] = bad ? qnan : (float)tb;
+        sums[2] = bad ? qnan : (float)((double)ca * ta + (double)cb * tb + (double)cc);  // the caller's loss value, no host-side arithmetic
+        work_count[0] = 0u;   // the list is consumed: a caller that keeps the workspace builds the next one without a memset
+        work_count[1] = 0u;
     }
 }
 
 
 // byte offset of the sum slots (64-bit atomics: aligned) behind the per-span sums, the work list and the 256 bytes of counters
+// (at +64: the span count, then the flag word of the sums' range check)
 static size_t il_slots_offset(int64_t nb) { return (((size_t)nb * (sizeof(float2) + sizeof(uint32_t)) + 256) + 63) & ~(size_t)63; }
 extern "C" size_t mgr_image_loss_workspace_bytes(int V, int H, int W) {
     if (V <= 0 || H <= 0 || W <= 0) return 0;
@@ -519,9 +530,11 @@ static int image_loss_impl(int V, int H, int W, const float* pred, const float* 
 #define IL_GRID (256 * 5)
 #endif
         const int64_t pb = nb < IL_GRID ? nb : IL_GRID;   // persistent: 5 workgroups of 32 KB LDS per CU are resident
+        // (a hair below 2^31 / nb: the limit's rounding to fp32 cannot let nb sums at the limit reach 2^31)
+        const float sum_lim = (float)(2147483648.0 * (1.0 - 1.0 / 1048576.0) / (double)nb);
         hipLaunchKernelGGL(k_image_loss, dim3((unsigned)pb), dim3(IL_T), 0, stream, H, W, pred, target, win, w_l1, w_ssim,
                            grad_scale, dL_dpred, partial, (const uint32_t*)work_list, (const uint32_t*)work_count,
-                           (int)grid.x, (int)grid.y, acc_slots);
+                           (int)grid.x, (int)grid.y, acc_slots, (uint32_t)nb, sum_lim, work_count + 1);
     }
     hipLaunchKernelGGL(k_image_loss_fold, dim3(1), dim3(IL_ACC_SLOTS), 0, stream, acc_slots, (long long)V * H * W * 3,
                        sums, grad_scale * w_l1, -grad_scale * w_ssim, loss_offset, work_count);

@@ -69,6 +69,7 @@ struct MgrProfScope {
 #define MGR_REP_CAND 8192          // instances behind the cut one repaired tile may hold (one LDS sort)
 #define MGR_REP_TARGET 3072        // ... of which the scan aims for this many: the depth window behind the cut (tile_zwin, k_fwd_items)
 #define MGR_REP_VIEW_TILES 256     // repaired tiles per view and forward
+#define MGR_REP_MAX_TILES 65536    // tiles of a view up to which the repair runs (k_repair_scan: one bit per tile in LDS)
 struct __attribute__((aligned(16))) MgrRepUnit {      // 64 bytes
     uint32_t vt, quad, nlist, start;      // tile (view * T + tile), quadrant, length and offset of the CUT list
     uint32_t ck0, done_lo, done_hi, ntail;   // first checkpoint of the tile; lanes whose walk had ended; entries appended (owner unit; 0: none)

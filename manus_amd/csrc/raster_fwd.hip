@@ -109,6 +109,8 @@ extern "C" int mgr_version(void) { return MGR_VERSION; }
 // instrumentation compiled into the library (include/manus_hip.h: 0 for the product build); the backward's half lives in
 // its translation unit, the macros being per-source -D flags of tools/instr/build_variant.sh
 int mgr_bwd_variant_bits(void);
+extern "C" int mgr_raster_repair_max_tiles(void) { return MGR_REP_MAX_TILES; }
+
 extern "C" int mgr_build_variant(void) {
     int bits = mgr_bwd_variant_bits();
 #ifdef FWD_KO_DEEP
@@ -2684,9 +2686,10 @@ __global__ __launch_bounds__(REP_SCAN_THREADS) void k_repair_scan(int N, int T, 
     __shared__ uint32_t s_hits[MGR_REP_VIEW_TILES], s_beyond[MGR_REP_VIEW_TILES];
     __shared__ uint4 s_stash[REP_STASH];   // (tile slot, rank among the workgroup's hits of that tile, depth bits, Gaussian)
     __shared__ uint2 s_hit[REP_HITS];      // (instance, tile slot | tile x << 8 | tile y << 20) of a batch
-    __shared__ uint32_t s_bits[2048];      // one bit per tile of the view (the ordered binning serves grids of up to 65535 tiles)
+    __shared__ uint32_t s_bits[MGR_REP_MAX_TILES / 32];   // one bit per tile of the view (mgr_raster_forward enables the repair
+                                                          // only on grids of at most MGR_REP_MAX_TILES tiles)
     if (tid == 0) s_stash_n = 0u;
-    for (int k = tid; k < 2048; k += REP_SCAN_THREADS) s_bits[k] = 0u;
+    for (int k = tid; k < MGR_REP_MAX_TILES / 32; k += REP_SCAN_THREADS) s_bits[k] = 0u;
     __syncthreads();
     for (uint32_t k = (uint32_t)tid; k < nt; k += REP_SCAN_THREADS) {
         const MgrRepTile e = rv->t[k];
@@ -3192,7 +3195,9 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
     const bool spread = (debug & 4096) != 0;       // bit 12: k_bin_scatter's lane-spreading instantiation (the previous forward met rectangles of more than 64 tiles)
     // bit 11 (2048, with bit 3): tiles whose cut list runs out under an unsaturated pixel are repaired on the device
     // (k_repair_scan / k_repair_blend) instead of flagging the forward
-    const bool repair = use_cut && (debug & 2048) && W < 65536 && H < 65536;   // (k_repair_scan packs tile coordinates in 12 bits)
+    // (k_repair_scan packs tile coordinates in 12 bits and keeps one bit per tile of a view in LDS: larger grids flag the forward)
+    const bool repair = use_cut && (debug & 2048) && W < 65536 && H < 65536 &&
+                        (int64_t)((W + 15) / 16) * ((H + 15) / 16) <= (int64_t)MGR_REP_MAX_TILES;
     debug &= 1;
     if (V <= 0 || N < 0 || W <= 0 || H <= 0 || cap < 0 || cap > 0xFFFFFFF0ll)
         return mgr_fail(MGR_EINVAL, "mgr_raster_forward: bad sizes");

@@ -249,11 +249,10 @@ def _compact_all_reduce(self, flat, fv, active=None):
     the fused backward's own list of the Gaussians that received a gradient when the compute function hands it over
     (`active`), otherwise from the rows --, the ordered row list (two launches), one pack, one unpack.  The host reads
     NOTHING in the middle of the step (round 6): the second collective is sized by a row capacity chosen beforehand -- the
-    union's size of the step before + 25 % (+ 1024; all N rows the first time) --, the pack / unpack kernels take the actual
+    union's size of the step before + 25 % (+ 1024; all N rows the first time), the same on every rank --, the pack / unpack kernels take the actual
     count from the device, rows between count and capacity travel as zeros, and a union that outgrows the capacity adds to
     the step's overflow word (summed over the ranks: `Trainer._run_step` runs the step again, by which time the count has
-    arrived on the host through an asynchronous copy and the capacity has grown).  `self.last_rows`: the count of the most
-    recent step whose copy has arrived.  Tensors on the CPU (the gloo tests of the rank logic, where a CPU stand-in
+    arrived on the host through an asynchronous copy and the capacity has grown).  `self.last_rows`: the count of the step before.  Tensors on the CPU (the gloo tests of the rank logic, where a CPU stand-in
     computes the gradients) take the same steps in torch."""
     N = self.N
     if self.n_views > 255:
@@ -276,7 +275,11 @@ def _compact_all_reduce(self, flat, fv, active=None):
                                   ws=torch.empty(L.mgr_exchange_index_workspace_bytes(N), dtype=torch.uint8, device=dev),
                                   host=torch.zeros(1, dtype=torch.int32).pin_memory(), buf=None, ev=None, cap_rows=N)
         small, idx, count = sc["small"], sc["idx"], sc["count"]
-        if sc["ev"] is not None and sc["ev"].query():          # the count of an earlier step has arrived: the capacity follows it
+        if sc["ev"] is not None:          # the count of the step before: the capacity follows it
+            # (waited for, never queried: the capacity sizes a collective, and a choice that depended on timing could give two
+            # ranks different sizes for the same all-reduce.  Under Trainer the copy is complete by now -- it reads the step's
+            # overflow word on the host -- so the wait costs nothing there.)
+            sc["ev"].synchronize()
             n_seen = int(sc["host"][0])
             self.last_rows, sc["ev"] = n_seen, None
             sc["cap_rows"] = min(N, int(n_seen * 1.25) + 1024)
@@ -777,8 +780,9 @@ class HipViewCompute:
             fwd(ws, 2 if overlap else 0)
 
         ctx = self.rz.context(dev)
-        ws, _ = ctx.forward(V, N, W, H, launch, sync_check=self.sync_check, defer_fence=True)
+        ws = None
         try:
+            ws, _ = ctx.forward(V, N, W, H, launch, sync_check=self.sync_check, defer_fence=True)
             if not overlap and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
             if mapped:
@@ -863,13 +867,15 @@ class HipViewCompute:
                                                  stream()), "mgr_skin_weights_bwd")
             overflow = ws.buf[4:8].view(torch.int32)
         except BaseException:
-            # a call that failed between the loss's list and finish passes leaves the kept loss workspace with a non-zero
-            # span count (the finish pass is what resets it) and the kept buffers in an unknown state: start over
+            # a call that failed between the loss's list and finish passes -- the forward included: its last kernel builds the
+            # attached list -- leaves the kept loss workspace with a non-zero span count (the finish pass is what resets it) and
+            # the kept buffers in an unknown state: start over
             self._lws.pop((V, H, W), None)
             self._pg_ws = self._pimg_ws = None
             raise
         finally:
-            ws.busy = False
+            if ws is not None:
+                ws.busy = False
         self.last_image, self.last_radii = out, radii
         self.last_active = active      # (device pointers into the workspace of this step: valid until the next forward on it)
         return dict(grads={"_xyz": d_xyz, "_scaling": d_ls, "_rotation": d_rot, "_opacity": d_op, "_features_dc": d_fdc,

@@ -16,6 +16,7 @@ multi-view batched form (V cameras in every launch) used by the training engine.
 from typing import NamedTuple
 
 import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -98,8 +99,12 @@ class RasterContext:
     # forwards of one (V, N, W, H) whose pair count fitted the learnt capacity, the blocking read of the pair count per forward
     # (upstream's cudaMemcpy; 0.23 ms of a 1.47 ms step at 1280x720, profiles/r05_other_configs/dropin_c*) is replaced by a
     # fence that the NEXT forward of the context resolves -- by then it has long been written.  The capacity keeps its 25 %
-    # headroom; should a forward outgrow it all the same, the next forward raises ManusHipError (the step before it used an
-    # incomplete image) and the context returns to the blocking mode.  0 = never switch; a densification (new N) starts over.
+    # headroom; should a forward outgrow it all the same, the next forward (or `poll()`) raises ManusHipError (the step before
+    # it used an incomplete image) and the context returns to the blocking mode.  0 = never switch; a densification (new N)
+    # starts over.  Two kinds of forward always read the count back, because nothing after them would report an overflow:
+    # one that builds no autograd graph (an evaluation render under no_grad), and one whose packed camera table -- the same
+    # tensor object at the same version while the caller's camera tensors are unmodified (_lib.cached_pack) -- has not been
+    # through a synchronous forward of this (V, N, W, H): a new camera may need far more pairs than the capacity learnt so far.
     AUTO_FENCE_AFTER = int(os.environ.get("MANUS_AUTO_FENCE_AFTER", "8"))
 
     def __init__(self, device):
@@ -114,6 +119,7 @@ class RasterContext:
         self.cut_retries = 0             # forwards flagged MGR_OVF_CUT (each is answered by a forward without the depth cut)
         self.cut_repairs = 0             # (tile, quadrant) units repaired on the device by forwards with the depth cut (bit 2048)
         self._clean = {}                 # (V, N, W, H) -> consecutive synchronised forwards that fitted their capacity
+        self._seen = {}                  # (V, N, W, H) -> {id: (weak reference, version)} of the camera tables read back synchronously
         self.auto_fenced = 0             # forwards that ran on an automatic fence instead of the blocking read
         self.tier_retries = 0            # forwards flagged MGR_OVF_TIER (answered by a forward with every binning launch)
 
@@ -149,12 +155,23 @@ class RasterContext:
         self._evicted_overflow = False
         self.last_ws = None
         self._clean.clear()
+        self._seen.clear()
 
     def _learn(self, key, npairs):
         self.cap_hint[key] = max(self.cap_hint.get(key, 0), int(npairs * 1.25) + 4096)
 
     # -- forward driver -------------------------------------------------------------------------
-    def forward(self, V, N, W, H, launch, sync_check=True, defer_fence=False, auto_fence=False):
+    def _seen_cams(self, key, cams):
+        ent = self._seen.get(key, {}).get(id(cams))
+        return ent is not None and ent[0]() is cams and ent[1] == cams._version
+
+    def _see_cams(self, key, cams):
+        seen = self._seen.setdefault(key, {})
+        if len(seen) >= 256:
+            seen.clear()
+        seen[id(cams)] = (weakref.ref(cams), cams._version)
+
+    def forward(self, V, N, W, H, launch, sync_check=True, defer_fence=False, auto_fence=False, cams=None):
         """Run `launch(ws)` (which enqueues one forward on the current stream) with a workspace large enough for
         the pairs it produces.  sync policy True: read the pair count back (one host sync, like upstream) and
         retry with a larger workspace on overflow; False: no host sync, an overflow fence is recorded instead
@@ -163,8 +180,9 @@ class RasterContext:
         the depth-cut flag in its second half."""
         key = (V, N, W, H)
         cap = max(self.cap_hint.get(key, 0), default_pair_capacity(V, N))
-        # auto_fence (the operator route): see AUTO_FENCE_AFTER
-        auto = bool(auto_fence) and sync_check and self.sync_every_forward and 0 < self.AUTO_FENCE_AFTER <= self._clean.get(key, 0)
+        # auto_fence (the operator route, False for a forward without autograd graph): see AUTO_FENCE_AFTER; cams: its camera table
+        auto = (bool(auto_fence) and sync_check and self.sync_every_forward and 0 < self.AUTO_FENCE_AFTER <= self._clean.get(key, 0)
+                and cams is not None and self._seen_cams(key, cams))
         if auto:
             try:
                 self.poll()              # the automatic fences of the forwards before (complete by now)
@@ -197,6 +215,8 @@ class RasterContext:
             if rc == 0:
                 self._learn(key, npairs.value)
                 self._clean[key] = self._clean.get(key, 0) + 1
+                if auto_fence and cams is not None:
+                    self._see_cams(key, cams)
                 return ws, int(npairs.value)
             self._clean[key] = 0
             if rc == -7 and not (ovf.value & 3):   # MGR_ETIER: a skipped binning launch was needed; same workspace, all launches
@@ -364,7 +384,7 @@ class _Lease:
         self.ws.busy = False
 
 
-def _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opacity, debug, sync_check=True):
+def _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opacity, debug, sync_check=True, graph=True):
     dev = means3D.device
     out = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((V, N), dtype=torch.int32, device=dev)
@@ -379,7 +399,7 @@ def _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opacity, debug, s
                                        ptr(ws.buf), ws.nbytes, ws.cap, int(bool(debug)) | ws.skip_bits(), stream()),
               "mgr_raster_forward")
 
-    ws, npairs = context(dev).forward(V, N, W, H, launch, sync_check, auto_fence=True)
+    ws, npairs = context(dev).forward(V, N, W, H, launch, sync_check, auto_fence=graph, cams=cams)
     return out, radii, ws, npairs
 
 
@@ -396,14 +416,14 @@ def _opacity_layout(op, V, N):
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, cov3D, cams, bg, W, H, debug):
+    def forward(ctx, means3D, means2D, colors, opacities, cov3D, cams, bg, W, H, debug, graph=True):
         V = cams.shape[0]
         means3D, colors, cov3D = f32c(means3D), f32c(colors), f32c(cov3D)
         opac = f32c(opacities)
         N = means3D.shape[-2]
         opac = _opacity_layout(opac, V, N)
         bg = f32c(bg).reshape(-1)
-        out, radii, ws, npairs = _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opac, debug)
+        out, radii, ws, npairs = _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opac, debug, graph=graph)
         ctx.lease = _Lease(ws)
         ctx.meta = (V, N, W, H, bool(debug), means2D.shape, opacities.shape)
         ctx.num_rendered = npairs
@@ -443,14 +463,20 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_col = fold(d_col, colors.dim() == 2)
         g_op = fold(d_op, opac.dim() == 1, op_shape)
         g_cov = fold(d_cov, cov3D.dim() == 2)
-        return g_m3, g_m2, g_col, g_op, g_cov, None, None, None, None, None
+        return g_m3, g_m2, g_col, g_op, g_cov, None, None, None, None, None, None
+
+
+def _builds_graph(*tensors):
+    """True when autograd records the operator (a backward will follow); False for an evaluation render."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
 def rasterize_views(cams, means3D, means2D, colors, opacities, cov3D, bg, W, H, debug=False):
     """V views in one call.  cams (V,40) from `_lib.pack_cameras`; per-Gaussian
     inputs are (N,..) shared by all views or (V,N,..).  Returns color (V,3,H,W),
     radii (V,N)."""
-    return _RasterizeGaussians.apply(means3D, means2D, colors, opacities, cov3D, cams, bg, int(W), int(H), debug)
+    return _RasterizeGaussians.apply(means3D, means2D, colors, opacities, cov3D, cams, bg, int(W), int(H), debug,
+                                     _builds_graph(means3D, means2D, colors, opacities, cov3D))
 
 
 class GaussianRasterizer(nn.Module):
@@ -493,5 +519,6 @@ class GaussianRasterizer(nn.Module):
             colors_precomp = sh_colors(sh, means3D, None, cams)[0]
         color, radii = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, cov3D_precomp,
                                                  cams, rs.bg, int(rs.image_width), int(rs.image_height),
-                                                 bool(rs.debug))
+                                                 bool(rs.debug), _builds_graph(means3D, means2D, colors_precomp, opacities,
+                                                                               cov3D_precomp))
         return color[0], radii[0]

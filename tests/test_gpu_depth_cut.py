@@ -19,11 +19,11 @@ DEV = "cuda:0"
 LEAVES = ("_xyz", "_scaling", "_rotation", "_opacity", "_features_dc", "_features_rest")
 
 
-def _scene(V=4, n=40000, W=256, H=192, seed=3):
+def _scene(V=4, n=40000, W=256, H=192, seed=3, sigma_range=(2e-3, 5e-3)):
     from manus_amd.synthetic import camera_table, make_scene
     # opaque, fairly large Gaussians on the hand, seen from close: the interior tiles saturate, the silhouette does not
     sc = make_scene(n_gaussians=n, kind="hand", seed=seed, grid_res=32, n_cameras=V, width=W, height=H, cam_radius=0.45,
-                    sigma_range=(2e-3, 5e-3), device=DEV)
+                    sigma_range=sigma_range, device=DEV)
     sc["params"]["_opacity"] = sc["params"]["_opacity"] + 2.0
     g = torch.Generator().manual_seed(seed + 100)
     targets = torch.rand((V, 3, H, W), generator=g).to(DEV)
@@ -137,14 +137,14 @@ def test_outdated_hints_are_flagged_and_the_rerun_is_exact(fenced):
     assert fenced.cut_retries == 1
 
 
-def _moving_model_run(fenced, V, W, H, n, steps, d_opacity, margin, seed=5, penalty=16):
+def _moving_model_run(fenced, V, W, H, n, steps, d_opacity, margin, seed=5, penalty=16, **scene_kw):
     """A model whose opacities fall by d_opacity per step (the walks lengthen under the hints of the step before), rendered
     by a compute object without the cut -- all states first: two objects taking turns on one workspace would wipe the hints --
     and then by one with the cut and tight margins.  Returns (repaired quadrants, flagged forwards)."""
     from manus_amd import rasterizer
     from manus_amd._lib import ManusHipError
     from util import keep
-    sc, targets, ct = _scene(V=V, n=n, W=W, H=H, seed=seed)
+    sc, targets, ct = _scene(V=V, n=n, W=W, H=H, seed=seed, **scene_kw)
     views = list(range(V))
     ref = _compute(sc, targets, ct, cut=False)
     _warm(ref, views)
@@ -196,6 +196,22 @@ def test_repair_capacity_exceeded_falls_back_to_the_flag(fenced):
     fenced.cut_repairs = 0
     _, flagged = _moving_model_run(fenced, V=2, W=256, H=192, n=40000, steps=2, d_opacity=3.0, margin=0.25)
     assert flagged >= 1
+
+
+@pytest.mark.parametrize("W,H,steps", [(6016, 4000, 3), (8192, 4320, 1)])
+def test_repair_on_a_grid_beyond_65536_tiles(fenced, W, H, steps):
+    """k_repair_scan keeps one bit per tile of a view in LDS, for at most mgr_raster_repair_max_tiles() tiles.  On a larger grid
+    (94 000 / 138 240 tiles) the repair stays off -- checked on the host before anything runs --, a tile that runs out flags
+    the forward, and every step, re-runs included, is bit for bit the step without the cut."""
+    from manus_amd._lib import lib
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    assert T > lib().mgr_raster_repair_max_tiles() == 65536
+    fenced.cut_repairs = 0
+    # small Gaussians (rectangles of at most 64 tiles are cut), enough of them that the interior tiles saturate
+    repairs, flagged = _moving_model_run(fenced, V=1, W=W, H=H, n=300000, steps=steps, d_opacity=0.15, margin=0.25,
+                                         sigma_range=(3e-4, 8e-4))
+    print("%dx%d: %d tiles, repaired quadrants %d, flagged forwards %d" % (W, H, T, repairs, flagged))
+    assert repairs == 0
 
 
 def test_alternating_view_sets_keep_their_hints(fenced):

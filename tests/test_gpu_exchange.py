@@ -66,6 +66,38 @@ def test_compact_exchange_kernels_equal_the_torch_steps(N, density, use_list):
     assert torch.equal(outs[0], flat_cpu) and torch.equal(outs[1], flat_cpu)
 
 
+def test_compact_exchange_capacity_does_not_depend_on_event_timing(monkeypatch):
+    """The row capacity sizes the second collective, so every rank must choose the same one: it may depend on the steps
+    (the union's size of the step before), never on whether an event has completed yet.  A rank whose events always look
+    pending (Event.query() False) and a rank that synchronises between the steps choose the same capacities."""
+    from manus_amd.engine import GRAD_LAYOUT, ViewShardedStep
+    N = 70001
+    flat_cpu, rows, _ = _flat(N, 0.07, seed=N)
+    shapes = {name: (N, w) for name, w in GRAD_LAYOUT}
+    f = min(N, int(len(rows) * 1.25) + 1024)
+    assert f < N
+
+    def run(sync):
+        st = ViewShardedStep(N, shapes, _Fn(), 8)
+        st._store = flat_cpu.clone().to(DEV)
+        caps = []
+        for _ in range(3):
+            st._compact_all_reduce(st._store, st._views())
+            caps.append(st.last_cap_rows)
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        assert torch.equal(st._store.cpu(), flat_cpu)
+        return caps
+
+    with monkeypatch.context() as mp:
+        mp.setattr(torch.cuda.Event, "query", lambda self: False)
+        slow = run(sync=False)
+    fast = run(sync=True)
+    assert fast == [N, f, f]
+    assert slow == fast, (slow, fast)
+
+
 def test_exchange_index_is_ordered_and_pack_layout_matches_the_torch_buffer():
     from manus_amd._lib import check, lib, ptr, stream
     from manus_amd.engine import GRAD_LAYOUT, GRAD_WIDTH

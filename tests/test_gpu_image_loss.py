@@ -266,3 +266,158 @@ def test_span_list_from_target_maps_equals_the_list_from_the_targets():
     diff = (diff[:, 0::2] | diff[:, 1::2]).view(V, (H + 1) // 2, -1, 32)
     want = (diff.long() << torch.arange(32, device=DEV)).sum(-1)
     assert torch.equal(want, tmap.view(V, (H + 1) // 2, -1).long() & 0xFFFFFFFF)
+
+
+def _ref_sums64(pred, gt, k=1.0, c=0.0, w_l1=0.8, w_ssim=0.2):
+    """The three sums of mgr_image_loss restated in float64 (test_kernel_matches_oracle's reference): sum |pred - gt|, sum
+    of the SSIM map, and k * (w_l1 * l1 - w_ssim * ssim) + c."""
+    V, _, H, W = pred.shape
+    l1 = s = torch.zeros((), dtype=torch.float64)
+    for v in range(V):
+        p, t = pred[v].permute(1, 2, 0).double().cpu(), gt[v].permute(1, 2, 0).double().cpu()
+        l1 = l1 + (p - t).abs().sum()
+        s = s + tr.ssim_hwc(p, t) * (3 * H * W)
+    return torch.stack([l1, s, k * (w_l1 * l1 - w_ssim * s) + c])
+
+
+def _same_finiteness(got, ref):
+    got = got.double().cpu()
+    assert torch.equal(torch.isfinite(got), torch.isfinite(ref)), (got, ref)
+    assert torch.isnan(got[torch.isnan(ref)]).all(), (got, ref)
+
+
+def _non_finite_cases(pred, gt, v, h, w):
+    for where, val in (("pred", float("nan")), ("pred", float("inf")), ("target", float("nan"))):
+        p, t = pred.clone(), gt.clone()
+        (p if where == "pred" else t)[v, 1, h, w] = val
+        yield where, val, p, t
+
+
+def test_non_finite_inputs_propagate_like_the_reference():
+    """A NaN / Inf in the rendered image or a NaN in the target makes the reference's loss NaN (or Inf).  The sums travel as
+    fixed-point integers: they must come out non-finite as well, not as a finite value the gradients do not belong to --
+    on the full comparison (k_image_loss_scan), the tile-aware list (mgr_image_loss_tiles) and the training step's
+    attached, mapped list."""
+    from manus_amd import ops, rasterizer as rz
+    from manus_amd.engine import HipViewCompute
+    from manus_amd.synthetic import camera_table, make_scene
+    g = torch.Generator().manual_seed(17)
+    V, H, W = 2, 7, 300
+    gt = torch.rand((V, 3, H, W), generator=g)
+    pred = (gt + 0.1 * torch.randn((V, 3, H, W), generator=g)).clamp(0, 1.1)
+    sums, _ = ops.image_loss_grad(pred.to(DEV), gt.to(DEV), 0.8, 0.2, 0.37, 0.125)
+    assert torch.isfinite(sums).all()
+    for where, val, p, t in _non_finite_cases(pred, gt, 1, 3, 150):
+        sums, _ = ops.image_loss_grad(p.to(DEV), t.to(DEV), 0.8, 0.2, 0.37, 0.125)
+        ref = _ref_sums64(p, t, 0.37, 0.125)
+        assert not torch.isfinite(ref).all()
+        _same_finiteness(sums, ref)
+    # the tile-aware list on a rendered scene
+    V, W, H, n = 2, 300, 170, 3000
+    sc = make_scene(n_gaussians=n, kind="hand", seed=9, grid_res=24, n_cameras=V, width=W, height=H, cam_radius=0.9,
+                    sigma_range=(2e-3, 8e-3), device=DEV)
+    ct = camera_table(sc["cameras"], DEV)
+    gs = torch.Generator(device="cpu").manual_seed(3)
+    tgt_scene = dict(sc)
+    tgt_scene["params"] = {k: (v + 0.02 * v.abs().mean() * torch.randn(v.shape, generator=gs).to(DEV)) for k, v in sc["params"].items()}
+    with torch.no_grad():
+        targets = HipViewCompute(tgt_scene, torch.zeros((V, 3, H, W), device=DEV), ct).forward_views_fused(list(range(V)))[0].contiguous()
+    rz.set_sync_policy(True)
+    hc = HipViewCompute(sc, targets, ct, loss="l1+ssim")
+    out = hc._step_direct(list(range(V)), 1.0 / V)
+    assert torch.isfinite(out["loss"])
+    ws = rz.context().last_ws
+    img = hc.last_image.clone()
+    ts_ptr = hc._tile_start_ptr(ws, V, n, W, H)
+    fg = (img[1] != sc["bg"].view(3, 1, 1)).any(0).nonzero()           # a rendered pixel: its tile holds Gaussians
+    assert fg.shape[0] > 0
+    h, w = int(fg[fg.shape[0] // 2, 0]), int(fg[fg.shape[0] // 2, 1])
+    sums, _ = ops.image_loss_grad(img, targets, 0.8, 0.2, 0.37, 0.125, bg=sc["bg"], tile_start_ptr=ts_ptr)
+    assert torch.isfinite(sums).all()
+    for where, val, p, t in _non_finite_cases(img, targets, 1, h, w):
+        sums, _ = ops.image_loss_grad(p, t, 0.8, 0.2, 0.37, 0.125, bg=sc["bg"], tile_start_ptr=ts_ptr)
+        _same_finiteness(sums, _ref_sums64(p, t, 0.37, 0.125))
+    # the training step (defaults: target maps, list attached to the forward)
+    bad = targets.clone()
+    bad[1, 0, 5, 10] = float("nan")
+    hc = HipViewCompute(sc, bad, ct, loss="l1+ssim")
+    assert hc.target_map and hc.attach_list
+    out = hc._step_direct(list(range(V)), 1.0 / V)
+    assert not torch.isfinite(out["loss"]), float(out["loss"])
+    # ... and the kept loss workspace is clean again: the next step of a finite target is finite
+    hc2 = HipViewCompute(sc, targets, ct, loss="l1+ssim")
+    assert torch.isfinite(hc2._step_direct(list(range(V)), 1.0 / V)["loss"])
+
+
+def test_l1_sum_beyond_2_to_the_31():
+    """The sums are 64-bit fixed point at 2^-32: totals of magnitude 2^31 or more do not fit.  The range is
+    bounded, not widened -- every workgroup's sum must stay within 2^31 / (spans of the batch), or all three sums are NaN --
+    so a total never wraps silently; a large total inside the bound is exact to fp32."""
+    from manus_amd import ops
+    g = torch.Generator(device=DEV).manual_seed(23)
+    V, H, W = 1, 1024, 1024
+    gt = torch.rand((V, 3, H, W), device=DEV, generator=g)
+    sums, grad = ops.image_loss_grad(gt + 1000.0, gt, 0.8, 0.2, 1.0)       # L1 sum 3.1e9 > 2^31
+    assert torch.isnan(sums).all(), sums
+    assert torch.isfinite(grad).all()
+    pred = gt + 300.0                                                      # L1 sum 9.4e8: within the bound
+    sums, _ = ops.image_loss_grad(pred, gt, 0.8, 0.2, 1.0)
+    l1 = float((pred.double() - gt.double()).abs().sum())
+    assert l1 > 2 ** 29
+    assert abs(float(sums[0]) - l1) <= 1e-6 * l1
+    assert torch.isfinite(sums).all()
+
+
+def test_failed_step_leaves_the_kept_loss_workspace_clean(monkeypatch):
+    """A step that raises after its forward -- whose last kernel has built the span list of the image loss into the kept
+    loss workspace -- must not leave that list behind: the next step would append its own behind it (spans counted twice,
+    a list running past its end).  The workspace is forgotten (or its count is zero) before anything else runs, and the
+    next step equals a fresh object's."""
+    from manus_amd import rasterizer as rz
+    from manus_amd._lib import ManusHipError
+    from manus_amd.engine import HipViewCompute
+    from manus_amd.synthetic import camera_table, make_scene
+    from util import keep
+    V, W, H, n = 2, 256, 160, 3000
+    sc = make_scene(n_gaussians=n, kind="hand", seed=4, grid_res=24, n_cameras=V, width=W, height=H, cam_radius=0.9,
+                    sigma_range=(2e-3, 8e-3), device=DEV)
+    ct = camera_table(sc["cameras"], DEV)
+    gs = torch.Generator(device="cpu").manual_seed(8)
+    tgt_scene = dict(sc)
+    tgt_scene["params"] = {k: (v + 0.02 * v.abs().mean() * torch.randn(v.shape, generator=gs).to(DEV)) for k, v in sc["params"].items()}
+    with torch.no_grad():
+        targets = HipViewCompute(tgt_scene, torch.zeros((V, 3, H, W), device=DEV), ct).forward_views_fused(list(range(V)))[0].contiguous()
+    rz.set_sync_policy(True)
+    views = list(range(V))
+    hc = HipViewCompute(sc, targets, ct, loss="l1+ssim")
+    assert hc.target_map and hc.attach_list                # the mapped list, attached to the forward
+    hc._step_direct(views, 1.0 / V)
+    ctx = rz.context(DEV)
+    real, calls = ctx.forward, []
+
+    def forward_then_fail(*a, **k):
+        r = real(*a, **k)
+        if not calls:
+            calls.append(1)
+            raise ManusHipError("injected failure after the forward")
+        return r
+
+    monkeypatch.setattr(ctx, "forward", forward_then_fail)
+    with pytest.raises(ManusHipError):
+        hc._step_direct(views, 1.0 / V)
+    monkeypatch.undo()
+    assert calls
+    lws = hc._lws.get((V, H, W))
+    if lws is not None:
+        torch.cuda.synchronize()
+        nb = V * ((H + 1) // 2) * ((W + 245) // 246)
+        assert int(lws[nb * 12 + 64: nb * 12 + 68].view(torch.int32).item()) == 0
+    got = keep(hc._step_direct(views, 1.0 / V))
+    img = hc.last_image.clone()
+    fresh = HipViewCompute(sc, targets, ct, loss="l1+ssim")
+    want = keep(fresh._step_direct(views, 1.0 / V))
+    assert torch.equal(got["loss"], want["loss"]), (float(got["loss"]), float(want["loss"]))
+    for k in want["grads"]:
+        assert torch.equal(got["grads"][k], want["grads"][k]), k
+    assert torch.equal(got["grad2d"], want["grad2d"])
+    assert torch.equal(img, fresh.last_image)

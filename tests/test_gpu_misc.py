@@ -116,6 +116,107 @@ def test_transposed_view_matrices_and_the_camera_cache():
     assert torch.equal(render(view_t), want_moved)
 
 
+def test_auto_fenced_operator_route_never_returns_a_truncated_image():
+    """Operator route after RasterContext.AUTO_FENCE_AFTER clean forwards of one (V, N, W, H): the blocking read of the pair
+    count gives way to a fence the next forward resolves.  A forward that nothing after it would check -- an evaluation render
+    under no_grad, or the first forward of a camera the context has not read back -- must not return an image cut short by the
+    capacity learnt on another camera; two cameras used in turn still reach the fenced mode; and an overflow of a fenced
+    forward (same camera, Gaussians grown in place) is reported by poll()."""
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+    from manus_amd import rasterizer as rz
+    from manus_amd._lib import ManusHipError
+    W, H, n = 320, 240, 20000
+    ctx = rz.context(DEV)
+    m, cov, col, op = [torch.tensor(x, device=DEV) for x in random_gaussians(n, seed=11)]
+    leaves = [t.requires_grad_(True) for t in (m, cov, col)]
+    op = op[:, None].clone().requires_grad_(True)
+    leaves.append(op)
+    m2 = torch.zeros_like(m, requires_grad=True)
+    w_img = torch.rand((3, H, W), generator=torch.Generator().manual_seed(4)).to(DEV)
+
+    def settings(focal=None, pos=(0.3, -0.2, -1.5)):
+        cam = make_camera(W, H, pos=pos, focal=focal)        # fresh camera tensor objects on every call
+        a = cam_args(cam)
+        return GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=a["tanfovx"], tanfovy=a["tanfovy"],
+                                             bg=torch.ones(3, device=DEV), scale_modifier=1,
+                                             viewmatrix=torch.tensor(a["view"], device=DEV).reshape(1, 4, 4),
+                                             projmatrix=torch.tensor(a["proj"], device=DEV).reshape(1, 4, 4), sh_degree=3,
+                                             campos=torch.tensor(cam["camera_center"], device=DEV).reshape(1, 3),
+                                             prefiltered=False, debug=False)
+
+    def render(st):
+        return GaussianRasterizer(raster_settings=st)(means3D=m, means2D=m2, opacities=op, colors_precomp=col, cov3D_precomp=cov)
+
+    def step(st):
+        for t in leaves + [m2]:
+            t.grad = None
+        img, radii = render(st)
+        (img * w_img).sum().backward()
+        return img.detach().clone(), radii.clone(), [t.grad.clone() for t in leaves + [m2]]
+
+    def pairs(st):
+        ctx.clear()
+        with torch.no_grad():
+            render(st)
+        return ctx.check_overflow()
+
+    st_a, st_b = settings(focal=0.6 * W), settings(focal=3.0 * W)    # B: the same view zoomed in
+    n_a, n_b = pairs(st_a), pairs(st_b)
+    # B outgrows the capacity learnt on A (at least the default capacity of the key)
+    assert n_b > max(1.25 * n_a + 4096, rz.default_pair_capacity(1, n)), (n_a, n_b)
+    ctx.clear()
+    with torch.no_grad():
+        want_img, want_radii = [t.clone() for t in render(st_b)]
+    ctx.clear()
+    want_step = step(st_b)
+    assert torch.equal(want_step[0], want_img)
+
+    def warm_on_a():
+        ctx.clear()
+        ctx.auto_fenced = 0
+        for _ in range(rz.RasterContext.AUTO_FENCE_AFTER + 1):
+            step(st_a)
+        assert ctx.auto_fenced > 0
+
+    try:
+        # (a) an evaluation render of B
+        warm_on_a()
+        with torch.no_grad():
+            img, radii = render(st_b)
+        assert torch.equal(img, want_img) and torch.equal(radii, want_radii)
+        rz.poll(DEV)
+        # (b) a training forward of B through camera tensors the context has not seen
+        warm_on_a()
+        got = step(settings(focal=3.0 * W))                    # (new tensors: a new packed camera table)
+        assert torch.equal(got[0], want_img) and torch.equal(got[1], want_radii)
+        for g, w in zip(got[2], want_step[2]):
+            assert torch.equal(g, w)
+        rz.poll(DEV)
+        # (c) two cameras in turn (bench.py --route dropin cycles over its cameras) still switch to the fences
+        st_c = settings(focal=0.6 * W, pos=(0.32, -0.18, -1.5))
+        ctx.clear()
+        ctx.auto_fenced = 0
+        for k in range(12):
+            step(st_a if k % 2 == 0 else st_c)
+        assert ctx.auto_fenced > 0
+        rz.poll(DEV)
+        # (d) a camera seen before, but the Gaussians grow in place beyond the capacity: reported by the poll after the forward
+        warm_on_a()
+        fenced_before = ctx.auto_fenced
+        with torch.no_grad():
+            cov.mul_(9.0)
+        try:
+            render(st_a)
+            assert ctx.auto_fenced == fenced_before + 1
+            with pytest.raises(ManusHipError):
+                rz.poll(DEV)
+        finally:
+            with torch.no_grad():
+                cov.div_(9.0)
+    finally:
+        ctx.clear()
+
+
 def test_render_gaussians_reference_signature(golden_dir):
     """The reference call sequence (hand module forward -> render_gaussians) end to end vs the oracles."""
     from types import SimpleNamespace
