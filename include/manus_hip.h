@@ -588,6 +588,43 @@ int mgr_contact_dist(int N1, const float* pt1, int N2, const float* pt2, float* 
                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Contact maps: near search, value formula and colour epilogue.  Together they replace get_cmap
+ * (src/utils/gaussian_utils.py:571-577), get_colors_from_cmap (src/utils/vis_util.py:22-25: a device -> numpy ->
+ * matplotlib -> device round trip per render) and the colour blends of Composite.render_contacts
+ * (src/modules/composite.py:143-214).
+ *
+ * mgr_contact_near: for each of the N1 points of pt1 the nearest point of pt2 WITHIN RADIUS c_thresh (> 0), with the
+ *   arithmetic and tie rule of mgr_contact_dist (fp32, (dx^2+dy^2)+dz^2 without contraction, correctly rounded root,
+ *   strict '<' on the rooted distance, lowest index wins a tie).  pt2 is counting-sorted on the device into a hashed
+ *   uniform grid of cell edge just above c_thresh whose table is sized from N2 (a far outlier costs nothing); a point
+ *   of pt1 visits at most 27 cells.  Contract:
+ *     out_value (N1)  = 1 - clamp(dist, 0, c_thresh) / c_thresh, fp32 in that order with an IEEE division, of the
+ *                       brute-force distance, bit for bit, for every point (get_cmap lines 573-574);
+ *     out_idx (N1)    = the brute-force index wherever out_value > 0, -1 elsewhere (the reference only reads indices
+ *                       under the mask dist > 0, composite.py:190-196);
+ *     out_dist (N1)   = (may be NULL) the brute-force distance where out_value > 0, 1e9 (the loop's initial minimum)
+ *                       elsewhere.
+ *   N1 = 0 and N2 = 0 (all values 0, indices -1) are valid; coincident and duplicated points follow the tie rule; a
+ *   point with a NaN coordinate is nobody's neighbour and has value 0 (the strict '<' of the reference loop).
+ *   workspace: mgr_contact_near_workspace_bytes(N1, N2).  No host read-back, everything on `stream`.
+ * mgr_contact_values: out_value (N) = the same formula applied to distances some other search produced.
+ * mgr_contact_colors: per point, out (N,3) =
+ *     table == NULL:  c = lut[k] (lut (256,3) fp32), k = min(int(value * 256.0f), 255), 0 for value < 0, 255 for
+ *                     value >= 1 (+inf included), c = (0,0,0) for NaN -- matplotlib's Colormap.__call__ on a float32
+ *                     array; then c itself (base == NULL) or base[n] * alpha + one_minus_alpha * c (base (N,3)), two
+ *                     rounded products and one rounded sum like rgb_colors * alpha + (1 - alpha) * cmap.  The caller
+ *                     passes one_minus_alpha = (float)(1.0 - alpha_as_double), which is what the reference multiplies by.
+ *     table != NULL:  value[n] > 0 ? table[idx_nn ? idx_nn[n] : n] : (0,0,0)   (table (M,3); the NOCS renders,
+ *                     composite.py:165-183; an index outside [0, M) gives black).
+ * ------------------------------------------------------------------------ */
+size_t mgr_contact_near_workspace_bytes(int N1, int N2);
+int mgr_contact_near(int N1, const float* pt1, int N2, const float* pt2, float c_thresh, float* out_value, int32_t* out_idx,
+                     float* out_dist, void* workspace, size_t workspace_bytes, void* stream);
+int mgr_contact_values(int N, const float* dist, float c_thresh, float* out_value, void* stream);
+int mgr_contact_colors(int N, const float* value, const float* lut, const float* base, float alpha, float one_minus_alpha,
+                       const float* table, int M, const int32_t* idx_nn, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Skin-weight initialisation from the MANO rest mesh (model-initialisation side of the
  * dataloader): the device half of init_mano_weights (src/utils/train_utils.py:48-89) as called by
  * Dataset.build_voxel_grid / Dataset.sample_gaussians_on_bones (src/datasets/brics_dynamic.py:69-144).
