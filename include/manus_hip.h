@@ -625,6 +625,38 @@ int mgr_contact_colors(int N, const float* value, const float* lut, const float*
                        const float* table, int M, const int32_t* idx_nn, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Validation pass (eval.hip): the metrics and the triptych of BaseTrainingModule.validation_step /
+ * on_validation_epoch_end (src/modules/base.py:112-188) with psnr of src/utils/loss_utils.py:100-108, for V views kept in
+ * the rasterizer's layout.  Forward only; everything on `stream`, no host read-back, no float atomics: two calls on the
+ * same inputs give bit-equal outputs, and a view's outputs depend on that view's pixels only.
+ *
+ * mgr_eval_views: pred, target (V,3,H,W) fp32; mask (V,H,W) fp32, possibly fractional, NULL = ones.  Per view v:
+ *     sq_sum[v]   = sum over all 3*H*W elements of (pred*mask - target*mask)^2, the two products and the difference each
+ *                   rounded to fp32 (`render * mask`, `gt * mask`, `inputs - targets`); masked-out pixels count in the mean
+ *                   like in the reference: psnr = -10 log10(sq_sum / (3*H*W)), +inf for equal masked images (sq_sum == 0);
+ *     ssim_sum[v] = sum of the reference's SSIM map of the two masked images in the HWC form it computes (the 11x11 window
+ *                   over the (W,3) plane of every row, zero padded -- the statistic of mgr_image_loss); ssim = / (3*H*W);
+ *     gt_max[v]   = maximum of the unmasked target (NaN if it holds one, as ndarray.max), for dump_image's rule below;
+ *     flags[v]    = (may be NULL) 1 when the view's pred / target / mask hold a NaN or Inf or a total is not finite: sq_sum
+ *                   and ssim_sum of THAT view are then NaN; 0 otherwise.
+ *   Per-workgroup partial sums are folded per view in fp64 by a second kernel.  workspace: mgr_eval_workspace_bytes(V,H,W).
+ *   Limits as mgr_image_loss: H, V <= 65535, W <= 16384.
+ * mgr_eval_triptych: out (V,3H,W,3) uint8 = three HWC panels stacked along the rows (concat_img_array, axis 0):
+ *     rows [0,H)    uint8(clamp(pred,0,1) * 255.0f), truncating, of the UNMASKED render (base.py:116-117);
+ *     rows [H,2H)   dump_image(gt): uint8(target * 255.0f) when gt_max[v] <= 1.0, else uint8(target) (extra.py:153-160);
+ *     rows [2H,3H)  diff_table[gt_byte * 256 + render_byte]: the reference's uint8((gt/255.0 - img/255.0) * 255.0) in float64
+ *                   (base.py:124-127) is a function of the two bytes; the caller builds the 256x256 table with that very
+ *                   numpy expression (manus_amd.validation.diff_table) and passes it on the device.
+ *   A NaN pixel gives byte 0 in its panel (this library's definition: numpy's cast of NaN is not defined); finite values
+ *   outside the byte range wrap like numpy's cast on x86-64 (truncate toward zero, low eight bits).
+ * ------------------------------------------------------------------------ */
+size_t mgr_eval_workspace_bytes(int V, int H, int W);
+int mgr_eval_views(int V, int H, int W, const float* pred, const float* target, const float* mask, float* sq_sum,
+                   float* ssim_sum, float* gt_max, int32_t* flags, void* workspace, size_t workspace_bytes, void* stream);
+int mgr_eval_triptych(int V, int H, int W, const float* pred, const float* target, const float* gt_max,
+                      const uint8_t* diff_table, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Skin-weight initialisation from the MANO rest mesh (model-initialisation side of the
  * dataloader): the device half of init_mano_weights (src/utils/train_utils.py:48-89) as called by
  * Dataset.build_voxel_grid / Dataset.sample_gaussians_on_bones (src/datasets/brics_dynamic.py:69-144).

@@ -97,6 +97,9 @@ SIGNATURES = {
     "mgr_image_loss_tiles_list": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_image_loss_tiles_finish": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_sz,
                                             c_vp]),
+    "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_eval_triptych": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_adam_step": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, c_vp]),
     "mgr_reset_opacity": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp]),

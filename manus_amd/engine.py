@@ -1052,6 +1052,81 @@ class Trainer:
             self.stepper.all_gather_params(self.opt.mflat)
             self.stepper.all_gather_params(self.opt.vflat)
 
+    def validate(self, view_ids, masks=None, validator=None, group=8):
+        """The validation pass over the views `view_ids` of the compute object (validation_step / on_validation_epoch_end,
+        src/modules/base.py:112-188): rendered under no_grad with `forward_views` in groups of `group` views (the group
+        size of `HipViewCompute.pairs_per_view`), compared with `compute.targets` by `ops.eval_views` / `ops.eval_triptych`
+        on the whole group, ONE host synchronisation per group (the read-back of its metrics; the render runs fenced and
+        is rendered again with more room should its pairs not have fitted).  masks: (len(view_ids),H,W), possibly fractional, or None
+        (ones).  validator: a `validation.Validator` that receives every view (metrics, its share of the group's render
+        time, triptych); the caller brackets the pass with its start() / end(global_step).
+
+        Returns dict(psnr, ssim: per-view lists; psnr_mean, ssim_mean; render_time: seconds from the start of each
+        group's render to the end of its last kernel, summed (two events on the stream: the group's host work included,
+        no extra synchronisation);
+        images: (len(view_ids),3H,W,3) uint8 on the device).
+
+        The training state is left as it was: the renders run in a rasterizer context of their own (workspace pool,
+        learnt capacities, fences and sync policy of the training context are not touched), the compute object's cache of
+        per-view constants is put back, nothing is written into the kept gradient / image / loss buffers, and
+        `global_step` does not move -- a train_step after a validate computes what it would have without it."""
+        from . import ops
+        from ._lib import ManusHipError
+        from .validation import psnr_from_sums
+        c = self.compute
+        ids = list(view_ids)
+        dev = getattr(c, "device", None)
+        if masks is not None and (masks.dim() != 3 or masks.shape[0] != len(ids)):
+            raise ValueError("validate: masks must be (len(view_ids),H,W)")
+        idx = self._rz.context(dev).device.index
+        train_ctx = self._rz._CONTEXTS[idx]
+        if getattr(self, "_val_ctx", None) is None or self._val_ctx.device != train_ctx.device:
+            self._val_ctx = self._rz.RasterContext(train_ctx.device)
+            self._val_ctx.sync_every_forward = False     # (of the private context: the training context keeps its policy)
+        n_now = c.params["_xyz"].shape[0]
+        if any(key[1] != n_now for key in self._val_ctx.pool):      # a densification changed N: the old workspaces are of no use
+            self._val_ctx.clear()
+        saved_cache, saved_stamp = c._cache, c._const_stamp
+        psnrs, ssims, images, render_time = [], [], [], 0.0
+        self._rz._CONTEXTS[idx] = self._val_ctx
+        try:
+            with torch.no_grad():
+                for k in range(0, len(ids), group):
+                    part = ids[k:k + group]
+                    m = masks[k:k + group] if masks is not None else None
+                    for attempt in range(4):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        img, _, _ = c.forward_views(part)       # no host read: the private context runs fenced
+                        e1.record()
+                        tgt = c._select(part)["targets"]
+                        sq, ss, gmax = ops.eval_views(img, tgt, m)
+                        trip = ops.eval_triptych(img, tgt, gmax)
+                        n = float(img[0].numel())
+                        both = torch.stack([psnr_from_sums(sq, n), ss / n]).cpu()      # the group's one synchronisation
+                        try:
+                            self._val_ctx.poll()                # the render's fence (long complete): did its pairs fit?
+                            break
+                        except ManusHipError:                   # no: the capacity was enlarged, render the group again
+                            if attempt == 3:
+                                raise
+                    dt = e0.elapsed_time(e1) * 1e-3
+                    render_time += dt
+                    psnrs += both[0].tolist()
+                    ssims += both[1].tolist()
+                    images.append(trip)
+                    if validator is not None:
+                        host = trip.cpu().numpy()
+                        for j in range(len(part)):
+                            validator.add(float(both[0, j]), float(both[1, j]), dt / len(part), host[j])
+        finally:
+            self._rz._CONTEXTS[idx] = train_ctx
+            c._cache, c._const_stamp = saved_cache, saved_stamp
+        import numpy as np
+        return dict(psnr=psnrs, ssim=ssims, psnr_mean=float(np.mean(psnrs)) if psnrs else float("nan"),
+                    ssim_mean=float(np.mean(ssims)) if ssims else float("nan"), render_time=render_time,
+                    images=torch.cat(images) if images else None)
+
     def train_step(self, views=None):
         """One optimisation step; returns the step's output dict (loss, statistics) plus "changed".
         views: optional list of per-view dicts for the pruning tests (default: `compute.prune_views`).

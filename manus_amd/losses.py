@@ -137,3 +137,49 @@ def isotropic_reg(log_scale, condition_number=0.4):
     """mean((min_scale / (max_scale + 1e-8) - condition_number)**2) of base.py:349-356, taking the log-scales
     (`model._scaling`; the reference reads `model.get_scaling = exp(_scaling)`)."""
     return _IsotropicReg.apply(log_scale, condition_number)
+
+
+def _hwc_batch(img, what):
+    """(H,W,3) or (B,H,W,3) -> (B,3,H,W) contiguous fp32."""
+    if img.dim() == 3:
+        img = img[None]
+    if img.dim() != 4 or img.shape[-1] != 3:
+        raise ManusHipError("psnr: %s must be (H,W,3) or (B,H,W,3) like the reference's render / gt" % what)
+    return img.detach().float().permute(0, 3, 1, 2).contiguous()
+
+
+def psnr(inputs, targets, valid_mask=None, reduction="mean"):
+    """psnr(inputs, targets, valid_mask, reduction) of loss_utils.py:100-108 on the reference's HWC images, over
+    `ops.eval_views` (forward only: the result carries no autograd graph -- the reference calls it in validation_step).
+
+        value = (inputs - targets) ** 2;  value = value[valid_mask];  -10 * log10(mean(value))
+
+    valid_mask: a per-pixel BOOLEAN selection, (H,W) / (H,W,1) (with the images' leading batch dimension if they have
+    one): the mean runs over the selected elements only, i.e. the squared error of the selected pixels divided by three
+    times their number (both sums come from the kernel).  No pixel selected gives NaN, like the mean of an empty tensor.
+    reduction="none" reduces per leading index (one value per image of a batch; a single (H,W,3) image gives a
+    one-element tensor)."""
+    if reduction not in ("mean", "none"):
+        raise ManusHipError("psnr: reduction must be 'mean' or 'none'")
+    x, y = _hwc_batch(inputs, "inputs"), _hwc_batch(targets, "targets")
+    if x.shape != y.shape:
+        raise ManusHipError("psnr: inputs and targets differ in shape")
+    B, _, H, W = x.shape
+    if valid_mask is None:
+        sq = ops.eval_views(x, y)[0]
+        cnt = torch.full_like(sq, float(3 * H * W))
+    else:
+        if valid_mask.dtype != torch.bool:
+            raise ManusHipError("psnr: valid_mask must be a boolean selection (the reference indexes with it)")
+        m = valid_mask
+        if m.dim() and m.shape[-1] == 1 and m.dim() == inputs.dim():
+            m = m[..., 0]
+        m = m.reshape(B, H, W) if m.numel() == B * H * W else None
+        if m is None:
+            raise ManusHipError("psnr: valid_mask must select pixels: (H,W) or (H,W,1), batched like the images")
+        m = m.float().contiguous()
+        sq = ops.eval_views(x, y, m)[0]                                                    # sum over the selected pixels (m is 0 / 1)
+        cnt = ops.eval_views(torch.ones_like(x), torch.zeros_like(x), m)[0]                # 3 * selected pixels, exact below 2^24 per image
+    if reduction == "mean":
+        return -10 * torch.log10(sq.sum() / cnt.sum())
+    return -10 * torch.log10(sq / cnt)

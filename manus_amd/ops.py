@@ -8,6 +8,7 @@ Each op mirrors one block of MANUS Python code (reference tree brown-ivl/manus):
     sh_colors      calculate_colors_from_sh / eval_sh    src/utils/gaussian_utils.py:431-449
     project_points project_points                        src/utils/transforms.py:304-311
     distCUDA2      simple_knn._C.distCUDA2               src/models/gaussian.py:110
+    eval_views, eval_triptych   validation_step's metrics / image   src/modules/base.py:112-154
 
 All of them require GPU tensors; there is no CPU or PyTorch fallback.
 """
@@ -265,3 +266,70 @@ def isotropic_reg_grad(log_scale, condition_number=0.4, weight=1.0, grad_out=Non
     check(lib().mgr_isotropic_reg(N, ptr(ls), float(condition_number), float(weight), ptr(g), 1 if acc else 0, ptr(loss),
                                   ptr(ws), nbytes, stream()), "mgr_isotropic_reg")
     return loss, g
+
+
+def _eval_images(name, pred, target):
+    for t in (pred, target):
+        if not t.is_cuda:
+            raise ManusHipError("%s needs GPU tensors (got %s); there is no CPU fallback" % (name, t.device))
+    pred, target = f32c(pred), f32c(target)
+    if pred.dim() == 3:
+        pred, target = pred[None], target[None]
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape[1] != 3:
+        raise ManusHipError("%s: pred and target must both be (V,3,H,W)" % name)
+    return pred, target
+
+
+def eval_views(pred, target, mask=None, flags=False):
+    """Validation metrics of V views in one launch chain (`mgr_eval_views`; base.py:138-147, loss_utils.py:100-108),
+    forward only.  pred, target (V,3,H,W); mask (V,H,W), possibly fractional, None = ones.
+
+    Returns (sq_sum, ssim_sum, gt_max), each (V,) fp32 on the device: sq_sum[v] = sum (pred*mask - target*mask)^2 over the
+    3*H*W elements (psnr = -10 log10(sq_sum / (3*H*W))), ssim_sum[v] = sum of the reference's HWC SSIM map of the two
+    masked images (ssim = ssim_sum / (3*H*W)), gt_max[v] = max of the unmasked target (for `eval_triptych`).  A view whose
+    inputs hold a NaN or Inf reports NaN for both sums, the other views are not affected; flags=True appends the (V,)
+    int32 flags of those views.  Deterministic: two calls give the same bits."""
+    pred, target = _eval_images("eval_views", pred, target)
+    V, _, H, W = pred.shape
+    if mask is not None:
+        if not mask.is_cuda:
+            raise ManusHipError("eval_views needs GPU tensors (got %s); there is no CPU fallback" % mask.device)
+        mask = f32c(mask)
+        if mask.dim() == 2:
+            mask = mask[None]
+        if tuple(mask.shape) != (V, H, W):
+            raise ManusHipError("eval_views: mask must be (V,H,W)")
+    dev = pred.device
+    out = torch.empty((3, V), dtype=torch.float32, device=dev)
+    fl = torch.empty(V, dtype=torch.int32, device=dev)
+    nbytes = int(lib().mgr_eval_workspace_bytes(V, H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib().mgr_eval_views(V, H, W, ptr(pred), ptr(target), ptr(mask), out[0].data_ptr(), out[1].data_ptr(),
+                               out[2].data_ptr(), fl.data_ptr(), ptr(ws), nbytes, stream()), "mgr_eval_views")
+    return (out[0], out[1], out[2], fl) if flags else (out[0], out[1], out[2])
+
+
+_DIFF_TABLES = {}     # device -> the 256x256 difference table (validation.diff_table) on that device
+
+
+def eval_triptych(pred, target, gt_max):
+    """render | ground truth | difference of V views as (V,3H,W,3) uint8 (`mgr_eval_triptych`; base.py:116-128): the
+    three HWC panels stacked along the rows.  gt_max (V,): the third output of `eval_views` (dump_image scales the
+    ground truth by 255 when its maximum is <= 1).  A NaN pixel is written as 0 -- this package's definition, numpy
+    leaves that cast undefined."""
+    pred, target = _eval_images("eval_triptych", pred, target)
+    if not gt_max.is_cuda:
+        raise ManusHipError("eval_triptych needs GPU tensors (got %s); there is no CPU fallback" % gt_max.device)
+    V, _, H, W = pred.shape
+    gt_max = f32c(gt_max).reshape(-1)
+    if gt_max.numel() != V:
+        raise ManusHipError("eval_triptych: gt_max must hold one value per view")
+    dev = pred.device
+    tab = _DIFF_TABLES.get(dev)
+    if tab is None:
+        from .validation import diff_table
+        tab = _DIFF_TABLES[dev] = torch.from_numpy(diff_table()).to(dev).contiguous()
+    out = torch.empty((V, 3 * H, W, 3), dtype=torch.uint8, device=dev)
+    check(lib().mgr_eval_triptych(V, H, W, ptr(pred), ptr(target), ptr(gt_max), ptr(tab), ptr(out), stream()),
+          "mgr_eval_triptych")
+    return out
