@@ -657,6 +657,57 @@ int mgr_eval_triptych(int V, int H, int W, const float* pred, const float* targe
                       const uint8_t* diff_table, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Contact evaluation (contact_eval.hip): the IoU / F1 scripts scripts/process/get_iou_ours.py and get_iou.py, for V
+ * evaluation cameras of one H x W per launch chain.  All images are uint8 and row-major; everything runs on `stream`
+ * without a host read-back; there are no float atomics, two calls on the same inputs give the same bytes, and a view's
+ * outputs depend on that view's images only.  H, W <= 16384, V <= 65535.  One workspace of
+ * mgr_ceval_workspace_bytes(V,H,W) serves labels -> fill -> counts.
+ *
+ * mgr_ceval_masks (get_iou_ours.py:313-322): frame (V,H,2W,3) = the 'acc_gt_eval' render, left half the skin-weight
+ *   colours, right half the grey contact map (the reference hard-codes the split at column 1080; here it is W), as
+ *   uint8, or (frame_is_f32) as the fp32 render, converted like test_step does (src/modules/base.py:245-246:
+ *   uint8(clamp(x,0,1) * 255) with the product in fp32, truncating; NaN -> 0) and ALSO written to frame_u8 (V,H,2W,3)
+ *   (required then, unused otherwise).  gt_seg (V,H,W,3), gt_rgba (V,H,W,4).  One byte (0/1) per pixel:
+ *     pred = every channel of the right half in [128,255]    (cv2.inRange(our_mask, (128,)*3, (255,)*3))
+ *     gt   = the same test on gt_seg
+ *     hand = alpha of gt_rgba > 128.
+ * mgr_ceval_labels (get_skin_mask, :74-138): frame (V,H,row_px,3) whose first W pixels of a row are the skin-weight
+ *   render in RGB (row_px = 2W: the whole frame; W: the half on its own).  labels (V,H,W): 0 when no palette mask holds
+ *   the pixel, else 1 + the index of the FIRST of the 16 palette masks that does (np.argmax over [background, m1..m16]);
+ *   mask i = "every channel within +-10 of colour i, inclusive" (cv2.inRange), eroded and then dilated with the 3x3
+ *   MORPH_ELLIPSE element = the 4-neighbour cross, OpenCV's default borders (outside the image: set for the erosion,
+ *   unset for the dilation).  hand (V,H,W) or NULL (= all ones): labels outside it are 0 (all_masks * gt_mask).  The
+ *   kernel also leaves in the workspace what mgr_ceval_fill reads: per 16x16 tile the bitmap of its labelled pixels,
+ *   the tile bounding box of the view's labelled pixels and the list of RESIDUAL pixels (hand != 0, label 0).
+ * mgr_ceval_fill (:136-144 and get_contact_dist, :44-71): in place, every residual pixel takes the label of its nearest
+ *   labelled pixel: Euclidean distance on integer (row, col), among equals the one that comes first in row-major order
+ *   (the reference scans np.argwhere order with a strict '<' on fp32 roots; below 2^11 distinct integer squared
+ *   distances have distinct fp32 roots) -- computed exactly as min over (d^2, row * W + col) by a ring search over the
+ *   tile bitmaps, never as the N_res x N_skin scan.  `workspace` is the one mgr_ceval_labels just filled for the SAME
+ *   labels.  flags (V) int32: 1 for a view with residual pixels and no labelled pixel at all (the reference raises an
+ *   IndexError there; such a view's labels are left as they are), 0 otherwise.
+ * mgr_ceval_counts (cal_iou and the f1_score inputs of evaluate_metric / calculate_per_bone_iou, :162-232): counts
+ *   (V,17,3) int64 = [I, A, B] = [|gt & pred|, |gt|, |pred|] restricted to labels == i for rows i = 0..15 (0 is "no
+ *   label"; label 16 is never scored -- the reference's range(16)) and unrestricted in row 16.  Per-workgroup records,
+ *   folded per view by a second kernel.
+ * mgr_ceval_collage (blend_masks / combine_images, :269-291): out (V,H,(1+M)W,3) = [photo on white | photo blended with
+ *   mask 0 in (0,128,0) | ... mask M-1]; masks (M,V,H,W) bytes (non-zero = set), 0 <= M <= 16.  Every output byte is
+ *   table[((photo_byte * 3 + kind) * 2 + alpha_bit) * 3 + channel], kind 0 = the plain panel, 1 / 2 = blended with a
+ *   clear / set mask pixel; the caller builds the 256x3x2x3 table with the reference's float64 numpy expression
+ *   (manus_amd.contact_eval.collage_table).
+ * ------------------------------------------------------------------------ */
+size_t mgr_ceval_workspace_bytes(int V, int H, int W);
+int mgr_ceval_masks(int V, int H, int W, const void* frame, int frame_is_f32, const uint8_t* gt_seg, const uint8_t* gt_rgba,
+                    uint8_t* frame_u8, uint8_t* pred, uint8_t* gt, uint8_t* hand, void* stream);
+int mgr_ceval_labels(int V, int H, int W, const uint8_t* frame, int row_px, const uint8_t* hand, uint8_t* labels,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int mgr_ceval_fill(int V, int H, int W, uint8_t* labels, int32_t* flags, void* workspace, size_t workspace_bytes, void* stream);
+int mgr_ceval_counts(int V, int H, int W, const uint8_t* pred, const uint8_t* gt, const uint8_t* labels, int64_t* counts,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int mgr_ceval_collage(int V, int H, int W, int M, const uint8_t* gt_rgba, const uint8_t* masks, const uint8_t* table,
+                      uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Skin-weight initialisation from the MANO rest mesh (model-initialisation side of the
  * dataloader): the device half of init_mano_weights (src/utils/train_utils.py:48-89) as called by
  * Dataset.build_voxel_grid / Dataset.sample_gaussians_on_bones (src/datasets/brics_dynamic.py:69-144).

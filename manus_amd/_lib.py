@@ -100,6 +100,12 @@ SIGNATURES = {
     "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_eval_triptych": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mgr_ceval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_ceval_masks": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mgr_ceval_labels": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_ceval_fill": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_ceval_counts": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_ceval_collage": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_adam_step": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, c_vp]),
     "mgr_reset_opacity": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -213,6 +213,22 @@ class CompositeRenderer:
         self.n_frames += 1
         return self.acc
 
+    def save_accumulated(self, path):
+        """The running sum of a 'gt_eval' / 'results' pass as the reference's `acc_contacts.npy` (on_test_epoch_end,
+        composite.py:262-266): the hand from the first pass of scripts/train/eval.sh to the second."""
+        import numpy as np
+        if self.acc is None:
+            raise ValueError("save_accumulated: no frame has been rendered with 'gt_eval' or 'results' yet")
+        with open(path, "wb") as f:      # (np.save on a name would append '.npy' to one without it)
+            np.save(f, self.acc.detach().cpu().numpy())
+
+    def load_accumulated(self, path):
+        """`acc_contacts` for 'acc_gt_eval' from such a file (on_test_epoch_start, composite.py:224-226), on the hand model's
+        device."""
+        import numpy as np
+        self.acc_contacts = torch.from_numpy(np.load(path)).to(self.hand_model._xyz.device)
+        return self.acc_contacts
+
     def _rgb(self, pred, batch):
         from .render import render_gaussians
         return render_gaussians(pred.posed_xyz, pred.posed_cov, pred.cano_xyz, pred.cano_features, pred.cano_opacity,
