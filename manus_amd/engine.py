@@ -16,16 +16,28 @@ which the backward kernels write in place (no packing copies).  max_radii2D need
 associative and idempotent, so every rank keeps the running maximum over ITS views and the ranks are only
 combined (one MAX all-reduce) right before the statistic is consumed, i.e. at a densification step.
 """
+import ctypes
+import functools
 import os
 
 import torch
 import torch.distributed as dist
+
+from . import fused as fused_mod, ops, rasterizer
+from ._lib import ManusHipError, check, lib, ptr, stream
 
 # packed leaf-gradient layout: 59 floats per Gaussian (SURVEY.md section 5)
 GRAD_LAYOUT = (("_xyz", 3), ("_features_dc", 3), ("_features_rest", 45), ("_opacity", 1),
                ("_scaling", 3), ("_rotation", 4))
 GRAD_WIDTH = sum(w for _, w in GRAD_LAYOUT)
 FLAT_TAIL = 2            # loss, overflow flag
+
+# positions in the array mgr_raster_layout fills (byte offsets of the regions of a rasterizer workspace, in the order of
+# MgrLayout) of the regions the Python side and tools/instr read
+LAYOUT_TILE_START, LAYOUT_TILE_DONE = 7, 9
+LAYOUT_FINAL_T, LAYOUT_N_CONTRIB, LAYOUT_INST_TAG = 16, 17, 22
+LAYOUT_TILE_ZCUT, LAYOUT_TILE_ZUSED, LAYOUT_TILE_QEND = 26, 27, 28
+LAYOUT_TILE_REP, LAYOUT_REP_UNIT, LAYOUT_REP_CNT, LAYOUT_TILE_ZWIN = 29, 30, 31, 32
 
 
 def flat_size(N):
@@ -259,8 +271,6 @@ def _compact_all_reduce(self, flat, fv, active=None):
         raise ValueError("compact all-reduce carries the visibility count in one byte: at most 255 views per step (use the dense mode)")
     live = self.world > 1 or self.force
     if flat.is_cuda:
-        import ctypes
-        from ._lib import check, lib, ptr, stream
         L = lib()
         dev = flat.device
         nseg = len(_XCH_SEGS)
@@ -331,6 +341,173 @@ def _compact_all_reduce(self, flat, fv, active=None):
 ViewShardedStep._compact_all_reduce = _compact_all_reduce
 
 
+class _DepthCut:
+    """The depth-cut hints of one `HipViewCompute` and the policy of using them (fused step only).
+
+    Every forward leaves, per tile whose pixels all saturated, the depth in front of which they had stopped (+ a margin);
+    the next forward of the SAME views leaves the instances behind it out of that tile's list (mgr_views_forward, debug bit 8)
+    -- the binning kernels then handle a fraction of the pairs, the image and the gradients stay bit for bit those of the full
+    lists (a cut list that runs out under an unsaturated pixel is flagged like a pair-capacity overflow and the step is run
+    again without the cut).  The hints live in the workspace; when the view set changes they are parked per view set
+    (`max_sets` sets of 4 bytes per tile and view, at most MAX_HINT_BYTES) and brought back when it returns -- a training
+    run revisits its (frame, camera) pairs every epoch.  OFF by default (`HipViewCompute.depth_cut`): it pays only while the
+    model stands still between two forwards of its views (fwd+bwd loops without an optimizer, evaluation sweeps); under a
+    moving model it is a wash.
+
+    A flagged forward costs a whole step, and with the optimizer in the loop no margin prevents them all: a pixel whose
+    transmittance ends just under the threshold needs many more entries after the slightest change (measured on the bench
+    scene with Adam at the reference's learning rates: a flagged forward every ~30 steps at 4x the margins).  So the cut backs
+    off: a flagged forward doubles the margins (every clean one takes 2 % off again, 1x .. 32x the library's defaults),
+    restricts the hints to interior tiles, and suspends the cut for `backoff` forwards -- 4, then 8, ... up to 512; 32 clean
+    forwards in a row halve it again.  A model that stands still between two forwards of its views (fwd+bwd benchmarks,
+    evaluation sweeps, several losses on one state) keeps the cut on; one that moves every step ends up trying it every few
+    hundred steps, at a cost below the run-to-run noise.  Hints that have seen more than `max_age` parameter updates are not
+    used at all (a dataset of thousands of views revisits each once per epoch: the forward then simply runs uncut and leaves
+    fresh hints).
+
+    With the on-device repair (round 6, `HipViewCompute.cut_repair`) tiles whose cut list runs out are completed on the device
+    (debug bit 2048) -- no flagged forward, no re-run, no back-off: a flagged forward is then a capacity matter, rare, and
+    the margins need neither widening nor the interior-only rule (the library's per-tile countdown keeps the repeat offenders
+    out).  `margin` scales the library's default margins there, `penalty` = forwards a tile that ran out goes without a hint.
+
+    `decide` is the policy: host arithmetic on this object's counters, no tensor and no library call.  `flag` is the workspace
+    part: it names the views in the workspace, sets the library's margins and parks / restores the hint tables."""
+
+    MAX_HINT_BYTES = 64 << 20
+
+    def __init__(self, max_hints=1024):
+        self.gen = 0              # model generation (`new_generation`)
+        self.clock = 0            # parameter updates so far
+        self.born = {}            # hint key -> clock at the last forward of those views
+        self.max_age = 16
+        self.scale = 1.0          # margin scale of the legacy mode
+        self.seen = 0             # the context's count of flagged forwards at the last launch
+        self.pause = 0            # forwards still to go without the cut
+        self.backoff = 4          # the pause the next flagged forward starts
+        self.clean = 0            # forwards with the cut in a row
+        self.store = {}           # hint key -> parked hint tables
+        self.max_sets = int(max_hints)
+        self.bit = 0              # debug bits of the step's current forward
+
+    def new_generation(self):
+        self.gen += 1
+        self.store.clear()
+        self.born.clear()
+
+    def decide(self, key, cut_retries, cut_block, repair, margin=1.0):
+        """(debug bits 0, 8 or 8 | 2048; arguments of mgr_raster_set_cut_margin) for a forward of the views `key`.  cut_retries:
+        the context's count of flagged forwards; cut_block: the previous forward on the workspace was flagged (this one
+        rebuilds the hints from full lists)."""
+        if cut_retries != self.seen:          # a forward of ours was flagged since the last launch
+            self.seen, self.scale = cut_retries, min(32.0, self.scale * 2.0)
+            self.pause, self.backoff, self.clean = self.backoff, min(512, self.backoff * 2), 0
+        else:
+            self.scale = max(1.0, self.scale * 0.98)
+        k = self.scale
+        if repair:
+            margins = (0.125 * margin, int(64 * margin), 0.0625 * margin, 2.0e-4 * margin, 0)
+        else:
+            margins = (min(4.0, 0.125 * k), int(64 * k), min(4.0, 0.0625 * k), 2.0e-4 * k, 1 if k > 1.0 else 0)
+        born, self.born[key] = self.born.get(key), self.clock
+        if len(self.born) > 4 * self.max_sets:     # view sets not seen for max_age updates have no usable hints
+            self.born = {k_: b_ for k_, b_ in self.born.items() if self.clock - b_ <= self.max_age}
+        if cut_block or born is None or self.clock - born > self.max_age:
+            return 0, margins
+        if self.pause > 0:     # backing off after a flagged forward (repair: one of its capacities was exceeded -- a few forwards
+            self.pause = (min(self.pause, 4) if repair else self.pause) - 1       # on full lists, no escalation)
+            return 0, margins
+        if repair:
+            return 8 | 2048, margins
+        self.clean += 1
+        if self.clean >= 32:
+            self.clean, self.backoff = 0, max(4, self.backoff // 2)
+        return 8, margins
+
+    def flag(self, ws, view_ids, cut_retries, hint_offsets, hint_bytes, repair, margin, penalty):
+        """Debug bits of mgr_views_forward for this forward on `ws`: bit 8 when the workspace holds the hints of exactly these
+        views (left by the previous forward, or parked earlier and brought back here) and `decide` lets them be used.
+        hint_offsets, hint_bytes: the hints (tile_zcut) and the repair's depth windows that belong to them (tile_zwin) in `ws.buf`."""
+        key = (id(self), self.gen, tuple(view_ids))
+        prev, ws.hint_key = ws.prev_hint_key, key
+        cut_block, ws.cut_block = ws.cut_block, False
+        bits, margins = self.decide(key, cut_retries, cut_block, repair, margin)
+        lib().mgr_raster_set_cut_margin(*margins)
+        if repair:
+            lib().mgr_raster_set_cut_penalty(int(penalty))
+        if prev != key:
+            regions = [ws.buf[o: o + hint_bytes] for o in hint_offsets]
+            nbytes = sum(r.numel() for r in regions)
+            if prev is not None and prev[:2] == key[:2]:      # park the hints of the views rendered last
+                max_sets = max(1, min(self.max_sets, self.MAX_HINT_BYTES // max(1, nbytes)))
+                while len(self.store) >= max_sets:
+                    self.store.pop(next(iter(self.store)))
+                self.store[prev] = torch.cat(regions)
+            saved = self.store.pop(key, None)
+            if saved is not None and saved.numel() == nbytes:
+                for r, part in zip(regions, saved.split(hint_bytes)):
+                    r.copy_(part)
+            else:
+                for r in regions:
+                    r.zero_()                                       # no hints for these views yet
+        return bits
+
+
+class _KeptBuffers:
+    """The gradient, statistics and image tensors a `HipViewCompute` with persistent_grads keeps from step to step (fused
+    step, no grad_arena): the leaf gradients, the skin-weight gradient, the statistics and the image are written into these
+    buffers (see HipViewCompute's docstring).  The backward then zeroes only the rows that were written by the previous step
+    and get nothing now, instead of every row of every gradient every step (mgr_views_backward, debug bit 512: 97 MB of stores
+    per bench step), and the forward writes the background only into empty tiles that held something else
+    (mgr_views_forward, bit 1024).  Both need the workspace's row / tile state to describe THESE buffers: `grad_ws` and
+    `image_ws` name the workspace whose last backward / forward wrote them, None when nobody's does."""
+
+    def __init__(self):
+        self.key = None           # (N, n_art, device) the tensors were made for
+        self.device = None
+        self.tensors = {}         # name -> tensor
+        self.versions = {}        # name -> torch version counter as of the end of the last step
+        self.grad_ws = None
+        self.image_ws = None
+
+    def begin(self, N, n_art, device):
+        """Start of a step: new tensors when the model or the device changed; full fills when somebody wrote into them."""
+        if self.key != (N, n_art, str(device)):
+            self.key, self.device, self.tensors, self.versions = (N, n_art, str(device)), device, {}, {}
+            self.invalidate()
+        elif self.touched():
+            self.invalidate()
+
+    def get(self, shape, name, zeroed=True):
+        t = self.tensors.get(name)
+        if t is None:
+            t = self.tensors[name] = (torch.zeros if zeroed else torch.empty)(shape, dtype=torch.float32, device=self.device)
+        return t
+
+    def touched(self):
+        """Somebody wrote into a buffer since it was handed out (torch bumps a tensor's version counter on every in-place op,
+        also through views): it no longer holds what the row / tile bookkeeping says."""
+        return any(self.tensors[n]._version != ver for n, ver in self.versions.items() if n in self.tensors)
+
+    def handed_out(self, ws):
+        """End of a backward on `ws`: its row state is ours, and the tensors go to the caller as they are now."""
+        self.grad_ws = ws
+        self.versions = {n: t._version for n, t in self.tensors.items()}
+
+    def invalidate(self):
+        self.grad_ws = self.image_ws = None
+
+
+def _arena_tensor(arena, device, shape, name):
+    """The arena's buffer of that name viewed as `shape` if it fits, else a fresh tensor."""
+    t = arena.get(name)
+    n = 1
+    for d in shape:
+        n *= d
+    if t is not None and t.numel() == n and t.is_contiguous() and t.dtype == torch.float32 and t.device == device:
+        return t.view(shape)
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
 class HipViewCompute:
     """compute_fn over the HIP kernels: skin weights once, LBS per pose, SH colour and rasterisation per view,
     image loss (rgb_loss / ssim_loss of src/modules/base.py:323-365), backward to the six leaf tensors.  All local
@@ -348,99 +525,96 @@ class HipViewCompute:
     into them is allowed: every step compares the tensors' torch version counters with those it recorded when it handed
     them out, and a buffer touched in between (any in-place torch op on it or on a view of it) is filled in full again
     instead of row- / tile-selectively (tests/test_gpu_fused.py::test_kept_buffers_survive_a_caller_writing_into_them).
-    Writes torch cannot see (raw pointers, `.data`) are the caller's to avoid."""
+    Writes torch cannot see (raw pointers, `.data`) are the caller's to avoid.
 
-    # bytes of parked depth-cut hint tables kept per compute object (4 bytes per tile and view each)
-    MAX_CUT_HINT_BYTES = 64 << 20
+    The image loss of the fused step ("l1+ssim") has four routes, chosen per step from plain attributes (settable after
+    construction; the MANUS_* environment switches set their defaults for A/B runs):
+      sparse_loss   the forward's tile-list offsets go to the image loss, which then settles the spans under empty tiles from
+                    the target alone (exact: the rasterizer writes the background colour there) and leaves their gradient
+                    unwritten (the backward never reads it).  False: the loss reads both images everywhere.
+      target_map    the span list is derived from column masks "target differs from the background here", which the list
+                    kernel otherwise recomputes from the full target images every step (0.2 GB at 8 views of 1080p).  A
+                    target is a constant of its view: the masks are computed once per view (1 bit per pixel column and row
+                    pair, 130 KB per 1080p view) and the list is built from them, in-stream, in a few microseconds -- no
+                    second stream, no forward split at the blend.  Same list, same loss and gradients.  MANUS_TARGET_MAP=0.
+      attach_list   that mapped list is built by the forward's last kernel (mgr_views_forward_attach_loss_list) instead of a
+                    launch of its own.  MANUS_LOSS_LIST_ATTACH=0.
+      overlap_loss  without target maps: the span list is built on a second stream while the forward blend runs (forward split
+                    at the blend, debug bits 2 / 4).  MANUS_OVERLAP_LOSS=0."""
+
     # per-view target maps kept (130 KB per 1080p view)
     MAX_TARGET_MAPS = 4096
 
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
                  persistent_grads=True):
-        from . import fused as fused_mod, ops, rasterizer
-        # persistent_grads (fused step, no grad_arena): the leaf gradients, the skin-weight gradient, the statistics and the
-        # image are written into buffers this object keeps (see the class docstring).  The backward then zeroes only the
-        # rows that were written by the previous step and get nothing now, instead of every row of every gradient every
-        # step (mgr_views_backward, debug bit 512: 97 MB of stores per bench step), and the forward writes the background
-        # only into empty tiles that held something else (mgr_views_forward, bit 1024).  `_pg_ver`: the torch version
-        # counter of every kept tensor as of the end of the last step -- a mismatch means somebody wrote into it.
-        self.persistent_grads, self._pg, self._pg_ws, self._pimg_ws, self._pg_ver = bool(persistent_grads), None, None, None, {}
-        # depth_cut (fused step only): every forward leaves, per tile whose pixels all saturated, the depth in front of
-        # which they had stopped (+ a margin); the next forward of the SAME views leaves the instances behind it out of
-        # that tile's list -- the binning kernels then handle a fraction of the pairs, the image and the gradients stay
-        # bit for bit those of the full lists (a cut list that runs out under an unsaturated pixel is flagged like a
-        # pair-capacity overflow and the step is run again without the cut).  The hints live in the workspace; when the
-        # view set changes they are parked per view set (max_cut_hints sets of 4 bytes per tile and view) and brought
-        # back when it returns -- a training run revisits its (frame, camera) pairs every epoch.  OFF by default: it pays only
-        # while the model stands still between two forwards of its views (fwd+bwd loops without an optimizer, evaluation
-        # sweeps); under a moving model it is a wash (DESIGN 5).  MANUS_DEPTH_CUT=0 in the environment forces it off.
-        self.depth_cut = bool(depth_cut) and os.environ.get("MANUS_DEPTH_CUT", "1") != "0"
-        self._cut_store, self._cut_max, self._cut_gen, self._cut_bit = {}, int(max_cut_hints), 0, 0
-        # A flagged forward costs a whole step, and with the optimizer in the loop no margin prevents them all: a pixel whose
-        # transmittance ends just under the threshold needs many more entries after the slightest change (measured on the
-        # bench scene with Adam at the reference's learning rates: a flagged forward every ~30 steps at 4x the margins).  So
-        # the cut backs off: a flagged forward doubles the margins (every clean one takes 2 % off again, 1x .. 32x the
-        # library's defaults), restricts the hints to interior tiles, and suspends the cut for `backoff` forwards -- 4, then
-        # 8, ... up to 512; 32 clean forwards in a row halve it again.  A model that stands still between two forwards of its
-        # views (fwd+bwd benchmarks, evaluation sweeps, several losses on one state) keeps the cut on; one that moves every
-        # step ends up trying it every few hundred steps, at a cost below the run-to-run noise.  Hints that have seen more
-        # than `cut_max_age` parameter updates are not used at all (a dataset of thousands of views revisits each once per
-        # epoch: the forward then simply runs uncut and leaves fresh hints).
-        self._cut_scale, self._cut_seen, self.cut_max_age, self._cut_clock, self._cut_born = 1.0, 0, 16, 0, {}
-        self._cut_pause, self._cut_backoff, self._cut_clean = 0, 4, 0
-        # cut_repair (round 6): tiles whose cut list runs out are repaired on the device (mgr_views_forward, debug bit 2048) --
-        # no flagged forward, no re-run, no back-off; cut_margin scales the library's default margins, cut_penalty = forwards
-        # a tile that ran out goes without a hint.  MANUS_CUT_REPAIR=0 in the environment: the round-5 behaviour (A/B).
-        self.cut_repair = os.environ.get("MANUS_CUT_REPAIR", "1") != "0"
-        self.cut_margin, self.cut_penalty = float(os.environ.get("MANUS_CUT_MARGIN", "1.0")), int(os.environ.get("MANUS_CUT_PENALTY", "16"))
-        # sparse_loss: the fused step hands the forward's tile-list offsets to the image loss, which then settles the
-        # spans under empty tiles from the target alone (exact: the rasterizer writes the background colour there) and
-        # leaves their gradient unwritten (the backward never reads it).  False: the loss reads both images everywhere.
-        self.sparse_loss, self._ts_off = bool(sparse_loss), {}
-        # overlap_loss: that span list is built on a second stream while the forward blend runs (MANUS_OVERLAP_LOSS=0
-        # in the environment switches it off for A/B runs)
-        self.overlap_loss, self._side = bool(overlap_loss) and os.environ.get("MANUS_OVERLAP_LOSS", "1") != "0", None
-        # target_map: the span list is derived from column masks "target differs from the background here", which the list
-        # kernel otherwise recomputes from the full target images every step (0.2 GB at 8 views of 1080p).  A target is a
-        # constant of its view: the masks are computed once per view (1 bit per pixel column and row pair, 130 KB per
-        # 1080p view) and the list is built from them, in-stream, in a few microseconds -- no second stream, no forward
-        # split at the blend.  Same list, same loss and gradients.  MANUS_TARGET_MAP=0 switches it off for A/B runs.
-        self.target_map, self._tmaps, self._lws = os.environ.get("MANUS_TARGET_MAP", "1") != "0", {}, {}
-        # the mapped span list built by the forward's last kernel (mgr_views_forward_attach_loss_list) instead of a launch of its own (A/B: 0)
-        self.attach_list = os.environ.get("MANUS_LOSS_LIST_ATTACH", "1") != "0"
-        # sh_storage "fp16" (BASELINE config 5): the fused kernels read an fp16 copy of _features_rest (96 B instead of
-        # 180 B per Gaussian and view group); arithmetic, gradients and the optimizer's master copy stay fp32.  The copy
-        # is refreshed lazily after the leaves changed (`mark_params_changed`).  The reference has no fp16 mode:
-        # parity is judged with "fp32".
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
-        self.sh_half, self._sh_copy, self._sh_dirty = sh_storage == "fp16", None, True
-        self.ops, self.rz, self.fz, self.fused = ops, rasterizer, fused_mod, fused
-        self.s = scene
-        self._cache, self._const_stamp = {}, None
-        self.targets = targets          # (V_all,3,H,W) on the GPU (a property: replacing it drops what was derived from it)
-        self.cams = cam_table           # (V_all,40)
-        self.loss_weight = loss_weight
-        # "l1": mean|render - gt| (rgb_loss alone); "l1+ssim": w_rgb * rgb_loss + w_ssim * ssim_loss, the
-        # image terms of config/HAND_GAUSSIAN.yaml:22-23 (src/modules/base.py:323-365), one fused kernel
         if loss not in ("l1", "l1+ssim"):
             raise ValueError("loss must be 'l1' or 'l1+ssim'")
-        self.loss, self.w_rgb, self.w_ssim = loss, w_rgb, w_ssim
+        env = os.environ.get
+        self.ops, self.rz, self.fz, self.fused = ops, rasterizer, fused_mod, fused
+        # -- scene and per-view constants
+        self.s = scene
         self.kind = scene["kind"]
+        self._cache = {}                # per-view-set gathers (`_select`)
+        self._const_stamp = None
+        self._tmaps = {}                # per-view target maps (`_target_map`)
+        self.targets = targets          # (V_all,3,H,W) on the GPU (a property: replacing it drops what was derived from it)
+        self.cams = cam_table           # (V_all,40)
+        # -- model
         self.params = {k: v.detach().clone().requires_grad_(True) for k, v in scene["params"].items()}
         N = self.params["_xyz"].shape[0]
         has_grid = scene.get("grid") is not None
         self.n_art = N if (self.kind == "hand" and has_grid) else (int(scene["n_hand"]) if (self.kind == "composite" and has_grid) else 0)
         self.is_hand = self.n_art > 0
         self.device = self.params["_xyz"].device
-        self.grad_arena = None   # set by ViewShardedStep: preallocated gradient outputs (fused path only)
-        # sync_check True: every fused forward reads the pair count back and retries on overflow (like the drop-in
+        self.grid = ops.SkinGrid(scene["grid"], scene["grid"].device) if self.is_hand else None
+        self._w_cache = None            # forward-only skin weights of the current model state (forward_views_fused under no_grad)
+        # -- image loss.  "l1": mean|render - gt| (rgb_loss alone); "l1+ssim": w_rgb * rgb_loss + w_ssim * ssim_loss, the image
+        # terms of config/HAND_GAUSSIAN.yaml:22-23 (src/modules/base.py:323-365), one fused kernel.  Routes: class docstring.
+        self.loss = loss
+        self.loss_weight = loss_weight
+        self.w_rgb = w_rgb
+        self.w_ssim = w_ssim
+        self.sparse_loss = bool(sparse_loss)
+        self.target_map = env("MANUS_TARGET_MAP", "1") != "0"
+        self.attach_list = env("MANUS_LOSS_LIST_ATTACH", "1") != "0"
+        self.overlap_loss = bool(overlap_loss) and env("MANUS_OVERLAP_LOSS", "1") != "0"
+        self._lws = {}                  # (V,H,W) -> kept workspace of the mapped span list
+        self._side = None               # second stream of the overlap route
+        self._ts_off = {}               # (V,N,W,H,capacity) -> mgr_raster_layout offsets (`_layout`)
+        # -- depth cut (`_DepthCut`).  MANUS_DEPTH_CUT=0 in the environment forces it off; MANUS_CUT_REPAIR=0: the round-5
+        # behaviour without the on-device repair (A/B)
+        self.depth_cut = bool(depth_cut) and env("MANUS_DEPTH_CUT", "1") != "0"
+        self.cut_repair = env("MANUS_CUT_REPAIR", "1") != "0"
+        self.cut_margin = float(env("MANUS_CUT_MARGIN", "1.0"))
+        self.cut_penalty = int(env("MANUS_CUT_PENALTY", "16"))
+        self._cut = _DepthCut(max_cut_hints)
+        # -- gradient outputs: kept buffers (`_KeptBuffers`), or the arena a ViewShardedStep sets (preallocated views of its
+        # step buffer; fused path only), or fresh tensors
+        self.persistent_grads = bool(persistent_grads)
+        self._kept = _KeptBuffers()
+        self.grad_arena = None
+        # -- sh_storage "fp16" (BASELINE config 5): the fused kernels read an fp16 copy of _features_rest (96 B instead of
+        # 180 B per Gaussian and view group); arithmetic, gradients and the optimizer's master copy stay fp32.  The copy
+        # is refreshed lazily after the leaves changed (`mark_params_changed`).  The reference has no fp16 mode:
+        # parity is judged with "fp32".
+        self.sh_half = sh_storage == "fp16"
+        self._sh_copy = None
+        self._sh_dirty = True
+        # -- sync_check True: every fused forward reads the pair count back and retries on overflow (like the drop-in
         # operator).  A Trainer sets it False on ITS compute object: no host sync, the forward leaves an overflow fence
         # that Trainer._run_step polls.  (The device-wide policy of rasterizer.set_sync_policy is left alone.)
         self.sync_check = True
-        self._w_cache = None     # forward-only skin weights of the current model state (forward_views_fused under no_grad)
-        self.grid = ops.SkinGrid(scene["grid"], scene["grid"].device) if self.is_hand else None
+
+    @property
+    def _pg_ws(self):      # (bench.py and the tests ask whether the selective fills are in use)
+        return self._kept.grad_ws
+
+    @property
+    def _pimg_ws(self):
+        return self._kept.image_ws
 
     @property
     def targets(self):
@@ -454,8 +628,7 @@ class HipViewCompute:
     def _drop_view_constants(self):
         """Forget everything derived from the per-view constants (targets, background, cameras, poses)."""
         self._cache = {}
-        if hasattr(self, "_tmaps"):
-            self._tmaps.clear()
+        self._tmaps.clear()
         self._const_stamp = None
 
     def _check_view_constants(self):
@@ -478,20 +651,17 @@ class HipViewCompute:
             self.n_art = self.params["_xyz"].shape[0]
         self.grad_arena = None
         self._sh_dirty = True
-        self._cut_gen += 1          # rows were added / removed: the hints of the old model are dropped
-        self._cut_store.clear()
-        self._cut_born.clear()
+        self._cut.new_generation()  # rows were added / removed: the hints of the old model are dropped
 
     def mark_params_changed(self):
         """The leaves were updated in place (optimizer step): derived storage copies are stale."""
         self._sh_dirty = True
-        self._cut_clock += 1
+        self._cut.clock += 1
 
     def _sh_storage(self, f_rest):
         """(pointer source tensor, sh_half flag) for the fused kernels."""
         if not self.sh_half:
             return f_rest, 0
-        from ._lib import check, lib, ptr, stream
         N = f_rest.shape[0]
         if self._sh_copy is None or self._sh_copy.shape[0] != N:
             self._sh_copy, self._sh_dirty = torch.empty((N, 48), dtype=torch.float16, device=f_rest.device), True
@@ -556,7 +726,7 @@ class HipViewCompute:
             # model state -- (generation, parameter-update clock, the leaf's storage and version) -- instead of gathered from
             # the grid again for every batch of views (0.04 ms for 300 k Gaussians: 13 % of a one-view forward).  Training
             # steps always recompute them (their gradient flows back into `_xyz`).
-            key = (self._cut_gen, self._cut_clock, p["_xyz"].data_ptr(), p["_xyz"]._version, na, id(self.grid))
+            key = (self._cut.gen, self._cut.clock, p["_xyz"].data_ptr(), p["_xyz"]._version, na, id(self.grid))
             if self._w_cache is None or self._w_cache[0] != key:
                 self._w_cache = (key, ops.skin_weights(p["_xyz"][:na], self.grid, s["grid_center"], s["grid_scale"]))
             w = self._w_cache[1]
@@ -566,25 +736,28 @@ class HipViewCompute:
                                     p["_features_rest"], w, sel["T"], sel["cams"], s["bg"], s["width"], s["height"],
                                     stats=stats, grad2d_scale=grad2d_scale, grad_arena=self.grad_arena)
 
+    def _loss_scales(self, img, scale):
+        """(k, const) of the image-loss kernels for scale * sum over the views of the per-view loss of `img` (V,3,H,W):
+        the factor on the per-pixel terms, and the "1 -" of 1 - ssim, once per view."""
+        k = self.loss_weight * scale / img[0].numel()
+        return k, self.w_ssim * self.loss_weight * scale * img.shape[0]
+
     def _image_loss(self, img, tgt, scale, tiles=None):
         """(loss value, dL/dimg) of scale * sum over the views of the per-view image loss.  tiles = (bg, device address
         of the tile-list offsets of the forward that rendered img): spans under empty tiles are not read (ops.image_loss_grad)."""
-        per_view = img[0].numel()
-        k = self.loss_weight * scale / per_view
+        k, const = self._loss_scales(img, scale)
         if self.loss == "l1":
             loss_sum, g = self.ops.l1_loss_grad(img, tgt, scale=k)
             return loss_sum[0] * k, g
-        const = self.w_ssim * self.loss_weight * scale * img.shape[0]   # the "1 -" of 1 - ssim, once per view
         bg, ts = tiles if (tiles is not None and self.sparse_loss) else (None, None)
         sums, g = self.ops.image_loss_grad(img, tgt, self.w_rgb, self.w_ssim, k, const, bg=bg, tile_start_ptr=ts)
         return sums[2], g
 
     def _layout(self, ws, V, N, W, H):
+        """Byte offsets of the regions of `ws.buf` (indexed by the LAYOUT_* constants)."""
         key = (V, N, W, H, ws.cap)
         off = self._ts_off.get(key)
         if off is None:
-            import ctypes
-            from ._lib import lib
             arr = (ctypes.c_size_t * 40)()
             lib().mgr_raster_layout(V, N, W, H, ws.cap, arr, 40)
             off = self._ts_off[key] = [int(x) for x in arr]
@@ -594,7 +767,6 @@ class HipViewCompute:
         """(V, rows / 2, ceil(W / 32)) int32: the target-vs-background column masks of the views (computed once per view)."""
         m = sel.get("tmap")
         if m is None:
-            from ._lib import check, lib, ptr, stream
             H, W = int(self.s["height"]), int(self.s["width"])
             per = int(lib().mgr_image_loss_target_map_words(1, H, W))
             rows = []
@@ -612,274 +784,206 @@ class HipViewCompute:
         return m
 
     def _tile_start_ptr(self, ws, V, N, W, H):
-        return ws.buf.data_ptr() + self._layout(ws, V, N, W, H)[7]
+        return ws.buf.data_ptr() + self._layout(ws, V, N, W, H)[LAYOUT_TILE_START]
 
     def _cut_flag(self, ws, view_ids, V, N, W, H):
-        """debug bit 8 of mgr_views_forward for this forward on `ws`: set when the workspace holds the depth-cut hints of
-        exactly these views (left by the previous forward, or parked earlier and brought back here) and the last forward
-        with them was not flagged."""
-        if not self.depth_cut or not self.rz.context(self.device).fenced(self.sync_check):
-            return 0      # (with a host sync per forward the split forward would need a second one after the blend: not worth it)
-        key = (id(self), self._cut_gen, tuple(view_ids))
-        prev = ws.prev_hint_key
-        ws.hint_key = key
-        from ._lib import lib
+        """Depth-cut debug bits of mgr_views_forward for this forward on `ws` (`_DepthCut.flag`); 0 with the cut off."""
         ctx = self.rz.context(self.device)
-        if ctx.cut_retries != self._cut_seen:          # a forward of ours was flagged since the last launch
-            self._cut_seen, self._cut_scale = ctx.cut_retries, min(32.0, self._cut_scale * 2.0)
-            self._cut_pause, self._cut_backoff, self._cut_clean = self._cut_backoff, min(512, self._cut_backoff * 2), 0
-        else:
-            self._cut_scale = max(1.0, self._cut_scale * 0.98)
-        k = self._cut_scale
-        if self.cut_repair:
-            # tiles that run out are completed on the device (bit 2048): a flagged forward is then a capacity matter, rare, and
-            # the margins need neither widening nor the interior-only rule -- the library's per-tile countdown keeps the
-            # repeat offenders out
-            lib().mgr_raster_set_cut_margin(0.125 * self.cut_margin, int(64 * self.cut_margin), 0.0625 * self.cut_margin,
-                                            2.0e-4 * self.cut_margin, 0)
-            lib().mgr_raster_set_cut_penalty(int(self.cut_penalty))
-        else:
-            lib().mgr_raster_set_cut_margin(min(4.0, 0.125 * k), int(64 * k), min(4.0, 0.0625 * k), 2.0e-4 * k, 1 if k > 1.0 else 0)
-        born, self._cut_born[key] = self._cut_born.get(key), self._cut_clock
-        if len(self._cut_born) > 4 * self._cut_max:     # view sets not seen for cut_max_age updates have no usable hints
-            self._cut_born = {k_: b_ for k_, b_ in self._cut_born.items() if self._cut_clock - b_ <= self.cut_max_age}
-        too_old = born is None or self._cut_clock - born > self.cut_max_age
-        if prev != key:
-            T = ((W + 15) // 16) * ((H + 15) // 16)
-            lay = self._layout(ws, V, N, W, H)
-            # the hints (tile_zcut) and the depth windows of the repair that belong to them (tile_zwin): 2 x 4 bytes per tile and view
-            regions = [ws.buf[o_: o_ + 4 * V * T] for o_ in (lay[26], lay[32])]
-            nbytes = sum(r.numel() for r in regions)
-            if prev is not None and prev[:2] == key[:2]:      # park the hints of the views rendered last
-                max_sets = max(1, min(self._cut_max, self.MAX_CUT_HINT_BYTES // max(1, nbytes)))
-                while len(self._cut_store) >= max_sets:
-                    self._cut_store.pop(next(iter(self._cut_store)))
-                self._cut_store[prev] = torch.cat(regions)
-            saved = self._cut_store.pop(key, None)
-            if saved is not None and saved.numel() == nbytes:
-                o_ = 0
-                for r in regions:
-                    r.copy_(saved[o_: o_ + r.numel()])
-                    o_ += r.numel()
-            else:
-                for r in regions:
-                    r.zero_()                                               # no hints for these views yet
-        if ws.cut_block:                  # the previous forward was flagged: this one rebuilds the hints from full lists
-            ws.cut_block = False
-            return 0
-        if too_old:
-            return 0
-        if self.cut_repair:
-            if self._cut_pause > 0:       # (a capacity of the repair was exceeded: a few forwards on full lists, no escalation)
-                self._cut_pause = min(self._cut_pause, 4) - 1
-                return 0
-            return 8 | 2048
-        if self._cut_pause > 0:           # backing off after a flagged forward
-            self._cut_pause -= 1
-            return 0
-        self._cut_clean += 1
-        if self._cut_clean >= 32:
-            self._cut_clean, self._cut_backoff = 0, max(4, self._cut_backoff // 2)
-        return 8
+        if not self.depth_cut or not ctx.fenced(self.sync_check):
+            return 0      # (with a host sync per forward the split forward would need a second one after the blend: not worth it)
+        lay = self._layout(ws, V, N, W, H)
+        T = ((W + 15) // 16) * ((H + 15) // 16)
+        return self._cut.flag(ws, view_ids, ctx.cut_retries, (lay[LAYOUT_TILE_ZCUT], lay[LAYOUT_TILE_ZWIN]), 4 * V * T,
+                              self.cut_repair, self.cut_margin, self.cut_penalty)
 
     # -- fused path, direct C-ABI calls ------------------------------------------------------------
     def _step_direct(self, view_ids, scale, g_img=None):
         """skin weights -> mgr_views_forward -> image loss -> mgr_views_backward -> skin-weight backward, every
         gradient written straight into the arena (the all-reduce buffer) when one is set.  g_img: optional dL/dimage
         (V,3,H,W) used instead of the image loss (parity tests)."""
-        from ._lib import check, lib, ptr, stream
         s, p = self.s, {k: v.detach() for k, v in self.params.items()}
         sel = self._select(view_ids)
-        cams, T = sel["cams"], sel["T"]
         dev = self.device
         N, na, V = p["_xyz"].shape[0], self.n_art, len(view_ids)
         W, H = int(s["width"]), int(s["height"])
-        arena = self.grad_arena or {}
-        own = None
-        if self.persistent_grads and not arena and self.fused:
-            key = (N, na, str(dev))
-            if self._pg is None or self._pg[0] != key:
-                self._pg, self._pg_ws, self._pimg_ws, self._pg_ver = (key, {}), None, None, {}
-            own = self._pg[1]
-            # a kept buffer somebody wrote into since it was handed out (torch bumps a tensor's version counter on every
-            # in-place op, also through views) no longer holds what the row / tile bookkeeping says: fill everything again
-            if any(own[n]._version != ver for n, ver in self._pg_ver.items() if n in own):
-                self._pg_ws = self._pimg_ws = None
-
-        def e(shape, name):
-            if own is not None:
-                t = own.get(name)
-                if t is None:
-                    t = own[name] = torch.zeros(shape, dtype=torch.float32, device=dev)
-                return t
-            t = arena.get(name)
-            n = 1
-            for d in shape:
-                n *= d
-            if t is not None and t.numel() == n and t.is_contiguous() and t.dtype == torch.float32 and t.device == dev:
-                return t.view(shape)
-            return torch.empty(shape, dtype=torch.float32, device=dev)
-
-        sg, B, w = self.grid, 0, None
-        if na:
-            B = sg.B
-            w = torch.empty((na, B), dtype=torch.float32, device=dev)
-            check(lib().mgr_skin_weights_fwd(na, ptr(p["_xyz"]), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride,
-                                             ptr(s["grid_center"]), ptr(s["grid_scale"]), ptr(w), stream()),
-                  "mgr_skin_weights_fwd")
-        if own is not None:   # persistent_grads: the image too is a buffer this object keeps -- a tile that held the background
-            out = own.get(("image", V, H, W))          # after the previous forward on the same workspace and is empty again is not
-            if out is None:                            # written again (mgr_views_forward, debug bit 1024)
-                out = own[("image", V, H, W)] = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
+        kept = self._kept if (self.persistent_grads and not self.grad_arena and self.fused) else None
+        if kept is not None:
+            kept.begin(N, na, dev)
+        w, B = self._skin_weights(p["_xyz"], na)
+        if kept is not None:      # the image too is a kept buffer (bit 1024 of the forward)
+            out = kept.get((V, 3, H, W), ("image", V, H, W), zeroed=False)
         else:
             out = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((V, N), dtype=torch.int32, device=dev)
-        op = p["_opacity"].reshape(-1)
-        bg = s["bg"]
         f_rest, sh_half = self._sh_storage(p["_features_rest"])
-
-        # The span list of the image loss needs the forward's tile offsets but not its image: with overlap_loss it is
-        # built on a second stream while the forward blend runs (forward split at the blend, debug bits 1 / 2).
-        mapped = g_img is None and self.loss == "l1+ssim" and self.sparse_loss and self.target_map
-        overlap = g_img is None and self.loss == "l1+ssim" and self.sparse_loss and self.overlap_loss and not mapped
-
-        def fwd(ws, phase):
-            check(lib().mgr_views_forward(V, N, B, na, sh_half, W, H, ptr(cams), ptr(bg), ptr(p["_xyz"]), ptr(p["_scaling"]),
-                                          ptr(p["_rotation"]), ptr(op), ptr(p["_features_dc"]), ptr(f_rest),
-                                          ptr(w), ptr(T), ptr(out), ptr(radii), ptr(ws.buf), ws.nbytes, ws.cap,
-                                          phase | self._cut_bit | ws.skip_bits() | (1024 if (own is not None and self._pimg_ws is ws) else 0),
-                                          stream()), "mgr_views_forward")
-            if own is not None:
-                self._pimg_ws = ws
-
-        # mapped: the span list of the loss is built by the forward itself (extra workgroups of its last kernel, attached per launch)
-        lws = tmap = None
-        lnbytes = 0
-        if mapped:
-            lnbytes = int(lib().mgr_image_loss_workspace_bytes(V, H, W))
-            lws = self._lws.get((V, H, W))      # kept across steps, zero-filled once: list / finish pairs leave it clean
-            if lws is None:
-                lws = self._lws[(V, H, W)] = torch.zeros(lnbytes, dtype=torch.uint8, device=dev)
-            tmap = self._target_map(view_ids, sel, bg)
-        launches = [0]
-
-        def launch(ws):
-            self._cut_bit = self._cut_flag(ws, view_ids, V, N, W, H)
-            if mapped and self.attach_list:
-                if launches[0]:          # a forward of this step ran before (capacity / tier retry): its list was never finished
-                    lws.zero_()
-                launches[0] += 1
-                check(lib().mgr_views_forward_attach_loss_list(ptr(ws.buf), V, H, W, ptr(tmap), ptr(lws), lnbytes),
-                      "mgr_views_forward_attach_loss_list")
-                try:
-                    fwd(ws, 0)
-                except Exception:        # (a forward that failed before its last kernel leaves the attachment pending: withdraw it)
-                    lib().mgr_views_forward_attach_loss_list(ptr(ws.buf), V, H, W, None, None, 0)
-                    raise
-                return
-            fwd(ws, 2 if overlap else 0)
-
+        # the leading arguments mgr_views_forward and mgr_views_backward share
+        head = (V, N, B, na, sh_half, W, H, ptr(sel["cams"]), ptr(s["bg"]), ptr(p["_xyz"]), ptr(p["_scaling"]), ptr(p["_rotation"]),
+                ptr(p["_opacity"].reshape(-1)), ptr(p["_features_dc"]), ptr(f_rest), ptr(w), ptr(sel["T"]))
+        fwd = (head, out, radii, kept)
+        # route of the image loss (class docstring): "mapped" / "overlap" span lists, or None = plain / g_img given
+        listed = g_img is None and self.loss == "l1+ssim" and self.sparse_loss
+        route = None if not listed else "mapped" if self.target_map else "overlap" if self.overlap_loss else None
+        loss_list = self._mapped_loss_list(view_ids, sel, V, H, W) if route == "mapped" else None
         ctx = self.rz.context(dev)
         ws = None
         try:
-            ws, _ = ctx.forward(V, N, W, H, launch, sync_check=self.sync_check, defer_fence=True)
-            if not overlap and ctx.fenced(self.sync_check):
+            ws, _ = ctx.forward(V, N, W, H, self._forward_launch(fwd, view_ids, loss_list, 2 if route == "overlap" else 0),
+                                sync_check=self.sync_check, defer_fence=True)
+            if route != "overlap" and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
-            if mapped:
-                tgt = sel["targets"]
-                nbytes = lnbytes
-                g_img = torch.empty_like(out)
-                sums = torch.empty(3, dtype=torch.float32, device=dev)
-                if not self.attach_list:
-                    import ctypes
-                    check(lib().mgr_image_loss_tiles_list_mapped(V, H, W, ptr(tmap), ptr(bg), ctypes.c_void_p(self._tile_start_ptr(ws, V, N, W, H)),
-                                                                 ptr(lws), nbytes, 1, stream()), "mgr_image_loss_tiles_list_mapped")
-                per_view = out[0].numel()
-                k = self.loss_weight * scale / per_view
-                const = self.w_ssim * self.loss_weight * scale * V
-                check(lib().mgr_image_loss_tiles_finish(V, H, W, ptr(out), ptr(tgt), self.w_rgb, self.w_ssim, k, const, ptr(g_img),
-                                                        ptr(sums), ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_finish")
-                loss = sums[2]
-            elif overlap:
-                import ctypes
-                tgt = sel["targets"]
-                nbytes = int(lib().mgr_image_loss_workspace_bytes(V, H, W))
-                lws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                g_img = torch.empty_like(out)
-                sums = torch.empty(3, dtype=torch.float32, device=dev)
-                cur = torch.cuda.current_stream(dev)
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=dev)
-                self._side.wait_stream(cur)
-                with torch.cuda.stream(self._side):
-                    check(lib().mgr_image_loss_tiles_list(V, H, W, ptr(tgt), ptr(bg), ctypes.c_void_p(self._tile_start_ptr(ws, V, N, W, H)),
-                                                          ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_list")
-                fwd(ws, 4)                                  # the blend, next to the list
-                if ctx.fenced(self.sync_check):
-                    ctx.fence(ws)                           # (after the blend: it is the blend that raises the depth-cut flag)
-                cur.wait_stream(self._side)
-                lws.record_stream(self._side)
-                per_view = out[0].numel()
-                k = self.loss_weight * scale / per_view
-                const = self.w_ssim * self.loss_weight * scale * V
-                check(lib().mgr_image_loss_tiles_finish(V, H, W, ptr(out), ptr(tgt), self.w_rgb, self.w_ssim, k, const, ptr(g_img),
-                                                        ptr(sums), ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_finish")
-                loss = sums[2]
-            elif g_img is None:
-                loss, g_img = self._image_loss(out, sel["targets"], scale, tiles=(bg, self._tile_start_ptr(ws, V, N, W, H)))
-            else:
-                loss, g_img = (out * g_img).sum(), g_img.contiguous()
-            d_xyz, d_ls, d_rot = e((N, 3), "_xyz"), e((N, 3), "_scaling"), e((N, 4), "_rotation")
-            d_op, d_fdc, d_frest = e((N, 1), "_opacity"), e((N, 1, 3), "_features_dc"), e((N, 15, 3), "_features_rest")
-            st_g, st_v = e((N,), "grad2d"), e((N,), "vis")
-            st_r = torch.empty(N, dtype=torch.int32, device=dev)
-            d_w = (e((na, B), "_skin_w") if own is not None else torch.empty((na, B), dtype=torch.float32, device=dev)) if na else None
-            # the buffers are those of the previous backward on this very workspace, untouched since: the library may skip the
-            # zero fill of the rows it knows to be zero (it checks that its row state is that call's; bit 512)
-            kept = 512 if (own is not None and self._pg_ws is ws and V <= 8) else 0
-            self._pg_ws = None
-            check(lib().mgr_views_backward(V, N, B, na, sh_half, W, H, ptr(cams), ptr(bg), ptr(p["_xyz"]), ptr(p["_scaling"]),
-                                           ptr(p["_rotation"]), ptr(op), ptr(p["_features_dc"]), ptr(f_rest),
-                                           ptr(w), ptr(T), ptr(radii), ptr(out), ptr(g_img), 1.0 / scale, ptr(d_xyz),
-                                           ptr(d_ls), ptr(d_rot), ptr(d_op), ptr(d_fdc), ptr(d_frest), ptr(d_w), ptr(st_g),
-                                           ptr(st_v), ptr(st_r), ptr(ws.buf), ws.nbytes, ws.cap, kept, stream()),
-                  "mgr_views_backward")
-            if own is not None:
-                self._pg_ws = ws
-                self._pg_ver = {n: t._version for n, t in own.items()}
-            active = None
-            if V <= 8 and N > 0:
-                # the backward's list of the Gaussians that received a gradient (device pointers: list, length)
-                import ctypes
-                lst, cnt = ctypes.c_void_p(), ctypes.c_void_p()
-                check(lib().mgr_views_active_list(ptr(ws.buf), V, N, W, H, ws.cap, ctypes.byref(lst), ctypes.byref(cnt)),
-                      "mgr_views_active_list")
-                active = (lst, cnt)
-            if na and V <= 8:
-                # d xyz += d w . d(trilinear weights)/d xyz (the leaf is used twice: gaussian_utils.py:167-196), for the
-                # Gaussians that received a gradient only (the others' d_w rows are zero)
-                check(lib().mgr_skin_weights_bwd_indexed(na, ptr(p["_xyz"]), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride,
-                                                         ptr(s["grid_center"]), ptr(s["grid_scale"]), ptr(d_w), ptr(d_xyz),
-                                                         lst, cnt, N, stream()), "mgr_skin_weights_bwd_indexed")
-            elif na:
-                check(lib().mgr_skin_weights_bwd(na, ptr(p["_xyz"]), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride,
-                                                 ptr(s["grid_center"]), ptr(s["grid_scale"]), ptr(d_w), ptr(d_xyz), 1,
-                                                 stream()), "mgr_skin_weights_bwd")
+            loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
+            grads, d_w, st_g, st_v, st_r = self._backward(ws, fwd, g_img, scale)
+            active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"])
             overflow = ws.buf[4:8].view(torch.int32)
         except BaseException:
             # a call that failed between the loss's list and finish passes -- the forward included: its last kernel builds the
             # attached list -- leaves the kept loss workspace with a non-zero span count (the finish pass is what resets it) and
             # the kept buffers in an unknown state: start over
             self._lws.pop((V, H, W), None)
-            self._pg_ws = self._pimg_ws = None
+            self._kept.invalidate()
             raise
         finally:
             if ws is not None:
                 ws.busy = False
         self.last_image, self.last_radii = out, radii
         self.last_active = active      # (device pointers into the workspace of this step: valid until the next forward on it)
-        return dict(grads={"_xyz": d_xyz, "_scaling": d_ls, "_rotation": d_rot, "_opacity": d_op, "_features_dc": d_fdc,
-                           "_features_rest": d_frest}, grad2d=st_g, vis=st_v, radii=st_r, loss=loss, overflow=overflow)
+        return dict(grads=grads, grad2d=st_g, vis=st_v, radii=st_r, loss=loss, overflow=overflow)
+
+    def _skin_weights(self, xyz, na):
+        """(skin weights (na,B) of the articulated rows, B); (None, 0) without any."""
+        if not na:
+            return None, 0
+        s, sg = self.s, self.grid
+        w = torch.empty((na, sg.B), dtype=torch.float32, device=self.device)
+        check(lib().mgr_skin_weights_fwd(na, ptr(xyz), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride,
+                                         ptr(s["grid_center"]), ptr(s["grid_scale"]), ptr(w), stream()),
+              "mgr_skin_weights_fwd")
+        return w, sg.B
+
+    def _mapped_loss_list(self, view_ids, sel, V, H, W):
+        """(workspace, target maps, workspace bytes) of the mapped span list.  The workspace is kept across steps, zero-filled
+        once: list / finish pairs leave it clean."""
+        nbytes = int(lib().mgr_image_loss_workspace_bytes(V, H, W))
+        lws = self._lws.get((V, H, W))
+        if lws is None:
+            lws = self._lws[(V, H, W)] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return lws, self._target_map(view_ids, sel, self.s["bg"]), nbytes
+
+    def _views_forward(self, ws, fwd, phase):
+        """One mgr_views_forward on `ws`.  phase: 0 whole, 2 up to the blend, 4 the blend."""
+        head, out, radii, kept = fwd
+        # kept image: a tile that held the background after the previous forward on the same workspace and is empty again is not
+        # written again (bit 1024)
+        bits = phase | self._cut.bit | ws.skip_bits() | (1024 if (kept is not None and kept.image_ws is ws) else 0)
+        check(lib().mgr_views_forward(*head, ptr(out), ptr(radii), ptr(ws.buf), ws.nbytes, ws.cap, bits, stream()), "mgr_views_forward")
+        if kept is not None:
+            kept.image_ws = ws
+
+    def _forward_launch(self, fwd, view_ids, loss_list, phase):
+        """What `RasterContext.forward` runs on the workspace it chose -- again after a capacity / tier retry: the depth-cut
+        decision and the forward, with the mapped span list of the loss attached to it when there is one (extra workgroups of
+        the forward's last kernel, attached per launch)."""
+        V, N, W, H = fwd[0][0], fwd[0][1], fwd[0][5], fwd[0][6]
+        launches = [0]
+
+        def launch(ws):
+            self._cut.bit = self._cut_flag(ws, view_ids, V, N, W, H)
+            if loss_list is None or not self.attach_list:
+                return self._views_forward(ws, fwd, phase)
+            lws, tmap, nbytes = loss_list
+            if launches[0]:          # a forward of this step ran before (capacity / tier retry): its list was never finished
+                lws.zero_()
+            launches[0] += 1
+            check(lib().mgr_views_forward_attach_loss_list(ptr(ws.buf), V, H, W, ptr(tmap), ptr(lws), nbytes),
+                  "mgr_views_forward_attach_loss_list")
+            try:
+                self._views_forward(ws, fwd, 0)
+            except Exception:        # (a forward that failed before its last kernel leaves the attachment pending: withdraw it)
+                lib().mgr_views_forward_attach_loss_list(ptr(ws.buf), V, H, W, None, None, 0)
+                raise
+
+        return launch
+
+    def _loss(self, ctx, ws, fwd, sel, scale, g_img, route, loss_list):
+        """(loss, dL/dimage) of the forward on `ws` by the step's route."""
+        head, out = fwd[0], fwd[1]
+        V, N, W, H = head[0], head[1], head[5], head[6]
+        tgt, bg = sel["targets"], self.s["bg"]
+        if route is None:
+            if g_img is not None:
+                return (out * g_img).sum(), g_img.contiguous()
+            return self._image_loss(out, tgt, scale, tiles=(bg, self._tile_start_ptr(ws, V, N, W, H)))
+        if route == "mapped":
+            lws, tmap, nbytes = loss_list
+            if not self.attach_list:      # the list in a launch of its own
+                check(lib().mgr_image_loss_tiles_list_mapped(V, H, W, ptr(tmap), ptr(bg), ctypes.c_void_p(self._tile_start_ptr(ws, V, N, W, H)),
+                                                             ptr(lws), nbytes, 1, stream()), "mgr_image_loss_tiles_list_mapped")
+        else:
+            # overlap: the span list needs the forward's tile offsets but not its image -- it is built on a second stream while
+            # the forward blend runs
+            nbytes = int(lib().mgr_image_loss_workspace_bytes(V, H, W))
+            lws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            cur = torch.cuda.current_stream(self.device)
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=self.device)
+            self._side.wait_stream(cur)
+            with torch.cuda.stream(self._side):
+                check(lib().mgr_image_loss_tiles_list(V, H, W, ptr(tgt), ptr(bg), ctypes.c_void_p(self._tile_start_ptr(ws, V, N, W, H)),
+                                                      ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_list")
+            self._views_forward(ws, fwd, 4)             # the blend, next to the list
+            if ctx.fenced(self.sync_check):
+                ctx.fence(ws)                           # (after the blend: it is the blend that raises the depth-cut flag)
+            cur.wait_stream(self._side)
+            lws.record_stream(self._side)
+        k, const = self._loss_scales(out, scale)
+        g_img = torch.empty_like(out)
+        sums = torch.empty(3, dtype=torch.float32, device=self.device)
+        check(lib().mgr_image_loss_tiles_finish(V, H, W, ptr(out), ptr(tgt), self.w_rgb, self.w_ssim, k, const, ptr(g_img),
+                                                ptr(sums), ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_finish")
+        return sums[2], g_img
+
+    def _backward(self, ws, fwd, g_img, scale):
+        """mgr_views_backward into the kept buffers, the arena or fresh tensors: (leaf gradients, skin-weight gradient,
+        grad2d, vis, radii)."""
+        head, out, radii, kept = fwd
+        V, N, B, na = head[:4]
+        dev = self.device
+        e = kept.get if kept is not None else functools.partial(_arena_tensor, self.grad_arena or {}, dev)
+        grads = {name: e(shape, name) for name, shape in (("_xyz", (N, 3)), ("_scaling", (N, 3)), ("_rotation", (N, 4)), ("_opacity", (N, 1)),
+                                                           ("_features_dc", (N, 1, 3)), ("_features_rest", (N, 15, 3)))}
+        st_g, st_v = e((N,), "grad2d"), e((N,), "vis")
+        st_r = torch.empty(N, dtype=torch.int32, device=dev)
+        d_w = e((na, B), "_skin_w") if na else None
+        # the buffers are those of the previous backward on this very workspace, untouched since: the library may skip the
+        # zero fill of the rows it knows to be zero (it checks that its row state is that call's; bit 512)
+        bits = 512 if (kept is not None and kept.grad_ws is ws and V <= 8) else 0
+        self._kept.grad_ws = None
+        check(lib().mgr_views_backward(*head, ptr(radii), ptr(out), ptr(g_img), 1.0 / scale, *[ptr(g) for g in grads.values()],
+                                       ptr(d_w), ptr(st_g), ptr(st_v), ptr(st_r), ptr(ws.buf), ws.nbytes, ws.cap, bits, stream()),
+              "mgr_views_backward")
+        if kept is not None:
+            kept.handed_out(ws)
+        return grads, d_w, st_g, st_v, st_r
+
+    def _skin_backward(self, ws, head, xyz, d_w, d_xyz):
+        """The backward's list of the Gaussians that received a gradient (device pointers: list, length; None beyond 8 views)
+        and, through it, d xyz += d w . d(trilinear weights)/d xyz (the leaf is used twice: gaussian_utils.py:167-196)."""
+        V, N, _, na, _, W, H = head[:7]
+        active = None
+        if V <= 8 and N > 0:
+            lst, cnt = ctypes.c_void_p(), ctypes.c_void_p()
+            check(lib().mgr_views_active_list(ptr(ws.buf), V, N, W, H, ws.cap, ctypes.byref(lst), ctypes.byref(cnt)),
+                  "mgr_views_active_list")
+            active = (lst, cnt)
+        if not na:
+            return active
+        s, sg = self.s, self.grid
+        grid = (na, ptr(xyz), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride, ptr(s["grid_center"]), ptr(s["grid_scale"]), ptr(d_w), ptr(d_xyz))
+        if V <= 8:      # for the Gaussians that received a gradient only (the others' d_w rows are zero)
+            check(lib().mgr_skin_weights_bwd_indexed(*grid, lst, cnt, N, stream()), "mgr_skin_weights_bwd_indexed")
+        else:
+            check(lib().mgr_skin_weights_bwd(*grid, 1, stream()), "mgr_skin_weights_bwd")
+        return active
 
     def __call__(self, view_ids, scale=1.0):
         if self.fused:
@@ -900,14 +1004,11 @@ class HipViewCompute:
     def pairs_per_view(self, view_ids=None, group=8):
         """Surviving (tile, Gaussian) pairs of every view (forward only, in groups of `group` views): the weights of the
         balanced view assignment.  Deterministic, so every rank computes the same list."""
-        import ctypes
-        from ._lib import lib
         ids = list(range(self.cams.shape[0])) if view_ids is None else list(view_ids)
         W, H = int(self.s["width"]), int(self.s["height"])
         T = ((W + 15) // 16) * ((H + 15) // 16)
         N = self.params["_xyz"].shape[0]
         out = []
-        from ._lib import ManusHipError
         ctx = self.rz.context(self.device)
         with torch.no_grad():
             for k in range(0, len(ids), group):
@@ -921,9 +1022,8 @@ class HipViewCompute:
                         if attempt == 3:
                             raise
                 ws = ctx.last_ws
-                arr = (ctypes.c_size_t * 32)()
-                lib().mgr_raster_layout(len(part), N, W, H, ws.cap, arr, 32)
-                ts = ws.buf[int(arr[7]): int(arr[7]) + 4 * (len(part) * T + 1)].view(torch.int32)[::T].cpu().tolist()
+                o = self._layout(ws, len(part), N, W, H)[LAYOUT_TILE_START]
+                ts = ws.buf[o: o + 4 * (len(part) * T + 1)].view(torch.int32)[::T].cpu().tolist()
                 out += [int(b - a) for a, b in zip(ts[:-1], ts[1:])]
         return out
 
@@ -979,7 +1079,6 @@ class Trainer:
             compute.persistent_grads = bool(compute.persistent_grads) and bool(persistent_grads) and world_size == 1
         self.compact_allreduce = compact_allreduce and not sharded_adam
         self.sharded_adam = bool(sharded_adam) and world_size > 1
-        from . import rasterizer
         from .density import DensityController
         from .optim import GaussianOptimizer
         global ALL_GROUPS
@@ -1070,8 +1169,6 @@ class Trainer:
         learnt capacities, fences and sync policy of the training context are not touched), the compute object's cache of
         per-view constants is put back, nothing is written into the kept gradient / image / loss buffers, and
         `global_step` does not move -- a train_step after a validate computes what it would have without it."""
-        from . import ops
-        from ._lib import ManusHipError
         from .validation import psnr_from_sums
         c = self.compute
         ids = list(view_ids)

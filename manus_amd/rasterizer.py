@@ -15,7 +15,9 @@ multi-view batched form (V cameras in every launch) used by the training engine.
 """
 from typing import NamedTuple
 
+import ctypes
 import os
+import time
 import weakref
 
 import torch
@@ -23,6 +25,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, f32c, lib, ptr, stream
+from .ops import lbs_cov, sh_colors
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -208,7 +211,6 @@ class RasterContext:
                 if not defer_fence:
                     self._fence(ws)
                 return ws, None
-            import ctypes
             npairs, ovf, tiers = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
             rc = lib().mgr_raster_status_tiers_sync(ptr(ws.buf), ctypes.byref(npairs), ctypes.byref(ovf), ctypes.byref(tiers), stream())
             ws.tiers = None if (ovf.value & 4) else int(tiers.value)
@@ -249,7 +251,6 @@ class RasterContext:
             self._evicted_overflow = self._evicted_overflow or bool(ovf)
         pinned = self._free_pinned.pop() if self._free_pinned else torch.zeros(4, dtype=torch.int32).pin_memory()
         pinned[3] = 0
-        import ctypes
         rc = lib().mgr_raster_set_status_mirror(ptr(ws.buf), ctypes.c_void_p(pinned.data_ptr()))
         ws.mirror = pinned if rc == 0 else None      # (not mappable: the fence falls back to a blocking read)
 
@@ -270,7 +271,6 @@ class RasterContext:
     @staticmethod
     def _wait_flag(pinned, seconds=5.0):
         """Spin (politely) until the device has written the valid flag of a status mirror."""
-        import time
         t0, n = time.perf_counter(), 0
         while int(pinned[3]) != 1:
             n += 1
@@ -291,7 +291,6 @@ class RasterContext:
             ovf = word & 0xFFFF
             self.cut_repairs += word >> 16       # quadrants of depth-cut tiles the forward repaired on the device (no re-run)
         else:   # (a forward that did not run its blend, or no mirror: read the header -- valid if nothing ran on ws since)
-            import ctypes
             n_, o_, t_ = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
             lib().mgr_raster_status_tiers_sync(ptr(ws.buf), ctypes.byref(n_), ctypes.byref(o_), ctypes.byref(t_), stream())
             npairs, ovf, tiers_seen = int(n_.value), int(o_.value), int(t_.value)
@@ -325,7 +324,6 @@ class RasterContext:
     def check_overflow(self):
         """Blocking check of every forward since the last check (fences) and of the most recent workspace; returns
         the most recent pair count, raises ManusHipError on overflow (after enlarging the capacity hint)."""
-        import ctypes
         polled = self.poll()
         ws = self.last_ws
         if ws is None:
@@ -504,11 +502,9 @@ class GaussianRasterizer(nn.Module):
             raise _lib.ManusHipError("GaussianRasterizer needs GPU tensors; there is no CPU fallback")
         cams = _lib.pack_cameras(rs.tanfovx, rs.tanfovy, rs.viewmatrix, rs.projmatrix, rs.campos, dev)
         if cov3D_precomp is None:
-            from .ops import lbs_cov
             _, cov, _ = lbs_cov(means3D, torch.log(scales * rs.scale_modifier), rotations, None, None)
             cov3D_precomp = cov[0]
         if colors_precomp is None:
-            from .ops import sh_colors
             K = (rs.sh_degree + 1) ** 2
             sh = shs
             if sh.shape[1] < 16 or K < 16:

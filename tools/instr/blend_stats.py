@@ -1,7 +1,7 @@
 import sys, ctypes, torch, numpy as np
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from manus_amd import rasterizer as rz, _lib
-from manus_amd.engine import HipViewCompute
+from manus_amd.engine import LAYOUT_TILE_DONE, LAYOUT_TILE_START, HipViewCompute, LAYOUT_FINAL_T, LAYOUT_N_CONTRIB
 from manus_amd.synthetic import camera_table, make_scene
 DEV='cuda:0'; V=8; N=300000; W,H=1920,1080
 sc = make_scene(n_gaussians=N, kind="hand", seed=0, n_cameras=V, width=W, height=H, device=DEV)
@@ -27,8 +27,8 @@ if d[9]:
 ws = rz.context().last_ws
 arr=(ctypes.c_size_t*32)(); L.mgr_raster_layout(V,N,W,H,ws.cap,arr,32)
 T=120*68; VT=V*T
-ts = ws.buf[int(arr[7]):int(arr[7])+4*(VT+1)].view(torch.int32).cpu().numpy().astype(np.int64)
-done = ws.buf[int(arr[9]):int(arr[9])+4*VT].view(torch.int32).cpu().numpy().astype(np.int64)
+ts = ws.buf[int(arr[LAYOUT_TILE_START]):int(arr[LAYOUT_TILE_START])+4*(VT+1)].view(torch.int32).cpu().numpy().astype(np.int64)
+done = ws.buf[int(arr[LAYOUT_TILE_DONE]):int(arr[LAYOUT_TILE_DONE])+4*VT].view(torch.int32).cpu().numpy().astype(np.int64)
 n = np.diff(ts)
 print("keys", n.sum(), "consumed", done.sum(), "tiles nonempty", (n>0).sum())
 for lo,hi in ((1,64),(64,512),(512,2048),(2048,4096),(4096,16384),(16384,1<<30)):
@@ -41,10 +41,10 @@ for fr in (0.125, 0.25, 0.5):
     ok = done[big] <= fr*n[big]
     print("tiles>=2048 with done <= %.3f n: %.3f of tiles, %.3f of keys" % (fr, ok.mean(), n[big][ok].sum()/n[big].sum()))
 # pixel-level: n_contrib vs tile_done is max; check how many pixels unsaturated in big tiles
-nc = ws.buf[int(arr[17]):int(arr[17])+4*V*W*H].view(torch.int32).reshape(V,H,W)
+nc = ws.buf[int(arr[LAYOUT_N_CONTRIB]):int(arr[LAYOUT_N_CONTRIB])+4*V*W*H].view(torch.int32).reshape(V,H,W)
 img = hc.last_image
 # a pixel is 'saturated' if rendering stopped early: approximate via final colour not containing bg... skip
-sp = ws.buf[int(arr[16]):int(arr[16])+4*V*W*H].view(torch.int32).reshape(V,H,W)
+sp = ws.buf[int(arr[LAYOUT_FINAL_T]):int(arr[LAYOUT_FINAL_T])+4*V*W*H].view(torch.int32).reshape(V,H,W)
 # per tile: all pixels saturated? and the max stop position
 sp_t = sp[:, :1072].reshape(V, 67, 16, 120, 16).permute(0,1,3,2,4).reshape(V, 67*120, 256)
 allsat = (sp_t > 0).all(-1).cpu().numpy()

@@ -17,7 +17,8 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from manus_amd import rasterizer  # noqa: E402
 from manus_amd._lib import lib  # noqa: E402
-from manus_amd.engine import HipViewCompute  # noqa: E402
+from manus_amd.engine import (LAYOUT_TILE_DONE, LAYOUT_TILE_QEND, LAYOUT_TILE_START, LAYOUT_TILE_ZUSED,  # noqa: E402
+                              HipViewCompute)
 from manus_amd.optim import GaussianOptimizer  # noqa: E402
 from manus_amd.synthetic import camera_table, make_scene  # noqa: E402
 
@@ -45,7 +46,7 @@ def run(scale, interior):
     orig = c._cut_flag
 
     def fixed_margins(ws, view_ids, V_, N_, W_, H_):
-        c._cut_pause, c._cut_scale, c._cut_seen = 0, 1.0, ctx.cut_retries      # no back-off, no widening
+        c._cut.pause, c._cut.scale, c._cut.seen = 0, 1.0, ctx.cut_retries      # no back-off, no widening
         bit = orig(ws, view_ids, V_, N_, W_, H_)
         lib().mgr_raster_set_cut_margin(0.125 * scale, int(64 * scale), 0.0625 * scale, 2.0e-4 * scale, interior)
         return bit
@@ -61,7 +62,7 @@ def run(scale, interior):
     flagged_steps, tiles, lack, lack_max, pairs_cut, pairs_full, cut_steps = 0, [], [], [], [], [], 0
     for step in range(STEPS):
         o = c(views, 1.0 / V)
-        used_cut = c._cut_bit != 0
+        used_cut = c._cut.bit != 0
         try:
             rasterizer.poll(dev)
             if used_cut:
@@ -69,18 +70,18 @@ def run(scale, interior):
                 torch.cuda.synchronize()
                 ws = ctx.last_ws
                 off = c._layout(ws, V, N, W, H)
-                pairs_cut.append(int(reg(ws, off, 7, V * T + 1)[-1]))
+                pairs_cut.append(int(reg(ws, off, LAYOUT_TILE_START, V * T + 1)[-1]))
         except RuntimeError:
             torch.cuda.synchronize()
             ws = ctx.last_ws
             off = c._layout(ws, V, N, W, H)
-            cnt = np.diff(reg(ws, off, 7, V * T + 1))
-            qend, zused = reg(ws, off, 28, V * T), reg(ws, off, 27, V * T)
+            cnt = np.diff(reg(ws, off, LAYOUT_TILE_START, V * T + 1))
+            qend, zused = reg(ws, off, LAYOUT_TILE_QEND, V * T), reg(ws, off, LAYOUT_TILE_ZUSED, V * T)
             bad = np.nonzero((zused != 0) & ((qend == 0xFFFFFFFF) | (cnt == 0)))[0]
             o = c(views, 1.0 / V)             # full lists (cut_block)
             rasterizer.poll(dev)
             torch.cuda.synchronize()
-            cnt2, done2 = np.diff(reg(ws, off, 7, V * T + 1)), reg(ws, off, 9, V * T)
+            cnt2, done2 = np.diff(reg(ws, off, LAYOUT_TILE_START, V * T + 1)), reg(ws, off, LAYOUT_TILE_DONE, V * T)
             flagged_steps += 1
             tiles.append(len(bad))
             need = np.maximum(done2[bad] - cnt[bad], 0)      # entries the deepest walk of the tile consumed beyond the cut list

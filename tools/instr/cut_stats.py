@@ -8,7 +8,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from manus_amd import rasterizer  # noqa: E402
-from manus_amd.engine import HipViewCompute  # noqa: E402
+from manus_amd.engine import (LAYOUT_TILE_DONE, LAYOUT_TILE_QEND, LAYOUT_TILE_START, LAYOUT_TILE_ZCUT,  # noqa: E402
+                              LAYOUT_TILE_ZUSED, HipViewCompute)
 from manus_amd.synthetic import camera_table, make_scene  # noqa: E402
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -33,9 +34,9 @@ def region(ws, off, idx, n):
 def snap():
     ws = rasterizer.context(dev).last_ws
     off = c._layout(ws, V, N, W, H)
-    ts = region(ws, off, 7, V * T + 1)
-    return dict(count=np.diff(ts), done=region(ws, off, 9, V * T), qend=region(ws, off, 28, V * T),
-                zcut=region(ws, off, 26, V * T), zused=region(ws, off, 27, V * T))
+    ts = region(ws, off, LAYOUT_TILE_START, V * T + 1)
+    return dict(count=np.diff(ts), done=region(ws, off, LAYOUT_TILE_DONE, V * T), qend=region(ws, off, LAYOUT_TILE_QEND, V * T),
+                zcut=region(ws, off, LAYOUT_TILE_ZCUT, V * T), zused=region(ws, off, LAYOUT_TILE_ZUSED, V * T))
 
 
 c(views)          # fenced, no hints: full lists

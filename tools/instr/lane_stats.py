@@ -1,8 +1,8 @@
 """How full are the lane groups of k_inst_bwd?  (view, Gaussian) instances with pair records against 8 lanes per active Gaussian."""
 import os, sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from manus_amd import rasterizer
-from manus_amd.engine import HipViewCompute
+from manus_amd.engine import LAYOUT_INST_TAG, HipViewCompute
 from manus_amd.synthetic import camera_table, make_scene
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 N = 300000; W, H = 1920, 1080
@@ -15,8 +15,7 @@ for _ in range(4): c(views, 1.0 / V)
 torch.cuda.synchronize()
 ws = rasterizer.context(dev).last_ws
 off = c._layout(ws, V, N, W, H)
-k = 22   # "inst_tag" in the order of mgr_raster_layout (tools/parity.py: layout)
-tag = ws.buf[off[k]: off[k] + 4 * V * N].view(torch.int32).cpu().numpy().reshape(V, N)
+tag = ws.buf[off[LAYOUT_INST_TAG]: off[LAYOUT_INST_TAG] + 4 * V * N].view(torch.int32).cpu().numpy().reshape(V, N)
 ep = np.bincount(tag.ravel().astype(np.int64) & 0xFFFF).argmax() if False else tag.max()
 has = tag == ep
 per_g = has.sum(0)

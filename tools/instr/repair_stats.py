@@ -12,7 +12,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from manus_amd import rasterizer  # noqa: E402
-from manus_amd.engine import HipViewCompute  # noqa: E402
+from manus_amd.engine import (LAYOUT_REP_CNT, LAYOUT_REP_UNIT, LAYOUT_TILE_REP, LAYOUT_TILE_START,  # noqa: E402
+                              HipViewCompute)
 from manus_amd.optim import GaussianOptimizer  # noqa: E402
 from manus_amd.synthetic import camera_table, make_scene  # noqa: E402
 
@@ -52,15 +53,15 @@ for step in range(STEPS):
     off = c._layout(ws, V, N, W, H)
     hdr = ws.buf[:4096].view(torch.int32).cpu().numpy().astype(np.int64) & 0xFFFFFFFF
     nu, lst, ck, why = int(hdr[32]), int(hdr[33]), int(hdr[34]), int(hdr[35])
-    pairs = int(ws.buf[off[7] + 4 * V * T: off[7] + 4 * V * T + 4].view(torch.int32).item())
-    if c._cut_bit and nu:
+    pairs = int(ws.buf[off[LAYOUT_TILE_START] + 4 * V * T: off[LAYOUT_TILE_START] + 4 * V * T + 4].view(torch.int32).item())
+    if c._cut.bit and nu:
         nuc = min(nu, 1024)
-        units = ws.buf[off[30]: off[30] + 64 * nuc].view(torch.int32).cpu().numpy().reshape(nuc, 16).astype(np.int64) & 0xFFFFFFFF
-        cnt = ws.buf[off[31]: off[31] + 4 * nuc].view(torch.int32).cpu().numpy().astype(np.int64)
-        trep = ws.buf[off[29]: off[29] + 4 * V * T].view(torch.int32).cpu().numpy()
+        units = ws.buf[off[LAYOUT_REP_UNIT]: off[LAYOUT_REP_UNIT] + 64 * nuc].view(torch.int32).cpu().numpy().reshape(nuc, 16).astype(np.int64) & 0xFFFFFFFF
+        cnt = ws.buf[off[LAYOUT_REP_CNT]: off[LAYOUT_REP_CNT] + 4 * nuc].view(torch.int32).cpu().numpy().astype(np.int64)
+        trep = ws.buf[off[LAYOUT_TILE_REP]: off[LAYOUT_TILE_REP] + 4 * V * T].view(torch.int32).cpu().numpy()
         owners = np.array([u for u in range(nuc) if trep[units[u, 0]] == u + 1])
         rows.append((nu, len(owners), int(cnt[owners].sum()), int(cnt[owners].max()), int(units[owners, 12].sum()), lst, ck, pairs))
-    elif c._cut_bit:
+    elif c._cut.bit:
         rows.append((0, 0, 0, 0, 0, 0, 0, pairs))
     if bad:
         flagged += 1

@@ -1,7 +1,7 @@
 import sys, ctypes, torch, numpy as np
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))))
 from manus_amd import rasterizer as rz, _lib
-from manus_amd.engine import HipViewCompute
+from manus_amd.engine import LAYOUT_TILE_DONE, LAYOUT_TILE_START, HipViewCompute
 from manus_amd.synthetic import camera_table, make_scene
 DEV='cuda:0'; V=8; N=300000; W,H=1920,1080
 sc = make_scene(n_gaussians=N, kind="hand", seed=0, n_cameras=V, width=W, height=H, device=DEV)
@@ -12,8 +12,8 @@ hc(ids, 1.0/V); torch.cuda.synchronize()
 ws = rz.context().last_ws
 arr=(ctypes.c_size_t*32)(); L.mgr_raster_layout(V,N,W,H,ws.cap,arr,32)
 T=120*68; VT=V*T
-ts = ws.buf[int(arr[7]):int(arr[7])+4*(VT+1)].view(torch.int32).cpu().numpy().astype(np.int64)
-done = ws.buf[int(arr[9]):int(arr[9])+4*VT].view(torch.int32).cpu().numpy().astype(np.int64)
+ts = ws.buf[int(arr[LAYOUT_TILE_START]):int(arr[LAYOUT_TILE_START])+4*(VT+1)].view(torch.int32).cpu().numpy().astype(np.int64)
+done = ws.buf[int(arr[LAYOUT_TILE_DONE]):int(arr[LAYOUT_TILE_DONE])+4*VT].view(torch.int32).cpu().numpy().astype(np.int64)
 n = np.diff(ts)
 o = np.argsort(-done)[:40]
 print("top tiles by consumed depth: (n, done)", [(int(n[i]), int(done[i])) for i in o])
