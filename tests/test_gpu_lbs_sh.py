@@ -1,7 +1,8 @@
 """GPU: articulation kernels (skin weights, LBS of means/covariances, SH colour) against the
 golden vectors produced by importing the reference, and against the torch oracle on larger
 seeded inputs.  fp32 tolerance: max-rel-err (max|a-b|/max|b|) < 1e-4 for gradients, < 2e-5
-for forward values."""
+for forward values.  That norm is tensor-wide; the per-row checks (`util.row_rel_err` against the fp64 oracle, over the
+bone counts, grid borders, ragged sizes and strides at which the kernels branch) are in tests/test_gpu_articulation_edges.py."""
 import glob
 import os
 

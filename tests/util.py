@@ -22,6 +22,23 @@ def max_rel_err(a, b):
     return float(np.max(np.abs(a - b))) / den
 
 
+def row_rel_err(a, r, tau=1e-3):
+    """max_i  max_j|a_ij - r_ij| / max(max_j|r_ij|, tau * max|r|): rows along the first axis, the rest flattened.  Every row
+    down to 1/tau times smaller than the largest is judged at its own scale, smaller ones at that floor -- an error confined
+    to small rows (or to the last partial wave) cannot hide behind the largest row as it can in `max_rel_err`.  A NaN on
+    either side gives NaN (which fails any `<=`)."""
+    a, r = (x.detach().cpu().double().numpy() if torch.is_tensor(x) else np.asarray(x, np.float64) for x in (a, r))
+    assert a.shape == r.shape, (a.shape, r.shape)
+    if r.size == 0:
+        return 0.0
+    a, r = a.reshape(a.shape[0], -1), r.reshape(r.shape[0], -1)
+    den = np.maximum(np.abs(r).max(1), tau * float(np.abs(r).max()))
+    num = np.abs(a - r).max(1)
+    if not np.all(den > 0):   # an all-zero (or NaN) reference: absolute error
+        return float(num.max())
+    return float((num / den).max())
+
+
 def make_camera(W, H, pos=(0.3, -0.2, -1.5), target=(0, 0, 0), focal=None):
     focal = focal if focal is not None else 1.2 * W
     K = np.array([[focal, 0, (W - 1) / 2.0], [0, focal, (H - 1) / 2.0], [0, 0, 1.0]])
