@@ -233,6 +233,35 @@ int mgr_views_backward(int V, int N, int B, int n_articulated, int sh_half, int 
  * workspace's row state is that previous call's and describes these very buffers (the library checks a call counter and
  * d_xyz; V <= 8, 3..8 views, run lists on) -- otherwise every row is zeroed as without the bit. */
 
+/* mgr_views_backward plus the gradient of the loss with respect to the pose: d_transforms (V,B,16), row-major 4x4 per
+ * (view, transform), d_transforms[v][b][r][c] = sum_n skin_w[n][b] * dL/d(blended transform of Gaussian n in view v)[r][c]
+ * for r < 3; row 3 is written as zero; the background (identity) transform is a row like any other.  No reference
+ * counterpart: the reference names a pose optimizer (config/model/pose_optimizer.yaml -> src.models.pose_optimizer) that
+ * was never released.  Needs articulated rows (skin_w, n_articulated > 0); the static rows of a composite contribute nothing.
+ * d_transforms is always fully written (all-zero rows for a view in which nothing was visible), whatever `debug` says about
+ * the leaf buffers; every other output is exactly that of mgr_views_backward.  The workspace keeps its layout and everything a
+ * later forward or backward reads, with one difference: the `inst_grad` slots (mgr_raster_layout) of the lanes that held records
+ * end up holding those lanes' dL/d(blended transform) (12 floats) instead of their nine gathered sums -- every gather rewrites
+ * the slots before a backward reads them, but a tool that inspects `inst_grad` after the call sees other contents.
+ * No float atomics, bit-reproducible: the per-instance backward leaves every lane's dL/d(blended transform) in the workspace
+ * slot it read its sums from (its order of work is that of the gather's atomics and differs from run to run, so nothing is
+ * summed there); at most 1024 workgroups then walk the slots in Gaussian order, each reducing its chunks of 256 / Gv Gaussians in
+ * a fixed order in LDS and writing one partial of Gv x B x 12 floats (Gv = views per lane group: 1, 2, 4 or 8) into
+ * pose_workspace; a fold kernel adds the partials in a fixed order.  With V > 8 every group of eight views writes its own rows.
+ * pose_workspace_bytes >= mgr_views_pose_workspace_bytes(V, N, B) = min(1024, ceil(N / (256 / Gv))) x Gv x B x 12 x 4 bytes of
+ * partials (at most 12.6 MB; 8.3 MB at 21 transforms and 8 views) + N x Gv flag bytes (2.4 MB at 300 k Gaussians). */
+size_t mgr_views_pose_workspace_bytes(int V, int N, int B);
+int mgr_views_backward_pose(int V, int N, int B, int n_articulated, int sh_half, int W, int H, const float* cams, const float* bg,
+                            const float* xyz, const float* log_scale, const float* rot,
+                            const float* opacity_logit, const float* f_dc, const float* f_rest,
+                            const float* skin_w, const float* transforms, const int32_t* radii,
+                            const float* out_color, const float* dL_dcolor, float grad2d_scale, float* d_xyz,
+                            float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_f_dc,
+                            float* d_f_rest, float* d_skin_w, float* stat_grad2d, float* stat_vis,
+                            int32_t* stat_radii, void* workspace, size_t workspace_bytes,
+                            int64_t pair_capacity, int debug, float* d_transforms, void* pose_workspace,
+                            size_t pose_workspace_bytes, void* stream);
+
 /* Device pointers (into the workspace) to the compacted list of Gaussians that received a gradient in the last
  * mgr_views_backward and to its length; V <= 8. */
 int mgr_views_active_list(void* workspace, int V, int N, int W, int H, int64_t pair_capacity, const uint32_t** list,
@@ -377,6 +406,21 @@ int mgr_lbs_cov_bwd_rows(int P, int N, int B, const float* xyz, const float* log
                          const float* rot, const float* skin_w, const float* transforms,
                          const float* dL_dposed_xyz, const float* dL_dposed_cov, const float* dL_dtf, int tf_row_floats,
                          float* dL_dxyz, float* dL_dlog_scale, float* dL_drot, float* dL_dw, void* stream);
+/* Pose gradient of the modular route: what mgr_lbs_cov_bwd_rows leaves out.  dL_dtransforms (P,B,16):
+ * dL_dtransforms[p][b][r][c] = sum_n skin_w[n][b] * G[p][n][r][c] for r < 3, where G is the dL/d(blended transform) that
+ * backward forms per Gaussian before it contracts it with T_b (dL_dposed_xyz (x) [xyz, 1], the covariance path into columns
+ * 0..2, plus the incoming dL_dtf, which may be NULL); row 3 is written as zero, the background transform is a row like any
+ * other, the output is fully written.  No reference counterpart (config/model/pose_optimizer.yaml names
+ * src.models.pose_optimizer, which was never released).  B <= MGR_MAX_BONES, tf_row_floats 12 or 16; skin_w == NULL is an
+ * error (a static object has no transforms).  Two stages, no float atomics, bit-reproducible: min(1024, ceil(N / 256))
+ * workgroups per pose reduce their chunks of 256 Gaussians in a fixed order and write one partial each, a fold kernel adds
+ * the partials in a fixed order.  workspace_bytes >= mgr_lbs_pose_workspace_bytes(P, N, B) =
+ * min(1024, ceil(N / 256)) x P x B x 12 x 4 bytes. */
+size_t mgr_lbs_pose_workspace_bytes(int P, int N, int B);
+int mgr_lbs_pose_bwd(int P, int N, int B, const float* xyz, const float* log_scale, const float* rot,
+                     const float* skin_w, const float* transforms, const float* dL_dposed_xyz,
+                     const float* dL_dposed_cov, const float* dL_dtf, int tf_row_floats, float* dL_dtransforms,
+                     void* workspace, size_t workspace_bytes, void* stream);
 int mgr_sh_color_fwd_rows(int V, int N, const float* sh, const float* xyz, int64_t stride_xyz,
                           const float* tf, int64_t stride_tf, int tf_row_floats, const float* cams, float* colors,
                           void* stream);

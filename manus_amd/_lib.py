@@ -37,6 +37,9 @@ SIGNATURES = {
     "mgr_sh_to_half": (c_int, [c_int, c_vp, c_vp, c_vp]),
     "mgr_views_forward": (c_int, [c_int] * 7 + [c_vp] * 12 + [c_vp, c_sz, c_i64, c_int, c_vp]),
     "mgr_views_backward": (c_int, [c_int] * 7 + [c_vp] * 13 + [c_f32] + [c_vp] * 10 + [c_vp, c_sz, c_i64, c_int, c_vp]),
+    "mgr_views_pose_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_views_backward_pose": (c_int, [c_int] * 7 + [c_vp] * 13 + [c_f32] + [c_vp] * 10 + [c_vp, c_sz, c_i64, c_int, c_vp, c_vp, c_sz,
+                                        c_vp]),
     "mgr_raster_record_bytes": (c_int, []),
     "mgr_raster_layout": (c_int, [c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_sz), c_int]),
     "mgr_raster_status_sync": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32), c_vp]),
@@ -62,6 +65,8 @@ SIGNATURES = {
     "mgr_lbs_cov_fwd_rows": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "mgr_lbs_cov_bwd_rows": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
                                      c_vp, c_vp, c_vp, c_vp]),
+    "mgr_lbs_pose_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_lbs_pose_bwd": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
     "mgr_sh_color_fwd_rows": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
     "mgr_sh_color_bwd_rows": (c_int, [c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp]),

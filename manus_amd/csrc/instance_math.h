@@ -448,4 +448,101 @@ __device__ __forceinline__ void gather_pair_grads(uint32_t off, uint32_t cnt, co
     }
 }
 
+// ---------------------------------------------------------------------------
+// Pose gradient dL/dT[v][b] = sum_n w[n][b] * dtf[n][v]: the reduction inside one workgroup (k_lbs_pose_part in lbs_sh.hip,
+// k_pose_part_views in raster_bwd.hip).  No reference counterpart (its pose optimizer,
+// config/model/pose_optimizer.yaml -> src.models.pose_optimizer, was never released).
+//   A lane that holds a dtf parks it with its Gaussian index in LDS (MGR_POSE_REC words per lane: an odd stride, so the
+//   lane-strided stores fall in distinct banks).  pose_wg_lists turns the lanes' view indices into one lane list per view,
+//   in lane order (wave ballots + the wave counts through LDS: no atomics, the same list every run).  pose_wg_accumulate
+//   gives every (view, bone) a thread that walks its view's list front to back and keeps the twelve sums in registers
+//   (one skin weight from L1 and twelve LDS words per entry); where NV * B leaves threads over, S = 2 / 4 / 8 threads share
+//   a (view, bone), each a contiguous segment of the list, and pose_wg_store adds the segments in ascending order before it
+//   writes the workgroup's partial: slot[(v * B + b) * 12 + k].  Every order is fixed by the launch: bit-reproducible.
+// ---------------------------------------------------------------------------
+#define MGR_POSE_REC 13
+#define MGR_POSE_MAX_WG 1024   // partial slots (= workgroups) of one launch; a workgroup takes every MGR_POSE_MAX_WG-th chunk beyond that
+
+__device__ __forceinline__ int pose_segments(int NT, int nvb) {
+    int s = 1;
+    while (s < 8 && 2 * s * nvb <= NT) s *= 2;
+    return s;
+}
+
+// pv: this lane's view (0 .. NV-1) when it parked a record, -1 otherwise.  s_wc: NV * (NT / 64) words.  Two barriers.
+template <int NT>
+__device__ __forceinline__ void pose_wg_lists(int tid, int NV, int pv, unsigned char* s_lst, int* s_cnt, int* s_wc) {
+    static_assert(NT <= 256 && NT % 64 == 0, "lane ids are kept in a byte");
+    constexpr int NW = NT / 64;
+    const int lane = tid & 63, wv = tid >> 6;
+    int rank = 0;
+    for (int v = 0; v < NV; ++v) {
+        const unsigned long long m = __ballot(pv == v);
+        if (pv == v) rank = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wc[v * NW + wv] = __popcll(m);
+    }
+    __syncthreads();
+    if (pv >= 0) {
+        int base = 0;
+        for (int w = 0; w < wv; ++w) base += s_wc[pv * NW + w];
+        s_lst[pv * NT + base + rank] = (unsigned char)tid;
+    }
+    if (tid < NV) {
+        int c = 0;
+        for (int w = 0; w < NW; ++w) c += s_wc[tid * NW + w];
+        s_cnt[tid] = c;
+    }
+    __syncthreads();
+}
+
+template <int NT>
+__device__ __forceinline__ void pose_wg_accumulate(int tid, int NV, int B, const float* s_rec, const unsigned char* s_lst,
+                                                   const int* s_cnt, const float* __restrict__ skin_w, float pacc[12]) {
+    const int nvb = NV * B, S = pose_segments(NT, nvb);
+    const int seg = tid / nvb, o = tid - seg * nvb;
+    if (seg >= S) return;
+    const int v = o / B, b = o - v * B;
+    const int cnt = s_cnt[v], per = (cnt + S - 1) / S;
+    const int j1 = min(cnt, (seg + 1) * per);
+    const unsigned char* lst = s_lst + v * NT;
+#pragma unroll 4
+    for (int j = seg * per; j < j1; ++j) {
+        const float* r = s_rec + (int)lst[j] * MGR_POSE_REC;
+        const float w = skin_w[(size_t)__float_as_int(r[12]) * B + b];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) pacc[k] = __builtin_fmaf(w, r[k], pacc[k]);
+    }
+}
+
+// s_scratch: NT * 12 floats (may be the record area: the barriers are taken here)
+template <int NT>
+__device__ __forceinline__ void pose_wg_store(int tid, int NV, int B, float* s_scratch, const float pacc[12],
+                                              float* __restrict__ slot) {
+    const int nvb = NV * B, S = pose_segments(NT, nvb);
+    const int seg = tid / nvb, o = tid - seg * nvb;
+    if (S > 1) {   // (workgroup-uniform)
+        __syncthreads();
+        if (seg > 0 && seg < S) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) s_scratch[(seg * nvb + o) * 12 + k] = pacc[k];
+        }
+        __syncthreads();
+    }
+    if (seg != 0) return;
+    float a[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a[k] = pacc[k];
+    for (int s = 1; s < S; ++s) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) a[k] += s_scratch[(s * nvb + o) * 12 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) slot[o * 12 + k] = a[k];
+}
+
 #endif  // __HIPCC__
+
+// Second stage (lbs_sh.hip): d_transforms[v_first + v][b] (16 floats, row 3 zero) = the sum over the n_slots partial slots, in a
+// fixed order; v < v_count of the NV views a slot holds.
+int mgr_pose_fold(int v_first, int v_count, int NV, int B, const float* part, int n_slots, float* d_transforms,
+                  hipStream_t stream);

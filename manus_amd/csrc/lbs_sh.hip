@@ -379,6 +379,91 @@ __global__ __launch_bounds__(256) void k_lbs_bwd(int P, int N, int B, const floa
     }
 }
 
+// Pose gradient of the modular route, first stage: dL/dT[p][b] = sum_n w[n][b] * dtf[p][n], a [B x N].[N x 12] contraction
+// per pose with a 12 B-float output -- a reduction.  Workgroup (x, p) takes the chunks x, x + gridDim.x, ... of 256 Gaussians
+// of pose p; per chunk the lanes park their dtf in LDS and thread b (of segment s, see instance_math.h) walks the chunk's
+// lanes in order.  Partial slot of the workgroup: part[(x * P + p) * B * 12 ...]; k_pose_fold adds the slots.
+__global__ __launch_bounds__(256) void k_lbs_pose_part(int N, int B, int n_chunks, const float* __restrict__ xyz,
+                                                       const float* __restrict__ log_scale,
+                                                       const float* __restrict__ rot,
+                                                       const float* __restrict__ skin_w,
+                                                       const float* __restrict__ transforms,
+                                                       const float* __restrict__ g_xyz,
+                                                       const float* __restrict__ g_cov,
+                                                       const float* __restrict__ g_tf, int tfr,
+                                                       float* __restrict__ part) {
+    __shared__ float s_rec[256 * MGR_POSE_REC];
+    __shared__ unsigned char s_lst[256];
+    __shared__ int s_cnt[1], s_wc[4];
+    const int tid = threadIdx.x, p = blockIdx.y, P = gridDim.y;
+    const float* Tp = transforms + (size_t)p * B * 16;
+    float pacc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pacc[k] = 0.f;
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const int i = c * 256 + tid;
+        const bool ok = i < N;
+        if (ok) {
+            GaussCano g;
+            cano_load(xyz, log_scale, rot, i, g);
+            float dxyz[3] = {0.f, 0.f, 0.f}, ds[3] = {0.f, 0.f, 0.f};
+            float dR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            // dtf exactly as k_lbs_bwd forms it (lbs_backward_view, instance_math.h); dxyz / ds / dR are its by-products
+            const size_t pi = (size_t)p * N + i;
+            float tf[12], dtf[12];
+            blend_tf(skin_w + (size_t)i * B, Tp, B, tf);
+            const float gp[3] = {g_xyz[pi * 3], g_xyz[pi * 3 + 1], g_xyz[pi * 3 + 2]};
+            const float g6[6] = {g_cov[pi * 6], g_cov[pi * 6 + 1], g_cov[pi * 6 + 2],
+                                 g_cov[pi * 6 + 3], g_cov[pi * 6 + 4], g_cov[pi * 6 + 5]};
+            float gt[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) gt[k] = g_tf ? g_tf[pi * (size_t)tfr + k] : 0.f;
+            lbs_backward_view<true>(tf, g, gp, g6, gt, dxyz, ds, dR, dtf);
+            float* r = s_rec + tid * MGR_POSE_REC;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) r[k] = dtf[k];
+            r[12] = __int_as_float(i);
+        }
+        pose_wg_lists<256>(tid, 1, ok ? 0 : -1, s_lst, s_cnt, s_wc);
+        pose_wg_accumulate<256>(tid, 1, B, s_rec, s_lst, s_cnt, skin_w, pacc);
+        __syncthreads();   // the next chunk's records
+    }
+    pose_wg_store<256>(tid, 1, B, s_rec, pacc, part + ((size_t)blockIdx.x * P + p) * B * 12);
+}
+
+// Second stage of both routes (mgr_pose_fold, instance_math.h).  Workgroup (b, v): thread 12 s + k adds the slots s, s + 21,
+// ... of element k of (v, b) in ascending order, thread k < 12 then the 21 slices in ascending order; row 3 is written as zero.
+#define POSE_FOLD_SLICES 21
+__global__ __launch_bounds__(256) void k_pose_fold(int v_first, int NV, int B, const float* __restrict__ part, int n_slots,
+                                                   float* __restrict__ out) {
+    __shared__ float s_sum[POSE_FOLD_SLICES * 12];
+    const int tid = threadIdx.x, b = blockIdx.x, v = blockIdx.y;
+    const int n = n_slots;
+    const int k = tid % 12, s = tid / 12;
+    if (s < POSE_FOLD_SLICES) {
+        const float* src = part + ((size_t)v * B + b) * 12 + k;
+        const size_t stride = (size_t)NV * B * 12;
+        float a = 0.f;
+        for (int j = s; j < n; j += POSE_FOLD_SLICES) a += src[(size_t)j * stride];
+        s_sum[s * 12 + k] = a;
+    }
+    __syncthreads();
+    if (tid < 16) {
+        float a = 0.f;
+        if (tid < 12)
+            for (int q = 0; q < POSE_FOLD_SLICES; ++q) a += s_sum[q * 12 + tid];
+        out[((size_t)(v_first + v) * B + b) * 16 + tid] = a;
+    }
+}
+
+int mgr_pose_fold(int v_first, int v_count, int NV, int B, const float* part, int n_slots, float* d_transforms,
+                  hipStream_t stream) {
+    MGR_PROF("k_pose_fold", stream);
+    hipLaunchKernelGGL(k_pose_fold, dim3(B, v_count), dim3(256), 0, stream, v_first, NV, B, part, n_slots, d_transforms);
+    MGR_LAUNCH_CHECK("k_pose_fold", stream, 0);
+    return MGR_OK;
+}
+
 // ---------------------------------------------------------------------------
 // SH colour (degree 3)
 // ---------------------------------------------------------------------------
@@ -709,6 +794,37 @@ extern "C" int mgr_lbs_cov_bwd(int P, int N, int B, const float* xyz, const floa
                                float* dL_drot, float* dL_dw, void* stream_) {
     return mgr_lbs_cov_bwd_rows(P, N, B, xyz, log_scale, rot, skin_w, transforms, dL_dposed_xyz, dL_dposed_cov, dL_dtf, 12, dL_dxyz,
                                 dL_dlog_scale, dL_drot, dL_dw, stream_);
+}
+
+static int lbs_pose_slots(int N) {
+    const int chunks = (N + 255) / 256;
+    return chunks < MGR_POSE_MAX_WG ? chunks : MGR_POSE_MAX_WG;
+}
+extern "C" size_t mgr_lbs_pose_workspace_bytes(int P, int N, int B) {
+    if (P <= 0 || N <= 0 || B <= 0) return 0;
+    return (size_t)lbs_pose_slots(N) * P * B * 12 * sizeof(float);
+}
+extern "C" int mgr_lbs_pose_bwd(int P, int N, int B, const float* xyz, const float* log_scale, const float* rot,
+                                const float* skin_w, const float* transforms, const float* dL_dposed_xyz,
+                                const float* dL_dposed_cov, const float* dL_dtf, int tf_row_floats, float* dL_dtransforms,
+                                void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!skin_w) return mgr_fail(MGR_EINVAL, "mgr_lbs_pose_bwd: skin_w is NULL (a static object has no transforms)");
+    if (P <= 0 || P > 65535 || N < 0 || B <= 0 || B > MGR_MAX_BONES || !tf_rows_ok(tf_row_floats))
+        return mgr_fail(MGR_EINVAL, "mgr_lbs_pose_bwd: bad sizes");
+    if (!dL_dtransforms || !transforms) return mgr_fail(MGR_EINVAL, "mgr_lbs_pose_bwd: null pointer");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N == 0) {   // fully written
+        MGR_HIP(hipMemsetAsync(dL_dtransforms, 0, (size_t)P * B * 16 * sizeof(float), stream));
+        return MGR_OK;
+    }
+    if (!xyz || !log_scale || !rot || !dL_dposed_xyz || !dL_dposed_cov) return mgr_fail(MGR_EINVAL, "mgr_lbs_pose_bwd: null pointer");
+    if (!workspace || workspace_bytes < mgr_lbs_pose_workspace_bytes(P, N, B))
+        return mgr_fail(MGR_ENOMEM, "mgr_lbs_pose_bwd: workspace too small");
+    const int slots = lbs_pose_slots(N);
+    { MGR_PROF("k_lbs_pose_part", stream); hipLaunchKernelGGL(k_lbs_pose_part, dim3(slots, P), dim3(256), 0, stream, N, B, (N + 255) / 256, xyz,
+                       log_scale, rot, skin_w, transforms, dL_dposed_xyz, dL_dposed_cov, dL_dtf, tf_row_floats, (float*)workspace); }
+    MGR_LAUNCH_CHECK("k_lbs_pose_part", stream, 0);
+    return mgr_pose_fold(0, P, P, B, (const float*)workspace, slots, dL_dtransforms, stream);
 }
 
 extern "C" int mgr_sh_color_fwd_rows(int V, int N, const float* sh, const float* xyz, int64_t stride_xyz,

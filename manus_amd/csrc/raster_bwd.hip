@@ -929,7 +929,11 @@ __global__ __launch_bounds__(256) void k_inst_gather_runs(
 // lane r of the run takes the r-th set bit, lanes beyond the popcount idle), not its G views -- at eight views 41 % of the
 // (active Gaussian, view) lanes had a record (tools/instr/lane_stats.py); runs rounded up to 8 / 4 / 2 lanes take 0.53 of the
 // lanes (k_inst_bwd_runs): k_inst_bwd 0.124 -> 0.099 ms -- not 0.53 of it: per Gaussian the rows loaded and stored stay the same.
-template <int G, int BMAX, bool MIXED, bool SH_HALF, bool RUNS, int NVV = 8>
+// POSE (mgr_views_backward_pose): besides the leaf gradients, every lane of an articulated Gaussian that holds records leaves its
+// dtf (3x4) in the 48-byte iacc slot it read its sums from, and sets the slot's byte in `pose_valid`.  The order of the active
+// list / the run lists is that of the gather's atomics and differs from run to run, so the sum over the lanes is NOT taken here:
+// k_pose_part_views behind this kernel walks the slots in Gaussian order.
+template <int G, int BMAX, bool MIXED, bool SH_HALF, bool RUNS, int NVV = 8, bool POSE = false>
 __device__ __forceinline__ void inst_bwd_body(
     int blk, int n_active, const uint32_t* __restrict__ active_list,
     int v_first, int v_count, int N, int B, int n_art, int W, int H, const float* __restrict__ cams,
@@ -938,7 +942,8 @@ __device__ __forceinline__ void inst_bwd_body(
     const float* __restrict__ skin_w, const float* __restrict__ transforms, const float4* __restrict__ iacc,
     float grad2d_scale, int accumulate,
     float* __restrict__ d_xyz, float* __restrict__ d_ls, float* __restrict__ d_rot, float* __restrict__ d_op,
-    float* __restrict__ d_fdc, float* __restrict__ d_frest, float* __restrict__ d_w, float* __restrict__ st_grad2d) {
+    float* __restrict__ d_fdc, float* __restrict__ d_frest, float* __restrict__ d_w, float* __restrict__ st_grad2d,
+    unsigned char* __restrict__ pose_valid = nullptr) {
     constexpr int IPB = IB_THREADS / G;
     constexpr int NV = RUNS ? NVV : G;          // view slabs in LDS, lanes per Gaussian of iacc (NVV: the views per group of a launch with run lists)
     extern __shared__ __align__(16) float s_view[];  // NV x (camera 40 | transforms IB_TSTRIDE(B))
@@ -1060,6 +1065,15 @@ __device__ __forceinline__ void inst_bwd_body(
     if (any) {
         float dtf[12];
         lbs_backward_view<true>(tf, g, dm, dc6, gt, dxyz, ds, dR, dtf);
+        if constexpr (POSE) {
+            if (has_tf) {   // (this lane alone reads and writes the slot)
+                float4* o = const_cast<float4*>(iacc) + ((size_t)i * NV + view) * 3;
+                o[0] = make_float4(dtf[0], dtf[1], dtf[2], dtf[3]);
+                o[1] = make_float4(dtf[4], dtf[5], dtf[6], dtf[7]);
+                o[2] = make_float4(dtf[8], dtf[9], dtf[10], dtf[11]);
+                pose_valid[(size_t)i * NV + view] = 1;
+            }
+        }
         if (has_tf) {
 #pragma unroll
             for (int b = 0; b < BMAX; ++b) {
@@ -1126,8 +1140,11 @@ __global__ __launch_bounds__(IB_THREADS) __attribute__((amdgpu_waves_per_eu(MGR_
 // lane group = a run of 8 / 4 / 2 lanes (active_list: the three run lists of k_inst_gather, N entries apart): the
 // workgroups of the three classes follow each other in one launch, so that the classes share the rounds of the launch
 // (NVV = views per group of the launch: 8, 4 or 2 -- with 4 there are the classes of 4 and 2 lanes, with 2 the one of 2)
-template <int NVV, int BMAX, bool MIXED, bool SH_HALF>
-__global__ __launch_bounds__(IB_THREADS) __attribute__((amdgpu_waves_per_eu(MGR_IB_WAVES, MGR_IB_WAVES))) void k_inst_bwd_runs(MGR_IB_PARAMS) {
+#define MGR_IB_ALL                                                                                                    \
+    v_first, v_count, N, B, n_art, W, H, cams, xyz, log_scale, rot, op_logit, f_dc, f_rest, skin_w, transforms, iacc,  \
+        active_list, hdr, grad2d_scale, accumulate, d_xyz, d_ls, d_rot, d_op, d_fdc, d_frest, d_w, st_grad2d
+template <int NVV, int BMAX, bool MIXED, bool SH_HALF, bool POSE>
+__device__ __forceinline__ void inst_bwd_runs(MGR_IB_PARAMS, unsigned char* __restrict__ pose_valid) {
     const int n8 = NVV >= 8 ? (int)hdr->n_runs[0] : 0, n4 = NVV >= 4 ? (int)hdr->n_runs[1] : 0, n2 = (int)hdr->n_runs[2];
     int blk = (int)blockIdx.x;
     if (blk == 0 && threadIdx.x == 0 && hdr->rows_pending == hdr->bwd_seq) {   // the gather left the row state of this call: from
@@ -1139,14 +1156,64 @@ __global__ __launch_bounds__(IB_THREADS) __attribute__((amdgpu_waves_per_eu(MGR_
     }
     const int b8 = (n8 + IB_THREADS / 8 - 1) / (IB_THREADS / 8), b4 = (n4 + IB_THREADS / 4 - 1) / (IB_THREADS / 4);
     if constexpr (NVV >= 8) {
-        if (blk < b8) { inst_bwd_body<8, BMAX, MIXED, SH_HALF, true, NVV>(blk, n8, active_list, MGR_IB_ARGS); return; }
+        if (blk < b8) { inst_bwd_body<8, BMAX, MIXED, SH_HALF, true, NVV, POSE>(blk, n8, active_list, MGR_IB_ARGS, pose_valid); return; }
     }
     blk -= b8;
     if constexpr (NVV >= 4) {
-        if (blk < b4) { inst_bwd_body<4, BMAX, MIXED, SH_HALF, true, NVV>(blk, n4, active_list + (size_t)N, MGR_IB_ARGS); return; }
+        if (blk < b4) { inst_bwd_body<4, BMAX, MIXED, SH_HALF, true, NVV, POSE>(blk, n4, active_list + (size_t)N, MGR_IB_ARGS, pose_valid); return; }
     }
     blk -= b4;
-    inst_bwd_body<2, BMAX, MIXED, SH_HALF, true, NVV>(blk, n2, active_list + 2 * (size_t)N, MGR_IB_ARGS);
+    inst_bwd_body<2, BMAX, MIXED, SH_HALF, true, NVV, POSE>(blk, n2, active_list + 2 * (size_t)N, MGR_IB_ARGS, pose_valid);
+}
+template <int NVV, int BMAX, bool MIXED, bool SH_HALF>
+__global__ __launch_bounds__(IB_THREADS) __attribute__((amdgpu_waves_per_eu(MGR_IB_WAVES, MGR_IB_WAVES))) void k_inst_bwd_runs(MGR_IB_PARAMS) {
+    inst_bwd_runs<NVV, BMAX, MIXED, SH_HALF, false>(MGR_IB_ALL, nullptr);
+}
+
+// The POSE instantiations: the same bodies and launches with one more kernel argument (kernels of their own, so that the
+// argument list -- and with it the code -- of the POSE = false kernels stays the parent's).
+template <int G, int BMAX, bool MIXED, bool SH_HALF>
+__global__ __launch_bounds__(IB_THREADS) __attribute__((amdgpu_waves_per_eu(MGR_IB_WAVES, MGR_IB_WAVES))) void k_inst_bwd_pose(MGR_IB_PARAMS, unsigned char* __restrict__ pose_valid) {
+    inst_bwd_body<G, BMAX, MIXED, SH_HALF, false, 8, true>((int)blockIdx.x, (int)hdr->n_active, active_list, MGR_IB_ARGS, pose_valid);
+}
+template <int NVV, int BMAX, bool MIXED, bool SH_HALF>
+__global__ __launch_bounds__(IB_THREADS) __attribute__((amdgpu_waves_per_eu(MGR_IB_WAVES, MGR_IB_WAVES))) void k_inst_bwd_runs_pose(MGR_IB_PARAMS, unsigned char* __restrict__ pose_valid) {
+    inst_bwd_runs<NVV, BMAX, MIXED, SH_HALF, true>(MGR_IB_ALL, pose_valid);
+}
+
+// First stage of the pose gradient's reduction on the fused route: dL/dT[v][b] = sum_i w[i][b] * dtf[i][v] over the slots the
+// POSE kernels left, in Gaussian order.  Lane (il, v) of a chunk of 256 / NV articulated Gaussians looks at slot (i, v): a valid
+// one is parked in LDS, and the workgroup reduces the chunk as k_lbs_pose_part does (instance_math.h).  Workgroup x takes the
+// chunks x, x + gridDim.x, ... and writes ONE partial of NV x B x 12 floats (part + x * NV * B * 12; k_pose_fold adds them):
+// at most MGR_POSE_MAX_WG x 8 x 32 x 12 floats = 12.6 MB, where one slot per chunk would be 75 MB at 300 k Gaussians.
+template <int NV>
+__global__ __launch_bounds__(256) void k_pose_part_views(int n_art, int B, int n_chunks, const float4* __restrict__ iacc,
+                                                         const unsigned char* __restrict__ valid,
+                                                         const float* __restrict__ skin_w, float* __restrict__ part) {
+    constexpr int IPB = 256 / NV;
+    __shared__ float s_rec[256 * MGR_POSE_REC];
+    __shared__ unsigned char s_lst[NV * 256];
+    __shared__ int s_cnt[8], s_wc[8 * 4];
+    const int tid = threadIdx.x, vl = tid & (NV - 1), il = tid / NV;
+    float pacc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pacc[k] = 0.f;
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const int i = c * IPB + il;
+        const bool on = i < n_art && valid[(size_t)i * NV + vl] != 0;
+        if (on) {
+            const float4* o = iacc + ((size_t)i * NV + vl) * 3;
+            const float4 a = o[0], b = o[1], d = o[2];
+            float* r = s_rec + tid * MGR_POSE_REC;
+            r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w; r[4] = b.x; r[5] = b.y; r[6] = b.z; r[7] = b.w;
+            r[8] = d.x; r[9] = d.y; r[10] = d.z; r[11] = d.w;
+            r[12] = __int_as_float(i);
+        }
+        pose_wg_lists<256>(tid, NV, on ? vl : -1, s_lst, s_cnt, s_wc);
+        pose_wg_accumulate<256>(tid, NV, B, s_rec, s_lst, s_cnt, skin_w, pacc);
+        __syncthreads();   // the next chunk's records
+    }
+    pose_wg_store<256>(tid, NV, B, s_rec, pacc, part + (size_t)blockIdx.x * NV * B * 12);
 }
 
 // process-wide switch of the run lists (default on; MANUS_INST_RUNS=0 in the environment starts with them off)
@@ -1160,7 +1227,19 @@ struct CanonGrads {  // fused articulated backward: canonical inputs and leaf-gr
     float grad2d_scale;
     float *d_xyz, *d_ls, *d_rot, *d_op, *d_fdc, *d_frest, *d_w, *st_grad2d, *st_vis;
     int32_t* st_radii;
+    float *d_T, *pose_part;   // mgr_views_backward_pose: dL/dtransforms (V,B,16) and the pose workspace (partial slots | slot flags); nullptr otherwise
 };
+
+static int pose_view_slots(int n_art, int Gv) {
+    const int ipb = 256 / Gv, chunks = (n_art + ipb - 1) / ipb;
+    return chunks < MGR_POSE_MAX_WG ? chunks : MGR_POSE_MAX_WG;
+}
+static size_t pose_part_bytes(int N, int B, int Gv) { return ((size_t)pose_view_slots(N, Gv) * Gv * B * 12 * sizeof(float) + 255) & ~(size_t)255; }
+extern "C" size_t mgr_views_pose_workspace_bytes(int V, int N, int B) {
+    if (V <= 0 || N <= 0 || B <= 0) return 0;
+    const int Gv = V <= 1 ? 1 : V <= 2 ? 2 : V <= 4 ? 4 : 8;
+    return pose_part_bytes(N, B, Gv) + (size_t)N * Gv;   // partial slots (sized for n_articulated = N) | one flag byte per (Gaussian, view lane)
+}
 
 static int raster_backward_impl(int V, int N, int W, int H, const float* cams, const float* bg,
                                    const float* means3D, int64_t s_means, const float* cov3D,
@@ -1268,7 +1347,7 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
                 else if (Gv == 2) MGR_IG_LAUNCH(2);
                 else MGR_IG_LAUNCH(1);
             }
-            MGR_PROF("k_inst_bwd", stream);
+            MgrProfScope prof_ib(canon->d_T ? "k_inst_bwd_pose" : "k_inst_bwd", stream);   // (closed early on the pose route: two more kernels follow)
 #define MGR_IBR_LAUNCH(MX, HF)                                                                                        \
     if (Gv == 8) MGR_IBR_LAUNCH2(8, MX, HF); else if (Gv == 4) MGR_IBR_LAUNCH2(4, MX, HF); else MGR_IBR_LAUNCH2(2, MX, HF)
 #define MGR_IBR_LAUNCH2(NN, MX, HF)                                                                                   \
@@ -1277,6 +1356,45 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
                        canon->transforms, (const float4*)iacc, (const uint32_t*)rlist, (const MgrHeader*)hdr,         \
                        canon->grad2d_scale, accm, canon->d_xyz, canon->d_ls, canon->d_rot, canon->d_op, canon->d_fdc, \
                        canon->d_frest, canon->d_w, canon->st_grad2d)
+            if (canon->d_T) {
+                // pose gradient: the POSE instantiations leave dtf in the iacc slots; partials in Gaussian order; fold of this group's views
+                const int slots = pose_view_slots(canon->n_art, Gv);
+                unsigned char* pvalid = (unsigned char*)canon->pose_part + pose_part_bytes(N, canon->B, Gv);
+                MGR_HIP(hipMemsetAsync(pvalid, 0, (size_t)canon->n_art * Gv, stream));
+#define MGR_IP_ARGS                                                                                                   \
+    v0, vc, N, canon->B, canon->n_art, W, H, cams, canon->xyz, canon->log_scale, canon->rot, canon->op_logit, canon->f_dc,  \
+        canon->f_rest, canon->skin_w, canon->transforms, (const float4*)iacc, (const uint32_t*)(runs && Gv >= 2 ? rlist : alist), \
+        (const MgrHeader*)hdr, canon->grad2d_scale, accm, canon->d_xyz, canon->d_ls, canon->d_rot, canon->d_op,          \
+        canon->d_fdc, canon->d_frest, canon->d_w, canon->st_grad2d, pvalid
+#define MGR_IP_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, dim3(runs && Gv >= 2 ? grid.x + 3 : grid.x), dim3(IB_THREADS), lds, stream, MGR_IP_ARGS)
+#define MGR_IP_FLAGS(K, GG, BB)                                                                                       \
+    if (mixed && canon->sh_half) MGR_IP_LAUNCH((K<GG, BB, true, true>));                                               \
+    else if (mixed) MGR_IP_LAUNCH((K<GG, BB, true, false>));                                                           \
+    else if (canon->sh_half) MGR_IP_LAUNCH((K<GG, BB, false, true>));                                                  \
+    else MGR_IP_LAUNCH((K<GG, BB, false, false>))
+#define MGR_IP_VIEWS(K, BB)                                                                                           \
+    if (Gv == 8) { MGR_IP_FLAGS(K, 8, BB); } else if (Gv == 4) { MGR_IP_FLAGS(K, 4, BB); } else if (Gv == 2) { MGR_IP_FLAGS(K, 2, BB); }
+                if (runs && Gv >= 2) { MGR_IP_VIEWS(k_inst_bwd_runs_pose, 24) }
+                else if (canon->B <= 24) { MGR_IP_VIEWS(k_inst_bwd_pose, 24) else { MGR_IP_FLAGS(k_inst_bwd_pose, 1, 24); } }
+                else { MGR_IP_VIEWS(k_inst_bwd_pose, MGR_MAX_BONES) else { MGR_IP_FLAGS(k_inst_bwd_pose, 1, MGR_MAX_BONES); } }
+#undef MGR_IP_VIEWS
+#undef MGR_IP_FLAGS
+#undef MGR_IP_LAUNCH
+#undef MGR_IP_ARGS
+                MGR_LAUNCH_CHECK("k_inst_bwd_pose", stream, debug & 1);
+                if (prof_ib.on) { mgr_prof_end(stream); prof_ib.on = false; }
+                {
+                    MGR_PROF("k_pose_part_views", stream);
+                    const int n_chunks = (canon->n_art + 256 / Gv - 1) / (256 / Gv);
+#define MGR_PP_LAUNCH(NN) hipLaunchKernelGGL((k_pose_part_views<NN>), dim3(slots), dim3(256), 0, stream, canon->n_art, canon->B, n_chunks, \
+                                             (const float4*)iacc, (const unsigned char*)pvalid, canon->skin_w, canon->pose_part)
+                    if (Gv == 8) MGR_PP_LAUNCH(8); else if (Gv == 4) MGR_PP_LAUNCH(4); else if (Gv == 2) MGR_PP_LAUNCH(2); else MGR_PP_LAUNCH(1);
+#undef MGR_PP_LAUNCH
+                    MGR_LAUNCH_CHECK("k_pose_part_views", stream, debug & 1);
+                }
+                const int rc = mgr_pose_fold(v0, vc, Gv, canon->B, canon->pose_part, slots, canon->d_T, stream);
+                if (rc != MGR_OK) return rc;
+            } else
             if (runs && Gv >= 2) {
                 if (mixed && canon->sh_half) MGR_IBR_LAUNCH(true, true);
                 else if (mixed) MGR_IBR_LAUNCH(true, false);
@@ -1355,6 +1473,33 @@ extern "C" int mgr_views_backward(int V, int N, int B, int n_articulated, int sh
     const CanonGrads cg = {B, skin_w ? n_articulated : 0, sh_half ? 1 : 0, xyz, log_scale, rot, opacity_logit, f_dc, f_rest, skin_w, transforms, radii,
                            grad2d_scale, d_xyz, d_log_scale, d_rot, d_opacity_logit, d_f_dc, d_f_rest, d_skin_w,
                            stat_grad2d, stat_vis, stat_radii};
+    return raster_backward_impl(V, N, W, H, cams, bg, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, out_color,
+                                dL_dcolor, nullptr, nullptr, nullptr, nullptr, nullptr, &cg, workspace, workspace_bytes,
+                                cap, debug, stream_);
+}
+
+// mgr_views_backward plus dL/dtransforms (see include/manus_hip.h)
+extern "C" int mgr_views_backward_pose(int V, int N, int B, int n_articulated, int sh_half, int W, int H, const float* cams, const float* bg,
+                                       const float* xyz, const float* log_scale, const float* rot,
+                                       const float* opacity_logit, const float* f_dc, const float* f_rest,
+                                       const float* skin_w, const float* transforms, const int32_t* radii,
+                                       const float* out_color, const float* dL_dcolor, float grad2d_scale,
+                                       float* d_xyz, float* d_log_scale, float* d_rot, float* d_opacity_logit,
+                                       float* d_f_dc, float* d_f_rest, float* d_skin_w, float* stat_grad2d,
+                                       float* stat_vis, int32_t* stat_radii, void* workspace, size_t workspace_bytes,
+                                       int64_t cap, int debug, float* d_transforms, void* pose_workspace,
+                                       size_t pose_workspace_bytes, void* stream_) {
+    if (!skin_w || !transforms || n_articulated <= 0)
+        return mgr_fail(MGR_EINVAL, "mgr_views_backward_pose: no articulated Gaussians (a static object has no transforms)");
+    if (B <= 0 || B > MGR_MAX_BONES || V <= 0 || N <= 0 || n_articulated > N) return mgr_fail(MGR_EINVAL, "mgr_views_backward_pose: bad sizes");
+    if (!xyz || !log_scale || !rot || !opacity_logit || !f_dc || !f_rest || !radii || !d_xyz || !d_log_scale || !d_rot ||
+        !d_opacity_logit || !d_f_dc || !d_f_rest || !d_skin_w || !d_transforms)
+        return mgr_fail(MGR_EINVAL, "mgr_views_backward_pose: null pointer");
+    if (!pose_workspace || pose_workspace_bytes < mgr_views_pose_workspace_bytes(V, N, B))
+        return mgr_fail(MGR_ENOMEM, "mgr_views_backward_pose: pose workspace too small");
+    const CanonGrads cg = {B, n_articulated, sh_half ? 1 : 0, xyz, log_scale, rot, opacity_logit, f_dc, f_rest, skin_w, transforms, radii,
+                           grad2d_scale, d_xyz, d_log_scale, d_rot, d_opacity_logit, d_f_dc, d_f_rest, d_skin_w,
+                           stat_grad2d, stat_vis, stat_radii, d_transforms, (float*)pose_workspace};
     return raster_backward_impl(V, N, W, H, cams, bg, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, out_color,
                                 dL_dcolor, nullptr, nullptr, nullptr, nullptr, nullptr, &cg, workspace, workspace_bytes,
                                 cap, debug, stream_);

@@ -547,7 +547,7 @@ class HipViewCompute:
 
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
-                 persistent_grads=True):
+                 persistent_grads=True, pose_grad=False):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -569,6 +569,12 @@ class HipViewCompute:
         self.n_art = N if (self.kind == "hand" and has_grid) else (int(scene["n_hand"]) if (self.kind == "composite" and has_grid) else 0)
         self.is_hand = self.n_art > 0
         self.device = self.params["_xyz"].device
+        # -- pose_grad True: the step's output dict gains "d_transforms" (len(view_ids), B, 4, 4) = dL/d(bone transforms of the
+        # view's pose), on the scale of `grads` (fused: mgr_views_backward_pose; modular: autograd with the transforms a leaf of
+        # the step).  No reference counterpart (its pose optimizer was never released); `manus_amd.pose` builds on it.
+        self.pose_grad = bool(pose_grad)
+        if self.pose_grad and not self.is_hand:
+            raise ValueError("pose_grad needs articulated Gaussians: a %r scene without a skin grid has no bone transforms" % self.kind)
         self.grid = ops.SkinGrid(scene["grid"], scene["grid"].device) if self.is_hand else None
         self._w_cache = None            # forward-only skin weights of the current model state (forward_views_fused under no_grad)
         # -- image loss.  "l1": mean|render - gt| (rgb_loss alone); "l1+ssim": w_rgb * rgb_loss + w_ssim * ssim_loss, the image
@@ -596,6 +602,7 @@ class HipViewCompute:
         self.persistent_grads = bool(persistent_grads)
         self._kept = _KeptBuffers()
         self.grad_arena = None
+        self._pose_ws = None            # partial slots of mgr_views_backward_pose (kept across steps)
         # -- sh_storage "fp16" (BASELINE config 5): the fused kernels read an fp16 copy of _features_rest (96 B instead of
         # 180 B per Gaussian and view group); arithmetic, gradients and the optimizer's master copy stay fp32.  The copy
         # is refreshed lazily after the leaves changed (`mark_params_changed`).  The reference has no fp16 mode:
@@ -701,14 +708,15 @@ class HipViewCompute:
             tf = torch.cat([tf, otf.expand(P, -1, -1)], dim=1)
         return pxyz, pcov, tf
 
-    def forward_views(self, view_ids):
+    def forward_views(self, view_ids, T=None):
+        """T: the bone transforms to pose with instead of the scene's (the pose-gradient step passes a leaf)."""
         s, p, ops = self.s, self.params, self.ops
         sel = self._select(view_ids)
         cams = sel["cams"]
         V = len(view_ids)
         feats = torch.cat([p["_features_dc"], p["_features_rest"]], dim=1)
         opac = torch.sigmoid(p["_opacity"])
-        pxyz, pcov, tf = self._posed(sel["T"])   # one pose per view (the reference trains one (frame, view) per step)
+        pxyz, pcov, tf = self._posed(sel["T"] if T is None else T)   # one pose per view (the reference trains one (frame, view) per step)
         col = ops.sh_colors(feats, p["_xyz"], tf, cams)
         N = p["_xyz"].shape[0]
         means2D = torch.zeros((V, N, 3), dtype=torch.float32, device=cams.device, requires_grad=True)
@@ -832,7 +840,7 @@ class HipViewCompute:
             if route != "overlap" and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
             loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
-            grads, d_w, st_g, st_v, st_r = self._backward(ws, fwd, g_img, scale)
+            grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale)
             active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"])
             overflow = ws.buf[4:8].view(torch.int32)
         except BaseException:
@@ -847,7 +855,10 @@ class HipViewCompute:
                 ws.busy = False
         self.last_image, self.last_radii = out, radii
         self.last_active = active      # (device pointers into the workspace of this step: valid until the next forward on it)
-        return dict(grads=grads, grad2d=st_g, vis=st_v, radii=st_r, loss=loss, overflow=overflow)
+        res = dict(grads=grads, grad2d=st_g, vis=st_v, radii=st_r, loss=loss, overflow=overflow)
+        if d_T is not None:
+            res["d_transforms"] = d_T
+        return res
 
     def _skin_weights(self, xyz, na):
         """(skin weights (na,B) of the articulated rows, B); (None, 0) without any."""
@@ -944,7 +955,7 @@ class HipViewCompute:
 
     def _backward(self, ws, fwd, g_img, scale):
         """mgr_views_backward into the kept buffers, the arena or fresh tensors: (leaf gradients, skin-weight gradient,
-        grad2d, vis, radii)."""
+        grad2d, vis, radii, dL/dtransforms or None)."""
         head, out, radii, kept = fwd
         V, N, B, na = head[:4]
         dev = self.device
@@ -958,12 +969,21 @@ class HipViewCompute:
         # zero fill of the rows it knows to be zero (it checks that its row state is that call's; bit 512)
         bits = 512 if (kept is not None and kept.grad_ws is ws and V <= 8) else 0
         self._kept.grad_ws = None
-        check(lib().mgr_views_backward(*head, ptr(radii), ptr(out), ptr(g_img), 1.0 / scale, *[ptr(g) for g in grads.values()],
-                                       ptr(d_w), ptr(st_g), ptr(st_v), ptr(st_r), ptr(ws.buf), ws.nbytes, ws.cap, bits, stream()),
-              "mgr_views_backward")
+        args = (*head, ptr(radii), ptr(out), ptr(g_img), 1.0 / scale, *[ptr(g) for g in grads.values()],
+                ptr(d_w), ptr(st_g), ptr(st_v), ptr(st_r), ptr(ws.buf), ws.nbytes, ws.cap, bits)
+        d_T = None
+        if self.pose_grad:
+            d_T = torch.empty((V, B, 4, 4), dtype=torch.float32, device=dev)
+            nbytes = int(lib().mgr_views_pose_workspace_bytes(V, N, B))
+            if self._pose_ws is None or self._pose_ws.numel() < nbytes:
+                self._pose_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            check(lib().mgr_views_backward_pose(*args, ptr(d_T), ptr(self._pose_ws), self._pose_ws.numel(), stream()),
+                  "mgr_views_backward_pose")
+        else:
+            check(lib().mgr_views_backward(*args, stream()), "mgr_views_backward")
         if kept is not None:
             kept.handed_out(ws)
-        return grads, d_w, st_g, st_v, st_r
+        return grads, d_w, st_g, st_v, st_r, d_T
 
     def _skin_backward(self, ws, head, xyz, d_w, d_xyz):
         """The backward's list of the Gaussians that received a gradient (device pointers: list, length; None beyond 8 views)
@@ -991,15 +1011,20 @@ class HipViewCompute:
         self.last_active = None
         for v in self.params.values():
             v.grad = None
-        img, radii, means2D = self.forward_views(view_ids)
-        tgt = self._select(view_ids)["targets"]
+        sel = self._select(view_ids)
+        T = sel["T"].detach().requires_grad_(True) if self.pose_grad else None     # a leaf for this step
+        img, radii, means2D = self.forward_views(view_ids, T=T)
+        tgt = sel["targets"]
         loss, g = self._image_loss(img, tgt, scale)
         img.backward(g)
         vis = radii > 0
         g2 = means2D.grad[..., :2].norm(dim=-1) * (1.0 / scale)
-        return dict(grads={n: v.grad for n, v in self.params.items()},
-                    grad2d=(g2 * vis).sum(0), vis=vis.sum(0).float(),
-                    radii=radii.max(dim=0).values, loss=loss)
+        res = dict(grads={n: v.grad for n, v in self.params.items()},
+                   grad2d=(g2 * vis).sum(0), vis=vis.sum(0).float(),
+                   radii=radii.max(dim=0).values, loss=loss)
+        if T is not None:
+            res["d_transforms"] = T.grad
+        return res
 
     def pairs_per_view(self, view_ids=None, group=8):
         """Surviving (tile, Gaussian) pairs of every view (forward only, in groups of `group` views): the weights of the

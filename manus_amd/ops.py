@@ -83,6 +83,7 @@ class _LbsCov(torch.autograd.Function):
         N = xyz.shape[0]
         if skin_w is not None:
             skin_w = f32c(skin_w)
+            t_shape = transforms.shape
             transforms = f32c(transforms)
             if transforms.dim() == 3:
                 transforms = transforms[None]
@@ -91,7 +92,7 @@ class _LbsCov(torch.autograd.Function):
                 raise ManusHipError("lbs_cov: skin weights have %d columns, %d transforms given"
                                     % (skin_w.shape[1], B))  # hand_dynamic.py:104
         else:
-            P, B = 1, 0
+            P, B, t_shape = 1, 0, None
         dev = xyz.device
         pxyz = torch.empty((P, N, 3), dtype=torch.float32, device=dev)
         pcov = torch.empty((P, N, 6), dtype=torch.float32, device=dev)
@@ -101,6 +102,7 @@ class _LbsCov(torch.autograd.Function):
                                          ptr(pxyz), ptr(pcov), ptr(tf), rows, stream()), "mgr_lbs_cov_fwd")
         ctx.save_for_backward(xyz, log_scale, rot, skin_w, transforms)
         ctx.meta = (P, N, B, rows)
+        ctx.t_shape = t_shape
         return pxyz, pcov, tf
 
     @staticmethod
@@ -118,7 +120,15 @@ class _LbsCov(torch.autograd.Function):
         check(lib().mgr_lbs_cov_bwd_rows(P, N, B, ptr(xyz), ptr(log_scale), ptr(rot), ptr(skin_w), ptr(transforms),
                                          ptr(g_xyz), ptr(g_cov), ptr(g_tf), rows, ptr(d_xyz), ptr(d_ls), ptr(d_rot),
                                          ptr(d_w), stream()), "mgr_lbs_cov_bwd")
-        return d_xyz, d_ls, d_rot, d_w, None, None
+        d_t = None
+        if ctx.needs_input_grad[4] and skin_w is not None:      # the pose gradient (no reference counterpart): two more launches
+            d_t = torch.empty((P, B, 4, 4), dtype=torch.float32, device=dev)
+            nbytes = int(lib().mgr_lbs_pose_workspace_bytes(P, N, B))
+            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+            check(lib().mgr_lbs_pose_bwd(P, N, B, ptr(xyz), ptr(log_scale), ptr(rot), ptr(skin_w), ptr(transforms), ptr(g_xyz),
+                                         ptr(g_cov), ptr(g_tf), rows, ptr(d_t), ptr(ws), nbytes, stream()), "mgr_lbs_pose_bwd")
+            d_t = d_t.reshape(ctx.t_shape)
+        return d_xyz, d_ls, d_rot, d_w, d_t, None
 
 
 def lbs_cov(xyz, log_scale, rot, skin_w, transforms, tf44=False):
@@ -126,7 +136,8 @@ def lbs_cov(xyz, log_scale, rot, skin_w, transforms, tf44=False):
 
     xyz (N,3), log_scale (N,3) (`_scaling`), rot (N,4) raw (`_rotation`),
     skin_w (N,B) or None (static object: identity transform),
-    transforms (P,B,4,4) / (B,4,4) = posed @ inv(rest) (+ identity background).
+    transforms (P,B,4,4) / (B,4,4) = posed @ inv(rest) (+ identity background); differentiable (`mgr_lbs_pose_bwd`:
+    the gradient has the shape of `transforms`, its rows 3 are zero).
     Returns posed_xyz (P,N,3), posed_cov (P,N,6), tf (P,N,12) (rows 0..2 of the
     blended 4x4) -- or, with tf44, (P,N,4,4): the reference's layout, constant last row included, written by the kernel."""
     return _LbsCov.apply(xyz, log_scale, rot, skin_w, transforms, bool(tf44))
