@@ -82,8 +82,10 @@ enum {
     MGR_EOVERFLOW = -4, /* pair capacity exceeded (reported by mgr_raster_status_sync) */
     MGR_ECUT = -6,      /* a forward run with the depth cut (debug bit 8) met a scene its hints no longer fit: its image is
                            incomplete; run it again without the bit (reported by mgr_raster_status_sync) */
-    MGR_ETIER = -7      /* a forward told to skip binning launches (debug bits 16 / 32) had a view that needed one: its image
+    MGR_ETIER = -7,     /* a forward told to skip binning launches (debug bits 16 / 32) had a view that needed one: its image
                            is incomplete; run it again without the bits */
+    MGR_ESTATE = -8     /* the workspace does not hold what the call needs (mgr_raster_blend_features: no complete forward
+                           of these sizes, or one whose tile lists are cut short or clipped) */
 };
 
 int mgr_version(void);
@@ -181,6 +183,40 @@ int mgr_raster_backward(int V, int N, int W, int H, const float* cams, const flo
                         const float* dL_dcolor, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors,
                         float* dL_dopacity, float* dL_dcov3D, void* workspace,
                         size_t workspace_bytes, int64_t pair_capacity, int debug, void* stream);
+
+/* Feature render: composite C caller channels, and optionally expected depth and accumulated opacity, over the tile lists
+ * the LAST FORWARD left in `workspace` -- no projection, no sort, no binning.  Forward only (no gradient).
+ *   out_feat[v, c, y, x] = sum_i w_i features[v, gid_i, c] + T_final bg_feat[c],   w_i = alpha_i T_i
+ * with exactly the (pixel, entry) contributions of that forward's image: the same alpha arithmetic and keep rule
+ * (alpha >= 1/255, clamped to 0.99), the same stop rule (an entry that would bring T below 1e-4 ends the pixel's walk and
+ * contributes nothing), the same list order.  Rendering the forward's colours as features reproduces its image up to the
+ * rounding of the sums.
+ * features: (N, C) rows shared by the views (stride_features = 0) or (V, N, C) with a view stride in floats (>= N * C); a row
+ * may start at any 4-byte alignment.  0 <= C <= 32; C = 0 is allowed when with_depth is set or out_alpha is given.
+ * bg_feat: C floats, NULL = zeros.
+ * out_feat: (V, C + (with_depth ? 1 : 0), H, W), every element written.  With with_depth the LAST channel is the EXPECTED
+ * depth sum_i w_i z_i, z = the view-space depth the forward sorted by: it is not divided by the accumulated opacity and its
+ * background is 0 (divide by out_alpha for a normalised depth).  out_alpha: (V, H, W) = 1 - T_final, or NULL.
+ * Pixels of tiles without a list get bg_feat, depth 0, alpha 0.
+ * Valid between a complete forward on `workspace` (mgr_raster_forward or mgr_views_forward, same V, N, W, H and
+ * pair_capacity) and the next forward on it.  A backward in between is fine: mgr_raster_backward / mgr_views_backward write
+ * the pair-gradient records and tags, the per-instance gradient rows and the header's backward counters, none of which this
+ * call reads (it reads the queue records, the sorted lists, the geometry half of the per-(view, Gaussian) records and the
+ * depths).  The workspace is only read.  One blocking read of its header decides, before anything is launched, whether the
+ * lists are usable; MGR_ESTATE (text in mgr_last_error) when
+ *   - no forward has run on the workspace, or the last one stopped before its blend (debug bit 1, value 2),
+ *   - the last forward applied the depth cut (mgr_views_forward debug bits 8 / 2048: lists cut short, repaired entries
+ *     behind the regular ones),
+ *   - the last forward raised an overflow bit (pair capacity, depth cut, skipped binning tier),
+ *   - the last forward was made for another V, N, W, H or pair_capacity.
+ * The depth-cut refusal reads what the call that ran the blend was given: a forward split with debug values 2 / 4 must pass
+ * bit 8 to BOTH calls (as the forward's own comment asks) -- a blend-only call without it stamps lists cut by the first call
+ * as uncut.
+ * A tile's list is walked once per group of up to 8 channels (groups of 8, 4 or 2 accumulators per lane; the depth is the
+ * last group's last slot, out_alpha is written by the first group). */
+int mgr_raster_blend_features(int V, int N, int C, int W, int H, const float* features, int64_t stride_features,
+                              const float* bg_feat, int with_depth, float* out_feat, float* out_alpha,
+                              const void* workspace, size_t workspace_bytes, int64_t pair_capacity, void* stream);
 
 /* ------------------------------------------------------------------------
  * Fused articulated path (training engine): canonical parameters in, image out.

@@ -34,6 +34,8 @@ SIGNATURES = {
     "mgr_raster_backward": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
                                     c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                                     c_i64, c_int, c_vp]),
+    "mgr_raster_blend_features": (c_int, [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp, c_sz,
+                                          c_i64, c_vp]),
     "mgr_sh_to_half": (c_int, [c_int, c_vp, c_vp, c_vp]),
     "mgr_views_forward": (c_int, [c_int] * 7 + [c_vp] * 12 + [c_vp, c_sz, c_i64, c_int, c_vp]),
     "mgr_views_backward": (c_int, [c_int] * 7 + [c_vp] * 13 + [c_f32] + [c_vp] * 10 + [c_vp, c_sz, c_i64, c_int, c_vp]),

@@ -139,7 +139,11 @@ struct MgrHeader {            // first 256 bytes of the workspace
     uint32_t sort_near_large; // items beyond 13/16 of MGR_DB_RANK_LARGE (bits 16..23 of the reported tiers word; sort_big -- bits 8..15 --
                               // counts those beyond 13/16 of MGR_DB_RANK_MAX: the caller skips the launch behind by the one that
                               // belongs to the instantiation it is going to ask for)
-    uint32_t spare[45 - sizeof(MgrRep) / 4];
+    // feature render (mgr_raster_blend_features, raster_feat.hip): the forward whose blend last completed on this workspace
+    // (k_fwd_items copies fwd_seq here: a forward stopped before its blend leaves the two apart), what it was made for
+    // (V, N, W, H, pair capacity) and MGR_FEAT_* bits -- all the host needs to tell whether the tile lists are a complete forward's
+    uint32_t feat_seq, feat_dims[5], feat_flags;
+    uint32_t spare[45 - 7 - sizeof(MgrRep) / 4];
     uint32_t queue_giant;     // queue index of the first tile with fewer than 16384 pairs
     uint32_t n_groups;        // depth groups produced by k_tile_split for the giant tiles
     uint32_t split_head, group_head;
@@ -153,6 +157,11 @@ struct MgrHeader {            // first 256 bytes of the workspace
     uint32_t qctr_f[16 * 64];
 };
 #define MGR_NCTR 16
+#define MGR_HOLE 0xFFFFFFFEu   // a position of the view-interleaved queue (tile_qrec) its view has no tile for
+#define MGR_FEAT_CUT 1u        // MgrHeader::feat_flags: the forward applied the depth cut (lists cut short, repaired behind the regular entries)
+struct MgrFeatStamp {          // what k_fwd_items leaves in MgrHeader::feat_dims / feat_flags
+    uint32_t dims[5], flags;
+};
 // bits of MgrHeader::overflow
 #define MGR_OVF_PAIRS 1u   // the pair capacity was exceeded: lists clipped, image and gradients incomplete
 #define MGR_OVF_CUT 2u     // a tile whose list was cut short by the depth cut ran out of entries with a pixel still unsaturated

@@ -626,7 +626,6 @@ struct DbinArgs {   // depth-bucket side of the two tile-scan launches (ordered 
     int items_per_view, zr_slots;      // (zr_slots: workgroups of the per-instance kernel per view = slots of db_zrange per view)
 };
 
-#define MGR_HOLE 0xFFFFFFFEu   // a position of the view-interleaved queue its view has no tile for
 #define DBR_MAX_ITEMS 4096    // sort items per view the bucket scan can table in LDS (1 M instances per view; beyond: the radix launch sorts everything)
 #define MGR_NCLS 34
 
@@ -2954,7 +2953,7 @@ __global__ __launch_bounds__(256) void k_fwd_items(const uint4* __restrict__ til
                                                    float cut_range, float cut_rel, int gx, int interior_only,
                                                    const uint32_t* __restrict__ tile_queue, int VT, unsigned char* __restrict__ tile_bgok,
                                                    const float* out_color, const float* __restrict__ bg, const MgrRep rep, uint32_t cut_penalty,
-                                                   uint32_t* __restrict__ tile_zwin, const IlListArgs ll, int n_item_blocks) {
+                                                   uint32_t* __restrict__ tile_zwin, const IlListArgs ll, int n_item_blocks, const MgrFeatStamp stamp) {
     __shared__ uint32_t s_scan[8];
     if ((int)blockIdx.x >= n_item_blocks) {      // the workgroups behind the items': the span list of the image loss (il_list.h), when attached
         const int lb = (int)blockIdx.x - n_item_blocks;
@@ -2989,6 +2988,10 @@ __global__ __launch_bounds__(256) void k_fwd_items(const uint4* __restrict__ til
         hdr->img_seq = hdr->fwd_seq;
         hdr->img_owner[0] = (uint32_t)owner; hdr->img_owner[1] = (uint32_t)(owner >> 32);
         hdr->img_bg[0] = __float_as_uint(bg[0]); hdr->img_bg[1] = __float_as_uint(bg[1]); hdr->img_bg[2] = __float_as_uint(bg[2]);
+        // ... and the tile lists are a complete forward's: what mgr_raster_blend_features checks before it walks them again
+        hdr->feat_seq = hdr->fwd_seq;
+        for (int k = 0; k < 5; ++k) hdr->feat_dims[k] = stamp.dims[k];
+        hdr->feat_flags = stamp.flags;
     }
     if (blockIdx.x >= nb) return;
     // strided over the queue (which is ordered by depth): every block gets its share of the deep tiles
@@ -3439,13 +3442,14 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
         ll.tile_start = tile_start;
     }
     const int n_item_blocks = (VT + 255) / 256;
+    const MgrFeatStamp stamp = {{(uint32_t)V, (uint32_t)N, (uint32_t)W, (uint32_t)H, (uint32_t)cap}, use_cut ? MGR_FEAT_CUT : 0u};
     { MGR_PROF("k_fwd_items", stream); hipLaunchKernelGGL(k_fwd_items, dim3((unsigned)(n_item_blocks + ll.nbx * V)), dim3(256), 0, stream, (const uint4*)(ws + L.tile_qrec),
                        (const uint32_t*)(ws + L.tile_qdone), (uint32_t*)(ws + L.tile_done), (uint4*)(ws + L.items), hdr,
                        N, T, (const uint32_t*)(ws + L.sorted_gid), (const float*)(ws + L.depth), (const uint32_t*)(ws + L.tile_zused),
                        (const uint32_t*)(ws + L.tile_qend), (uint32_t*)(ws + L.tile_zcut), mgr_take_status_mirror(workspace),
                        g_cut_frac, (uint32_t)g_cut_min, g_cut_range, g_cut_rel, gx, g_cut_interior,
                        (const uint32_t*)(ws + L.tile_queue), VT, (unsigned char*)(ws + L.tile_bgok), (const float*)out_color, bg, rep_all,
-                       (uint32_t)g_cut_penalty, (uint32_t*)(ws + L.tile_zwin), ll, n_item_blocks); }
+                       (uint32_t)g_cut_penalty, (uint32_t*)(ws + L.tile_zwin), ll, n_item_blocks, stamp); }
     MGR_LAUNCH_CHECK("k_blend_fwd", stream, debug);
     return MGR_OK;
 }

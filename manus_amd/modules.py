@@ -108,9 +108,13 @@ def _contact(pt1, pt2, search, c_thresh):
 
 def contact_render_inputs(pred, camera, render_type, cmap_type="magma", alpha=0.3, acc_dist=None, hand_model=None,
                           obj_model=None, nocs_grid=None, skin_colors=None, search="near", c_thresh=0.004,
-                          reference_opacity_rows=False):
+                          reference_opacity_rows=False, geometry=None):
     """What `render_contacts` hands to `render_gaussians` for one render type: Pred(dist, posed_xyz, posed_cov,
     colors_precomp, opacity), with the reference's choice of positions / covariances / colours (composite.py:150-206).
+
+    `geometry`: what this function returned for another render type of the SAME positions ('hand_only' / 'accumulated',
+    'acc_gt_eval' / 'skin_wts'): covariances and opacities are then taken from it -- the same tensor objects, nothing computed
+    again -- and only the colours are this type's (CompositeRenderer(share_binning=True)).
 
     Opacities: the reference passes the opacities of the WHOLE composite (hand rows first) next to the n rows of ONE body,
     and its rasterizer reads the first n of them -- right for the hand, the hand's first n_object values for the object.
@@ -150,7 +154,8 @@ def contact_render_inputs(pred, camera, render_type, cmap_type="magma", alpha=0.
         colors = contact.contact_table_colors(dist, need(nocs_grid, "nocs_grid"), idx)
     elif render_type == "accumulated":
         dist = need(acc_dist, "acc_dist")
-        xyz, cov = h.cano_xyz, _canonical_cov(need(hand_model, "hand_model"))
+        # (the one type whose covariances would be computed again for a shared render: taken from `geometry` when given)
+        xyz, cov = h.cano_xyz, geometry.posed_cov if geometry is not None else _canonical_cov(need(hand_model, "hand_model"))
         colors = contact.contact_colors(dist, cmap_type, sh_colors_of(h), alpha)
     elif render_type == "acc_gt_eval":
         dist = need(acc_dist, "acc_dist")
@@ -166,6 +171,10 @@ def contact_render_inputs(pred, camera, render_type, cmap_type="magma", alpha=0.
         opacity = pred.cano_opacity[:n]
     else:
         opacity = pred.cano_opacity[n_h:]
+    if geometry is not None:
+        if geometry.posed_xyz is not xyz:
+            raise ValueError("geometry= comes from a render type with other positions than %r" % (render_type,))
+        cov, opacity = geometry.posed_cov, geometry.opacity
     return Pred(dist=dist, posed_xyz=xyz, posed_cov=cov, colors_precomp=colors, opacity=opacity)
 
 
@@ -192,8 +201,13 @@ class CompositeRenderer:
     additions ((h0 + h1) + h2) + ...).  `reset()` starts a new sequence."""
 
     def __init__(self, hand_model, obj_model, render_contact_type="results", nocs_grid=None, skin_colors=None, acc_contacts=None,
-                 sh_degree=3, search="near", c_thresh=0.004, reference_opacity_rows=False):
+                 sh_degree=3, search="near", c_thresh=0.004, reference_opacity_rows=False, share_binning=False):
         self.hand_model, self.obj_model = hand_model, obj_model
+        # share_binning: the second render of a pair that shows the same Gaussians through the same camera in other colours
+        # ('hand_only' + 'accumulated', 'acc_gt_eval' + 'skin_wts') is composited on the first render's tile lists
+        # (rasterizer.blend_features) instead of projecting, sorting and binning them again -- the same contributions, the
+        # panel equal up to the rounding of its sums
+        self.share_binning = bool(share_binning)
         self.render_contact_type = render_contact_type
         self.nocs_grid, self.skin_colors, self.acc_contacts = nocs_grid, skin_colors, acc_contacts
         self.sh_degree = sh_degree
@@ -234,26 +248,58 @@ class CompositeRenderer:
         return render_gaussians(pred.posed_xyz, pred.posed_cov, pred.cano_xyz, pred.cano_features, pred.cano_opacity,
                                 batch["camera"], batch["bg_color"], None, sh_degree=self.sh_degree, tf=pred.tf)
 
+    def _first_of_pair(self, pred, batch, camera, rtype, *a, **k):
+        """`render_contacts` that keeps what the second render of the pair shares: (inputs, image)."""
+        from .rasterizer import context
+        from .render import render_gaussians
+        r = contact_render_inputs(pred, camera, rtype, *a, **dict(self.kw, **k))
+        img = render_gaussians(r.posed_xyz, r.posed_cov, pred.cano_xyz, pred.cano_features, r.opacity, camera, batch["bg_color"],
+                               r.colors_precomp, sh_degree=3, tf=pred.tf)["render"]
+        r["camera"], r["workspace"] = camera, context(r.posed_xyz.device).last_ws
+        return r, img
+
+    def _second_of_pair(self, pred, batch, camera, first, rtype, *a, **k):
+        """(dist, image) of `rtype` composited on the tile lists of the render `first` came from."""
+        from .rasterizer import blend_features, context
+        r = contact_render_inputs(pred, camera, rtype, *a, **dict(self.kw, geometry=first, **k))
+        assert r.posed_xyz is first.posed_xyz and r.posed_cov is first.posed_cov and r.opacity is first.opacity
+        assert camera is first.camera and context(r.posed_xyz.device).last_ws is first.workspace
+        out = blend_features(r.colors_precomp, bg=batch["bg_color"], device=r.posed_xyz.device)
+        return r.dist, out["features"][0].permute(1, 2, 0)
+
     def render(self, batch, render_contact_type=None):
         kind = self.render_contact_type if render_contact_type is None else render_contact_type
         pred = composite_pred(self.hand_model, self.obj_model, batch)
         rc = lambda camera, rtype, *a, **k: render_contacts(pred, batch, camera, rtype, *a, **dict(self.kw, **k))
+
+        def hand_pair():      # 'hand_only' and 'accumulated': the canonical hand through the canonical camera, twice
+            if not self.share_binning:
+                h_dist, h_cmap = rc(batch["cano_camera"], "hand_only")
+                _, acc_h_cmap = rc(batch["cano_camera"], "accumulated", acc_dist=self._accumulate(h_dist))
+                return h_cmap, acc_h_cmap
+            first, h_cmap = self._first_of_pair(pred, batch, batch["cano_camera"], "hand_only")
+            _, acc_h_cmap = self._second_of_pair(pred, batch, batch["cano_camera"], first, "accumulated",
+                                                 acc_dist=self._accumulate(first.dist))
+            return h_cmap, acc_h_cmap
+
         rendered = None
         if kind == "gt_eval":
-            h_dist, h_cmap = rc(batch["cano_camera"], "hand_only")
-            _, acc_h_cmap = rc(batch["cano_camera"], "accumulated", acc_dist=self._accumulate(h_dist))
+            h_cmap, acc_h_cmap = hand_pair()
             panels = [h_cmap, acc_h_cmap]
         elif kind == "acc_gt_eval":
             if self.acc_contacts is None:
                 raise ValueError("'acc_gt_eval' colours the recorded sum `acc_contacts`")
-            _, acc_h_cmap = rc(batch["camera"], "acc_gt_eval", "gray", 0, self.acc_contacts)
-            _, skin_wts = rc(batch["camera"], "skin_wts", "gray", 0, None)
+            if self.share_binning:
+                first, acc_h_cmap = self._first_of_pair(pred, batch, batch["camera"], "acc_gt_eval", "gray", 0, self.acc_contacts)
+                _, skin_wts = self._second_of_pair(pred, batch, batch["camera"], first, "skin_wts", "gray", 0, None)
+            else:
+                _, acc_h_cmap = rc(batch["camera"], "acc_gt_eval", "gray", 0, self.acc_contacts)
+                _, skin_wts = rc(batch["camera"], "skin_wts", "gray", 0, None)
             panels = [skin_wts, acc_h_cmap]
         elif kind == "results":
             rendered = self._rgb(pred, batch)
             _, o_cmap = rc(batch["camera"], "object_only")
-            h_dist, h_cmap = rc(batch["cano_camera"], "hand_only")
-            _, acc_h_cmap = rc(batch["cano_camera"], "accumulated", acc_dist=self._accumulate(h_dist))
+            h_cmap, acc_h_cmap = hand_pair()
             panels = [rendered["render"], h_cmap, o_cmap, acc_h_cmap]
         elif kind == "nocs":
             rendered = self._rgb(pred, batch)

@@ -477,6 +477,60 @@ def rasterize_views(cams, means3D, means2D, colors, opacities, cov3D, bg, W, H, 
                                      _builds_graph(means3D, means2D, colors, opacities, cov3D))
 
 
+MAX_FEATURE_CHANNELS = 32
+
+
+def _feature_request(features, bg, depth, alpha):
+    """The checks of a feature render that need no device: (C, bg as a flat fp32 tensor or None).  ManusHipError on a request
+    the library would refuse for its shape alone."""
+    C = 0
+    if features is not None:
+        if not torch.is_tensor(features) or features.dim() not in (2, 3):
+            raise _lib.ManusHipError("features must be a tensor (N,C), shared by the views, or (V,N,C)")
+        C = int(features.shape[-1])
+        if not 1 <= C <= MAX_FEATURE_CHANNELS:
+            raise _lib.ManusHipError("features carry %d channels; 1 .. %d are supported" % (C, MAX_FEATURE_CHANNELS))
+    if C == 0 and not depth and not alpha:
+        raise _lib.ManusHipError("nothing to render: no features, no depth, no alpha")
+    if bg is not None:
+        bg = torch.as_tensor(bg, dtype=torch.float32).reshape(-1)
+        if bg.numel() != C:
+            raise _lib.ManusHipError("bg has %d values for %d feature channels" % (bg.numel(), C))
+    return C, bg
+
+
+def blend_features(features=None, bg=None, depth=False, alpha=False, device=None):
+    """Composite other per-Gaussian values over the tile lists of the context's LAST forward (mgr_raster_blend_features): no
+    projection, no sort, no binning, and exactly the contributions of that forward's image.  features (N,C) shared by the
+    views or (V,N,C), 1 <= C <= 32 (a non-contiguous tensor is copied); bg: C values (None: zeros).  Returns
+    {"features": (V,C,H,W), "depth": (V,H,W), "alpha": (V,H,W)}, None for what was not asked for.  `depth` is the EXPECTED
+    depth sum_i w_i z_i (not divided by alpha, background 0), `alpha` the accumulated opacity 1 - T.  Forward only: no
+    gradient flows through it.  ManusHipError when the context has no forward, or its last forward left no complete lists
+    (stopped before the blend, depth cut applied, overflow raised)."""
+    C, bg = _feature_request(features, bg, depth, alpha)
+    with torch.no_grad():
+        ctx = context(device)
+        ws = ctx.last_ws
+        if ws is None:
+            raise _lib.ManusHipError("blend_features: no forward has run on this context")
+        V, N, W, H = ws.key
+        dev = ws.buf.device
+        s_f = 0
+        if features is not None:
+            if features.shape[-2] != N or (features.dim() == 3 and features.shape[0] != V):
+                raise _lib.ManusHipError("features %s do not fit the last forward's %d views of %d Gaussians" % (tuple(features.shape), V, N))
+            features = f32c(features.detach().to(dev))
+            s_f = N * C if features.dim() == 3 else 0
+        if bg is not None:
+            bg = bg.to(dev).contiguous()
+        n_out = C + (1 if depth else 0)
+        out = torch.empty((V, n_out, H, W), dtype=torch.float32, device=dev) if n_out else None
+        out_a = torch.empty((V, H, W), dtype=torch.float32, device=dev) if alpha else None
+        check(lib().mgr_raster_blend_features(V, N, C, W, H, ptr(features), s_f, ptr(bg), int(bool(depth)), ptr(out), ptr(out_a),
+                                              ptr(ws.buf), ws.nbytes, ws.cap, stream()), "mgr_raster_blend_features")
+        return {"features": out[:, :C] if C else None, "depth": out[:, C] if depth else None, "alpha": out_a}
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()

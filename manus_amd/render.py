@@ -6,7 +6,7 @@ import torch
 
 from . import _lib
 from .ops import sh_colors
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _feature_request, blend_features
 
 
 def _tf12(tf):
@@ -40,9 +40,20 @@ def calculate_colors_from_sh(posed_means, cano_features, cano_means, camera, sh_
 
 
 def render_gaussians(posed_means, posed_cov, cano_means, cano_features, cano_opacity, camera, bg_color,
-                     colors_precomp=None, sh_degree=3, tf=None, device=None):
+                     colors_precomp=None, sh_degree=3, tf=None, device=None, extra_features=None, return_depth=False,
+                     return_alpha=False, feature_bg=None):
     """gaussian_utils.py:349-428: same arguments, same returned dict
-    (`render` (H,W,3), `viewspace_points`, `visibility_filter`, `radii`)."""
+    (`render` (H,W,3), `viewspace_points`, `visibility_filter`, `radii`).
+
+    Beyond the reference: `extra_features` (N,C), 1 <= C <= 32, `return_depth`, `return_alpha` add the keys `features`
+    (H,W,C; background `feature_bg`, C values, default zeros), `depth` (H,W; expected depth sum_i w_i z_i, not divided by
+    alpha) and `alpha` (H,W; accumulated opacity) -- composited over the tile lists of this render
+    (rasterizer.blend_features), without gradient.  Without them the dict is the reference's."""
+    extras = extra_features is not None or return_depth or return_alpha
+    if extras:
+        _feature_request(extra_features, feature_bg, return_depth, return_alpha)
+        if extra_features is not None and (extra_features.dim() != 2 or extra_features.shape[0] != posed_means.shape[0]):
+            raise _lib.ManusHipError("extra_features must be (N,C) with one row per Gaussian")
     device = posed_means.device if device is None else device
     screenspace_points = torch.zeros_like(posed_means, dtype=posed_means.dtype, requires_grad=True,
                                           device=device) + 0
@@ -65,5 +76,14 @@ def render_gaussians(posed_means, posed_cov, cano_means, cano_features, cano_opa
                                        colors_precomp=colors_precomp, opacities=cano_opacity, scales=None,
                                        rotations=None, cov3D_precomp=posed_cov)
     rendered_image = torch.permute(rendered_image, (1, 2, 0))
-    return {"render": rendered_image, "viewspace_points": screenspace_points,
-            "visibility_filter": radii > 0, "radii": radii}
+    out = {"render": rendered_image, "viewspace_points": screenspace_points,
+           "visibility_filter": radii > 0, "radii": radii}
+    if extras:
+        r = blend_features(extra_features, bg=feature_bg, depth=return_depth, alpha=return_alpha, device=device)
+        if extra_features is not None:
+            out["features"] = r["features"][0].permute(1, 2, 0)
+        if return_depth:
+            out["depth"] = r["depth"][0]
+        if return_alpha:
+            out["alpha"] = r["alpha"][0]
+    return out
