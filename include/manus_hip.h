@@ -80,13 +80,47 @@ enum {
     MGR_ENOMEM = -2,   /* workspace too small (see mgr_raster_workspace_bytes) */
     MGR_EHIP = -3,     /* a HIP call failed; text in mgr_last_error() */
     MGR_EOVERFLOW = -4, /* pair capacity exceeded (reported by mgr_raster_status_sync) */
-    MGR_ECUT = -6,      /* a forward run with the depth cut (debug bit 8) met a scene its hints no longer fit: its image is
-                           incomplete; run it again without the bit (reported by mgr_raster_status_sync) */
-    MGR_ETIER = -7,     /* a forward told to skip binning launches (debug bits 16 / 32) had a view that needed one: its image
-                           is incomplete; run it again without the bits */
+    MGR_ECUT = -6,      /* a forward run with the depth cut (MGR_FWD_DEPTH_CUT) met a scene its hints no longer fit: its image is
+                           incomplete; run it again without the flag (reported by mgr_raster_status_sync) */
+    MGR_ETIER = -7,     /* a forward told to skip binning launches (MGR_FWD_SKIP_*) had a view that needed one: its image
+                           is incomplete; run it again without those flags */
     MGR_ESTATE = -8     /* the workspace does not hold what the call needs (mgr_raster_blend_features: no complete forward
                            of these sizes, or one whose tile lists are cut short or clipped) */
 };
+
+/* `flags` of mgr_raster_forward / mgr_views_forward, OR-ed together (0 = none); spelt out at mgr_raster_forward. */
+#define MGR_FWD_CHECK 1              /* synchronise and check after every kernel (upstream's `debug=True`) */
+#define MGR_FWD_NO_BLEND 2           /* stop before the blend */
+#define MGR_FWD_BLEND_ONLY 4         /* the blend only */
+#define MGR_FWD_DEPTH_CUT 8          /* mgr_views_forward only: apply the depth-cut hints */
+#define MGR_FWD_SKIP_BOX_LARGE 16    /* skip the binning launches for tile boxes of more than 2048 tiles */
+#define MGR_FWD_SKIP_BOX_MID 32      /* skip the binning launch for tile boxes of 1537..2048 tiles */
+#define MGR_FWD_SKIP_SORT_BEHIND 128 /* skip the radix launch behind the instance sort (k_dbin_rank) */
+#define MGR_FWD_RANK_LARGE 256       /* k_dbin_rank's instantiation for items of up to 3072 keys */
+#define MGR_FWD_IMAGE_KEPT 1024      /* the caller vouches that out_color is the kept image (see below mgr_views_backward) */
+#define MGR_FWD_REPAIR 2048          /* with MGR_FWD_DEPTH_CUT: repair depth-cut tiles on the device instead of flagging */
+#define MGR_FWD_SPREAD 4096          /* k_bin_scatter's lane-spreading instantiation */
+
+/* `flags` of mgr_raster_backward / mgr_views_backward / mgr_views_backward_pose. */
+#define MGR_BWD_CHECK 1              /* synchronise and check after every kernel */
+#define MGR_BWD_OUTPUTS_KEPT 512     /* mgr_views_backward*: the caller vouches for the leaf-gradient buffers (see there) */
+
+/* The overflow word of a forward (mgr_raster_status_sync, word 1 of the status mirror): non-zero = the image is incomplete. */
+#define MGR_OVF_PAIRS 1u   /* the pair capacity was exceeded: lists clipped, image and gradients incomplete (MGR_EOVERFLOW) */
+#define MGR_OVF_CUT 2u     /* a tile's depth-cut list ran out of entries with a pixel still unsaturated (MGR_ECUT) */
+#define MGR_OVF_TIER 4u    /* a view needed a binning launch the caller had asked to skip, MGR_FWD_SKIP_* (MGR_ETIER) */
+#define MGR_OVF_FLAGS_MASK 0xFFFF  /* the status mirror's word carries, above the flags, ... */
+#define MGR_OVF_REPAIRED_SHIFT 16  /* ... the number of (tile, quadrant) units the forward repaired on the device */
+
+/* The tiers word of a forward (mgr_raster_status_tiers_sync, word 2 of the status mirror): what its views needed. */
+#define MGR_TIERS_BOX_LARGE 1          /* a view's tile box had more than 2048 tiles: do not pass MGR_FWD_SKIP_BOX_LARGE */
+#define MGR_TIERS_BOX_MID 2            /* one had 1537..2048 tiles: do not pass MGR_FWD_SKIP_BOX_MID */
+#define MGR_TIERS_WIDE_RECT 4          /* rectangles of more than 64 tiles were met: pass MGR_FWD_SPREAD */
+#define MGR_TIERS_NEAR_SMALL_SHIFT 8   /* bits 8..15: items of the instance sort beyond 13/16 of k_dbin_rank's 2048 keys ... */
+#define MGR_TIERS_NEAR_LARGE_SHIFT 16  /* bits 16..23: ... and of the 3072 keys of MGR_FWD_RANK_LARGE (both capped at 255) */
+#define MGR_TIERS_NEAR_MASK 0xFF
+#define MGR_TIERS_BEYOND_SMALL_SHIFT 24 /* bits 24..30: items beyond 2048 keys (capped at 127): pass MGR_FWD_RANK_LARGE */
+#define MGR_TIERS_BEYOND_SMALL_MASK 0x7F
 
 int mgr_version(void);
 /* 0 for the product build.  Non-zero when the library was compiled with one of the instrumentation macros of tools/instr
@@ -96,7 +130,7 @@ int mgr_version(void);
  * non-default MGR_BIN_BLOCK: results unchanged).  bench.py labels such a run and refuses to call it the headline; the parity
  * block does not run on a library that reports bit 0. */
 int mgr_build_variant(void);
-/* Tiles per view (ceil(W/16) * ceil(H/16)) up to which the depth cut's on-device repair (mgr_views_forward debug bit 2048) is
+/* Tiles per view (ceil(W/16) * ceil(H/16)) up to which the depth cut's on-device repair (mgr_views_forward with MGR_FWD_REPAIR) is
  * used; on a larger grid a depth-cut tile that runs out flags the forward (MGR_ECUT) and the caller runs it again uncut. */
 int mgr_raster_repair_max_tiles(void);
 /* Thread-local text of the last error returned on this host thread. */
@@ -121,53 +155,58 @@ size_t mgr_raster_workspace_bytes(int V, int N, int W, int H, int64_t pair_capac
  * If the number of pairs exceeds pair_capacity the image is still written but
  * is incomplete and the overflow flag is raised: check with
  * mgr_raster_status_sync and retry with a larger workspace.
- * debug (here and in mgr_views_forward) is a bit set: 1 = synchronise and check after every kernel (upstream's
- * `debug=True`); 2 = stop before the blend (projection and binning only: radii, the pair total and the tile lists are
- * final, out_color is not written); 4 = the blend only, after a call with bit 2 on the same workspace and arguments.
- * Bits 2 / 4 let a caller put work that needs the tile lists but not the image next to the blend (the image loss's
- * span list, mgr_image_loss_tiles_list).  The tile lists come from the depth-ordered binning; MGR_BINNING=sorted in
- * the environment selects the per-tile sorts instead (identical lists).
- * 8 (mgr_views_forward only) = depth cut.  Every forward leaves, per tile whose pixels all saturated, the depth in front
- * of which they had all stopped plus a margin; with bit 8 the next forward on the same workspace leaves the instances
- * behind that depth out of the tile's list (they lie behind every pixel's stop: image, n_contrib and gradients are bit
- * for bit those of the full lists, but the binning handles a fraction of the pairs).  Only valid when that previous
- * forward rendered the SAME views (camera + pose) of a model that has moved little since; if a cut list runs out under
- * a pixel that has not saturated the forward raises the overflow word's bit 1 (mgr_raster_status_sync: MGR_ECUT) and
- * the caller runs it again without bit 8.  Pass the bit to both calls of a forward split with bits 2 / 4.  No
- * counterpart upstream (the reference renders one view per step and re-bins everything).
- * 2048 (with bit 8) = repair on the device.  A tile whose cut list runs out under an unsaturated pixel is completed by
- * two kernels behind the blend instead of flagging the forward: the instances the cut dropped from that tile are found
- * (one pass over the view's rectangles), sorted by (depth, index) -- the tail of the tile's full list --, appended
- * behind the regular lists, and the walks of the tile's unsaturated quadrants continue from their saved state; the
- * backward's work items of such a tile point at the appended entries / checkpoints.  Image, n_contrib and gradients
- * stay bit for bit those of the full lists and NO re-run is needed; MGR_ECUT is only raised when a capacity of the repair
- * is exceeded (repaired quadrants, 256 tiles per view, 8192 entries behind the cut of one tile, the appended entries: all
- * sized from pair_capacity), or when a hinted tile ends up with no list at all.  A tile that ran out gets no hint for the
- * next mgr_raster_set_cut_penalty forwards (the same few tiles at the rim of the saturating region otherwise run out
- * step after step under a moving model).  The status mirror's overflow word carries the number of repaired quadrants
- * of the forward in its bits 16..31.
- * 16 / 32 = skip the binning launches that only serve views whose box of non-empty tiles has more than 2048 / has
- * 1537..2048 tiles (they hold more LDS per workgroup; three launches of ~6 us each that do nothing for smaller boxes).
- * mgr_raster_status_tiers_sync reports which of them a forward needed (bit 0 / bit 1); pass the bits for the tiers the
- * previous forward did not need.  A view that needs a skipped launch raises the overflow word's bit 2 (MGR_ETIER).
- * 128 = skip the launch behind the instance sort.  Since round 6 the (depth, index) keys of a view are sorted in items of
- * ~768 keys, one workgroup each (k_dbin_rank: depth buckets uniform over the depth range of the view's visible instances in
- * this forward); an item of more than 2048 keys -- a dense depth slice -- is left to a radix launch behind, which returns at
- * once when there is none.  Bit 128 omits that launch (mgr_raster_status_tiers_sync reported no item near the limit for the
- * previous forward: bits 8..15 of its tiers word for the usual instantiation, bits 16..23 for the one bit 256 asks for);
- * an item that needs it then raises the overflow word's bit 2 (MGR_ETIER:
- * run the forward again without the bit), like a skipped tile-box tier.  256 = k_dbin_rank's instantiation for items of up
- * to 3072 keys (the previous forward met items of more than 2048: bits 24..30 of the tiers word) -- ~4 us slower for all its
- * items, but the dense slice no longer waits for the launch behind (33 us).  4096 = k_bin_scatter's lane-spreading
- * instantiation (the previous forward met rectangles of more than 64 tiles: bit 2 of the tiers word): a batch that holds such
- * a rectangle is spread over lanes, one row piece per lane, instead of going instance by instance (correct either way;
- * cameras close to the hand: 1.2 -> 0.87 ms).  Without the bit the producer is the plain one of round 5. */
+ * flags (here and in mgr_views_forward): MGR_FWD_* OR-ed together.  The tile lists come from the depth-ordered binning
+ * whatever the flags; MGR_BINNING=sorted in the environment selects the per-tile sorts instead (identical lists).
+ *   MGR_FWD_CHECK  synchronise and check after every kernel (upstream's `debug=True`).
+ *   MGR_FWD_NO_BLEND  stop before the blend (projection and binning only): radii, the pair total and the tile lists are
+ *     final, out_color is not written.
+ *   MGR_FWD_BLEND_ONLY  the blend only, after a call with MGR_FWD_NO_BLEND on the same workspace and arguments.  The pair lets
+ *     a caller put work that needs the tile lists but not the image next to the blend (the image loss's span list,
+ *     mgr_image_loss_tiles_list).
+ *   MGR_FWD_DEPTH_CUT  (mgr_views_forward only) depth cut.  Every forward leaves, per tile whose pixels all saturated, the
+ *     depth in front of which they had all stopped plus a margin; with this flag the next forward on the same workspace leaves
+ *     the instances behind that depth out of the tile's list (they lie behind every pixel's stop: image, n_contrib and
+ *     gradients are bit for bit those of the full lists, but the binning handles a fraction of the pairs).  Only valid when
+ *     that previous forward rendered the SAME views (camera + pose) of a model that has moved little since; if a cut list
+ *     runs out under a pixel that has not saturated the forward raises MGR_OVF_CUT (mgr_raster_status_sync: MGR_ECUT) and
+ *     the caller runs it again without the flag.  Pass it to both calls of a forward split with MGR_FWD_NO_BLEND /
+ *     MGR_FWD_BLEND_ONLY.  No counterpart upstream (the reference renders one view per step and re-bins everything).
+ *   MGR_FWD_REPAIR  (with MGR_FWD_DEPTH_CUT) repair on the device.  A tile whose cut list runs out under an unsaturated pixel
+ *     is completed by two kernels behind the blend instead of flagging the forward: the instances the cut dropped from that
+ *     tile are found (one pass over the view's rectangles), sorted by (depth, index) -- the tail of the tile's full list --,
+ *     appended behind the regular lists, and the walks of the tile's unsaturated quadrants continue from their saved state;
+ *     the backward's work items of such a tile point at the appended entries / checkpoints.  Image, n_contrib and gradients
+ *     stay bit for bit those of the full lists and NO re-run is needed; MGR_OVF_CUT is only raised when a capacity of the
+ *     repair is exceeded (repaired quadrants, 256 tiles per view, 8192 entries behind the cut of one tile, the appended
+ *     entries: all sized from pair_capacity), or when a hinted tile ends up with no list at all.  A tile that ran out gets no
+ *     hint for the next mgr_raster_set_cut_penalty forwards (the same few tiles at the rim of the saturating region otherwise
+ *     run out step after step under a moving model).  The status mirror's overflow word carries the number of repaired
+ *     quadrants of the forward above MGR_OVF_REPAIRED_SHIFT.
+ *   MGR_FWD_SKIP_BOX_LARGE, MGR_FWD_SKIP_BOX_MID  skip the binning launches that only serve views whose box of non-empty
+ *     tiles has more than 2048 / has 1537..2048 tiles (they hold more LDS per workgroup; three launches of ~6 us each that do
+ *     nothing for smaller boxes).  mgr_raster_status_tiers_sync reports which of them a forward needed (MGR_TIERS_BOX_LARGE /
+ *     MGR_TIERS_BOX_MID); pass the flags for the tiers the previous forward did not need.  A view that needs a skipped launch
+ *     raises MGR_OVF_TIER (MGR_ETIER).
+ *   MGR_FWD_SKIP_SORT_BEHIND  skip the launch behind the instance sort.  Since round 6 the (depth, index) keys of a view are
+ *     sorted in items of ~768 keys, one workgroup each (k_dbin_rank: depth buckets uniform over the depth range of the view's
+ *     visible instances in this forward); an item of more than 2048 keys -- a dense depth slice -- is left to a radix launch
+ *     behind, which returns at once when there is none.  The flag omits that launch (mgr_raster_status_tiers_sync reported no
+ *     item near the limit for the previous forward: the tiers word's field at MGR_TIERS_NEAR_SMALL_SHIFT for the usual
+ *     instantiation, at MGR_TIERS_NEAR_LARGE_SHIFT for the one MGR_FWD_RANK_LARGE asks for); an item that needs it then raises
+ *     MGR_OVF_TIER (MGR_ETIER: run the forward again without the flag), like a skipped tile-box tier.
+ *   MGR_FWD_RANK_LARGE  k_dbin_rank's instantiation for items of up to 3072 keys (the previous forward met items of more than
+ *     2048: the tiers word's field at MGR_TIERS_BEYOND_SMALL_SHIFT) -- ~4 us slower for all its items, but the dense slice no
+ *     longer waits for the launch behind (33 us).
+ *   MGR_FWD_SPREAD  k_bin_scatter's lane-spreading instantiation (the previous forward met rectangles of more than 64 tiles:
+ *     MGR_TIERS_WIDE_RECT): a batch that holds such a rectangle is spread over lanes, one row piece per lane, instead of going
+ *     instance by instance (correct either way; cameras close to the hand: 1.2 -> 0.87 ms).  Without the flag the producer is
+ *     the plain one of round 5.  (MGR_FWD_IMAGE_KEPT: see below mgr_views_backward.) */
 int mgr_raster_forward(int V, int N, int W, int H, const float* cams, const float* bg,
                        const float* means3D, int64_t stride_means3D, const float* cov3D,
                        int64_t stride_cov3D, const float* colors, int64_t stride_colors,
                        const float* opacity, int64_t stride_opacity, float* out_color,
                        int32_t* radii, void* workspace, size_t workspace_bytes,
-                       int64_t pair_capacity, int debug, void* stream);
+                       int64_t pair_capacity, int flags, void* stream);
 
 /* Backward of the forward that last used `workspace` (same inputs again, plus the
  * image that forward produced: out_color (V,3,H,W)).
@@ -182,7 +221,7 @@ int mgr_raster_backward(int V, int N, int W, int H, const float* cams, const flo
                         const float* opacity, int64_t stride_opacity, const float* out_color,
                         const float* dL_dcolor, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors,
                         float* dL_dopacity, float* dL_dcov3D, void* workspace,
-                        size_t workspace_bytes, int64_t pair_capacity, int debug, void* stream);
+                        size_t workspace_bytes, int64_t pair_capacity, int flags, void* stream);
 
 /* Feature render: composite C caller channels, and optionally expected depth and accumulated opacity, over the tile lists
  * the LAST FORWARD left in `workspace` -- no projection, no sort, no binning.  Forward only (no gradient).
@@ -204,13 +243,13 @@ int mgr_raster_backward(int V, int N, int W, int H, const float* cams, const flo
  * call reads (it reads the queue records, the sorted lists, the geometry half of the per-(view, Gaussian) records and the
  * depths).  The workspace is only read.  One blocking read of its header decides, before anything is launched, whether the
  * lists are usable; MGR_ESTATE (text in mgr_last_error) when
- *   - no forward has run on the workspace, or the last one stopped before its blend (debug bit 1, value 2),
- *   - the last forward applied the depth cut (mgr_views_forward debug bits 8 / 2048: lists cut short, repaired entries
+ *   - no forward has run on the workspace, or the last one stopped before its blend (MGR_FWD_NO_BLEND),
+ *   - the last forward applied the depth cut (mgr_views_forward with MGR_FWD_DEPTH_CUT: lists cut short, repaired entries
  *     behind the regular ones),
- *   - the last forward raised an overflow bit (pair capacity, depth cut, skipped binning tier),
+ *   - the last forward raised an MGR_OVF_* bit (pair capacity, depth cut, skipped binning tier),
  *   - the last forward was made for another V, N, W, H or pair_capacity.
- * The depth-cut refusal reads what the call that ran the blend was given: a forward split with debug values 2 / 4 must pass
- * bit 8 to BOTH calls (as the forward's own comment asks) -- a blend-only call without it stamps lists cut by the first call
+ * The depth-cut refusal reads what the call that ran the blend was given: a forward split with MGR_FWD_NO_BLEND / MGR_FWD_BLEND_ONLY must pass
+ * MGR_FWD_DEPTH_CUT to BOTH calls (as the forward's own comment asks) -- a blend-only call without it stamps lists cut by the first call
  * as uncut.
  * A tile's list is walked once per group of up to 8 channels (groups of 8, 4 or 2 accumulators per lane; the depth is the
  * last group's last slot, out_alpha is written by the first group). */
@@ -242,7 +281,7 @@ int mgr_views_forward(int V, int N, int B, int n_articulated, int sh_half, int W
                       const float* xyz, const float* log_scale, const float* rot,
                       const float* opacity_logit, const float* f_dc, const float* f_rest,
                       const float* skin_w, const float* transforms, float* out_color, int32_t* radii,
-                      void* workspace, size_t workspace_bytes, int64_t pair_capacity, int debug,
+                      void* workspace, size_t workspace_bytes, int64_t pair_capacity, int flags,
                       void* stream);
 int mgr_views_backward(int V, int N, int B, int n_articulated, int sh_half, int W, int H, const float* cams, const float* bg,
                        const float* xyz, const float* log_scale, const float* rot,
@@ -252,29 +291,29 @@ int mgr_views_backward(int V, int N, int B, int n_articulated, int sh_half, int 
                        float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_f_dc,
                        float* d_f_rest, float* d_skin_w, float* stat_grad2d, float* stat_vis,
                        int32_t* stat_radii, void* workspace, size_t workspace_bytes,
-                       int64_t pair_capacity, int debug, void* stream);
+                       int64_t pair_capacity, int flags, void* stream);
 
-/* debug bit 1024 of mgr_views_forward / mgr_raster_forward = "image kept": the caller vouches that out_color is the image the
+/* MGR_FWD_IMAGE_KEPT of mgr_views_forward / mgr_raster_forward = "image kept": the caller vouches that out_color is the image the
  * previous complete forward on this workspace wrote, untouched since.  A tile that held the background colour then and is
  * empty again is not written again (85 % of the tiles of a capture-like frame are empty: 170 MB of stores at eight 1080p
  * views); the image is identical.  Honoured only when the header says so: that forward was the last one binned on this
- * workspace, wrote this very buffer, with this background colour -- otherwise every empty tile is written as without the bit.
- * (Without the bit the background of the empty tiles is written by extra workgroups of the instance sort's launch when the
+ * workspace, wrote this very buffer, with this background colour -- otherwise every empty tile is written as without the flag.
+ * (Without the flag the background of the empty tiles is written by extra workgroups of the instance sort's launch when the
  * depth-ordered binning runs, by the blend otherwise; MANUS_BG_FILL=blend in the environment: always by the blend.) */
 
-/* debug of mgr_views_backward: bit 1 as above.  Bit 512 = "outputs kept": the caller vouches that the leaf-gradient buffers
+/* flags of mgr_views_backward: MGR_BWD_CHECK as in the forward.  MGR_BWD_OUTPUTS_KEPT = "outputs kept": the caller vouches that the leaf-gradient buffers
  * (d_xyz ... d_skin_w, stat_grad2d) are the ones the previous mgr_views_backward on this workspace wrote, untouched since
  * (persistent .grad-like tensors).  The backward then zeroes only the rows that call wrote and this one does not, instead
  * of every row of every buffer (97 MB of stores on the bench step); the results are identical.  Honoured only when the
  * workspace's row state is that previous call's and describes these very buffers (the library checks a call counter and
- * d_xyz; V <= 8, 3..8 views, run lists on) -- otherwise every row is zeroed as without the bit. */
+ * d_xyz; V <= 8, 3..8 views, run lists on) -- otherwise every row is zeroed as without the flag. */
 
 /* mgr_views_backward plus the gradient of the loss with respect to the pose: d_transforms (V,B,16), row-major 4x4 per
  * (view, transform), d_transforms[v][b][r][c] = sum_n skin_w[n][b] * dL/d(blended transform of Gaussian n in view v)[r][c]
  * for r < 3; row 3 is written as zero; the background (identity) transform is a row like any other.  No reference
  * counterpart: the reference names a pose optimizer (config/model/pose_optimizer.yaml -> src.models.pose_optimizer) that
  * was never released.  Needs articulated rows (skin_w, n_articulated > 0); the static rows of a composite contribute nothing.
- * d_transforms is always fully written (all-zero rows for a view in which nothing was visible), whatever `debug` says about
+ * d_transforms is always fully written (all-zero rows for a view in which nothing was visible), whatever `flags` says about
  * the leaf buffers; every other output is exactly that of mgr_views_backward.  The workspace keeps its layout and everything a
  * later forward or backward reads, with one difference: the `inst_grad` slots (mgr_raster_layout) of the lanes that held records
  * end up holding those lanes' dL/d(blended transform) (12 floats) instead of their nine gathered sums -- every gather rewrites
@@ -295,7 +334,7 @@ int mgr_views_backward_pose(int V, int N, int B, int n_articulated, int sh_half,
                             float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_f_dc,
                             float* d_f_rest, float* d_skin_w, float* stat_grad2d, float* stat_vis,
                             int32_t* stat_radii, void* workspace, size_t workspace_bytes,
-                            int64_t pair_capacity, int debug, float* d_transforms, void* pose_workspace,
+                            int64_t pair_capacity, int flags, float* d_transforms, void* pose_workspace,
                             size_t pose_workspace_bytes, void* stream);
 
 /* Device pointers (into the workspace) to the compacted list of Gaussians that received a gradient in the last
@@ -333,7 +372,7 @@ int mgr_raster_record_bytes(void);
 /* Blocking read-back of the workspace header after a forward: total number of
  * (Gaussian, tile) pairs (`num_rendered`, summed over views) and the overflow
  * flag.  Returns MGR_EOVERFLOW when the flag is set. */
-/* Margins of the depth-cut hints the forwards of this host thread leave (debug bit 8): a tile keeps the entries its walks
+/* Margins of the depth-cut hints the forwards of this host thread leave (MGR_FWD_DEPTH_CUT): a tile keeps the entries its walks
  * used plus max(min_entries, frac_entries x that many), and at least the depth of the last one plus depth_range_frac of the
  * walked depth range plus depth_rel of that depth.  interior_only: hints only for tiles whose eight neighbours saturated
  * too (a silhouette tile stops saturating when an edge moves by a fraction of a pixel).  Defaults 0.125, 64, 0.0625, 2e-4, 0.
@@ -348,11 +387,8 @@ int mgr_raster_set_cut_penalty(int forwards);
  * caller zeroes word 3 beforehand and keeps the memory alive until it has read it.  (The reference's rasterizer returns
  * num_rendered through a blocking read-back, SURVEY App. A.) */
 int mgr_raster_set_status_mirror(const void* workspace, void* host_words);
-/* mgr_raster_status_sync plus `tiers` (see debug bits 16 / 32 / 128 / 256 / 4096 of the forward): bit 0 = a view's tile box
- * had more than 2048 tiles, bit 1 = one had 1537..2048, bit 2 = rectangles of more than 64 tiles were met (pass bit 4096
- * next time); bits 8..15 / 16..23 = items of the instance sort beyond 13/16 of k_dbin_rank's 2048 / 3072 keys (capped at
- * 255): zero in the field that belongs to the instantiation the next forward asks for lets it pass bit 128; bits 24..30 =
- * items beyond 2048 keys (pass bit 256 next time). */
+/* mgr_raster_status_sync plus `tiers`: the MGR_TIERS_* word, from which the caller picks the next forward's MGR_FWD_SKIP_*,
+ * MGR_FWD_RANK_LARGE and MGR_FWD_SPREAD. */
 int mgr_raster_status_tiers_sync(const void* workspace, int64_t* num_pairs, int32_t* overflow, int32_t* tiers,
                                  void* stream);
 int mgr_raster_status_sync(const void* workspace, int64_t* num_pairs, int32_t* overflow,
@@ -547,7 +583,7 @@ int mgr_image_loss_tiles(int V, int H, int W, const float* pred, const float* ta
                          float* dL_dpred, float* sums, void* workspace, size_t workspace_bytes, void* stream);
 /* mgr_image_loss_tiles in two calls.  _list builds the span list: it needs the forward's tile offsets but not its
  * image, so it can run on another stream while the forward blend runs (mgr_views_forward / mgr_raster_forward with
- * debug bit 1 = "stop before the blend", then bit 2 = "the blend only").  _finish does the rest on that list (same
+ * MGR_FWD_NO_BLEND, then MGR_FWD_BLEND_ONLY).  _finish does the rest on that list (same
  * workspace; the caller orders it after both the list and the blend). */
 int mgr_image_loss_tiles_list(int V, int H, int W, const float* target, const float* bg3, const uint32_t* tile_start,
                               void* workspace, size_t workspace_bytes, void* stream);

@@ -20,6 +20,18 @@ _LIB = None
 MGR_CAM_FLOATS = 40
 MGR_MAX_BONES = 32
 
+# The words of the rasterizer's ABI, value for value those of include/manus_hip.h (tests/test_abi_constants.py compares them).
+# Plain ints: the operator route is bound by host time, and enum.IntFlag arithmetic costs microseconds per operation.
+MGR_OK, MGR_EINVAL, MGR_ENOMEM, MGR_EHIP, MGR_EOVERFLOW, MGR_ECUT, MGR_ETIER, MGR_ESTATE = 0, -1, -2, -3, -4, -6, -7, -8
+MGR_FWD_CHECK, MGR_FWD_NO_BLEND, MGR_FWD_BLEND_ONLY, MGR_FWD_DEPTH_CUT = 1, 2, 4, 8
+MGR_FWD_SKIP_BOX_LARGE, MGR_FWD_SKIP_BOX_MID, MGR_FWD_SKIP_SORT_BEHIND, MGR_FWD_RANK_LARGE = 16, 32, 128, 256
+MGR_FWD_IMAGE_KEPT, MGR_FWD_REPAIR, MGR_FWD_SPREAD = 1024, 2048, 4096
+MGR_BWD_CHECK, MGR_BWD_OUTPUTS_KEPT = 1, 512
+MGR_OVF_PAIRS, MGR_OVF_CUT, MGR_OVF_TIER, MGR_OVF_FLAGS_MASK, MGR_OVF_REPAIRED_SHIFT = 1, 2, 4, 0xFFFF, 16
+MGR_TIERS_BOX_LARGE, MGR_TIERS_BOX_MID, MGR_TIERS_WIDE_RECT = 1, 2, 4
+MGR_TIERS_NEAR_SMALL_SHIFT, MGR_TIERS_NEAR_LARGE_SHIFT, MGR_TIERS_NEAR_MASK = 8, 16, 0xFF
+MGR_TIERS_BEYOND_SMALL_SHIFT, MGR_TIERS_BEYOND_SMALL_MASK = 24, 0x7F
+
 c_int, c_i64, c_f32, c_vp, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 # name -> (restype, argtypes); must list every symbol of include/manus_hip.h

@@ -112,22 +112,22 @@ struct MgrHeader {            // first 256 bytes of the workspace
     uint32_t acc_pairs, acc_flags;
     // ordered binning: LDS tiers the views' tile boxes of the most recent forward needed beyond the smallest one
     // (bit 0: a box of more than 2048 tiles, bit 1: one of 1537..2048) -- a caller may skip the launches of tiers the
-    // previous forward did not need (debug bits 16 / 32); a skipped tier that IS needed raises MGR_OVF_TIER
+    // previous forward did not need (MGR_FWD_SKIP_BOX_*); a skipped tier that IS needed raises MGR_OVF_TIER
     uint32_t tiers;
     uint32_t sort_big;        // items of the instance sort holding a single bucket of more than DBS_LIGHT_KEYS keys (bits 8.. of the reported tiers word)
     // fused backward, 5..8 views per group: the active Gaussians by the number of their views that hold pair records, rounded up
     // to 8 / 4 / 2 lanes -- k_inst_bwd_runs gives a Gaussian that many lanes instead of eight (k_inst_gather counts and lists them)
     uint32_t n_runs[4];       // (three classes; the fourth word is spare)
-    // "outputs kept" (mgr_views_backward, debug bit 512): backward calls on this workspace (k_blend_bwd counts), the call whose
+    // "outputs kept" (mgr_views_backward, MGR_BWD_OUTPUTS_KEPT): backward calls on this workspace (k_blend_bwd counts), the call whose
     // gather left the per-Gaussian row state (which gradient rows of the caller's buffers may be non-zero), the gather's note
     // for the kernel behind it
     uint32_t bwd_seq, rows_seq, rows_pending;
     uint32_t rows_owner[2];   // d_xyz of the call that left the row state: the state describes THOSE buffers
-    // "image kept" (forward, debug bit 1024): forwards binned on this workspace (k_tile_scan_a counts), the forward that last
+    // "image kept" (forward, MGR_FWD_IMAGE_KEPT): forwards binned on this workspace (k_tile_scan_a counts), the forward that last
     // completed an image (k_fwd_items), the image it wrote and its background colour -- tile_bgok says which tiles of THAT image
     // hold the background
     uint32_t fwd_seq, img_seq, img_owner[2], img_bg[3];
-    // depth cut, repaired on the device (forward debug bit 2048; see MgrRepUnit): (tile, quadrant) units registered by the blend
+    // depth cut, repaired on the device (forward MGR_FWD_REPAIR; see MgrRepUnit): (tile, quadrant) units registered by the blend
     // of the forward in flight, entries / checkpoints handed out behind the regular lists; reset by k_tile_scan_b
     uint32_t n_rep_units, rep_list_used, rep_ck_used;
     uint32_t rep_why;         // why the forward in flight raised MGR_OVF_CUT (bits MGR_WHY_*; k_tile_scan_a clears it)
@@ -135,7 +135,7 @@ struct MgrHeader {            // first 256 bytes of the workspace
                               // forward blend reads them in its rare "list ran out" branch instead of carrying 17 more scalars)
     uint32_t sort_huge;       // items of the instance sort beyond the LDS of the k_dbin_rank launch (it counts; the launch behind it returns at once on 0)
     uint32_t sort_large;      // items beyond MGR_DB_RANK_MAX keys, whatever the launch's LDS (bits 24.. of the reported tiers word: the caller asks
-                              // the next forward for the large LDS, debug bit 256)
+                              // the next forward for the large LDS, MGR_FWD_RANK_LARGE)
     uint32_t sort_near_large; // items beyond 13/16 of MGR_DB_RANK_LARGE (bits 16..23 of the reported tiers word; sort_big -- bits 8..15 --
                               // counts those beyond 13/16 of MGR_DB_RANK_MAX: the caller skips the launch behind by the one that
                               // belongs to the instantiation it is going to ask for)
@@ -162,10 +162,12 @@ struct MgrHeader {            // first 256 bytes of the workspace
 struct MgrFeatStamp {          // what k_fwd_items leaves in MgrHeader::feat_dims / feat_flags
     uint32_t dims[5], flags;
 };
-// bits of MgrHeader::overflow
-#define MGR_OVF_PAIRS 1u   // the pair capacity was exceeded: lists clipped, image and gradients incomplete
-#define MGR_OVF_CUT 2u     // a tile whose list was cut short by the depth cut ran out of entries with a pixel still unsaturated
-#define MGR_OVF_TIER 4u    // a view's tile box needed a binning launch the caller had asked to skip (debug bits 16 / 32)
+// (the bits of MgrHeader::overflow are the public MGR_OVF_* of manus_hip.h)
+// The forward's MGR_FWD_SKIP_* / MGR_FWD_RANK_LARGE flags as the host code and k_bin_scatter's `skipped` argument carry them
+#define MGR_SKIP_BOX_LARGE 1     // MGR_FWD_SKIP_BOX_LARGE: no launches for tile boxes of more than BIN_SMALL_TILES tiles
+#define MGR_SKIP_BOX_MID 2       // MGR_FWD_SKIP_BOX_MID: none for boxes of BIN_MID_TILES + 1 .. BIN_SMALL_TILES tiles
+#define MGR_SKIP_SORT_BEHIND 4   // MGR_FWD_SKIP_SORT_BEHIND: no radix launch behind k_dbin_rank
+#define MGR_SKIP_RANK_LARGE 8    // MGR_FWD_RANK_LARGE (not a skip: it rides in the same word): k_dbin_rank<MGR_DB_RANK_LARGE>
 
 // Per-(view, Gaussian) record gathered by the blend kernels: 48 bytes of content in a 64-byte slot on a 64-byte boundary.
 // The memory side serves gathers in 128-byte requests (profiles/r06_counter_calibration.txt): a quarter of 48-byte records at
@@ -189,7 +191,7 @@ struct __attribute__((aligned(MGR_GREC_BYTES == 64 ? 64 : 16))) MgrGRec {
 #define MGR_CHUNK 64         // list entries per backward work item / forward checkpoint interval (one batch of the blend waves)
 
 // ---------------------------------------------------------------------------
-// Depth cut, repaired on the device (round 6; mgr_views_forward debug bits 8 + 2048).
+// Depth cut, repaired on the device (round 6; mgr_views_forward MGR_FWD_DEPTH_CUT | MGR_FWD_REPAIR).
 //
 // A forward with the depth cut drops, per tile, the instances behind the depth at which the tile's pixels had all saturated
 // in the previous forward (+ a margin).  When the model moves, a few tiles per step run out of list under a pixel that has
@@ -231,8 +233,8 @@ struct MgrLayout {
 #define MGR_DB_ITEM 768       // keys per item of the instance sort (whole buckets: an item ends with the bucket it is in)
 #endif
 #define MGR_DB_RANK_MAX 2048  // items of at most this many keys are sorted by k_dbin_rank (16 + 8 KB of LDS), larger ones by the launch behind it --
-                              // 33 us on the critical path -- unless the caller asked for the instantiation for MGR_DB_RANK_LARGE keys (debug bit
-                              // 256: the previous forward met such items), which costs k_dbin_rank ~4 us (six keys per thread compiled in) and
+                              // 33 us on the critical path -- unless the caller asked for the instantiation for MGR_DB_RANK_LARGE keys (MGR_FWD_RANK_LARGE:
+                              // the previous forward met such items), which costs k_dbin_rank ~4 us (six keys per thread compiled in) and
                               // spares the launch behind.  (3584: eight keys per thread, +15 us.)
 #define MGR_DB_RANK_LARGE 3072
 #ifndef MGR_BIN_BLOCK
@@ -266,7 +268,7 @@ static inline MgrLayout mgr_layout(int V, int N, int W, int H, int64_t cap) {
     L.tile_cursor = o; o += mgr_align(VT * 4);
     L.tile_done = o;   o += mgr_align(VT * 4);
     L.tile_qdone = o;  o += mgr_align(VT * 16);       // list depth each 8x8 quadrant of a tile consumed in the forward blend
-    // depth cut (mgr_views_forward, debug bit 8): per tile the complement of the float bits of the depth beyond which the
+    // depth cut (mgr_views_forward, MGR_FWD_DEPTH_CUT): per tile the complement of the float bits of the depth beyond which the
     // NEXT forward may leave instances out of the tile's list (0 = no cut), written by k_fwd_items from how deep THIS
     // forward's walk went; the value a forward applied (k_tile_scan_b moves it there); the list position at which the
     // tile's last quadrant saturated (0xFFFFFFFF: some pixel never did)

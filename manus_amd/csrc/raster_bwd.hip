@@ -1247,7 +1247,7 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
                                    const float* opacity, int64_t s_op, const float* out_color,
                                    const float* dL_dcolor, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors,
                                    float* dL_dopacity, float* dL_dcov3D, const CanonGrads* canon, void* workspace,
-                                   size_t workspace_bytes, int64_t cap, int debug, void* stream_) {
+                                   size_t workspace_bytes, int64_t cap, int flags, void* stream_) {
     (void)colors; (void)s_col; (void)opacity; (void)s_op;  // captured in the workspace records
     hipStream_t stream = (hipStream_t)stream_;
     if (V <= 0 || N < 0 || W <= 0 || H <= 0 || cap < 0)
@@ -1277,7 +1277,7 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
                        (const float4*)(ws + L.ckpt), (const uint4*)(ws + L.items), hdr, out_color,
                        dL_dcolor, (uint32_t*)(ws + L.pair_tag), (float4*)(ws + L.pair_grad),
                        (uint32_t*)(ws + L.inst_tag), (uint32_t)cap, epoch); }
-    MGR_LAUNCH_CHECK("k_blend_bwd", stream, debug & 1);
+    MGR_LAUNCH_CHECK("k_blend_bwd", stream, flags & MGR_BWD_CHECK);
     if (canon) {
         // views of a Gaussian share a lane group; more than 8 views go in groups of 8, the later
         // groups adding to the outputs of the first
@@ -1306,9 +1306,9 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
             const int rounds_r = rounds < Gv ? rounds : Gv;   // (at most 256 Gaussians per workgroup of k_inst_gather_runs)
             const dim3 grid_gr((N + ipb * rounds_r - 1) / (ipb * rounds_r));
             uint32_t* rlist = alist + (size_t)N;   // three lists of N entries behind the active list
-            // row state of the "outputs kept" mode (debug bit 512): one byte per Gaussian behind the run lists, single view group only
+            // row state of the "outputs kept" mode (MGR_BWD_OUTPUTS_KEPT): one byte per Gaussian behind the run lists, single view group only
             unsigned char* row_state = V <= Gv ? (unsigned char*)(rlist + 3 * (size_t)N) : nullptr;
-            const int kept = (debug & 512) && V <= Gv ? 1 : 0;
+            const int kept = (flags & MGR_BWD_OUTPUTS_KEPT) && V <= Gv ? 1 : 0;
 #define MGR_IG_LAUNCH(GG)                                                                                             \
     hipLaunchKernelGGL((k_inst_gather<GG>), grid_g, dim3(256), 0, stream, v0, vc, N, canon->B, canon->n_art, canon->radii, \
                        (const ushort4*)(ws + L.rect), (const uint32_t*)(ws + L.pair_off),                             \
@@ -1381,7 +1381,7 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
 #undef MGR_IP_FLAGS
 #undef MGR_IP_LAUNCH
 #undef MGR_IP_ARGS
-                MGR_LAUNCH_CHECK("k_inst_bwd_pose", stream, debug & 1);
+                MGR_LAUNCH_CHECK("k_inst_bwd_pose", stream, flags & MGR_BWD_CHECK);
                 if (prof_ib.on) { mgr_prof_end(stream); prof_ib.on = false; }
                 {
                     MGR_PROF("k_pose_part_views", stream);
@@ -1390,7 +1390,7 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
                                              (const float4*)iacc, (const unsigned char*)pvalid, canon->skin_w, canon->pose_part)
                     if (Gv == 8) MGR_PP_LAUNCH(8); else if (Gv == 4) MGR_PP_LAUNCH(4); else if (Gv == 2) MGR_PP_LAUNCH(2); else MGR_PP_LAUNCH(1);
 #undef MGR_PP_LAUNCH
-                    MGR_LAUNCH_CHECK("k_pose_part_views", stream, debug & 1);
+                    MGR_LAUNCH_CHECK("k_pose_part_views", stream, flags & MGR_BWD_CHECK);
                 }
                 const int rc = mgr_pose_fold(v0, vc, Gv, canon->B, canon->pose_part, slots, canon->d_T, stream);
                 if (rc != MGR_OK) return rc;
@@ -1425,7 +1425,7 @@ static int raster_backward_impl(int V, int N, int W, int H, const float* cams, c
                        (const uint32_t*)(ws + L.pair_tag), (const float4*)(ws + L.pair_grad),
                        dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dcov3D,
                        (const uint32_t*)(ws + L.inst_tag), (uint32_t)cap, epoch, hdr); }
-    MGR_LAUNCH_CHECK("k_preprocess_bwd", stream, debug & 1);
+    MGR_LAUNCH_CHECK("k_preprocess_bwd", stream, flags & MGR_BWD_CHECK);
     return MGR_OK;
 }
 
@@ -1449,10 +1449,10 @@ extern "C" int mgr_raster_backward(int V, int N, int W, int H, const float* cams
                                    const float* opacity, int64_t s_op, const float* out_color,
                                    const float* dL_dcolor, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors,
                                    float* dL_dopacity, float* dL_dcov3D, void* workspace,
-                                   size_t workspace_bytes, int64_t cap, int debug, void* stream_) {
+                                   size_t workspace_bytes, int64_t cap, int flags, void* stream_) {
     return raster_backward_impl(V, N, W, H, cams, bg, means3D, s_means, cov3D, s_cov, colors, s_col, opacity, s_op,
                                 out_color, dL_dcolor, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dcov3D,
-                                nullptr, workspace, workspace_bytes, cap, debug, stream_);
+                                nullptr, workspace, workspace_bytes, cap, flags, stream_);
 }
 
 extern "C" int mgr_views_backward(int V, int N, int B, int n_articulated, int sh_half, int W, int H, const float* cams, const float* bg,
@@ -1463,7 +1463,7 @@ extern "C" int mgr_views_backward(int V, int N, int B, int n_articulated, int sh
                                   float* d_xyz, float* d_log_scale, float* d_rot, float* d_opacity_logit,
                                   float* d_f_dc, float* d_f_rest, float* d_skin_w, float* stat_grad2d,
                                   float* stat_vis, int32_t* stat_radii, void* workspace, size_t workspace_bytes,
-                                  int64_t cap, int debug, void* stream_) {
+                                  int64_t cap, int flags, void* stream_) {
     if (N > 0 && (!xyz || !log_scale || !rot || !opacity_logit || !f_dc || !f_rest || !radii || !d_xyz ||
                   !d_log_scale || !d_rot || !d_opacity_logit || !d_f_dc || !d_f_rest ||
                   (skin_w && (!transforms || !d_skin_w))))
@@ -1475,7 +1475,7 @@ extern "C" int mgr_views_backward(int V, int N, int B, int n_articulated, int sh
                            stat_grad2d, stat_vis, stat_radii};
     return raster_backward_impl(V, N, W, H, cams, bg, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, out_color,
                                 dL_dcolor, nullptr, nullptr, nullptr, nullptr, nullptr, &cg, workspace, workspace_bytes,
-                                cap, debug, stream_);
+                                cap, flags, stream_);
 }
 
 // mgr_views_backward plus dL/dtransforms (see include/manus_hip.h)
@@ -1487,7 +1487,7 @@ extern "C" int mgr_views_backward_pose(int V, int N, int B, int n_articulated, i
                                        float* d_xyz, float* d_log_scale, float* d_rot, float* d_opacity_logit,
                                        float* d_f_dc, float* d_f_rest, float* d_skin_w, float* stat_grad2d,
                                        float* stat_vis, int32_t* stat_radii, void* workspace, size_t workspace_bytes,
-                                       int64_t cap, int debug, float* d_transforms, void* pose_workspace,
+                                       int64_t cap, int flags, float* d_transforms, void* pose_workspace,
                                        size_t pose_workspace_bytes, void* stream_) {
     if (!skin_w || !transforms || n_articulated <= 0)
         return mgr_fail(MGR_EINVAL, "mgr_views_backward_pose: no articulated Gaussians (a static object has no transforms)");
@@ -1502,5 +1502,5 @@ extern "C" int mgr_views_backward_pose(int V, int N, int B, int n_articulated, i
                            stat_grad2d, stat_vis, stat_radii, d_transforms, (float*)pose_workspace};
     return raster_backward_impl(V, N, W, H, cams, bg, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, out_color,
                                 dL_dcolor, nullptr, nullptr, nullptr, nullptr, nullptr, &cg, workspace, workspace_bytes,
-                                cap, debug, stream_);
+                                cap, flags, stream_);
 }

@@ -208,12 +208,12 @@ extern "C" int mgr_raster_blend_features(int V, int N, int C, int W, int H, cons
     MGR_HIP(hipStreamSynchronize(stream));
     if (h.fwd_seq == 0u) return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: no forward has run on this workspace");
     if (h.feat_seq != h.fwd_seq)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward on this workspace did not run its blend (debug bit 1, value 2)");
+        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward on this workspace did not run its blend (MGR_FWD_NO_BLEND)");
     if (h.feat_dims[0] != (uint32_t)V || h.feat_dims[1] != (uint32_t)N || h.feat_dims[2] != (uint32_t)W ||
         h.feat_dims[3] != (uint32_t)H || h.feat_dims[4] != (uint32_t)cap)
         return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward on this workspace was made for another V, N, W, H or pair capacity");
     if (h.feat_flags & MGR_FEAT_CUT)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward applied the depth cut (debug bit 8): its lists are cut short");
+        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward applied the depth cut (MGR_FWD_DEPTH_CUT): its lists are cut short");
     if (h.overflow != 0u)
         return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward raised an overflow bit: its lists are incomplete");
     const int VT = V * gx * gy;

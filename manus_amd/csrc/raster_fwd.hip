@@ -1377,7 +1377,7 @@ __device__ __forceinline__ uint32_t db_lower_bound(const uint32_t* __restrict__ 
 // two, so the ~530 items of the bench step run in one round instead of two) takes the items of at most that many keys and
 // larger ones bucket by bucket, all but those with a single bucket beyond its LDS -- those (a dense depth slice: typical
 // with one view and rows of 1024 keys) are the full launch's (SORT_LDS_KEYS), or, when the caller skips the full launch
-// (debug bit 128), go through the light one's global-memory fallback.  The header counts them (sort_big) so that the caller
+// (MGR_FWD_SKIP_SORT_BEHIND), go through the light one's global-memory fallback.  The header counts them (sort_big) so that the caller
 // can choose for the next forward: none -> the light launch alone (with the depth cut the instances that take part halve:
 // 0.051 -> 0.044 ms at eight views), some -> the full launch alone (one view: 0.039 ms; the light one alone took 0.093 there);
 // either way every item is sorted by exactly one launch.  lds_keys: capacity of this launch; min_keys: items of at most this many keys belong to the other launch;
@@ -1398,7 +1398,7 @@ struct BgFill {
     const uint32_t* tile_queue;    // non-empty tiles first (hdr->queue_len of them), the empty ones behind
     const float* bg;
     int VT, T, gx, W, H;
-    // "image kept" (debug bit 1024): the caller vouches that `out` is the image of the previous complete forward on this
+    // "image kept" (MGR_FWD_IMAGE_KEPT): the caller vouches that `out` is the image of the previous complete forward on this
     // workspace, untouched -- a tile that was background then (tile_bgok, kept by k_tile_scan_b / k_fwd_items) and is empty now
     // is left alone.  Honoured when the header says that forward was the last one binned here, wrote THIS buffer, with THIS colour.
     const unsigned char* tile_bgok;
@@ -1598,7 +1598,7 @@ __global__ __launch_bounds__(DBR_THREADS) void k_dbin_rank(int N, int V, int ite
     if (n > cap_keys) {
         if (tid == 0) {
             atomicAdd(&hdr->sort_huge, 1u);
-            // the caller skipped the launch behind (debug bit 128: the previous forward met no such item): flagged like a skipped
+            // the caller skipped the launch behind (MGR_FWD_SKIP_SORT_BEHIND: the previous forward met no such item): flagged like a skipped
             // binning tier -- the forward is run again with every launch
             if (no_launch_behind) atomicOr(&hdr->overflow, MGR_OVF_TIER);
         }
@@ -1881,7 +1881,7 @@ __device__ __forceinline__ bool bin_sc_mine(ushort4 box, int masks) {
     return tier == masks;
 }
 // SPREAD (round 6, end): the lane-spreading producer is an instantiation of its own, asked for when the previous forward met
-// rectangles of more than 64 tiles (MgrHeader::tiers bit 2 -> debug bit 4096).  Without it a batch that holds such a rectangle
+// rectangles of more than 64 tiles (MGR_TIERS_WIDE_RECT -> MGR_FWD_SPREAD).  Without it a batch that holds such a rectangle
 // goes instance by instance, as up to round 5: correct for any input, and the usual producer keeps round 5's loop and
 // registers (0.094 -> 0.087 ms at eight views of the capture-like set, where no rectangle is that large).
 template <int MASKS, bool SPREAD>
@@ -1909,7 +1909,7 @@ __global__ __launch_bounds__(BIN_SC_THREADS) void k_bin_scatter(int N, int T, in
         // BIN_SMALL_TILES tiles -- k_bin_count<false>, k_bin_scatter<0>; bit 1: k_bin_scatter<BIN_SMALL_TILES>)
         if (MASKS == BIN_MID_TILES && skipped && b == 0 && tid == 0) {
             const uint32_t tb = (uint32_t)box.z * (uint32_t)box.w;
-            if ((tb > (uint32_t)BIN_SMALL_TILES && (skipped & 1)) || (tb > (uint32_t)BIN_MID_TILES && tb <= (uint32_t)BIN_SMALL_TILES && (skipped & 2)))
+            if ((tb > (uint32_t)BIN_SMALL_TILES && (skipped & MGR_SKIP_BOX_LARGE)) || (tb > (uint32_t)BIN_MID_TILES && tb <= (uint32_t)BIN_SMALL_TILES && (skipped & MGR_SKIP_BOX_MID)))
                 atomicOr(&hdr->overflow, MGR_OVF_TIER);
         }
         return;
@@ -2974,7 +2974,7 @@ __global__ __launch_bounds__(256) void k_fwd_items(const uint4* __restrict__ til
         uint32_t ovf = hdr->overflow;
         if (f) { ovf |= f; hdr->overflow = ovf; hdr->acc_flags = 0u; }
         if (mirror) {   // the caller's host-mapped status words (mgr_raster_set_status_mirror): no copy, no launch
-            // (bits 16.. of the overflow word: quadrants of depth-cut tiles repaired on the device in this forward)
+            // (above MGR_OVF_REPAIRED_SHIFT in the overflow word: quadrants of depth-cut tiles repaired on the device in this forward)
             mirror[0] = hdr->total_pairs; mirror[1] = ovf | (min(hdr->n_rep_units, 0xFFFFu) << 16); mirror[2] = hdr->tiers | (min(hdr->sort_big, 0xFFu) << 8) | (min(hdr->sort_near_large, 0xFFu) << 16) | (min(hdr->sort_large, 0x7Fu) << 24);
             __threadfence_system();
             mirror[3] = 1u;
@@ -3117,48 +3117,48 @@ static MgrSideStream& mgr_side_stream(int device) {   // one per (host thread, d
     return s[device];
 }
 
-// Host-mapped status words per workspace (mgr_raster_set_status_mirror): the forward's last kernel writes (pair total,
-// overflow word, binning tiers, 1) there, so that a caller who does not want to synchronise needs neither a device-to-host
-// copy nor a read-back launch per forward -- an event behind the forward is enough.  One shot: taken by the forward that
-// runs the blend on that workspace.
-static std::mutex g_mirror_mu;
-static struct { const void* ws; uint32_t* dev; } g_mirror[64];
-static uint32_t* mgr_take_status_mirror(const void* workspace) {
-    std::lock_guard<std::mutex> lk(g_mirror_mu);
-    for (auto& m : g_mirror)
-        if (m.ws == workspace) { uint32_t* p = m.dev; m.ws = nullptr; m.dev = nullptr; return p; }
-    return nullptr;
-}
-// The span list of the image loss, attached to the next forward that runs its last kernel on `workspace` (one shot, like the
-// status mirror): k_fwd_items' launch then carries the list's workgroups (il_list.h) -- the list needs the forward's tile offsets
-// only, and as a launch of its own it was 8 us of the chain of small kernels between the forward blend and the loss.
-static struct { const void* ws; IlListArgs a; } g_loss_list[64];
-static IlListArgs mgr_take_loss_list(const void* workspace) {
-    std::lock_guard<std::mutex> lk(g_mirror_mu);
-    for (auto& m : g_loss_list)
-        if (m.ws == workspace) { IlListArgs a = m.a; m.ws = nullptr; return a; }
-    IlListArgs none;
-    memset(&none, 0, sizeof(none));
-    return none;
-}
+// One-shot attachments per workspace (status mirror, loss list): set by the caller, taken by the next forward that runs its last
+// kernel on that workspace.
+static std::mutex g_slot_mu;
+template <typename T>
+struct MgrSlots {
+    struct { const void* ws; T v; } slot[64];
+    bool set(const void* workspace, const T* v) {      // v == nullptr withdraws; false: no free slot
+        std::lock_guard<std::mutex> lk(g_slot_mu);
+        int k_free = -1;
+        for (int k = 0; k < 64; ++k) {
+            if (slot[k].ws == workspace) { k_free = k; break; }
+            if (!slot[k].ws && k_free < 0) k_free = k;
+        }
+        if (k_free < 0) return false;
+        if (v) { slot[k_free].ws = workspace; slot[k_free].v = *v; }
+        else if (slot[k_free].ws == workspace) slot[k_free].ws = nullptr;
+        return true;
+    }
+    T take(const void* workspace) {                    // T() when nothing is attached
+        std::lock_guard<std::mutex> lk(g_slot_mu);
+        for (auto& m : slot)
+            if (m.ws == workspace) { m.ws = nullptr; return m.v; }
+        return T();
+    }
+};
+// Host-mapped status words (mgr_raster_set_status_mirror): the forward's last kernel writes (pair total, overflow word, binning
+// tiers, 1) there, so that a caller who does not want to synchronise needs neither a device-to-host copy nor a read-back
+// launch per forward -- an event behind the forward is enough.
+static MgrSlots<uint32_t*> g_mirror;
+// The span list of the image loss (mgr_views_forward_attach_loss_list): k_fwd_items' launch then carries the list's workgroups
+// (il_list.h) -- the list needs the forward's tile offsets only, and as a launch of its own it was 8 us of the chain of small
+// kernels between the forward blend and the loss.
+static MgrSlots<IlListArgs> g_loss_list;
+
 extern "C" int mgr_views_forward_attach_loss_list(const void* workspace, int V, int H, int W, const uint32_t* target_map,
                                                   void* loss_workspace, size_t loss_workspace_bytes) {
     if (!workspace) return mgr_fail(MGR_EINVAL, "mgr_views_forward_attach_loss_list: null workspace");
-    std::lock_guard<std::mutex> lk(g_mirror_mu);
-    int free_slot = -1;
-    for (int k = 0; k < 64; ++k) {
-        if (g_loss_list[k].ws == workspace) { free_slot = k; break; }
-        if (!g_loss_list[k].ws && free_slot < 0) free_slot = k;
-    }
-    if (!target_map) {      // withdraw
-        if (free_slot >= 0 && g_loss_list[free_slot].ws == workspace) g_loss_list[free_slot].ws = nullptr;
-        return MGR_OK;
-    }
+    if (!target_map) { g_loss_list.set(workspace, nullptr); return MGR_OK; }      // withdraw
     if (V <= 0 || H <= 0 || W <= 0 || W > ILS_MAXW || !loss_workspace) return mgr_fail(MGR_EINVAL, "mgr_views_forward_attach_loss_list: bad arguments");
     if (loss_workspace_bytes < (size_t)il_blocks(V, H, W) * 12 + 256) return mgr_fail(MGR_ENOMEM, "mgr_views_forward_attach_loss_list: loss workspace too small");
-    if (free_slot < 0) return mgr_fail(MGR_ENOMEM, "mgr_views_forward_attach_loss_list: too many pending lists");
-    g_loss_list[free_slot].ws = workspace;
-    g_loss_list[free_slot].a = il_list_args(V, H, W, target_map, nullptr, loss_workspace);
+    const IlListArgs a = il_list_args(V, H, W, target_map, nullptr, loss_workspace);
+    if (!g_loss_list.set(workspace, &a)) return mgr_fail(MGR_ENOMEM, "mgr_views_forward_attach_loss_list: too many pending lists");
     return MGR_OK;
 }
 
@@ -3166,15 +3166,9 @@ extern "C" int mgr_raster_set_status_mirror(const void* workspace, void* host_wo
     if (!workspace) return mgr_fail(MGR_EINVAL, "mgr_raster_set_status_mirror: null workspace");
     void* dev = nullptr;
     if (host_words) MGR_HIP(hipHostGetDevicePointer(&dev, host_words, 0));
-    std::lock_guard<std::mutex> lk(g_mirror_mu);
-    int free_slot = -1;
-    for (int k = 0; k < 64; ++k) {
-        if (g_mirror[k].ws == workspace) { free_slot = k; break; }
-        if (!g_mirror[k].ws && free_slot < 0) free_slot = k;
-    }
-    if (free_slot < 0) return mgr_fail(MGR_EINVAL, "mgr_raster_set_status_mirror: too many workspaces with a pending mirror");
-    g_mirror[free_slot].ws = host_words ? workspace : nullptr;
-    g_mirror[free_slot].dev = (uint32_t*)dev;
+    uint32_t* const words = (uint32_t*)dev;
+    if (!g_mirror.set(workspace, host_words ? &words : nullptr))
+        return mgr_fail(MGR_EINVAL, "mgr_raster_set_status_mirror: too many workspaces with a pending mirror");
     return MGR_OK;
 }
 
@@ -3183,25 +3177,24 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
                                int64_t s_cov, const float* colors, int64_t s_col,
                                const float* opacity, int64_t s_op, const CanonInputs* canon, float* out_color,
                                int32_t* radii, void* workspace, size_t workspace_bytes,
-                               int64_t cap, int debug, void* stream_) {
+                               int64_t cap, int flags, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    // debug bit 0: synchronise and check after every kernel; bit 1: stop before the blend (instance kernels and binning
-    // only); bit 2: the blend only (after a call with bit 1 on the same workspace and arguments)
-    // bit 3 (8): depth cut -- apply the hints the previous forward on this workspace left in tile_zcut (fused path only)
-    // bits 4 / 5 (16 / 32): skip the binning launches for tile boxes of more than 2048 / of 1537..2048 tiles (the caller saw
-    // in the previous forward's header that no view needed them; a view that does now raises MGR_OVF_TIER)
-    const bool do_bin = !(debug & 4), do_blend = !(debug & 2), use_cut = (debug & 8) && canon != nullptr;
+    // (MGR_FWD_* are described in manus_hip.h; the depth cut applies the hints the previous forward on this workspace left in
+    // tile_zcut: fused path only)
+    const bool do_bin = !(flags & MGR_FWD_BLEND_ONLY), do_blend = !(flags & MGR_FWD_NO_BLEND), use_cut = (flags & MGR_FWD_DEPTH_CUT) && canon != nullptr;
     static const bool bg_fill_on = [] { const char* e = getenv("MANUS_BG_FILL"); return !(e && e[0] == 'b'); }();   // MANUS_BG_FILL=blend: by the blend, as before (A/B)
     bool bg_filled = false;   // the background of the empty tiles has been written by the instance sort's launch
-    const int skip_tiers = ((debug & 16) ? 1 : 0) | ((debug & 32) ? 2 : 0) | ((debug & 128) ? 4 : 0) | ((debug & 256) ? 8 : 0);
-    const int img_kept = (debug & 1024) ? 1 : 0;   // bit 10: "image kept" (see BgFill)
-    const bool spread = (debug & 4096) != 0;       // bit 12: k_bin_scatter's lane-spreading instantiation (the previous forward met rectangles of more than 64 tiles)
-    // bit 11 (2048, with bit 3): tiles whose cut list runs out under an unsaturated pixel are repaired on the device
-    // (k_repair_scan / k_repair_blend) instead of flagging the forward
+    // (a view that needs a launch skipped here raises MGR_OVF_TIER)
+    const int skip_tiers = ((flags & MGR_FWD_SKIP_BOX_LARGE) ? MGR_SKIP_BOX_LARGE : 0) | ((flags & MGR_FWD_SKIP_BOX_MID) ? MGR_SKIP_BOX_MID : 0) |
+                           ((flags & MGR_FWD_SKIP_SORT_BEHIND) ? MGR_SKIP_SORT_BEHIND : 0) | ((flags & MGR_FWD_RANK_LARGE) ? MGR_SKIP_RANK_LARGE : 0);
+    const int img_kept = (flags & MGR_FWD_IMAGE_KEPT) ? 1 : 0;   // (see BgFill)
+    const bool spread = (flags & MGR_FWD_SPREAD) != 0;
+    // tiles whose cut list runs out under an unsaturated pixel are repaired on the device (k_repair_scan / k_repair_blend) instead
+    // of flagging the forward
     // (k_repair_scan packs tile coordinates in 12 bits and keeps one bit per tile of a view in LDS: larger grids flag the forward)
-    const bool repair = use_cut && (debug & 2048) && W < 65536 && H < 65536 &&
+    const bool repair = use_cut && (flags & MGR_FWD_REPAIR) && W < 65536 && H < 65536 &&
                         (int64_t)((W + 15) / 16) * ((H + 15) / 16) <= (int64_t)MGR_REP_MAX_TILES;
-    debug &= 1;
+    const int debug = flags & MGR_FWD_CHECK;
     if (V <= 0 || N < 0 || W <= 0 || H <= 0 || cap < 0 || cap > 0xFFFFFFF0ll)
         return mgr_fail(MGR_EINVAL, "mgr_raster_forward: bad sizes");
     if (!cams || !bg || !out_color || !workspace ||
@@ -3330,18 +3323,18 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
           // larger ones (returns at once when there are none) -- it also carries the background of the empty tiles (BgFill)
           const int ipv = (N + MGR_DB_ITEM - 1) / MGR_DB_ITEM + 1;
           const bool ranked = ipv <= DBR_MAX_ITEMS;      // (more instances per view than the scan can table: everything through the radix launch)
-          // debug bit 128 (skip_tiers & 4): the previous forward met no item beyond k_dbin_rank -- the launch behind it is skipped
+          // MGR_FWD_SKIP_SORT_BEHIND: the previous forward met no item beyond k_dbin_rank -- the launch behind it is skipped
           // (7 us of workgroups that return at once); an item that needs it after all raises MGR_OVF_TIER
-          const bool behind = !ranked || !(skip_tiers & 4);
+          const bool behind = !ranked || !(skip_tiers & MGR_SKIP_SORT_BEHIND);
           BgFill fill = {do_blend && bg_fill_on ? out_color : nullptr, (const uint32_t*)(ws + L.tile_queue), bg, VT, T, gx, W, H,
                          (const unsigned char*)(ws + L.tile_bgok), img_kept};
           const BgFill none = {nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, 0};
           const int n_fill = fill.out ? 1024 : 0;
           bg_filled = fill.out != nullptr;
-          // debug bit 256 (skip_tiers & 8): the previous forward met items beyond MGR_DB_RANK_MAX keys (one dense depth bucket: the palm
+          // MGR_FWD_RANK_LARGE: the previous forward met items beyond MGR_DB_RANK_MAX keys (one dense depth bucket: the palm
           // seen face on, in the trained state of the bench scene) -- this launch gets LDS for MGR_DB_RANK_LARGE keys per workgroup
-          const uint32_t cap_keys = (skip_tiers & 8) ? (uint32_t)MGR_DB_RANK_LARGE : (uint32_t)MGR_DB_RANK_MAX;
-          if (ranked && (skip_tiers & 8))
+          const uint32_t cap_keys = (skip_tiers & MGR_SKIP_RANK_LARGE) ? (uint32_t)MGR_DB_RANK_LARGE : (uint32_t)MGR_DB_RANK_MAX;
+          if (ranked && (skip_tiers & MGR_SKIP_RANK_LARGE))
               hipLaunchKernelGGL((k_dbin_rank<MGR_DB_RANK_LARGE>), dim3((unsigned)(ipv * V + n_fill)), dim3(DBR_THREADS), 0, stream, N, V, ipv, (const uint32_t*)db_start, (const uint32_t*)(ws + L.db_item),
                                  (const unsigned long long*)db_keys, db_order, hdr, behind ? 0 : 1, fill, ipv * V);
           else if (ranked)
@@ -3359,7 +3352,7 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
           const dim3 grid_c = (V % 8 == 0) ? dim3(nblk * V) : grid_b;   // (XCD-aware order, see the kernel)
           hipLaunchKernelGGL((k_bin_count<true>), grid_c, dim3(BCNT_THREADS), (size_t)BIN_SMALL_TILES * 4, stream, N, T, nblk, bb, (const uint32_t*)db_nvis,
                              (const ushort4*)db_bbox, (const uint32_t*)db_order, rect, alive, db_rec, bin_mat, V % 8 == 0 ? 1 : 0);
-          if (big_possible && !(skip_tiers & 1))
+          if (big_possible && !(skip_tiers & MGR_SKIP_BOX_LARGE))
               hipLaunchKernelGGL((k_bin_count<false>), grid_c, dim3(BCNT_THREADS), (size_t)T * 4, stream, N, T, nblk, bb, (const uint32_t*)db_nvis,
                                  (const ushort4*)db_bbox, (const uint32_t*)db_order, rect, alive, db_rec, bin_mat, V % 8 == 0 ? 1 : 0); }
         { MGR_PROF("k_bin_scan", stream); hipLaunchKernelGGL(k_bin_scan, dim3((T + BSCAN_COLS - 1) / BSCAN_COLS, V), dim3(BSCAN_COLS * BSCAN_SEGS), 0, stream, gx, T, nblk, bb, (const uint32_t*)db_nvis,
@@ -3373,11 +3366,11 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
           MGR_SC_LAUNCH(BIN_MID_TILES, (size_t)BIN_MID_TILES * 12 + rec_bytes, N, T, nblk, bb,
                              (const uint32_t*)db_nvis, (const ushort4*)db_bbox, (const uint32_t*)db_order, (const uint4*)db_rec, (const uint32_t*)bin_mat,
                              (uint32_t*)(ws + L.sorted_gid), (uint32_t)cap, hdr, skip_tiers);
-          if (T > BIN_MID_TILES && !(skip_tiers & 2))
+          if (T > BIN_MID_TILES && !(skip_tiers & MGR_SKIP_BOX_MID))
               MGR_SC_LAUNCH(BIN_SMALL_TILES, (size_t)BIN_SMALL_TILES * 12 + rec_bytes, N, T, nblk, bb,
                             (const uint32_t*)db_nvis, (const ushort4*)db_bbox, (const uint32_t*)db_order, (const uint4*)db_rec, (const uint32_t*)bin_mat,
                             (uint32_t*)(ws + L.sorted_gid), (uint32_t)cap, hdr, 0);
-          if (big_possible && !(skip_tiers & 1))
+          if (big_possible && !(skip_tiers & MGR_SKIP_BOX_LARGE))
               MGR_SC_LAUNCH(0, (size_t)T * 4 + rec_bytes, N, T, nblk, bb,
                             (const uint32_t*)db_nvis, (const ushort4*)db_bbox, (const uint32_t*)db_order, (const uint4*)db_rec, (const uint32_t*)bin_mat,
                             (uint32_t*)(ws + L.sorted_gid), (uint32_t)cap, hdr, 0);
@@ -3436,7 +3429,7 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
         MGR_LAUNCH_CHECK("k_repair_blend", stream, debug);
     }
     // the span list of the image loss rides on this launch when the caller attached one (mgr_views_forward_attach_loss_list)
-    IlListArgs ll = mgr_take_loss_list(workspace);
+    IlListArgs ll = g_loss_list.take(workspace);
     if (ll.nbx) {
         if (ll.H != H || ll.W != W || ll.list_views != V) return mgr_fail(MGR_EINVAL, "attached loss list: views or image size differ from the forward's");
         ll.tile_start = tile_start;
@@ -3446,7 +3439,7 @@ static int raster_forward_impl(int V, int N, int W, int H, const float* cams, co
     { MGR_PROF("k_fwd_items", stream); hipLaunchKernelGGL(k_fwd_items, dim3((unsigned)(n_item_blocks + ll.nbx * V)), dim3(256), 0, stream, (const uint4*)(ws + L.tile_qrec),
                        (const uint32_t*)(ws + L.tile_qdone), (uint32_t*)(ws + L.tile_done), (uint4*)(ws + L.items), hdr,
                        N, T, (const uint32_t*)(ws + L.sorted_gid), (const float*)(ws + L.depth), (const uint32_t*)(ws + L.tile_zused),
-                       (const uint32_t*)(ws + L.tile_qend), (uint32_t*)(ws + L.tile_zcut), mgr_take_status_mirror(workspace),
+                       (const uint32_t*)(ws + L.tile_qend), (uint32_t*)(ws + L.tile_zcut), g_mirror.take(workspace),
                        g_cut_frac, (uint32_t)g_cut_min, g_cut_range, g_cut_rel, gx, g_cut_interior,
                        (const uint32_t*)(ws + L.tile_queue), VT, (unsigned char*)(ws + L.tile_bgok), (const float*)out_color, bg, rep_all,
                        (uint32_t)g_cut_penalty, (uint32_t*)(ws + L.tile_zwin), ll, n_item_blocks, stamp); }
@@ -3459,9 +3452,9 @@ extern "C" int mgr_raster_forward(int V, int N, int W, int H, const float* cams,
                                   int64_t s_cov, const float* colors, int64_t s_col,
                                   const float* opacity, int64_t s_op, float* out_color,
                                   int32_t* radii, void* workspace, size_t workspace_bytes,
-                                  int64_t cap, int debug, void* stream_) {
+                                  int64_t cap, int flags, void* stream_) {
     return raster_forward_impl(V, N, W, H, cams, bg, means3D, s_means, cov3D, s_cov, colors, s_col, opacity, s_op,
-                               nullptr, out_color, radii, workspace, workspace_bytes, cap, debug, stream_);
+                               nullptr, out_color, radii, workspace, workspace_bytes, cap, flags, stream_);
 }
 
 extern "C" int mgr_views_forward(int V, int N, int B, int n_articulated, int sh_half, int W, int H, const float* cams, const float* bg,
@@ -3469,7 +3462,7 @@ extern "C" int mgr_views_forward(int V, int N, int B, int n_articulated, int sh_
                                  const float* opacity_logit, const float* f_dc, const float* f_rest,
                                  const float* skin_w, const float* transforms, float* out_color,
                                  int32_t* radii, void* workspace, size_t workspace_bytes, int64_t cap,
-                                 int debug, void* stream_) {
+                                 int flags, void* stream_) {
     if (N > 0 && (!xyz || !log_scale || !rot || !opacity_logit || !f_dc || !f_rest || (skin_w && !transforms)))
         return mgr_fail(MGR_EINVAL, "mgr_views_forward: null pointer");
     if (skin_w && (B <= 0 || B > MGR_MAX_BONES)) return mgr_fail(MGR_EINVAL, "mgr_views_forward: bad B");
@@ -3477,7 +3470,7 @@ extern "C" int mgr_views_forward(int V, int N, int B, int n_articulated, int sh_
     if (sh_half && ((uintptr_t)f_rest & 15)) return mgr_fail(MGR_EINVAL, "mgr_views_forward: fp16 f_rest must be 16-byte aligned");
     const CanonInputs ci = {B, skin_w ? n_articulated : 0, sh_half ? 1 : 0, xyz, log_scale, rot, opacity_logit, f_dc, f_rest, skin_w, transforms};
     return raster_forward_impl(V, N, W, H, cams, bg, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, &ci, out_color,
-                               radii, workspace, workspace_bytes, cap, debug, stream_);
+                               radii, workspace, workspace_bytes, cap, flags, stream_);
 }
 
 #ifdef BIN_PROF
@@ -3525,6 +3518,13 @@ extern "C" int mgr_debug_pair_alpha(int n, const float* rec, const int32_t* px, 
     return MGR_OK;
 }
 
+static int mgr_overflow_code(uint32_t ovf) {   // the return code that reports a forward's overflow word
+    if (ovf & MGR_OVF_PAIRS) return mgr_fail(MGR_EOVERFLOW, "pair capacity exceeded");
+    if (ovf & MGR_OVF_CUT) return mgr_fail(MGR_ECUT, "depth cut violated: run the forward again without MGR_FWD_DEPTH_CUT");
+    if (ovf & MGR_OVF_TIER) return mgr_fail(MGR_ETIER, "a skipped binning launch was needed: run the forward again without MGR_FWD_SKIP_*");
+    return MGR_OK;
+}
+
 extern "C" int mgr_raster_status_sync(const void* workspace, int64_t* num_pairs, int32_t* overflow,
                                       void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -3533,10 +3533,7 @@ extern "C" int mgr_raster_status_sync(const void* workspace, int64_t* num_pairs,
     MGR_HIP(hipStreamSynchronize(stream));
     if (num_pairs) *num_pairs = h[0];
     if (overflow) *overflow = (int32_t)h[1];
-    if (h[1] & MGR_OVF_PAIRS) return mgr_fail(MGR_EOVERFLOW, "pair capacity exceeded");
-    if (h[1] & MGR_OVF_CUT) return mgr_fail(MGR_ECUT, "depth cut violated: run the forward again without debug bit 8");
-    if (h[1] & MGR_OVF_TIER) return mgr_fail(MGR_ETIER, "a skipped binning tier was needed: run the forward again without debug bits 16 / 32");
-    return MGR_OK;
+    return mgr_overflow_code(h[1]);
 }
 
 extern "C" int mgr_raster_status_tiers_sync(const void* workspace, int64_t* num_pairs, int32_t* overflow, int32_t* tiers,
@@ -3548,16 +3545,13 @@ extern "C" int mgr_raster_status_tiers_sync(const void* workspace, int64_t* num_
     MGR_HIP(hipStreamSynchronize(stream));
     if (num_pairs) *num_pairs = h[0];
     if (overflow) *overflow = (int32_t)h[1];
-    if (tiers) {   // bits 0-1: binning tiers needed; bits 8..15 / 16..23: items of the instance sort beyond 13/16 of
-                   // MGR_DB_RANK_MAX / MGR_DB_RANK_LARGE keys (capped at 255); bits 24..30: items beyond MGR_DB_RANK_MAX keys (the
-                   // next forward should ask for the large instantiation: debug bit 256)
+    if (tiers) {   // MGR_TIERS_*: the header's low bits, then the three counts of the instance sort, each capped at its field's mask
         const uint32_t sb = h[offsetof(MgrHeader, sort_big) / 4], sn = h[offsetof(MgrHeader, sort_near_large) / 4], sl = h[offsetof(MgrHeader, sort_large) / 4];
-        *tiers = (int32_t)(h[offsetof(MgrHeader, tiers) / 4] | ((sb < 0xFFu ? sb : 0xFFu) << 8) | ((sn < 0xFFu ? sn : 0xFFu) << 16) | ((sl < 0x7Fu ? sl : 0x7Fu) << 24));
+        const uint32_t near_max = MGR_TIERS_NEAR_MASK, beyond_max = MGR_TIERS_BEYOND_SMALL_MASK;
+        *tiers = (int32_t)(h[offsetof(MgrHeader, tiers) / 4] | ((sb < near_max ? sb : near_max) << MGR_TIERS_NEAR_SMALL_SHIFT) |
+                           ((sn < near_max ? sn : near_max) << MGR_TIERS_NEAR_LARGE_SHIFT) | ((sl < beyond_max ? sl : beyond_max) << MGR_TIERS_BEYOND_SMALL_SHIFT));
     }
-    if (h[1] & MGR_OVF_PAIRS) return mgr_fail(MGR_EOVERFLOW, "pair capacity exceeded");
-    if (h[1] & MGR_OVF_CUT) return mgr_fail(MGR_ECUT, "depth cut violated: run the forward again without debug bit 8");
-    if (h[1] & MGR_OVF_TIER) return mgr_fail(MGR_ETIER, "a skipped binning tier was needed: run the forward again without debug bits 16 / 32");
-    return MGR_OK;
+    return mgr_overflow_code(h[1]);
 }
 
 extern "C" int mgr_raster_debug_binning_sync(const void* workspace, int V, int N, int W, int H,

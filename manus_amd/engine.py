@@ -24,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import fused as fused_mod, ops, rasterizer
+from . import _lib
 from ._lib import ManusHipError, check, lib, ptr, stream
 
 # packed leaf-gradient layout: 59 floats per Gaussian
@@ -345,7 +346,7 @@ class _DepthCut:
     """The depth-cut hints of one `HipViewCompute` and the policy of using them (fused step only).
 
     Every forward leaves, per tile whose pixels all saturated, the depth in front of which they had stopped (+ a margin);
-    the next forward of the SAME views leaves the instances behind it out of that tile's list (mgr_views_forward, debug bit 8)
+    the next forward of the SAME views leaves the instances behind it out of that tile's list (mgr_views_forward, MGR_FWD_DEPTH_CUT)
     -- the binning kernels then handle a fraction of the pairs, the image and the gradients stay bit for bit those of the full
     lists (a cut list that runs out under an unsaturated pixel is flagged like a pair-capacity overflow and the step is run
     again without the cut).  The hints live in the workspace; when the view set changes they are parked per view set
@@ -366,7 +367,7 @@ class _DepthCut:
     fresh hints).
 
     With the on-device repair (round 6, `HipViewCompute.cut_repair`) tiles whose cut list runs out are completed on the device
-    (debug bit 2048) -- no flagged forward, no re-run, no back-off: a flagged forward is then a capacity matter, rare, and
+    (MGR_FWD_REPAIR) -- no flagged forward, no re-run, no back-off: a flagged forward is then a capacity matter, rare, and
     the margins need neither widening nor the interior-only rule (the library's per-tile countdown keeps the repeat offenders
     out).  `margin` scales the library's default margins there, `penalty` = forwards a tile that ran out goes without a hint.
 
@@ -387,7 +388,7 @@ class _DepthCut:
         self.clean = 0            # forwards with the cut in a row
         self.store = {}           # hint key -> parked hint tables
         self.max_sets = int(max_hints)
-        self.bit = 0              # debug bits of the step's current forward
+        self.bit = 0              # MGR_FWD_* flags of the step's current forward
 
     def new_generation(self):
         self.gen += 1
@@ -395,7 +396,7 @@ class _DepthCut:
         self.born.clear()
 
     def decide(self, key, cut_retries, cut_block, repair, margin=1.0):
-        """(debug bits 0, 8 or 8 | 2048; arguments of mgr_raster_set_cut_margin) for a forward of the views `key`.  cut_retries:
+        """(0, MGR_FWD_DEPTH_CUT or MGR_FWD_DEPTH_CUT | MGR_FWD_REPAIR; arguments of mgr_raster_set_cut_margin) for a forward of the views `key`.  cut_retries:
         the context's count of flagged forwards; cut_block: the previous forward on the workspace was flagged (this one
         rebuilds the hints from full lists)."""
         if cut_retries != self.seen:          # a forward of ours was flagged since the last launch
@@ -417,14 +418,14 @@ class _DepthCut:
             self.pause = (min(self.pause, 4) if repair else self.pause) - 1       # on full lists, no escalation)
             return 0, margins
         if repair:
-            return 8 | 2048, margins
+            return _lib.MGR_FWD_DEPTH_CUT | _lib.MGR_FWD_REPAIR, margins
         self.clean += 1
         if self.clean >= 32:
             self.clean, self.backoff = 0, max(4, self.backoff // 2)
-        return 8, margins
+        return _lib.MGR_FWD_DEPTH_CUT, margins
 
     def flag(self, ws, view_ids, cut_retries, hint_offsets, hint_bytes, repair, margin, penalty):
-        """Debug bits of mgr_views_forward for this forward on `ws`: bit 8 when the workspace holds the hints of exactly these
+        """MGR_FWD_* flags of mgr_views_forward for this forward on `ws`: MGR_FWD_DEPTH_CUT when the workspace holds the hints of exactly these
         views (left by the previous forward, or parked earlier and brought back here) and `decide` lets them be used.
         hint_offsets, hint_bytes: the hints (tile_zcut) and the repair's depth windows that belong to them (tile_zwin) in `ws.buf`."""
         key = (id(self), self.gen, tuple(view_ids))
@@ -456,9 +457,9 @@ class _KeptBuffers:
     """The gradient, statistics and image tensors a `HipViewCompute` with persistent_grads keeps from step to step (fused
     step, no grad_arena): the leaf gradients, the skin-weight gradient, the statistics and the image are written into these
     buffers (see HipViewCompute's docstring).  The backward then zeroes only the rows that were written by the previous step
-    and get nothing now, instead of every row of every gradient every step (mgr_views_backward, debug bit 512: 97 MB of stores
+    and get nothing now, instead of every row of every gradient every step (mgr_views_backward, MGR_BWD_OUTPUTS_KEPT: 97 MB of stores
     per bench step), and the forward writes the background only into empty tiles that held something else
-    (mgr_views_forward, bit 1024).  Both need the workspace's row / tile state to describe THESE buffers: `grad_ws` and
+    (mgr_views_forward, MGR_FWD_IMAGE_KEPT).  Both need the workspace's row / tile state to describe THESE buffers: `grad_ws` and
     `image_ws` name the workspace whose last backward / forward wrote them, None when nobody's does."""
 
     def __init__(self):
@@ -540,7 +541,7 @@ class HipViewCompute:
       attach_list   that mapped list is built by the forward's last kernel (mgr_views_forward_attach_loss_list) instead of a
                     launch of its own.  MANUS_LOSS_LIST_ATTACH=0.
       overlap_loss  without target maps: the span list is built on a second stream while the forward blend runs (forward split
-                    at the blend, debug bits 2 / 4).  MANUS_OVERLAP_LOSS=0."""
+                    at the blend, MGR_FWD_NO_BLEND / MGR_FWD_BLEND_ONLY).  MANUS_OVERLAP_LOSS=0."""
 
     # per-view target maps kept (130 KB per 1080p view)
     MAX_TARGET_MAPS = 4096
@@ -795,7 +796,7 @@ class HipViewCompute:
         return ws.buf.data_ptr() + self._layout(ws, V, N, W, H)[LAYOUT_TILE_START]
 
     def _cut_flag(self, ws, view_ids, V, N, W, H):
-        """Depth-cut debug bits of mgr_views_forward for this forward on `ws` (`_DepthCut.flag`); 0 with the cut off."""
+        """Depth-cut flags of mgr_views_forward for this forward on `ws` (`_DepthCut.flag`); 0 with the cut off."""
         ctx = self.rz.context(self.device)
         if not self.depth_cut or not ctx.fenced(self.sync_check):
             return 0      # (with a host sync per forward the split forward would need a second one after the blend: not worth it)
@@ -818,7 +819,7 @@ class HipViewCompute:
         if kept is not None:
             kept.begin(N, na, dev)
         w, B = self._skin_weights(p["_xyz"], na)
-        if kept is not None:      # the image too is a kept buffer (bit 1024 of the forward)
+        if kept is not None:      # the image too is a kept buffer (MGR_FWD_IMAGE_KEPT)
             out = kept.get((V, 3, H, W), ("image", V, H, W), zeroed=False)
         else:
             out = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
@@ -835,7 +836,7 @@ class HipViewCompute:
         ctx = self.rz.context(dev)
         ws = None
         try:
-            ws, _ = ctx.forward(V, N, W, H, self._forward_launch(fwd, view_ids, loss_list, 2 if route == "overlap" else 0),
+            ws, _ = ctx.forward(V, N, W, H, self._forward_launch(fwd, view_ids, loss_list, _lib.MGR_FWD_NO_BLEND if route == "overlap" else 0),
                                 sync_check=self.sync_check, defer_fence=True)
             if route != "overlap" and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
@@ -881,11 +882,11 @@ class HipViewCompute:
         return lws, self._target_map(view_ids, sel, self.s["bg"]), nbytes
 
     def _views_forward(self, ws, fwd, phase):
-        """One mgr_views_forward on `ws`.  phase: 0 whole, 2 up to the blend, 4 the blend."""
+        """One mgr_views_forward on `ws`.  phase: 0 whole, MGR_FWD_NO_BLEND up to the blend, MGR_FWD_BLEND_ONLY the blend."""
         head, out, radii, kept = fwd
         # kept image: a tile that held the background after the previous forward on the same workspace and is empty again is not
-        # written again (bit 1024)
-        bits = phase | self._cut.bit | ws.skip_bits() | (1024 if (kept is not None and kept.image_ws is ws) else 0)
+        # written again (MGR_FWD_IMAGE_KEPT)
+        bits = phase | self._cut.bit | ws.skip_bits() | (_lib.MGR_FWD_IMAGE_KEPT if (kept is not None and kept.image_ws is ws) else 0)
         check(lib().mgr_views_forward(*head, ptr(out), ptr(radii), ptr(ws.buf), ws.nbytes, ws.cap, bits, stream()), "mgr_views_forward")
         if kept is not None:
             kept.image_ws = ws
@@ -941,7 +942,7 @@ class HipViewCompute:
             with torch.cuda.stream(self._side):
                 check(lib().mgr_image_loss_tiles_list(V, H, W, ptr(tgt), ptr(bg), ctypes.c_void_p(self._tile_start_ptr(ws, V, N, W, H)),
                                                       ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_list")
-            self._views_forward(ws, fwd, 4)             # the blend, next to the list
+            self._views_forward(ws, fwd, _lib.MGR_FWD_BLEND_ONLY)   # the blend, next to the list
             if ctx.fenced(self.sync_check):
                 ctx.fence(ws)                           # (after the blend: it is the blend that raises the depth-cut flag)
             cur.wait_stream(self._side)
@@ -966,8 +967,8 @@ class HipViewCompute:
         st_r = torch.empty(N, dtype=torch.int32, device=dev)
         d_w = e((na, B), "_skin_w") if na else None
         # the buffers are those of the previous backward on this very workspace, untouched since: the library may skip the
-        # zero fill of the rows it knows to be zero (it checks that its row state is that call's; bit 512)
-        bits = 512 if (kept is not None and kept.grad_ws is ws and V <= 8) else 0
+        # zero fill of the rows it knows to be zero (it checks that its row state is that call's)
+        bits = _lib.MGR_BWD_OUTPUTS_KEPT if (kept is not None and kept.grad_ws is ws and V <= 8) else 0
         self._kept.grad_ws = None
         args = (*head, ptr(radii), ptr(out), ptr(g_img), 1.0 / scale, *[ptr(g) for g in grads.values()],
                 ptr(d_w), ptr(st_g), ptr(st_v), ptr(st_r), ptr(ws.buf), ws.nbytes, ws.cap, bits)

@@ -24,7 +24,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, f32c, lib, ptr, stream
+from ._lib import (check, f32c, lib, ptr, stream, MGR_FWD_RANK_LARGE, MGR_FWD_SKIP_BOX_LARGE, MGR_FWD_SKIP_BOX_MID, MGR_FWD_SKIP_SORT_BEHIND,
+                   MGR_FWD_SPREAD, MGR_OVF_CUT, MGR_OVF_FLAGS_MASK, MGR_OVF_PAIRS, MGR_OVF_REPAIRED_SHIFT, MGR_OVF_TIER, MGR_TIERS_BEYOND_SMALL_MASK,
+                   MGR_TIERS_BEYOND_SMALL_SHIFT, MGR_TIERS_BOX_LARGE, MGR_TIERS_BOX_MID, MGR_TIERS_NEAR_LARGE_SHIFT, MGR_TIERS_NEAR_MASK,
+                   MGR_TIERS_NEAR_SMALL_SHIFT, MGR_TIERS_WIDE_RECT)
 from .ops import lbs_cov, sh_colors
 
 
@@ -60,32 +63,32 @@ class RasterWorkspace:
         # zero-filled once: pair tags start at 0 = "never written"
         self.buf = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
         self.busy = False
-        # depth cut (mgr_views_forward, debug bit 8): whose views the per-tile hints in this workspace describe (set by
+        # depth cut (mgr_views_forward, MGR_FWD_DEPTH_CUT): whose views the per-tile hints in this workspace describe (set by
         # the caller that opts in), and "the last forward with the cut was flagged: run the next one without it"
         self.hint_key = self.prev_hint_key = None
         self.cut_block = False
         self.mirror = None
-        # binning tiers (debug bits 16 / 32 of the forward): which LDS tiers beyond the smallest the most recent forward
-        # whose header was read needed (None: unknown -- launch them all)
+        # binning tiers: the MGR_TIERS_* word of the most recent forward whose status was read (None: unknown, launch everything)
         self.tiers = None
         # set by a forward that runs without a host read but promises the caller a complete result (the operator route's
         # automatic fences): launches whose absence would have to be answered by a re-run are then never skipped
         self.no_flagging_skips = False
 
     def skip_bits(self):
-        """debug bits that spare the forward the binning launches its views did not need last time (they are verified on
-        the device: a view that needs a skipped launch flags the forward, which is then run again with all of them)."""
-        if self.tiers is None:
+        """MGR_FWD_* flags that spare the forward the binning launches its views did not need last time (verified on the device:
+        a view that needs a skipped launch flags the forward, MGR_OVF_TIER, which is then run again with all of them)."""
+        t = self.tiers
+        if t is None:
             return 0
-        # sort items of the previous forward beyond 13/16 of k_dbin_rank's small / large capacity, and beyond the small capacity
-        near_s, near_l, large = (self.tiers >> 8) & 0xFF, (self.tiers >> 16) & 0xFF, (self.tiers >> 24) & 0x7F
-        near = near_l if large else near_s          # (the count that belongs to the instantiation this forward asks for)
-        bits = (0 if self.tiers & 1 else 16) | (0 if self.tiers & 2 else 32) | (128 if near <= RasterWorkspace.SORT_BIG_MAX else 0) | (256 if large else 0)
-        bits |= 4096 if self.tiers & 4 else 0       # rectangles of more than 64 tiles met: k_bin_scatter's lane-spreading instantiation
-        # (bit 128 = "the previous forward met no sort item near the LDS of k_dbin_rank: skip the launch behind it" -- verified on the
-        # device like the tile-box tiers, MGR_OVF_TIER; bit 256 = "it met items beyond MGR_DB_RANK_MAX keys: k_dbin_rank's instantiation
-        # for larger items" -- a dense depth slice then costs that kernel ~4 us instead of 33 us in the launch behind)
-        return bits & ~(48 | 128) if self.no_flagging_skips else bits
+        # sort items beyond MGR_DB_RANK_MAX keys met (a dense depth slice): ~4 us in k_dbin_rank's large instantiation, 33 us behind it
+        large = (t >> MGR_TIERS_BEYOND_SMALL_SHIFT) & MGR_TIERS_BEYOND_SMALL_MASK
+        # ... and no item near the LDS of the instantiation this forward asks for: skip the launch behind it
+        near = (t >> (MGR_TIERS_NEAR_LARGE_SHIFT if large else MGR_TIERS_NEAR_SMALL_SHIFT)) & MGR_TIERS_NEAR_MASK
+        bits = ((MGR_FWD_RANK_LARGE if large else 0) | (MGR_FWD_SPREAD if t & MGR_TIERS_WIDE_RECT else 0))
+        if not self.no_flagging_skips:
+            bits |= ((0 if t & MGR_TIERS_BOX_LARGE else MGR_FWD_SKIP_BOX_LARGE) | (0 if t & MGR_TIERS_BOX_MID else MGR_FWD_SKIP_BOX_MID)
+                     | (MGR_FWD_SKIP_SORT_BEHIND if near <= RasterWorkspace.SORT_BIG_MAX else 0))
+        return bits
 
 
 def default_pair_capacity(V, N):
@@ -120,7 +123,7 @@ class RasterContext:
         self._free_pinned = []
         self._evicted_overflow = False   # an overflow seen while retiring old fences: raised by the next poll()
         self.cut_retries = 0             # forwards flagged MGR_OVF_CUT (each is answered by a forward without the depth cut)
-        self.cut_repairs = 0             # (tile, quadrant) units repaired on the device by forwards with the depth cut (bit 2048)
+        self.cut_repairs = 0             # (tile, quadrant) units repaired on the device by forwards with the depth cut (MGR_FWD_REPAIR)
         self._clean = {}                 # (V, N, W, H) -> consecutive synchronised forwards that fitted their capacity
         self._seen = {}                  # (V, N, W, H) -> {id: (weak reference, version)} of the camera tables read back synchronously
         self.auto_fenced = 0             # forwards that ran on an automatic fence instead of the blocking read
@@ -148,7 +151,7 @@ class RasterContext:
                 self._free_pinned.append(pinned)
         for lst in self.pool.values():          # withdraw mirrors that no forward took
             for ws in lst:
-                if getattr(ws, "mirror", None) is not None:
+                if ws.mirror is not None:
                     lib().mgr_raster_set_status_mirror(ptr(ws.buf), None)
                     self._free_pinned.append(ws.mirror)
                     ws.mirror = None
@@ -160,8 +163,34 @@ class RasterContext:
         self._clean.clear()
         self._seen.clear()
 
-    def _learn(self, key, npairs):
-        self.cap_hint[key] = max(self.cap_hint.get(key, 0), int(npairs * 1.25) + 4096)
+    # -- status of a forward --------------------------------------------------------------------
+    # Where the three callers of _digest differ (kept as found, listed in LAB.md): (learn the capacity from a flagged forward
+    # too, MGR_OVF_* bits that hide MGR_OVF_CUT, bits that hide MGR_OVF_TIER -- a hidden flag blocks / counts nothing)
+    _SYNC = (False, MGR_OVF_PAIRS, MGR_OVF_PAIRS | MGR_OVF_CUT)   # forward(): acts on the return code = the first flag set; its retry learns
+    _FENCE = (True, 0, 0)                                         # _resolve(): every flag on its own
+    _RECHECK = (True, MGR_OVF_PAIRS, 0)                           # check_overflow(): the cut by the return code, the tiers by the flag
+
+    def _read_header(self, ws):
+        """Blocking read of the status in the workspace header: (return code, pair count, overflow word, tiers word)."""
+        npairs, ovf, tiers = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = lib().mgr_raster_status_tiers_sync(ptr(ws.buf), ctypes.byref(npairs), ctypes.byref(ovf), ctypes.byref(tiers), stream())
+        return rc, int(npairs.value), int(ovf.value), int(tiers.value)
+
+    def _digest(self, ws, npairs, word, tiers, route):
+        """All the context keeps of one forward's status words, whatever they were read from: the learnt capacity, the tiers
+        for the next forward's skip_bits(), the depth-cut block, the counters.  Returns the MGR_OVF_* flags."""
+        learn_flagged, cut_hidden_by, tier_hidden_by = route
+        ovf = word & MGR_OVF_FLAGS_MASK
+        self.cut_repairs += word >> MGR_OVF_REPAIRED_SHIFT   # quadrants repaired on the device (no re-run); the mirror's word alone carries them
+        if learn_flagged or not ovf:    # the capacity of the next forwards of these sizes: 25 % of headroom
+            self.cap_hint[ws.key] = max(self.cap_hint.get(ws.key, 0), int(npairs * 1.25) + 4096)
+        ws.tiers = None if ovf & MGR_OVF_TIER else tiers          # flagged: the next forward runs every binning launch
+        if ovf & MGR_OVF_CUT and not ovf & cut_hidden_by:         # ... and must not use the hints
+            ws.cut_block = True
+            self.cut_retries += 1
+        if ovf & MGR_OVF_TIER and not ovf & tier_hidden_by:
+            self.tier_retries += 1
+        return ovf
 
     # -- forward driver -------------------------------------------------------------------------
     def _seen_cams(self, key, cams):
@@ -211,29 +240,21 @@ class RasterContext:
                 if not defer_fence:
                     self._fence(ws)
                 return ws, None
-            npairs, ovf, tiers = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
-            rc = lib().mgr_raster_status_tiers_sync(ptr(ws.buf), ctypes.byref(npairs), ctypes.byref(ovf), ctypes.byref(tiers), stream())
-            ws.tiers = None if (ovf.value & 4) else int(tiers.value)
-            if rc == 0:
-                self._learn(key, npairs.value)
+            rc, npairs, word, tiers = self._read_header(ws)
+            self._digest(ws, npairs, word, tiers, self._SYNC)
+            if rc == _lib.MGR_OK:
                 self._clean[key] = self._clean.get(key, 0) + 1
                 if auto_fence and cams is not None:
                     self._see_cams(key, cams)
-                return ws, int(npairs.value)
+                return ws, npairs
             self._clean[key] = 0
-            if rc == -7 and not (ovf.value & 3):   # MGR_ETIER: a skipped binning launch was needed; same workspace, all launches
-                self.tier_retries += 1
-                ws.busy = False
-                continue
-            if rc == -6 and not (ovf.value & 1):   # MGR_ECUT: the depth-cut hints no longer fit; same workspace, no cut
-                ws.cut_block = True
-                self.cut_retries += 1
-                ws.busy = False
-                continue
-            if rc != -4:
-                check(rc, "mgr_raster_status_sync")
-            ws.busy = False  # overflow: retry with room for the observed count
-            cap = int(npairs.value * 1.5) + 4096
+            # MGR_ETIER: a skipped binning launch was needed; MGR_ECUT: the depth-cut hints no longer fit -- the same workspace again,
+            # with all launches / without the cut (_digest has seen to both)
+            if rc not in (_lib.MGR_ETIER, _lib.MGR_ECUT):
+                if rc != _lib.MGR_EOVERFLOW:
+                    check(rc, "mgr_raster_status_sync")
+                cap = int(npairs * 1.5) + 4096   # overflow: retry with room for the observed count
+            ws.busy = False
 
     # -- overflow fences ------------------------------------------------------------------------
     def fence(self, ws):
@@ -252,7 +273,7 @@ class RasterContext:
         pinned = self._free_pinned.pop() if self._free_pinned else torch.zeros(4, dtype=torch.int32).pin_memory()
         pinned[3] = 0
         rc = lib().mgr_raster_set_status_mirror(ptr(ws.buf), ctypes.c_void_p(pinned.data_ptr()))
-        ws.mirror = pinned if rc == 0 else None      # (not mappable: the fence falls back to a blocking read)
+        ws.mirror = pinned if rc == _lib.MGR_OK else None      # (not mappable: the fence falls back to a blocking read)
 
     def _fence(self, ws):
         """Remember the forward just queued: the host can later wait for THIS forward only, while the kernels queued after
@@ -260,8 +281,7 @@ class RasterContext:
         the status words and then their valid flag into pinned memory, and the host waits on that flag (an event behind
         the forward costs ~6 us of idle GPU: the next kernel does not start until it has signalled).  Without a mirror:
         an event."""
-        mirror = getattr(ws, "mirror", None)
-        ev = None
+        mirror, ev = ws.mirror, None
         if mirror is None:
             ev = torch.cuda.Event()
             ev.record()
@@ -287,25 +307,12 @@ class RasterContext:
         elif pinned is not None and not self._wait_flag(pinned):
             torch.cuda.synchronize(self.device)      # (a forward whose blend never ran: nothing will write the flag)
         if pinned is not None and int(pinned[3].item()) == 1:
-            npairs, word, tiers_seen = int(pinned[0].item()) & 0xFFFFFFFF, int(pinned[1].item()) & 0xFFFFFFFF, int(pinned[2].item())
-            ovf = word & 0xFFFF
-            self.cut_repairs += word >> 16       # quadrants of depth-cut tiles the forward repaired on the device (no re-run)
+            npairs, word, tiers = int(pinned[0].item()) & 0xFFFFFFFF, int(pinned[1].item()) & 0xFFFFFFFF, int(pinned[2].item())
         else:   # (a forward that did not run its blend, or no mirror: read the header -- valid if nothing ran on ws since)
-            n_, o_, t_ = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
-            lib().mgr_raster_status_tiers_sync(ptr(ws.buf), ctypes.byref(n_), ctypes.byref(o_), ctypes.byref(t_), stream())
-            npairs, ovf, tiers_seen = int(n_.value), int(o_.value), int(t_.value)
+            _, npairs, word, tiers = self._read_header(ws)
         if pinned is not None:
             self._free_pinned.append(pinned)
-        self._learn(ws.key, npairs)
-        if ovf & 2:     # MGR_OVF_CUT: the caller re-runs the step; that forward must not use the hints
-            ws.cut_block = True
-            self.cut_retries += 1
-        if ovf & 4:     # MGR_OVF_TIER: ... and with every binning launch
-            ws.tiers = None
-            self.tier_retries += 1
-        else:
-            ws.tiers = tiers_seen
-        return npairs, ovf
+        return npairs, self._digest(ws, npairs, word, tiers, self._FENCE)   # (flagged: the caller re-runs the step)
 
     def poll(self):
         """Wait for the forwards recorded so far (not for what was queued after them) and raise ManusHipError if one
@@ -328,18 +335,10 @@ class RasterContext:
         ws = self.last_ws
         if ws is None:
             return polled
-        npairs, ovf, tiers = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        rc = lib().mgr_raster_status_tiers_sync(ptr(ws.buf), ctypes.byref(npairs), ctypes.byref(ovf), ctypes.byref(tiers), stream())
-        self._learn(ws.key, npairs.value)
-        ws.tiers = None if (ovf.value & 4) else int(tiers.value)
-        if ovf.value & 4:
-            self.tier_retries += 1
-        if rc == -6:
-            ws.cut_block = True
-            self.cut_retries += 1
-        if rc != 0:
-            check(rc, "rasterizer overflow check (retry: capacity hint was enlarged)")
-        return int(npairs.value)
+        rc, npairs, word, tiers = self._read_header(ws)
+        self._digest(ws, npairs, word, tiers, self._RECHECK)
+        check(rc, "rasterizer overflow check (retry: capacity hint was enlarged)")
+        return npairs
 
 
 _CONTEXTS = {}
@@ -394,7 +393,7 @@ def _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opacity, debug, s
     def launch(ws):
         check(lib().mgr_raster_forward(V, N, W, H, ptr(cams), ptr(bg), ptr(means3D), s_m, ptr(cov3D), s_c,
                                        ptr(colors), s_col, ptr(opacity), s_o, ptr(out), ptr(radii),
-                                       ptr(ws.buf), ws.nbytes, ws.cap, int(bool(debug)) | ws.skip_bits(), stream()),
+                                       ptr(ws.buf), ws.nbytes, ws.cap, (_lib.MGR_FWD_CHECK if debug else 0) | ws.skip_bits(), stream()),
               "mgr_raster_forward")
 
     ws, npairs = context(dev).forward(V, N, W, H, launch, sync_check, auto_fence=graph, cams=cams)
@@ -448,7 +447,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         check(lib().mgr_raster_backward(V, N, W, H, ptr(cams), ptr(bg), ptr(means3D), s_m, ptr(cov3D), s_c,
                                         ptr(colors), s_col, ptr(opac), s_o, ptr(out), ptr(g_color), ptr(d_m3), ptr(d_m2),
                                         ptr(d_col), ptr(d_op), ptr(d_cov), ptr(ws.buf), ws.nbytes, ws.cap,
-                                        int(debug), stream()), "mgr_raster_backward")
+                                        _lib.MGR_BWD_CHECK if debug else 0, stream()), "mgr_raster_backward")
 
         def fold(g, shared, shape=None):
             # inputs shared by all views receive the sum over views

@@ -265,6 +265,43 @@ def test_skipped_binning_tiers_are_verified_and_retried():
         assert np.array_equal(got_far[k], want_far[k]), k
 
 
+def test_status_reader_learns_the_same_on_every_route():
+    """What RasterContext keeps of a forward's status -- the learnt capacity, the binning tiers, the retry counters -- must not
+    depend on where the status words came from: the blocking read of a synchronous forward, the pinned mirror a fence
+    resolves in poll(), or the header re-read of check_overflow().  Two views of 3000 Gaussians at 160x96 (a partial tile
+    column and row), small enough to fit the default pair capacity: no route retries."""
+    from manus_amd import rasterizer as rz
+    from manus_amd._lib import lib, ptr, stream
+    W, H, n = 160, 96, 3000
+    cams = [make_camera(W, H, pos=p) for p in [(0.3, -0.2, -1.5), (-0.8, 0.1, -1.2)]]
+    m, c, col, op = random_gaussians(n, seed=5, sigma=(0.005, 0.03))
+    ctx = rz.context()
+
+    def learnt(sync, read):
+        ctx.clear()
+        ctx.cut_retries = ctx.tier_retries = 0
+        rz.set_sync_policy(sync)
+        try:
+            _hip(cams, m, c, col, op)
+            npairs = read()
+        finally:
+            rz.set_sync_policy(True)
+        ws = ctx.last_ws
+        return npairs, ctx.cap_hint[(2, n, W, H)], ws.tiers, ws.skip_bits(), ctx.cut_retries, ctx.tier_retries
+
+    def header_pairs():      # the pair count of the workspace header, past the context
+        npairs, ovf = ctypes.c_int64(0), ctypes.c_int32(0)
+        assert lib().mgr_raster_status_sync(ptr(ctx.last_ws.buf), ctypes.byref(npairs), ctypes.byref(ovf), stream()) == 0
+        return int(npairs.value)
+
+    sync = learnt(True, header_pairs)
+    assert 0 < sync[0] <= 8 * 2 * n and sync[1] == int(sync[0] * 1.25) + 4096
+    assert sync[2] is not None and sync[4:] == (0, 0)
+    assert learnt(False, ctx.poll) == sync
+    assert learnt(False, ctx.check_overflow) == sync
+    ctx.clear()
+
+
 def test_multi_view_batch_equals_single_views_bitwise():
     W, H = 160, 96
     cams = [make_camera(W, H, pos=p) for p in [(0.3, -0.2, -1.5), (-0.8, 0.1, -1.2), (0.1, 0.9, -1.3)]]

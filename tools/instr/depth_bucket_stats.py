@@ -14,7 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from manus_amd import rasterizer  # noqa: E402
+from manus_amd import _lib, rasterizer  # noqa: E402
 from manus_amd.engine import HipViewCompute, Trainer  # noqa: E402
 from manus_amd.synthetic import camera_table, make_scene  # noqa: E402
 from parity import layout  # noqa: E402
@@ -43,7 +43,9 @@ def report(tag):
     vis = ((rect[..., 2] - rect[..., 0]) * (rect[..., 3] - rect[..., 1]) > 0)
     t = ws.tiers or 0
     print("%s: sort items of the last forward beyond 13/16 of k_dbin_rank's small capacity: %d, of its large one: %d; beyond the small capacity: %d; "
-          "debug bits of the next forward: %d" % (tag, (t >> 8) & 0xFF, (t >> 16) & 0xFF, (t >> 24) & 0x7F, ws.skip_bits()))
+          "MGR_FWD_* flags of the next forward: %d"
+          % (tag, (t >> _lib.MGR_TIERS_NEAR_SMALL_SHIFT) & _lib.MGR_TIERS_NEAR_MASK, (t >> _lib.MGR_TIERS_NEAR_LARGE_SHIFT) & _lib.MGR_TIERS_NEAR_MASK,
+             (t >> _lib.MGR_TIERS_BEYOND_SMALL_SHIFT) & _lib.MGR_TIERS_BEYOND_SMALL_MASK, ws.skip_bits()))
     for v in range(V):
         z = depth[v][vis[v]]
         lo, hi = z.min(), z.max()
