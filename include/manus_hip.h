@@ -224,7 +224,8 @@ int mgr_raster_backward(int V, int N, int W, int H, const float* cams, const flo
                         size_t workspace_bytes, int64_t pair_capacity, int flags, void* stream);
 
 /* Feature render: composite C caller channels, and optionally expected depth and accumulated opacity, over the tile lists
- * the LAST FORWARD left in `workspace` -- no projection, no sort, no binning.  Forward only (no gradient).
+ * the LAST FORWARD left in `workspace` -- no projection, no sort, no binning.  (Its gradients:
+ * mgr_raster_blend_features_backward below.)
  *   out_feat[v, c, y, x] = sum_i w_i features[v, gid_i, c] + T_final bg_feat[c],   w_i = alpha_i T_i
  * with exactly the (pixel, entry) contributions of that forward's image: the same alpha arithmetic and keep rule
  * (alpha >= 1/255, clamped to 0.99), the same stop rule (an entry that would bring T below 1e-4 ends the pixel's walk and
@@ -256,6 +257,39 @@ int mgr_raster_backward(int V, int N, int W, int H, const float* cams, const flo
 int mgr_raster_blend_features(int V, int N, int C, int W, int H, const float* features, int64_t stride_features,
                               const float* bg_feat, int with_depth, float* out_feat, float* out_alpha,
                               const void* workspace, size_t workspace_bytes, int64_t pair_capacity, void* stream);
+
+/* Backward of the feature render: gradients of a loss on the maps of the mgr_raster_blend_features call described by the same
+ * V, N, C, W, H, features, with_depth, through the tile lists of the SAME forward (still the last one on `workspace`).
+ * out_feat (V, C + (with_depth ? 1 : 0), H, W) and out_alpha (V, H, W) are what that call produced (each needed only where
+ * its gradient is given; bg_feat is accepted for symmetry and not read: the background's share is in out_feat).
+ * dL_dout_feat: (V, C + (with_depth ? 1 : 0), H, W) or NULL; dL_dalpha: (V, H, W) or NULL; both NULL is MGR_EINVAL.
+ * Per pixel, with g the upstream gradients and s_i = f_i . g (the depth a channel f = z, the alpha a channel f = 1, both on
+ * background 0):  dL/df_ic = w_i g_c,  dL/dz_i = w_i g_depth,  dL/dalpha_i = T_i s_i - (suffix_i . g) / (1 - alpha_i) -- the
+ * conventions of mgr_raster_backward: the forward's keep and stop rules and list order, the gradient passes through the 0.99
+ * clamp, the sort order is not differentiated.  From dL/dalpha the path is mgr_raster_backward's (conic, mean2D, opacity,
+ * then the projection's backward); the depth adds dL/dz times the z row of the view matrix to dL_dmeans3D.
+ * Outputs, every element written (zero rows for culled Gaussians and Gaussians without a contributing pair):
+ * dL_dmeans3D (V,N,3), dL_dmeans2D (V,N,3; units and z = 0 as mgr_raster_backward), dL_dopacity (V,N), dL_dcov3D (V,N,6),
+ * dL_dfeatures (V,N,C) per view (NULL when C = 0).  cams, means3D, cov3D and their strides are the forward's.
+ * The workspace is ONLY READ: a colour backward before, between or after changes nothing, and the two backwards of one
+ * forward may run in either order.  All temporary state lives in the caller's `scratch` of at least
+ * mgr_raster_feat_backward_workspace_bytes bytes (MGR_ENOMEM below that); its contents need not be initialised and mean nothing
+ * after the call.  Deterministic: one record per (tile, Gaussian) pair in the pair's private slot, summed per (view, Gaussian)
+ * in slot order; no atomics.  Channels go in the forward's groups of up to 8, one walk of the lists per group.
+ * Refusals before anything is launched: the MGR_ESTATE cases of mgr_raster_blend_features (one blocking read of the header).
+ * flags: MGR_BWD_CHECK synchronises and checks after every launch. */
+size_t mgr_raster_feat_backward_workspace_bytes(int V, int N, int C, int W, int H, int64_t pair_capacity);
+int mgr_raster_blend_features_backward(int V, int N, int C, int W, int H, const float* cams, const float* means3D,
+                                       int64_t stride_means3D, const float* cov3D, int64_t stride_cov3D, const float* features,
+                                       int64_t stride_features, const float* bg_feat, int with_depth, const float* out_feat,
+                                       const float* out_alpha, const float* dL_dout_feat, const float* dL_dalpha,
+                                       float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity, float* dL_dcov3D,
+                                       float* dL_dfeatures, const void* workspace, size_t workspace_bytes, int64_t pair_capacity,
+                                       void* scratch, size_t scratch_bytes, int flags, void* stream);
+
+/* Sequence number of the last forward binned on `workspace` (0: none yet), one blocking read on `stream`.  A caller that comes
+ * back to a forward's lists later notes it behind the forward and compares before it calls the backward below. */
+int mgr_raster_forward_seq_sync(const void* workspace, uint32_t* seq, void* stream);
 
 /* ------------------------------------------------------------------------
  * Fused articulated path (training engine): canonical parameters in, image out.

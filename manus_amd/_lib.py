@@ -48,6 +48,10 @@ SIGNATURES = {
                                     c_i64, c_int, c_vp]),
     "mgr_raster_blend_features": (c_int, [c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp, c_sz,
                                           c_i64, c_vp]),
+    "mgr_raster_feat_backward_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_i64]),
+    "mgr_raster_blend_features_backward": (c_int, [c_int] * 5 + [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_int] + [c_vp] * 9
+                                           + [c_vp, c_sz, c_i64, c_vp, c_sz, c_int, c_vp]),
+    "mgr_raster_forward_seq_sync": (c_int, [c_vp, ctypes.POINTER(ctypes.c_uint32), c_vp]),
     "mgr_sh_to_half": (c_int, [c_int, c_vp, c_vp, c_vp]),
     "mgr_views_forward": (c_int, [c_int] * 7 + [c_vp] * 12 + [c_vp, c_sz, c_i64, c_int, c_vp]),
     "mgr_views_backward": (c_int, [c_int] * 7 + [c_vp] * 13 + [c_f32] + [c_vp] * 10 + [c_vp, c_sz, c_i64, c_int, c_vp]),

@@ -1,5 +1,6 @@
 // Feature render: composite caller channels, expected depth and accumulated opacity over the tile lists the last forward
-// left in a workspace (mgr_raster_blend_features).  Forward only, the workspace is read and never written.
+// left in a workspace (mgr_raster_blend_features), and the gradients of a loss on those maps
+// (mgr_raster_blend_features_backward).  The workspace is read and never written by either.
 //
 //   out[v, c, y, x] = sum_i w_i f[v, gid_i, c] + T_final bg[c],   w_i = alpha_i T_i
 //   depth           = sum_i w_i z_i          (EXPECTED depth: not divided by the accumulated opacity, background 0)
@@ -15,7 +16,27 @@
 // Channels: a launch carries up to CG accumulators per lane (CG = 2, 4, 8); more channels are further launches, each walking the
 // lists again.  Lane l of a wave fetches entry l of the batch -- its record, its CG feature values (a row is C floats at any
 // 4-byte alignment: scalar loads), its depth -- and writes them to LDS; all 64 lanes then consume the staged entries.
-#include "mgr_common.h"
+//
+// Backward (mgr_raster_blend_features_backward, second half of this file): gradients of a loss on those maps.  With g the upstream
+// gradients of the maps at a pixel and s_i = f_i . g over the channels of a launch (the depth is the channel f = z, the alpha
+// the channel f = 1, both on background 0),
+//   dL/df_ic    = sum_pixels w_i g_c,      dL/dz_i = sum_pixels w_i g_depth,
+//   dL/dalpha_i = T_i s_i - (suffix_i . g) / (1 - alpha_i),     suffix_i . g = (out . g) - (prefix through i) . g
+// -- the colour backward's expression (k_blend_bwd, raster_bwd.hip) with the total taken from the forward's own output maps,
+// walked FRONT TO BACK with the running prefix, the keep and stop rules of the walk above, the gradient passed through the
+// 0.99 clamp as upstream.  k_blend_feat_bwd: one workgroup per tile, one wave per 8x8 quadrant, the walk of k_blend_feat; per
+// contributing entry a wave reduces its 64 pixels' six geometry terms (v = G dL/dalpha: sum v dx, v dy, v dx^2, v dx dy, v dy^2,
+// v) and the launch's channel terms (w g_c) with mgr_wave_reduce8, parks the totals in its LDS row of the entry, and after the
+// batch (workgroup barrier) lane j of wave 0 adds the four quadrants' rows of entry j in quadrant order, applies the
+// per-Gaussian factors of the colour backward's flush and writes ONE 64-byte record to the (tile, Gaussian) pair's private slot
+// (slot base + by * rect width + bx of the grec) in the CALLER'S scratch, with the launch's tag.  The four waves leave the walk
+// at different times, so the batch loop's trip count is made uniform by a workgroup vote: a finished wave still meets every
+// barrier.  k_feat_gather: one thread per (view, Gaussian) sums its slots in slot order (tag == the launch's), writes the
+// launch's dL/dfeatures columns, keeps the geometry sums in the scratch across the launches of a call (they add: the
+// expression is linear in g) and, behind the last launch, applies project_backward and the depth's z row.  No atomics, fixed
+// orders: bit-reproducible.  The workspace is only read; the tags of the scratch are CLEARED at the start of every call (a
+// slot nobody wrote counts as zero because its tag is 0, the launches' tags are 1, 2, ...).
+#include "instance_math.h"
 
 #define FEAT_MAX_C 32
 #define FEAT_GRID 4096
@@ -183,6 +204,38 @@ __global__ __launch_bounds__(256) void k_blend_feat(const FeatArgs a) {
     }
 }
 
+// What the last forward left in a workspace: one blocking read of the header, then every refusal is the host's (nothing is
+// launched).  `who` names the caller in the error text.
+static int feat_read_state(const char* who, const char* ws, const MgrLayout& L, int V, int N, int W, int H, int64_t cap, int VT,
+                           hipStream_t stream, MgrHeader& h) {
+    const size_t head_bytes = offsetof(MgrHeader, qctr);
+    MGR_HIP(hipMemcpyAsync(&h, ws + L.header, head_bytes, hipMemcpyDeviceToHost, stream));
+    MGR_HIP(hipStreamSynchronize(stream));
+    if (h.fwd_seq == 0u) return mgr_fail(MGR_ESTATE, "%s: no forward has run on this workspace", who);
+    if (h.feat_seq != h.fwd_seq)
+        return mgr_fail(MGR_ESTATE, "%s: the last forward on this workspace did not run its blend (MGR_FWD_NO_BLEND)", who);
+    if (h.feat_dims[0] != (uint32_t)V || h.feat_dims[1] != (uint32_t)N || h.feat_dims[2] != (uint32_t)W ||
+        h.feat_dims[3] != (uint32_t)H || h.feat_dims[4] != (uint32_t)cap)
+        return mgr_fail(MGR_ESTATE, "%s: the last forward on this workspace was made for another V, N, W, H or pair capacity", who);
+    if (h.feat_flags & MGR_FEAT_CUT)
+        return mgr_fail(MGR_ESTATE, "%s: the last forward applied the depth cut (MGR_FWD_DEPTH_CUT): its lists are cut short", who);
+    if (h.overflow != 0u)
+        return mgr_fail(MGR_ESTATE, "%s: the last forward raised an overflow bit: its lists are incomplete", who);
+    if (h.queue_len > (uint32_t)VT || h.queue_len_i > (uint32_t)VT)
+        return mgr_fail(MGR_ESTATE, "%s: the header's queue lengths do not fit these sizes", who);
+    return MGR_OK;
+}
+
+// Sequence number of the last forward binned on a workspace (MgrHeader::fwd_seq; 0: none yet), one blocking read: a caller that
+// comes back to a forward's lists later (the feature backward under autograd) compares it with the number it noted.
+extern "C" int mgr_raster_forward_seq_sync(const void* workspace, uint32_t* seq, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!workspace || !seq) return mgr_fail(MGR_EINVAL, "mgr_raster_forward_seq_sync: null pointer");
+    MGR_HIP(hipMemcpyAsync(seq, (const char*)workspace + offsetof(MgrHeader, fwd_seq), 4, hipMemcpyDeviceToHost, stream));
+    MGR_HIP(hipStreamSynchronize(stream));
+    return MGR_OK;
+}
+
 extern "C" int mgr_raster_blend_features(int V, int N, int C, int W, int H, const float* features, int64_t stride_features,
                                          const float* bg_feat, int with_depth, float* out_feat, float* out_alpha,
                                          const void* workspace, size_t workspace_bytes, int64_t cap, void* stream_) {
@@ -200,25 +253,13 @@ extern "C" int mgr_raster_blend_features(int V, int N, int C, int W, int H, cons
     if (gx > 65535 || gy > 65535) return mgr_fail(MGR_EINVAL, "mgr_raster_blend_features: image too large");
     const MgrLayout L = mgr_layout(V, N, W, H, cap);
     if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_raster_blend_features: workspace too small for these sizes");
-    // what the last forward left: one blocking read of the header, then every refusal is the host's (nothing is launched)
     const char* ws = (const char*)workspace;
     MgrHeader h;
-    const size_t head_bytes = offsetof(MgrHeader, qctr);
-    MGR_HIP(hipMemcpyAsync(&h, ws + L.header, head_bytes, hipMemcpyDeviceToHost, stream));
-    MGR_HIP(hipStreamSynchronize(stream));
-    if (h.fwd_seq == 0u) return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: no forward has run on this workspace");
-    if (h.feat_seq != h.fwd_seq)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward on this workspace did not run its blend (MGR_FWD_NO_BLEND)");
-    if (h.feat_dims[0] != (uint32_t)V || h.feat_dims[1] != (uint32_t)N || h.feat_dims[2] != (uint32_t)W ||
-        h.feat_dims[3] != (uint32_t)H || h.feat_dims[4] != (uint32_t)cap)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward on this workspace was made for another V, N, W, H or pair capacity");
-    if (h.feat_flags & MGR_FEAT_CUT)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward applied the depth cut (MGR_FWD_DEPTH_CUT): its lists are cut short");
-    if (h.overflow != 0u)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the last forward raised an overflow bit: its lists are incomplete");
     const int VT = V * gx * gy;
-    if (h.queue_len > (uint32_t)VT || h.queue_len_i > (uint32_t)VT)
-        return mgr_fail(MGR_ESTATE, "mgr_raster_blend_features: the header's queue lengths do not fit these sizes");
+    {
+        const int rc = feat_read_state("mgr_raster_blend_features", ws, L, V, N, W, H, cap, VT, stream, h);
+        if (rc != MGR_OK) return rc;
+    }
 
     FeatArgs a;
     a.N = N; a.W = W; a.H = H; a.gx = gx; a.gy = gy; a.VT = VT;
@@ -247,5 +288,407 @@ extern "C" int mgr_raster_blend_features(int V, int N, int C, int W, int H, cons
         c0 += n;
         first = false;
     } while (c0 < Cout);
+    return MGR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Backward
+// ---------------------------------------------------------------------------------------------------------------------
+#define FEAT_REC 16                   // floats per pair record of the scratch: [0..5] geometry, [6 ..] the launch's channel slots
+#define FEAT_GEO 8                    // floats per (view, Gaussian) kept across the launches: geometry, dL/dz, records seen
+
+struct FeatScratch {
+    size_t tag, rec, geo, total;
+};
+static inline FeatScratch feat_scratch_layout(int V, int N, int64_t cap) {
+    FeatScratch S;
+    const size_t c = (size_t)(cap > 0 ? cap : 1), VN = (size_t)V * (size_t)(N > 0 ? N : 1);
+    size_t o = 0;
+    S.tag = o; o += mgr_align(c * 4);
+    S.rec = o; o += mgr_align(c * FEAT_REC * 4);
+    S.geo = o; o += mgr_align(VN * FEAT_GEO * 4);
+    S.total = o;
+    return S;
+}
+
+extern "C" size_t mgr_raster_feat_backward_workspace_bytes(int V, int N, int C, int W, int H, int64_t cap) {
+    (void)C; (void)W; (void)H;        // (a record carries one launch's channels, whatever C; nothing is kept per pixel)
+    if (V <= 0 || N < 0 || cap < 0) return 0;
+    return feat_scratch_layout(V, N, cap).total;
+}
+
+struct FeatBwdArgs {
+    int N, W, H, gx, gy, VT;
+    uint32_t n_queue, cap;
+    const uint4* tile_qrec;
+    const uint32_t* sorted_gid;
+    const MgrGRec* grec;
+    const float* depth;
+    const float* feat;
+    long long s_feat;
+    int C, c0, nc, with_z;           // as FeatArgs
+    const float* out;                // (V, Cout, H, W): what the forward call produced
+    const float* g_out;              // its upstream gradient
+    int Cout;
+    const float* out_alpha;          // (V, H, W) and its upstream gradient: the launch that carries the alpha, null otherwise
+    const float* g_alpha;
+    float* rec;                      // scratch: FEAT_REC floats per pair slot
+    uint32_t* tag;
+    uint32_t tagval;
+};
+
+// The 64 pixels' terms of one entry -> the wave's LDS row of the entry: [Sx, Sy, Sxx, Sxy, Syy, sum v, sum w g_0, ...].
+// mgr_wave_reduce8 leaves the total of x[MGR_R8_SLOT(lane >> 3)] in the 8 lanes of group lane >> 3: a fixed tree.
+template <int CG>
+__device__ __forceinline__ void feat_bwd_reduce(float v, float w, float dx, float dy, const float gk[CG], float* arow, int lane) {
+    const float vx = v * dx, vy = v * dy;
+    const int k = MGR_R8_SLOT(lane >> 3);
+    const float t0 = mgr_wave_reduce8(vx, vy, vx * dx, vx * dy, vy * dy, v, w * gk[0], w * gk[1], lane);
+    if ((lane & 7) == 0) arow[k] = t0;
+    if (CG > 2) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = j + 2 < CG ? w * gk[j + 2 < CG ? j + 2 : 0] : 0.0f;
+        const float t1 = mgr_wave_reduce8(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], lane);
+        if ((lane & 7) == 0) arow[8 + k] = t1;
+    }
+}
+
+template <int CG>
+__global__ __launch_bounds__(256) void k_blend_feat_bwd(const FeatBwdArgs a) {
+    constexpr int NV = CG == 2 ? 8 : 16;                      // floats of a record in use
+    __shared__ __align__(16) float s_pair[4][32][MGR_PAIR_FLOATS];
+    __shared__ __align__(16) float s_feat[4][64 + 1][CG];
+    __shared__ float s_acc[4][64][NV + 1];                    // (+ 1: rows of an odd stride)
+    __shared__ uint32_t s_flag[4][64];                        // entry j of the batch has a row in quadrant q
+    __shared__ uint32_t s_alive[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int quad = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int N = a.N, W = a.W, H = a.H, gx = a.gx, T = a.gx * a.gy;
+    const size_t P = (size_t)W * H;
+    const int ns = a.nc + (a.with_z ? 1 : 0);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    float* const slab = &s_pair[quad][0][0];
+    float* const frow = &s_feat[quad][0][0];
+    const uint32_t gid_max = (uint32_t)(N > 0 ? N - 1 : 0);
+
+    for (uint32_t q = blockIdx.x; q < a.n_queue; q += gridDim.x) {
+        const uint4 qrec = a.tile_qrec[q];
+        const uint32_t vt = qrec.x;
+        if (vt == MGR_HOLE || vt >= (uint32_t)a.VT) continue;             // (uniform over the workgroup)
+        const int v = (int)(vt / (uint32_t)T), t = (int)(vt % (uint32_t)T);
+        const int bx = t % gx, by = t / gx;
+        const uint32_t start = min(qrec.y, a.cap), nlist = min(qrec.z, a.cap - start);
+        const int px = bx * 16 + (quad & 1) * 8 + (lane & 7);
+        const int py = by * 16 + (quad >> 1) * 8 + (lane >> 3);
+        const bool inside = px < W && py < H;
+        const mgr_v2f fpx2 = {(float)px, (float)px}, fpy2 = {(float)py, (float)py};
+        const float qx0 = (float)(bx * 16 + (quad & 1) * 8), qy0 = (float)(by * 16 + (quad >> 1) * 8);
+        const MgrGRec* const gv = a.grec + (size_t)v * N;
+        const float* const zv = a.depth + (size_t)v * N;
+        const float* const fv = a.feat ? a.feat + (size_t)v * (size_t)a.s_feat + a.c0 : nullptr;
+        const uint32_t* const sg = a.sorted_gid + start;
+        const uint32_t lastidx = (nlist ? nlist : 1u) - 1u;
+
+        // the pixel's upstream gradients and (forward output) . g = everything the walk will sum, background included
+        float gk[CG], ga = 0.0f, Og = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CG; ++k) gk[k] = 0.0f;
+        if (inside) {
+            const size_t pix = (size_t)py * W + px;
+            if (ns > 0) {
+                const size_t o = ((size_t)v * a.Cout + a.c0) * P + pix;
+#pragma unroll
+                for (int k = 0; k < CG; ++k)
+                    if (k < ns) {
+                        gk[k] = a.g_out[o + (size_t)k * P];
+                        Og += a.out[o + (size_t)k * P] * gk[k];
+                    }
+            }
+            if (a.g_alpha) {
+                ga = a.g_alpha[(size_t)v * P + pix];
+                Og += a.out_alpha[(size_t)v * P + pix] * ga;
+            }
+        }
+        float Tr = 1.0f, pg = 0.0f;       // transmittance in front of the next entry, (prefix through the last one) . g
+        bool done = !inside;
+
+        for (uint32_t off = 0; off < nlist; off += 64) {
+            // the vote: the batch is walked while any of the four quadrants has a pixel that still accumulates
+            const unsigned long long live = __builtin_amdgcn_ballot_w64(!done);
+            if (lane == 0) s_alive[quad] = live != 0ull ? 1u : 0u;
+            __syncthreads();
+            if ((s_alive[0] | s_alive[1] | s_alive[2] | s_alive[3]) == 0u) break;
+            // lane l: entry l of the batch (every wave: wave 0 writes the records from these)
+            const uint32_t gid = min(sg[min(off + (uint32_t)lane, lastidx)], gid_max);
+            const float4 ra = *(const float4*)(gv + gid), rb = *((const float4*)(gv + gid) + 1), rcz = *((const float4*)(gv + gid) + 2);
+            s_flag[quad][lane] = 0u;
+            int bx0, by0, bx1, by1;
+            if (mgr_quad_bbox(live, bx0, by0, bx1, by1)) {
+                bool alive = false;
+                if (off + lane < nlist)
+                    alive = !mgr_box_dead(ra.x, ra.y, ra.z, ra.w, rb.x, mgr_qmax(rb.y), qx0 + (float)bx0, qy0 + (float)by0,
+                                          qx0 + (float)bx1, qy0 + (float)by1);
+                const unsigned long long m = __ballot(alive);
+                const int cnt = __popcll(m);
+                __builtin_amdgcn_wave_barrier();
+                if (alive) {
+                    const int rank = __popcll(m & lt);
+                    float f[CG];
+#pragma unroll
+                    for (int k = 0; k < CG; ++k) f[k] = k < a.nc ? fv[(size_t)gid * a.C + k] : 0.0f;
+                    if (a.with_z) {
+                        const float z = zv[gid];
+#pragma unroll
+                        for (int k = 0; k < CG; ++k) f[k] = k == a.nc ? z : f[k];
+                    }
+                    float* pb = slab + (rank >> 1) * MGR_PAIR_FLOATS;
+                    mgr_pair_store(pb, rank & 1, ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, 0.f, 0.f, 0.f, (uint32_t)lane);   // pos = place in the batch
+                    float* fr = frow + rank * CG;
+#pragma unroll
+                    for (int k = 0; k < CG; ++k) fr[k] = f[k];
+                    if ((cnt & 1) && rank == cnt - 1) {
+                        mgr_pair_pad(pb);
+#pragma unroll
+                        for (int k = 0; k < CG; ++k) fr[CG + k] = 0.0f;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                const int npair = (cnt + 1) >> 1;
+                for (int p = 0; p < npair; ++p) {
+                    const float4* pp = (const float4*)(slab + p * MGR_PAIR_FLOATS);
+                    const float4 R0 = pp[0], R1 = pp[1], R2 = pp[2], R4 = pp[4];
+                    float fa[CG], fb[CG];
+                    const float* fp = frow + 2 * p * CG;
+#pragma unroll
+                    for (int k = 0; k < CG; ++k) { fa[k] = fp[k]; fb[k] = fp[CG + k]; }
+                    mgr_v2f dx, dy, G, al;
+                    bool va, vb;
+                    mgr_pair_alpha(R0, R1, R2, fpx2, fpy2, dx, dy, G, al, va, vb);
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const float al_e = ((e ? vb : va) && !done) ? (e ? al.y : al.x) : 0.0f;
+                        const float oma = 1.0f - al_e;
+                        const float testT = Tr * oma;
+                        const bool stop = testT < 0.0001f;
+                        const bool valid = al_e > 0.0f && !stop;             // the forward's contribution set
+                        if (__builtin_amdgcn_ballot_w64(valid) != 0ull) {    // (wave-uniform)
+                            const float* f = e ? fb : fa;
+                            float s = ga;
+#pragma unroll
+                            for (int k = 0; k < CG; ++k) s += f[k] * gk[k];
+                            const float w = valid ? al_e * Tr : 0.0f;
+                            pg += w * s;
+                            const float da = valid ? Tr * s - (Og - pg) * __builtin_amdgcn_rcpf(oma) : 0.0f;
+                            const uint32_t j = __float_as_uint(e ? R4.w : R4.z) & 63u;
+                            feat_bwd_reduce<CG>((e ? G.y : G.x) * da, w, e ? dx.y : dx.x, e ? dy.y : dy.x, gk, &s_acc[quad][j][0], lane);
+                            if (lane == 0) s_flag[quad][j] = 1u;
+                        }
+                        Tr = stop ? Tr : testT;
+                        done = done || stop;
+                    }
+                    if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+                }
+            }
+            __syncthreads();
+            // lane j of wave 0: the record of entry j, the quadrants' rows added in quadrant order
+            if (tid < 64 && off + (uint32_t)tid < nlist) {
+                const uint32_t f0 = s_flag[0][tid], f1 = s_flag[1][tid], f2 = s_flag[2][tid], f3 = s_flag[3][tid];
+                const int32_t slot = __float_as_int(rcz.y) + by * __float_as_int(rcz.z) + bx;
+                if ((f0 | f1 | f2 | f3) != 0u && slot >= 0 && (uint32_t)slot < a.cap) {
+                    float r[NV];
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) {
+                        float x = 0.0f;
+                        if (f0) x += s_acc[0][tid][k];
+                        if (f1) x += s_acc[1][tid][k];
+                        if (f2) x += s_acc[2][tid][k];
+                        if (f3) x += s_acc[3][tid][k];
+                        r[k] = x;
+                    }
+                    // the per-Gaussian factors of the colour backward's flush (k_blend_bwd): q = opacity v,
+                    // dL/dmean2D = -W/2 (A Sx + B Sy), -H/2 (C Sy + B Sx), dL/dconic = -1/2 (Sxx, Sxy, Syy), dL/dopacity = sum v
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) r[c] *= rb.y;
+                    const float cA = ra.z, cB = ra.w, cC = rb.x;
+                    const float mx = (-0.5f * (float)W) * (cA * r[0] + cB * r[1]);
+                    const float my = (-0.5f * (float)H) * (cC * r[1] + cB * r[0]);
+                    float4* o = (float4*)(a.rec + (size_t)slot * FEAT_REC);
+                    o[0] = make_float4(mx, my, -0.5f * r[2], -0.5f * r[3]);
+                    o[1] = make_float4(-0.5f * r[4], r[5], r[6], r[7]);
+                    if (NV > 8) {
+                        o[2] = make_float4(r[8 % NV], r[9 % NV], r[10 % NV], r[11 % NV]);
+                        o[3] = make_float4(r[12 % NV], r[13 % NV], r[14 % NV], r[15 % NV]);
+                    }
+                    a.tag[slot] = a.tagval;
+                }
+            }
+            __syncthreads();
+        }
+        __syncthreads();      // (a wave that left on the vote must not post the next tile's vote before the others have read this one)
+    }
+}
+
+// One thread per (view, Gaussian): the records of its slots, in slot order.  `first`: the geometry sums start here, otherwise they
+// add to what the launches before left in geo; `last`: the chain to the caller's outputs.
+__global__ __launch_bounds__(256) void k_feat_gather(int N, int W, int H, const float* __restrict__ cams,
+                                                     const float* __restrict__ means3D, int64_t s_means,
+                                                     const float* __restrict__ cov3D, int64_t s_cov,
+                                                     const ushort4* __restrict__ rect, const uint32_t* __restrict__ pair_off,
+                                                     const uint32_t* __restrict__ tag, const float* __restrict__ rec, uint32_t cap,
+                                                     uint32_t tagval, int C, int c0, int nc, int with_z, int wide, int first, int last,
+                                                     float* __restrict__ geo, float* __restrict__ dL_dmeans3D,
+                                                     float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dopacity,
+                                                     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dfeatures) {
+    const int v = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const size_t vi = (size_t)v * N + i;
+    const ushort4 rc = rect[vi];
+    uint32_t cnt = (uint32_t)((rc.z - rc.x) * (rc.w - rc.y));
+    const uint32_t off = pair_off[vi];
+    float g[FEAT_GEO], f[8];
+#pragma unroll
+    for (int k = 0; k < FEAT_GEO; ++k) g[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = 0.0f;
+    if (cnt > 0 && off < cap) {
+        cnt = min(cnt, cap - off);
+        for (uint32_t s = 0; s < cnt; ++s) {
+            if (tag[off + s] != tagval) continue;
+            const float4* r = (const float4*)(rec + (size_t)(off + s) * FEAT_REC);
+            const float4 r0 = r[0], r1 = r[1];
+            g[0] += r0.x; g[1] += r0.y; g[2] += r0.z; g[3] += r0.w; g[4] += r1.x; g[5] += r1.y;
+            f[0] += r1.z; f[1] += r1.w;
+            if (wide) {
+                const float4 r2 = r[2], r3 = r[3];
+                f[2] += r2.x; f[3] += r2.y; f[4] += r2.z; f[5] += r2.w;
+                f[6] += r3.x; f[7] += r3.y;
+            }
+            g[7] += 1.0f;
+        }
+    }
+    if (dL_dfeatures) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < nc) dL_dfeatures[vi * (size_t)C + c0 + k] = f[k];
+    }
+    if (with_z) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) g[6] += k == nc ? f[k] : 0.0f;
+    }
+    float* gp = geo + vi * FEAT_GEO;
+    if (!first) {
+#pragma unroll
+        for (int k = 0; k < FEAT_GEO; ++k) g[k] += gp[k];
+    }
+    if (!last) {
+#pragma unroll
+        for (int k = 0; k < FEAT_GEO; ++k) gp[k] = g[k];
+        return;
+    }
+    float dm[3] = {0.f, 0.f, 0.f}, dc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (g[7] > 0.0f) {                 // some launch of the call wrote a record for this (view, Gaussian)
+        MgrCam cam;
+        mgr_load_cam(cams, v, cam);
+        const float* mp = means3D + (size_t)v * s_means + (size_t)i * 3;
+        const float p[3] = {mp[0], mp[1], mp[2]};
+        const float* cp = cov3D + (size_t)v * s_cov + (size_t)i * 6;
+        const float c6[6] = {cp[0], cp[1], cp[2], cp[3], cp[4], cp[5]};
+        const float acc[9] = {g[0], g[1], g[2], g[3], g[4], g[5], 0.f, 0.f, 0.f};
+        project_backward(cam, W, H, p, c6, acc, dm, dc6);
+        // z = view row 2 . (p, 1) (project_gaussian): the expected depth's own path to the mean
+        dm[0] += cam.view[2] * g[6]; dm[1] += cam.view[6] * g[6]; dm[2] += cam.view[10] * g[6];
+    }
+    float* o3 = dL_dmeans3D + vi * 3;
+    o3[0] = dm[0]; o3[1] = dm[1]; o3[2] = dm[2];
+    float* o2 = dL_dmeans2D + vi * 3;
+    o2[0] = g[0]; o2[1] = g[1]; o2[2] = 0.f;
+    dL_dopacity[vi] = g[5];
+    float* ov = dL_dcov3D + vi * 6;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) ov[j] = dc6[j];
+}
+
+extern "C" int mgr_raster_blend_features_backward(int V, int N, int C, int W, int H, const float* cams, const float* means3D,
+                                                  int64_t s_means, const float* cov3D, int64_t s_cov, const float* features,
+                                                  int64_t stride_features, const float* bg_feat, int with_depth,
+                                                  const float* out_feat, const float* out_alpha, const float* dL_dout_feat,
+                                                  const float* dL_dalpha, float* dL_dmeans3D, float* dL_dmeans2D,
+                                                  float* dL_dopacity, float* dL_dcov3D, float* dL_dfeatures, const void* workspace,
+                                                  size_t workspace_bytes, int64_t cap, void* scratch, size_t scratch_bytes, int flags,
+                                                  void* stream_) {
+    static const char* const who = "mgr_raster_blend_features_backward";
+    (void)bg_feat;                    // (the background's share of a pixel is in out_feat already)
+    hipStream_t stream = (hipStream_t)stream_;
+    if (V <= 0 || N < 0 || W <= 0 || H <= 0 || cap < 0 || cap > 0xFFFFFFF0ll) return mgr_fail(MGR_EINVAL, "%s: bad sizes", who);
+    if (C < 0 || C > FEAT_MAX_C) return mgr_fail(MGR_EINVAL, "%s: C must be 0 .. 32", who);
+    if (!dL_dout_feat && !dL_dalpha) return mgr_fail(MGR_EINVAL, "%s: no upstream gradient (dL_dout_feat and dL_dalpha are both NULL)", who);
+    const int Cout = C + (with_depth ? 1 : 0);
+    if (dL_dout_feat && Cout == 0) return mgr_fail(MGR_EINVAL, "%s: dL_dout_feat given for C = 0 without depth", who);
+    if (!workspace || !scratch || !cams || (dL_dout_feat && !out_feat) || (dL_dalpha && !out_alpha))
+        return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
+    if (N > 0 && (!means3D || !cov3D || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity || !dL_dcov3D || (C > 0 && (!features || !dL_dfeatures))))
+        return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
+    if (stride_features != 0 && stride_features < (int64_t)N * C)
+        return mgr_fail(MGR_EINVAL, "%s: view stride of the features smaller than N * C", who);
+    const int gx = (W + 15) / 16, gy = (H + 15) / 16;
+    if (gx > 65535 || gy > 65535 || V > 65535) return mgr_fail(MGR_EINVAL, "%s: image too large or too many views", who);
+    const MgrLayout L = mgr_layout(V, N, W, H, cap);
+    if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "%s: workspace too small for these sizes", who);
+    const FeatScratch S = feat_scratch_layout(V, N, cap);
+    if (scratch_bytes < S.total) return mgr_fail(MGR_ENOMEM, "%s: scratch smaller than mgr_raster_feat_backward_workspace_bytes", who);
+    const char* ws = (const char*)workspace;
+    MgrHeader h;
+    const int VT = V * gx * gy;
+    {
+        const int rc = feat_read_state(who, ws, L, V, N, W, H, cap, VT, stream, h);
+        if (rc != MGR_OK) return rc;
+    }
+    if (N == 0) return MGR_OK;
+    char* sc = (char*)scratch;
+    // a slot nobody writes must count as zero: the tags are cleared once per call, the launches tag with 1, 2, ...
+    MGR_HIP(hipMemsetAsync(sc + S.tag, 0, (size_t)(cap > 0 ? cap : 1) * 4, stream));
+    const int Cw = dL_dout_feat ? Cout : 0;          // channels that carry a gradient (none: one launch for the alpha alone)
+    if (C > 0 && !dL_dout_feat) MGR_HIP(hipMemsetAsync(dL_dfeatures, 0, (size_t)V * N * C * sizeof(float), stream));
+
+    FeatBwdArgs a;
+    a.N = N; a.W = W; a.H = H; a.gx = gx; a.gy = gy; a.VT = VT;
+    a.n_queue = h.queue_len_i; a.cap = (uint32_t)cap;
+    a.tile_qrec = (const uint4*)(ws + L.tile_qrec);
+    a.sorted_gid = (const uint32_t*)(ws + L.sorted_gid);
+    a.grec = (const MgrGRec*)(ws + L.grec);
+    a.depth = (const float*)(ws + L.depth);
+    a.feat = features; a.s_feat = (long long)stride_features; a.C = C;
+    a.out = out_feat; a.g_out = dL_dout_feat; a.Cout = Cout;
+    a.rec = (float*)(sc + S.rec); a.tag = (uint32_t*)(sc + S.tag);
+    int c0 = 0;
+    uint32_t launch = 0;
+    do {   // the forward's groups: 8, 4 or 2 slots, the depth in the last group's last slot, the alpha with the first group
+        const int rem = Cw - c0, g = rem > 4 ? 8 : (rem > 2 ? 4 : 2), n = rem < g ? rem : g;
+        a.c0 = c0;
+        a.with_z = (with_depth && Cw > 0 && c0 + n == Cw) ? 1 : 0;
+        a.nc = n - a.with_z;
+        a.out_alpha = launch == 0 && dL_dalpha ? out_alpha : nullptr;
+        a.g_alpha = launch == 0 ? dL_dalpha : nullptr;
+        a.tagval = ++launch;
+        {
+            MGR_PROF("k_blend_feat_bwd", stream);
+            if (g == 8) hipLaunchKernelGGL(k_blend_feat_bwd<8>, dim3(FEAT_GRID), dim3(256), 0, stream, a);
+            else if (g == 4) hipLaunchKernelGGL(k_blend_feat_bwd<4>, dim3(FEAT_GRID), dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL(k_blend_feat_bwd<2>, dim3(FEAT_GRID), dim3(256), 0, stream, a);
+        }
+        MGR_LAUNCH_CHECK("k_blend_feat_bwd", stream, flags & MGR_BWD_CHECK);
+        c0 += n;
+        {
+            MGR_PROF("k_feat_gather", stream);
+            hipLaunchKernelGGL(k_feat_gather, dim3((N + 255) / 256, V), dim3(256), 0, stream, N, W, H, cams, means3D, s_means, cov3D, s_cov,
+                               (const ushort4*)(ws + L.rect), (const uint32_t*)(ws + L.pair_off), (const uint32_t*)a.tag,
+                               (const float*)a.rec, (uint32_t)cap, a.tagval, C, a.c0, a.nc, a.with_z, g > 2 ? 1 : 0, launch == 1 ? 1 : 0,
+                               c0 >= Cw ? 1 : 0, (float*)(sc + S.geo), dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dcov3D,
+                               C > 0 && dL_dout_feat ? dL_dfeatures : (float*)nullptr);
+        }
+        MGR_LAUNCH_CHECK("k_feat_gather", stream, flags & MGR_BWD_CHECK);
+    } while (c0 < Cw);
     return MGR_OK;
 }

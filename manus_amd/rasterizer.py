@@ -413,7 +413,7 @@ def _opacity_layout(op, V, N):
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, cov3D, cams, bg, W, H, debug, graph=True):
+    def forward(ctx, means3D, means2D, colors, opacities, cov3D, cams, bg, W, H, debug, graph=True, share=None):
         V = cams.shape[0]
         means3D, colors, cov3D = f32c(means3D), f32c(colors), f32c(cov3D)
         opac = f32c(opacities)
@@ -422,6 +422,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         bg = f32c(bg).reshape(-1)
         out, radii, ws, npairs = _run_forward(cams, V, N, W, H, bg, means3D, cov3D, colors, opac, debug, graph=graph)
         ctx.lease = _Lease(ws)
+        if share is not None:      # (rasterize_views_features: a second graph node on the same workspace holds the same lease)
+            share.lease = ctx.lease
         ctx.meta = (V, N, W, H, bool(debug), means2D.shape, opacities.shape)
         ctx.num_rendered = npairs
         ctx.save_for_backward(means3D, colors, opac, cov3D, cams, bg, out)
@@ -460,7 +462,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_col = fold(d_col, colors.dim() == 2)
         g_op = fold(d_op, opac.dim() == 1, op_shape)
         g_cov = fold(d_cov, cov3D.dim() == 2)
-        return g_m3, g_m2, g_col, g_op, g_cov, None, None, None, None, None, None
+        return g_m3, g_m2, g_col, g_op, g_cov, None, None, None, None, None, None, None
 
 
 def _builds_graph(*tensors):
@@ -528,6 +530,119 @@ def blend_features(features=None, bg=None, depth=False, alpha=False, device=None
         check(lib().mgr_raster_blend_features(V, N, C, W, H, ptr(features), s_f, ptr(bg), int(bool(depth)), ptr(out), ptr(out_a),
                                               ptr(ws.buf), ws.nbytes, ws.cap, stream()), "mgr_raster_blend_features")
         return {"features": out[:, :C] if C else None, "depth": out[:, C] if depth else None, "alpha": out_a}
+
+
+class _LeaseShare:
+    """Carries the colour node's lease out of _RasterizeGaussians.forward."""
+    lease = None
+
+
+def _forward_seq(ws):
+    """The workspace's forward sequence number (one blocking read)."""
+    seq = ctypes.c_uint32(0)
+    check(lib().mgr_raster_forward_seq_sync(ptr(ws.buf), ctypes.byref(seq), stream()), "mgr_raster_forward_seq_sync")
+    return int(seq.value)
+
+
+class _BlendFeatures(torch.autograd.Function):
+    """Feature, depth and alpha maps over the lists of the forward that holds `lease`, with their backward
+    (mgr_raster_blend_features_backward).  The node notes the workspace's forward sequence number and refuses a backward
+    once another forward has used the workspace."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, cov3D, features, cams, bg, lease, depth, alpha, debug):
+        # opacities: laid out (N) or (V,N) by the caller; like means2D it is here for its gradient only (the workspace holds the values)
+        ws = lease.ws
+        V, N, W, H = ws.key
+        dev = ws.buf.device
+        means3D, cov3D = f32c(means3D), f32c(cov3D)
+        C, s_f = 0, 0
+        if features is not None:
+            features = f32c(features)
+            C = int(features.shape[-1])
+            s_f = N * C if features.dim() == 3 else 0
+        n_out = C + (1 if depth else 0)
+        out = torch.empty((V, n_out, H, W), dtype=torch.float32, device=dev) if n_out else None
+        out_a = torch.empty((V, H, W), dtype=torch.float32, device=dev) if alpha else None
+        check(lib().mgr_raster_blend_features(V, N, C, W, H, ptr(features), s_f, ptr(bg), int(bool(depth)), ptr(out), ptr(out_a),
+                                              ptr(ws.buf), ws.nbytes, ws.cap, stream()), "mgr_raster_blend_features")
+        ctx.lease = lease
+        ctx.seq = _forward_seq(ws)
+        ctx.meta = (C, s_f, bool(depth), bool(debug), means2D.shape, opacities.shape, opacities.dim(), n_out > 0, bool(alpha))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(means3D, cov3D, features, cams, bg, out, out_a)
+        empty = torch.empty(0, device=dev)
+        outs = (out if out is not None else empty, out_a if out_a is not None else empty)
+        if out is None:
+            ctx.mark_non_differentiable(outs[0])
+        if out_a is None:
+            ctx.mark_non_differentiable(outs[1])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_out, g_alpha):
+        means3D, cov3D, features, cams, bg, out, out_a = ctx.saved_tensors
+        C, s_f, depth, debug, m2d_shape, op_shape, op_dim, has_out, has_alpha = ctx.meta
+        ws = ctx.lease.ws
+        V, N, W, H = ws.key
+        dev = ws.buf.device
+        g_out = f32c(g_out) if (g_out is not None and has_out) else None
+        g_alpha = f32c(g_alpha) if (g_alpha is not None and has_alpha) else None
+        if g_out is None and g_alpha is None:
+            return (None,) * 11
+        if _forward_seq(ws) != ctx.seq:
+            raise _lib.ManusHipError("rasterize_views_features: another forward has used this workspace since the maps were "
+                                     "rendered (forward %d then); their tile lists are gone" % ctx.seq)
+        d_m3 = torch.empty((V, N, 3), dtype=torch.float32, device=dev)
+        d_m2 = torch.empty((V, N, 3), dtype=torch.float32, device=dev)
+        d_op = torch.empty((V, N), dtype=torch.float32, device=dev)
+        d_cov = torch.empty((V, N, 6), dtype=torch.float32, device=dev)
+        d_f = torch.empty((V, N, C), dtype=torch.float32, device=dev) if C else None
+        nbytes = int(lib().mgr_raster_feat_backward_workspace_bytes(V, N, C, W, H, ws.cap))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        s_m = means3D.stride(0) if means3D.dim() == 3 else 0
+        s_c = cov3D.stride(0) if cov3D.dim() == 3 else 0
+        check(lib().mgr_raster_blend_features_backward(V, N, C, W, H, ptr(cams), ptr(means3D), s_m, ptr(cov3D), s_c, ptr(features), s_f,
+                                                       ptr(bg), int(depth), ptr(out), ptr(out_a), ptr(g_out), ptr(g_alpha), ptr(d_m3),
+                                                       ptr(d_m2), ptr(d_op), ptr(d_cov), ptr(d_f), ptr(ws.buf), ws.nbytes, ws.cap,
+                                                       ptr(scratch), nbytes, _lib.MGR_BWD_CHECK if debug else 0, stream()),
+              "mgr_raster_blend_features_backward")
+
+        def fold(g, shared, shape=None):   # as _RasterizeGaussians.backward: inputs shared by the views receive the sum
+            if shared:
+                g = g.sum(0) if V > 1 else g[0]
+            return g.reshape(shape) if shape is not None else g
+
+        return (fold(d_m3, means3D.dim() == 2), fold(d_m2, len(m2d_shape) == 2, m2d_shape), fold(d_op, op_dim == 1, op_shape),
+                fold(d_cov, cov3D.dim() == 2), fold(d_f, features.dim() == 2) if C else None, None, None, None, None, None, None)
+
+
+def rasterize_views_features(cams, means3D, means2D, colors, opacities, cov3D, bg, W, H, features=None, feature_bg=None,
+                             depth=False, alpha=False, debug=False):
+    """`rasterize_views` plus differentiable feature / depth / alpha maps of the same forward: -> (color (V,3,H,W), radii (V,N),
+    extras), extras = {"features": (V,C,H,W), "depth": (V,H,W), "alpha": (V,H,W)}, None for what was not asked for (the maps of
+    `blend_features`).  The maps carry gradient to features, means3D, means2D, opacities and cov3D (inputs shared by the
+    views receive the sum over views); their backward walks the colour forward's tile lists, so both graph nodes hold ONE lease
+    on the workspace, and the maps' backward raises ManusHipError if another forward has used the workspace in between."""
+    C, fbg = _feature_request(features, feature_bg, depth, alpha)
+    if not (torch.is_tensor(means3D) and means3D.is_cuda):
+        raise _lib.ManusHipError("rasterize_views_features needs GPU tensors; there is no CPU fallback")
+    V, N = cams.shape[0], means3D.shape[-2]
+    if features is not None and (features.shape[-2] != N or (features.dim() == 3 and features.shape[0] != V)):
+        raise _lib.ManusHipError("features %s do not fit %d views of %d Gaussians" % (tuple(features.shape), V, N))
+    dev = means3D.device
+    share = _LeaseShare()
+    graph = _builds_graph(means3D, means2D, colors, opacities, cov3D, features)
+    color, radii = _RasterizeGaussians.apply(means3D, means2D, colors, opacities, cov3D, cams, bg, int(W), int(H), debug, graph, share)
+    if features is not None:
+        features = features.to(dev)
+    if fbg is not None:
+        fbg = fbg.to(dev).contiguous()
+    opac = _opacity_layout(opacities, V, N)      # (a view: the gradient finds its way back to `opacities`)
+    out, out_a = _BlendFeatures.apply(means3D, means2D, opac, cov3D, features, cams, fbg, share.lease, bool(depth), bool(alpha),
+                                      bool(debug))
+    return color, radii, {"features": out[:, :C] if C else None, "depth": out[:, C] if depth else None,
+                          "alpha": out_a if alpha else None}
 
 
 class GaussianRasterizer(nn.Module):

@@ -6,7 +6,8 @@ import torch
 
 from . import _lib
 from .ops import sh_colors
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _feature_request, blend_features
+from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _builds_graph, _feature_request, blend_features,
+                         rasterize_views_features)
 
 
 def _tf12(tf):
@@ -47,8 +48,10 @@ def render_gaussians(posed_means, posed_cov, cano_means, cano_features, cano_opa
 
     Beyond the reference: `extra_features` (N,C), 1 <= C <= 32, `return_depth`, `return_alpha` add the keys `features`
     (H,W,C; background `feature_bg`, C values, default zeros), `depth` (H,W; expected depth sum_i w_i z_i, not divided by
-    alpha) and `alpha` (H,W; accumulated opacity) -- composited over the tile lists of this render
-    (rasterizer.blend_features), without gradient.  Without them the dict is the reference's."""
+    alpha) and `alpha` (H,W; accumulated opacity) -- composited over the tile lists of this render.  When autograd is recording
+    (one of the caller's tensors requires gradient) they carry gradient to extra_features, the means, the covariances and the
+    opacities (rasterizer.rasterize_views_features); otherwise they come from rasterizer.blend_features, without a graph.
+    Without them the dict is the reference's."""
     extras = extra_features is not None or return_depth or return_alpha
     if extras:
         _feature_request(extra_features, feature_bg, return_depth, return_alpha)
@@ -69,17 +72,28 @@ def render_gaussians(posed_means, posed_cov, cano_means, cano_features, cano_opa
         bg=as_dev(bg_color), scale_modifier=1, viewmatrix=as_dev(camera.world_view_transform),
         projmatrix=as_dev(camera.full_proj_transform), sh_degree=sh_degree,
         campos=as_dev(camera.camera_center), prefiltered=False, debug=False)
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     if colors_precomp is None:
         colors_precomp = calculate_colors_from_sh(posed_means, cano_features, cano_means, camera, sh_degree, tf)
-    rendered_image, radii = rasterizer(means3D=posed_means, means2D=screenspace_points, shs=None,
-                                       colors_precomp=colors_precomp, opacities=cano_opacity, scales=None,
-                                       rotations=None, cov3D_precomp=posed_cov)
+    # (screenspace_points always requires gradient: it does not decide the route)
+    with_grad = extras and _builds_graph(posed_means, posed_cov, cano_opacity, colors_precomp, extra_features)
+    if with_grad:
+        rs = raster_settings
+        cams = _lib.pack_cameras(rs.tanfovx, rs.tanfovy, rs.viewmatrix, rs.projmatrix, rs.campos, posed_means.device)
+        color, radii, r = rasterize_views_features(cams, posed_means, screenspace_points, colors_precomp, cano_opacity, posed_cov,
+                                                   rs.bg, rs.image_width, rs.image_height, features=extra_features,
+                                                   feature_bg=feature_bg, depth=return_depth, alpha=return_alpha)
+        rendered_image, radii = color[0], radii[0]
+    else:
+        rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+        rendered_image, radii = rasterizer(means3D=posed_means, means2D=screenspace_points, shs=None,
+                                           colors_precomp=colors_precomp, opacities=cano_opacity, scales=None,
+                                           rotations=None, cov3D_precomp=posed_cov)
     rendered_image = torch.permute(rendered_image, (1, 2, 0))
     out = {"render": rendered_image, "viewspace_points": screenspace_points,
            "visibility_filter": radii > 0, "radii": radii}
     if extras:
-        r = blend_features(extra_features, bg=feature_bg, depth=return_depth, alpha=return_alpha, device=device)
+        if not with_grad:
+            r = blend_features(extra_features, bg=feature_bg, depth=return_depth, alpha=return_alpha, device=device)
         if extra_features is not None:
             out["features"] = r["features"][0].permute(1, 2, 0)
         if return_depth:
