@@ -469,6 +469,41 @@ int mgr_skin_weights_bwd_indexed(int N, const float* xyz, const float* grid, int
                                  float* dL_dxyz, const uint32_t* index, const uint32_t* index_count, int max_count,
                                  void* stream);
 
+/* dL/d(grid): the half of the chain rule mgr_skin_weights_bwd drops, as a SPARSE gradient.  No reference kernel counterpart:
+ * the reference gets it from autograd through F.grid_sample (src/utils/gaussian_utils.py:173) once grid_weights requires grad.
+ * For every processed Gaussian n (all N when index is NULL -- max_count is then taken as N --, else index[0 .. min(*index_count,
+ * max_count)), entries >= N skipped as in mgr_skin_weights_bwd_indexed): corner weights t_c, raw samples s_b = sum_c t_c g[c][b],
+ * S = sum_b s_b, a = dL_dw[n], r_b = (a_b - sum_k a_k s_k / S) / S, and G[voxel(c)][b] += t_c r_b for every corner inside the
+ * grid (zero padding: an outside corner receives nothing).
+ *   out_voxel[0 .. *out_count)  linear indices (z*H + y)*W + x, strictly ascending: every in-bounds corner of every contributing
+ *                               Gaussian, nothing else
+ *   out_grad                    row i: grid_stride floats, channels >= B written as zero
+ * Entries beyond *out_count are left untouched.  capacity (rows of out_voxel / out_grad) >= min(8 * max_count, D*H*W) is
+ * required, so nothing can overflow and there is no overflow flag.
+ * A Gaussian whose S is zero or not finite (every corner outside, or every in-bounds corner zero) contributes nothing and lists
+ * nothing -- a stated deviation from autograd, which would write 0/0 into a leaf every Gaussian shares; the forward still
+ * returns NaN weights for it.
+ * No float atomics: a voxel's contributions are added in an order fixed by the Gaussian indices, never by positions in `index`,
+ * so the result is bit-identical for any permutation of the same list.
+ * grid_stride as in mgr_skin_weights_fwd.  D*H*W < 2^31, max_count < 2^27.  workspace_bytes >=
+ * mgr_skin_grid_bwd_workspace_bytes(D, H, W, max_count): 4 bytes per voxel + 292 per list entry.
+ * MGR_EINVAL (nothing launched, outputs untouched): B > MGR_MAX_BONES, grid_stride neither B nor 24, the padded layout on a base
+ * that is not 16-byte aligned, capacity too small, max_count < 0; MGR_ENOMEM: workspace too small. */
+size_t mgr_skin_grid_bwd_workspace_bytes(int D, int H, int W, int max_count);
+int mgr_skin_grid_bwd(int N, const float* xyz, const float* grid, int D, int H, int W, int B, int grid_stride,
+                      const float* center3, const float* scale3, const float* dL_dw,
+                      const uint32_t* index, const uint32_t* index_count, int max_count,
+                      int32_t* out_voxel, float* out_grad, uint32_t* out_count, int capacity,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* Row Adam on such a list, torch.optim.SparseAdam's semantics: the moments (laid out like the grid) are updated and the grid is
+ * stepped on the rows voxel[0 .. min(*count, capacity)) only, channels < B (pad channels stay zero); the bias correction uses
+ * the global `step` (>= 1).  The hyper-parameters are doubles, as in mgr_adam_step: 1 - beta2 taken from a float 0.999 is off by
+ * 1e-5 of itself.  clamp != 0: x = max(x, clamp_min) afterwards (weights below zero make S cancel). */
+int mgr_skin_grid_adam(const int32_t* voxel, const float* grad, const uint32_t* count, int capacity,
+                       float* grid, int grid_stride, int B, float* exp_avg, float* exp_avg_sq,
+                       double lr, double beta1, double beta2, double eps, int step, int clamp, float clamp_min,
+                       void* stream);
+
 /* LBS for P poses.  transforms: (P,B,16) row-major 4x4 bone transforms
  * T_b = posed_b * inv(rest_b) (+ identity background).  skin_w (N,B) or NULL for
  * the static-object path (identity transform: posed = xyz, cov = Sigma).

@@ -131,6 +131,9 @@ class ViewShardedStep:
                  scatter=False, view_weights=None, force_collectives=False):
         self.N, self.shapes, self.compute_fn = n_gaussians, shapes, compute_fn
         self.n_views, self.rank, self.world, self.group = n_views, rank, world_size, group
+        if world_size > 1 and getattr(compute_fn, "skin_grid_grad", False):
+            # a sparse grid gradient has a different voxel list on every rank: nothing here reduces it
+            raise ValueError("ViewShardedStep does not reduce the sparse skin-grid gradient across ranks: skin_grid_grad needs world_size == 1")
         self.local_views = shard_views(n_views, rank, world_size, view_weights)
         self.always_pack = False   # tests: take the packing path without a process group
         # force_collectives: issue every collective even in a world of one rank (a single-process "nccl" group on a one-GPU
@@ -548,7 +551,7 @@ class HipViewCompute:
 
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
-                 persistent_grads=True, pose_grad=False):
+                 persistent_grads=True, pose_grad=False, skin_grid_grad=False):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -577,6 +580,15 @@ class HipViewCompute:
         if self.pose_grad and not self.is_hand:
             raise ValueError("pose_grad needs articulated Gaussians: a %r scene without a skin grid has no bone transforms" % self.kind)
         self.grid = ops.SkinGrid(scene["grid"], scene["grid"].device) if self.is_hand else None
+        # -- skin_grid_grad True: the step's output dict gains "d_skin_grid", the sparse dL/d(skin-weight grid) (`ops.SkinGridGrad`,
+        # on the scale of `grads`) of `self.grid` -- one mgr_skin_grid_bwd behind the skin-weight backward, on its list (fused) or
+        # on all articulated rows (modular, and fused beyond 8 views).  `optim.SkinGridAdam(self.grid, ...)` steps the grid on it.
+        self.skin_grid_grad = bool(skin_grid_grad)
+        if self.skin_grid_grad and not self.is_hand:
+            raise ValueError("skin_grid_grad needs articulated Gaussians: a %r scene without a skin grid has nothing to differentiate" % self.kind)
+        self._sg_kept = {}              # fused route: outputs and workspace of mgr_skin_grid_bwd, kept across steps
+        self._skin_w = None             # modular route with skin_grid_grad: the step's skin weights, kept for their gradient
+        self.last_skin_w_grad = None    # with skin_grid_grad: dL/dw (n_art,B) of the last step, what "d_skin_grid" was formed from
         self._w_cache = None            # forward-only skin weights of the current model state (forward_views_fused under no_grad)
         # -- image loss.  "l1": mean|render - gt| (rgb_loss alone); "l1+ssim": w_rgb * rgb_loss + w_ssim * ssim_loss, the image
         # terms of config/HAND_GAUSSIAN.yaml:22-23 (src/modules/base.py:323-365), one fused kernel.  Routes: class docstring.
@@ -700,6 +712,9 @@ class HipViewCompute:
             _, pcov1, _ = ops.lbs_cov(p["_xyz"], p["_scaling"], p["_rotation"], None, None)
             return p["_xyz"], pcov1[0], None
         w = ops.skin_weights(p["_xyz"][:na], self.grid, self.s["grid_center"], self.s["grid_scale"])
+        if self.skin_grid_grad and w.requires_grad:
+            w.retain_grad()
+            self._skin_w = w
         pxyz, pcov, tf = ops.lbs_cov(p["_xyz"][:na], p["_scaling"][:na], p["_rotation"][:na], w, T)
         if na < N:   # composite.py:50-59: concat, identity tf for the object
             P = T.shape[0]
@@ -735,7 +750,7 @@ class HipViewCompute:
             # model state -- (generation, parameter-update clock, the leaf's storage and version) -- instead of gathered from
             # the grid again for every batch of views (0.04 ms for 300 k Gaussians: 13 % of a one-view forward).  Training
             # steps always recompute them (their gradient flows back into `_xyz`).
-            key = (self._cut.gen, self._cut.clock, p["_xyz"].data_ptr(), p["_xyz"]._version, na, id(self.grid))
+            key = (self._cut.gen, self._cut.clock, p["_xyz"].data_ptr(), p["_xyz"]._version, na, id(self.grid), self.grid.version)
             if self._w_cache is None or self._w_cache[0] != key:
                 self._w_cache = (key, ops.skin_weights(p["_xyz"][:na], self.grid, s["grid_center"], s["grid_scale"]))
             w = self._w_cache[1]
@@ -843,6 +858,7 @@ class HipViewCompute:
             loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
             grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale)
             active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"])
+            d_grid = self._skin_grid_backward(head, p["_xyz"], d_w, active) if self.skin_grid_grad else None
             overflow = ws.buf[4:8].view(torch.int32)
         except BaseException:
             # a call that failed between the loss's list and finish passes -- the forward included: its last kernel builds the
@@ -859,6 +875,8 @@ class HipViewCompute:
         res = dict(grads=grads, grad2d=st_g, vis=st_v, radii=st_r, loss=loss, overflow=overflow)
         if d_T is not None:
             res["d_transforms"] = d_T
+        if d_grid is not None:
+            res["d_skin_grid"] = d_grid
         return res
 
     def _skin_weights(self, xyz, na):
@@ -1006,6 +1024,17 @@ class HipViewCompute:
             check(lib().mgr_skin_weights_bwd(*grid, 1, stream()), "mgr_skin_weights_bwd")
         return active
 
+    def _skin_grid_backward(self, head, xyz, d_w, active):
+        """Sparse dL/d(grid) from the skin-weight gradient the backward wrote: on the active list up to 8 views (the other
+        rows of d_w are zero), on all articulated rows beyond."""
+        V, N, _, na = head[:4]
+        s = self.s
+        lst, cnt = active if active is not None else (None, None)
+        self.last_skin_w_grad = d_w
+        # (outputs and workspace kept across steps like the gradient buffers: "d_skin_grid" is valid until the next step)
+        return self.ops._skin_grid_grad(na, xyz, self.grid, s["grid_center"], s["grid_scale"], d_w, lst, cnt, N if active is not None else na,
+                                        kept=self._sg_kept if self.persistent_grads else None)
+
     def __call__(self, view_ids, scale=1.0):
         if self.fused:
             return self._step_direct(view_ids, scale)
@@ -1025,6 +1054,16 @@ class HipViewCompute:
                    radii=radii.max(dim=0).values, loss=loss)
         if T is not None:
             res["d_transforms"] = T.grad
+        if self.skin_grid_grad:
+            w, self._skin_w = self._skin_w, None
+            if w is None or w.grad is None:
+                raise ManusHipError("skin_grid_grad: the step formed no skin-weight gradient (do the leaves require grad?)")
+            self.last_skin_w_grad = w.grad
+            # only the Gaussians that received a gradient, as the fused route's active list: the row Adam steps every LISTED voxel
+            # (SparseAdam's semantics), so voxels under all-zero rows must not be listed on one route and left out on the other
+            live = torch.nonzero((w.grad != 0).any(1)).reshape(-1).to(torch.int32)
+            res["d_skin_grid"] = self.ops.skin_grid_grad(self.params["_xyz"].detach()[:self.n_art], self.grid, self.s["grid_center"],
+                                                         self.s["grid_scale"], w.grad, index=live)
         return res
 
     def pairs_per_view(self, view_ids=None, group=8):

@@ -3,6 +3,7 @@
 Each op mirrors one block of MANUS Python code (reference tree brown-ivl/manus):
 
     skin_weights   skinning_weights_from_voxel_grid      src/utils/gaussian_utils.py:167-196
+    skin_grid_grad the grid's gradient of the same line   src/utils/gaussian_utils.py:173 (autograd there)
     lbs_cov        TrainingModule.forward LBS block      src/modules/hand_dynamic.py:106-127
                    + GaussianModel.get_covariance        src/models/gaussian.py:49-53,84-93
     sh_colors      calculate_colors_from_sh / eval_sh    src/utils/gaussian_utils.py:431-449
@@ -22,7 +23,9 @@ from ._lib import MGR_MAX_BONES, ManusHipError, check, f32c, lib, ptr, stream
 class SkinGrid:
     """Skin-weight voxel grid prepared for the kernels: the reference's channel-last (D,H,W,B)
     tensor, uploaded once and zero-padded to 24 channels (96 B per voxel) so that every trilinear
-    corner is six aligned float4 loads."""
+    corner is six aligned float4 loads.
+
+    `version` counts the writes to `data`, and what is derived from the grid (the engine's kept skin weights) is keyed on it."""
 
     def __init__(self, grid_weights, device=None):
         g = torch.as_tensor(grid_weights, dtype=torch.float32)
@@ -39,11 +42,95 @@ class SkinGrid:
         else:
             self.stride = self.B
             self.data = g.contiguous()
+        self._bumps, self._v0 = 0, self.data._version
+
+    @property
+    def version(self):
+        """Writes to `data` so far: torch's in-place operations on it (counted by the tensor itself) plus the `bump()`s of those
+        who wrote it through its device pointer."""
+        return self._bumps + self.data._version - self._v0
+
+    def bump(self):
+        """`data` was written by a kernel through its pointer (torch does not see such a write)."""
+        self._bumps += 1
+
+    def dense(self):
+        """The (D,H,W,B) tensor in the reference's layout (a copy without the pad channels): what `checkpoint` stores as
+        `grid_weights`."""
+        return self.data[..., : self.B].clone(memory_format=torch.contiguous_format)
+
+
+class SkinGridGrad:
+    """Sparse dL/d(grid) of `mgr_skin_grid_bwd`: `voxel` (capacity,) int32 linear indices (z*H + y)*W + x, ascending over the
+    first `count[0]` entries; `grad` (capacity, stride) one row per listed voxel, channels >= B zero; `count` (1,) int32 on the
+    same device; `shape` = (D,H,W,B).  Entries beyond the count are undefined."""
+
+    def __init__(self, voxel, grad, count, shape):
+        self.voxel, self.grad, self.count, self.shape = voxel, grad, count, tuple(int(x) for x in shape)
+
+    def rows(self):
+        """(voxel (n,), grad (n, stride)) trimmed to the count (synchronises with the host)."""
+        n = int(self.count.reshape(-1)[0])
+        return self.voxel[:n], self.grad[:n]
+
+    def to_dense(self):
+        """(D,H,W,B): zeros plus the rows."""
+        D, H, W, B = self.shape
+        v, g = self.rows()
+        out = torch.zeros((D * H * W, B), dtype=self.grad.dtype, device=self.grad.device)
+        out[v.long()] = g[:, :B]
+        return out.reshape(D, H, W, B)
+
+
+def _skin_grid_grad(N, xyz, sg, center, scale, g_w, index, index_count, max_count, kept=None):
+    """`mgr_skin_grid_bwd` on raw list pointers (index None: all N rows).  kept: a dict in which the outputs and the workspace are
+    kept from call to call (the engine's: at the bench size they are 230 MB + 100 MB) -- the result then lives until the next call."""
+    dev = xyz.device
+    nvox = sg.D * sg.H * sg.W
+    cap = max(1, min(8 * max_count, nvox))
+    nbytes = int(lib().mgr_skin_grid_bwd_workspace_bytes(sg.D, sg.H, sg.W, max_count))
+    key = (cap, sg.stride, nbytes, str(dev))
+    if kept is not None and kept.get("key") == key:
+        voxel, grad, count, ws = kept["bufs"]
+    else:
+        voxel = torch.empty(cap, dtype=torch.int32, device=dev)
+        grad = torch.empty((cap, sg.stride), dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+        if kept is not None:
+            kept["key"], kept["bufs"] = key, (voxel, grad, count, ws)
+    check(lib().mgr_skin_grid_bwd(N, ptr(xyz), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride, ptr(center), ptr(scale), ptr(g_w),
+                                  index, index_count, max_count, ptr(voxel), ptr(grad), ptr(count), cap, ptr(ws), nbytes, stream()),
+          "mgr_skin_grid_bwd")
+    return SkinGridGrad(voxel, grad, count, (sg.D, sg.H, sg.W, sg.B))
+
+
+def skin_grid_grad(xyz, sg, center, scale, g_w, index=None, index_count=None):
+    """Sparse dL/d(grid) of `skin_weights(xyz, sg, center, scale)` for dL/dw = g_w (N,B) -> `SkinGridGrad`.  index (int32
+    Gaussian indices, entries >= N skipped) + index_count ((1,) int32 on the device, default: the whole list): only those
+    Gaussians are processed; the result does not depend on the order of the list.  A Gaussian whose raw sum is zero or not
+    finite contributes nothing (include/manus_hip.h).  No reference counterpart (autograd through F.grid_sample there)."""
+    if not isinstance(sg, SkinGrid):
+        raise ManusHipError("skin_grid_grad takes a SkinGrid")
+    xyz, g_w = f32c(xyz), f32c(g_w)
+    center, scale = f32c(center).reshape(-1), f32c(scale).reshape(-1)
+    N = xyz.shape[0]
+    if tuple(g_w.shape) != (N, sg.B):
+        raise ManusHipError("skin_grid_grad: g_w must be (N,B) = (%d,%d)" % (N, sg.B))
+    if index is None:
+        return _skin_grid_grad(N, xyz, sg, center, scale, g_w, None, None, N)
+    if index.dtype != torch.int32 or (index_count is not None and index_count.dtype != torch.int32):
+        raise ManusHipError("skin_grid_grad: index and index_count must be int32")
+    index = index.contiguous()
+    if index_count is None:
+        index_count = torch.full((1,), index.numel(), dtype=torch.int32, device=index.device)
+    return _skin_grid_grad(N, xyz, sg, center, scale, g_w, ptr(index), ptr(index_count), index.numel())
 
 
 class _SkinWeights(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz, sg, center, scale):
+    def forward(ctx, xyz, sg, center, scale, grid_leaf=None):
+        # grid_leaf: the caller's (D,H,W,B) tensor when it requires grad (sg was prepared from it), for autograd's bookkeeping
         xyz = f32c(xyz)
         center, scale = f32c(center).reshape(-1), f32c(scale).reshape(-1)
         N = xyz.shape[0]
@@ -63,17 +150,26 @@ class _SkinWeights(torch.autograd.Function):
         g_xyz = torch.empty((N, 3), dtype=torch.float32, device=xyz.device)
         check(lib().mgr_skin_weights_bwd(N, ptr(xyz), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride, ptr(center),
                                          ptr(scale), ptr(g_w), ptr(g_xyz), 0, stream()), "mgr_skin_weights_bwd")
-        return g_xyz, None, None, None
+        g_grid = None
+        if len(ctx.needs_input_grad) > 4 and ctx.needs_input_grad[4]:
+            g_grid = _skin_grid_grad(N, xyz, sg, center, scale, g_w, None, None, N).to_dense()
+        return (g_xyz, None, None, None, g_grid)[:len(ctx.needs_input_grad)]
 
 
 def skin_weights(xyz, grid_weights, grid_center, grid_scale):
     """xyz (N,3); grid_weights: a `SkinGrid` (prepared once) or the reference's (D,H,W,B)
-    channel-last tensor (prepared on the fly) -> (N,B), rows sum to 1."""
+    channel-last tensor (prepared on the fly) -> (N,B), rows sum to 1.  A tensor that requires grad receives the dense
+    dL/d(grid) (`mgr_skin_grid_bwd`; training on a `SkinGrid` uses the sparse `skin_grid_grad` instead)."""
+    leaf = None
     if not isinstance(grid_weights, SkinGrid):
         if not xyz.is_cuda:
             raise ManusHipError("manus_amd ops need GPU tensors; there is no CPU fallback")
-        grid_weights = SkinGrid(grid_weights, xyz.device)
-    return _SkinWeights.apply(xyz, grid_weights, grid_center, grid_scale)
+        if torch.is_tensor(grid_weights) and grid_weights.requires_grad and torch.is_grad_enabled():
+            leaf = grid_weights
+        grid_weights = SkinGrid(grid_weights.detach() if torch.is_tensor(grid_weights) else grid_weights, xyz.device)
+    if leaf is None:
+        return _SkinWeights.apply(xyz, grid_weights, grid_center, grid_scale)
+    return _SkinWeights.apply(xyz, grid_weights, grid_center, grid_scale, leaf)
 
 
 class _LbsCov(torch.autograd.Function):

@@ -414,3 +414,29 @@ class GaussianOptimizer:
                     self.reset_opacity()
                     changed = True
         return changed
+
+
+class SkinGridAdam:
+    """Row Adam of a `ops.SkinGrid` on the sparse gradient of `ops.skin_grid_grad` (`mgr_skin_grid_adam`): the semantics of
+    torch.optim.SparseAdam -- moments and parameter move on the listed voxels only, the bias correction uses the global step
+    count -- followed by max(x, clamp_min) (None: no clamp; weights below zero make the raw sum cancel).  The moments have the
+    grid's layout and are allocated at the first step.  The reference (HandGaussianModel.optimizing_skin_weights) would use a
+    dense Adam on the whole grid."""
+
+    def __init__(self, sg, lr, betas=(0.9, 0.999), eps=1e-8, clamp_min=0.0):
+        self.sg, self.lr, self.betas, self.eps, self.clamp_min = sg, float(lr), (float(betas[0]), float(betas[1])), float(eps), clamp_min
+        self.steps = 0
+        self.exp_avg = self.exp_avg_sq = None
+
+    def step(self, grad):
+        sg = self.sg
+        if tuple(grad.shape) != (sg.D, sg.H, sg.W, sg.B) or grad.grad.shape[1] != sg.stride:
+            raise ManusHipError("SkinGridAdam: the gradient is not of this grid")
+        if self.exp_avg is None:
+            self.exp_avg, self.exp_avg_sq = torch.zeros_like(sg.data), torch.zeros_like(sg.data)
+        self.steps += 1
+        clamp = self.clamp_min is not None
+        check(lib().mgr_skin_grid_adam(ptr(grad.voxel), ptr(grad.grad), ptr(grad.count), grad.voxel.numel(), ptr(sg.data), sg.stride,
+                                       sg.B, ptr(self.exp_avg), ptr(self.exp_avg_sq), self.lr, self.betas[0], self.betas[1], self.eps,
+                                       self.steps, int(clamp), float(self.clamp_min) if clamp else 0.0, stream()), "mgr_skin_grid_adam")
+        sg.bump()
