@@ -371,6 +371,33 @@ int mgr_views_backward_pose(int V, int N, int B, int n_articulated, int sh_half,
                             int64_t pair_capacity, int flags, float* d_transforms, void* pose_workspace,
                             size_t pose_workspace_bytes, void* stream);
 
+/* Map backward of the fused route: gradients of a loss on the accumulated-opacity and expected-depth maps that
+ * mgr_raster_blend_features (C = 0) rendered over the lists of the last mgr_views_forward on `workspace`, carried to the
+ * canonical leaves.  The leading arguments are those of mgr_views_backward without the SH tensors.  No reference counterpart
+ * (the reference uses its masks for pruning only).
+ *   out_alpha, dL_dalpha   (V,H,W) the alpha map of that render and its upstream gradient, or both NULL
+ *   out_depth, dL_ddepth   (V,H,W) the depth map (with_depth = 1, C = 0) and its upstream gradient, or both NULL
+ *                          (both gradients NULL: MGR_EINVAL)
+ *   accumulate             0: every row of every output is written, zeros where no view holds a contribution;
+ *                          1: rows with a contribution are added to, every other row is left bit for bit as it was
+ *   d_xyz (N,3) d_log_scale (N,3) d_rot (N,4) d_opacity_logit (N) d_skin_w (n_articulated,B; NULL without skin_w)
+ * One walk of the lists (the feature backward's kernel, one 64-byte record per (tile, Gaussian) pair into `scratch`), then one
+ * launch per group of up to eight views that sums a Gaussian's records in slot order, recomputes its posed mean and covariance
+ * from the canonical parameters as the forward did, and runs the projection, depth, LBS, quaternion and sigmoid backward in
+ * registers; views are summed in ascending order over a fixed tree, groups in group order.  No atomics: bit-reproducible.
+ * Gaussians >= n_articulated take the identity transform; skin_w == NULL (or n_articulated == 0): a static object.
+ * The workspace is only read.  scratch_bytes >= mgr_views_maps_backward_workspace_bytes (68 bytes per pair of capacity); its
+ * contents need not be initialised.  flags: MGR_BWD_CHECK.
+ * Refused with nothing launched and no output touched: MGR_ESTATE as mgr_raster_blend_features (no complete forward on the
+ * workspace, a depth-cut forward, an overflow bit, other sizes), MGR_ENOMEM below either size. */
+size_t mgr_views_maps_backward_workspace_bytes(int V, int N, int W, int H, int64_t pair_capacity);
+int mgr_views_maps_backward(int V, int N, int B, int n_articulated, int W, int H, const float* cams, const float* xyz,
+                            const float* log_scale, const float* rot, const float* opacity_logit, const float* skin_w,
+                            const float* transforms, const float* out_alpha, const float* out_depth, const float* dL_dalpha,
+                            const float* dL_ddepth, int accumulate, float* d_xyz, float* d_log_scale, float* d_rot,
+                            float* d_opacity_logit, float* d_skin_w, const void* workspace, size_t workspace_bytes,
+                            int64_t pair_capacity, void* scratch, size_t scratch_bytes, int flags, void* stream);
+
 /* Device pointers (into the workspace) to the compacted list of Gaussians that received a gradient in the last
  * mgr_views_backward and to its length; V <= 8. */
 int mgr_views_active_list(void* workspace, int V, int N, int W, int H, int64_t pair_capacity, const uint32_t** list,
@@ -678,6 +705,22 @@ int mgr_views_forward_attach_loss_list(const void* raster_workspace, int V, int 
 int mgr_image_loss_tiles_finish(int V, int H, int W, const float* pred, const float* target, float w_l1, float w_ssim,
                                 float grad_scale, float loss_offset, float* dL_dpred, float* sums, void* workspace,
                                 size_t workspace_bytes, void* stream);
+
+/* Silhouette and depth terms on the maps of mgr_raster_blend_features, value and gradient in one pass.  No reference
+ * counterpart.
+ *   L_mask  = mean over V H W of |alpha - mask|               mask (V,H,W) fp32 in [0,1]
+ *   L_depth = mean over V H W of mask |depth - depth_target|  (depth: the expected, un-normalised depth; term off when depth,
+ *                                                              depth_target and dL_ddepth are NULL -- all three or none)
+ *   dL_dalpha = fp32(grad_scale w_mask / (V H W)) sign(alpha - mask), every element written (sign(0) = 0)
+ *   dL_ddepth = (fp32(grad_scale w_depth / (V H W)) mask) sign(depth - depth_target), every element written
+ *   sums[0] = L_mask, sums[1] = L_depth (0 with the term off), sums[2] = w_mask L_mask + w_depth L_depth (without grad_scale)
+ * The sums are fp64 over a fixed two-stage tree (4096 elements per workgroup in a fixed assignment, then one workgroup over
+ * the partials): no atomics, bit-reproducible; a term that is not finite makes its sum and sums[2] NaN.
+ * workspace_bytes >= mgr_map_loss_workspace_bytes (16 bytes per 4096 elements); contents need not be initialised. */
+size_t mgr_map_loss_workspace_bytes(int V, int H, int W);
+int mgr_map_loss(int V, int H, int W, const float* alpha, const float* mask, const float* depth, const float* depth_target,
+                 float w_mask, float w_depth, float grad_scale, float* dL_dalpha, float* dL_ddepth, float* sums,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Optimizer step and densification of the Gaussian parameter model

@@ -58,6 +58,8 @@ SIGNATURES = {
     "mgr_views_pose_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_views_backward_pose": (c_int, [c_int] * 7 + [c_vp] * 13 + [c_f32] + [c_vp] * 10 + [c_vp, c_sz, c_i64, c_int, c_vp, c_vp, c_sz,
                                         c_vp]),
+    "mgr_views_maps_backward_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_i64]),
+    "mgr_views_maps_backward": (c_int, [c_int] * 6 + [c_vp] * 11 + [c_int] + [c_vp] * 5 + [c_vp, c_sz, c_i64, c_vp, c_sz, c_int, c_vp]),
     "mgr_raster_record_bytes": (c_int, []),
     "mgr_raster_layout": (c_int, [c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_sz), c_int]),
     "mgr_raster_status_sync": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32), c_vp]),
@@ -125,6 +127,8 @@ SIGNATURES = {
     "mgr_image_loss_tiles_list": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_image_loss_tiles_finish": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_sz,
                                             c_vp]),
+    "mgr_map_loss_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_map_loss": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_eval_triptych": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

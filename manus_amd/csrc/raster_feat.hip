@@ -692,3 +692,240 @@ extern "C" int mgr_raster_blend_features_backward(int V, int N, int C, int W, in
     } while (c0 < Cw);
     return MGR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Map backward of the fused route (mgr_views_maps_backward): gradients of a loss on the alpha and depth maps, rendered over the
+// lists of a mgr_views_forward, to the CANONICAL leaves.  The fused forward never writes posed means or covariances to memory,
+// which k_feat_gather reads; here the walk is the same k_blend_feat_bwd<2> (C = 0: the depth in slot 0, the alpha beside it,
+// ONE launch, tag 1) and the gather is k_views_feat_gather, laid out like k_inst_bwd without run lists (raster_bwd.hip):
+//   * lane = Gaussian_local * G + view_local, G = 1 / 2 / 4 / 8 views of a group in adjacent lanes, cameras and bone transforms of
+//     the group's views in LDS (one padded slab per view);
+//   * every lane sums the records of its (view, Gaussian) in slot order, recomputes the posed mean and covariance from the
+//     canonical parameters with the forward's own functions (blend_tf, lbs_apply: the rounding of the forward's records), and
+//     runs project_backward, the depth's z row of the view matrix, lbs_backward_view and the bone-weight products in registers;
+//   * the views are summed over the group with DPP (grp_sum: a fixed tree, ascending lanes), lane 0 of the group applies the
+//     quaternion backward and the sigmoid and writes the Gaussian's rows.  V > 8: groups of eight, in group order, the later ones
+//     adding.  No atomics: bit-reproducible.
+// EVERY Gaussian has a lane group (no active list: nothing of the workspace is written).  accumulate = 0: every row is written,
+// zeros where no view holds a record; accumulate = 1: rows with a record are added to, all others are not touched.
+// ---------------------------------------------------------------------------------------------------------------------
+#define VM_THREADS 256
+#define VM_TSTRIDE(B) ((B) * 16 + 4)      // LDS words per view of bone transforms (+4: the slabs of a group fall in distinct banks)
+
+template <int G>
+__global__ __launch_bounds__(VM_THREADS) void k_views_feat_gather(
+    int v_first, int v_count, int N, int B, int n_art, int W, int H, const float* __restrict__ cams,
+    const float* __restrict__ xyz, const float* __restrict__ log_scale, const float* __restrict__ rot,
+    const float* __restrict__ op_logit, const float* __restrict__ skin_w, const float* __restrict__ transforms,
+    const ushort4* __restrict__ rect, const uint32_t* __restrict__ pair_off, const uint32_t* __restrict__ tag,
+    const float* __restrict__ rec, uint32_t cap, int with_z, int accumulate, float* __restrict__ d_xyz, float* __restrict__ d_ls,
+    float* __restrict__ d_rot, float* __restrict__ d_op, float* __restrict__ d_w) {
+    constexpr int IPB = VM_THREADS / G;
+    extern __shared__ __align__(16) float s_vm[];        // G x (camera 40 | transforms VM_TSTRIDE(B))
+    const int tid = threadIdx.x, vl = tid & (G - 1), il = tid / G;
+    const int i_raw = blockIdx.x * IPB + il;
+    const int i = min(i_raw, N - 1);
+    const bool ok = i_raw < N;                           // (all lanes stay for the DPP sums)
+    const bool any_tf = skin_w != nullptr;               // workgroup-uniform: the pose slabs are staged
+    const bool has_tf = any_tf && i < n_art;             // uniform over the lane group
+    const int tstride = VM_TSTRIDE(B), vstride = MGR_CAM_FLOATS + (any_tf ? tstride : 0);
+    for (int k = tid; k < G * MGR_CAM_FLOATS; k += VM_THREADS) {
+        const int g = k / MGR_CAM_FLOATS, e = k % MGR_CAM_FLOATS;
+        s_vm[g * vstride + e] = g < v_count ? cams[(size_t)(v_first + g) * MGR_CAM_FLOATS + e] : 0.f;
+    }
+    if (any_tf)
+        for (int k = tid; k < G * B * 16; k += VM_THREADS) {
+            const int g = k / (B * 16), e = k % (B * 16);
+            s_vm[g * vstride + MGR_CAM_FLOATS + e] = g < v_count ? transforms[(size_t)(v_first + g) * B * 16 + e] : 0.f;
+        }
+    __syncthreads();
+    const float* const Tp = s_vm + vl * vstride + MGR_CAM_FLOATS;
+
+    // the records of this (view, Gaussian), in slot order: [mean2D.x, .y, conic A, B, C, opacity] and dL/dz
+    float acc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float gz = 0.f;
+    bool any = false;
+    if (ok && vl < v_count) {
+        const size_t vi = (size_t)(v_first + vl) * N + i;
+        const ushort4 rc = rect[vi];
+        uint32_t cnt = (uint32_t)((rc.z - rc.x) * (rc.w - rc.y));
+        const uint32_t off = pair_off[vi];
+        if (cnt > 0 && off < cap) {
+            cnt = min(cnt, cap - off);
+            for (uint32_t s = 0; s < cnt; ++s) {
+                if (tag[off + s] != 1u) continue;
+                const float4* r = (const float4*)(rec + (size_t)(off + s) * FEAT_REC);
+                const float4 r0 = r[0], r1 = r[1];
+                acc[0] += r0.x; acc[1] += r0.y; acc[2] += r0.z; acc[3] += r0.w; acc[4] += r1.x; acc[5] += r1.y;
+                gz += r1.z;
+                any = true;
+            }
+        }
+    }
+    if (!with_z) gz = 0.f;
+    const bool grp_any = grp_sum<G>(any ? 1.0f : 0.0f) > 0.0f;
+
+    GaussCano g;
+    cano_load(xyz, log_scale, rot, i, g);
+    float dxyz[3] = {0.f, 0.f, 0.f}, ds[3] = {0.f, 0.f, 0.f};
+    float dR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float dw[MGR_MAX_BONES];
+#pragma unroll
+    for (int b = 0; b < MGR_MAX_BONES; ++b) dw[b] = 0.f;
+    float dop = 0.f;
+    if (any) {
+        MgrCam cam;
+        {
+            const float* p = s_vm + vl * vstride;
+            cam.tanfovx = p[0];
+            cam.tanfovy = p[1];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                cam.view[k] = p[2 + k];
+                cam.proj[k] = p[18 + k];
+            }
+            cam.campos[0] = p[34]; cam.campos[1] = p[35]; cam.campos[2] = p[36];
+        }
+        float tf[12], p3[3], c6[6], dm[3], dc6[6], dtf[12];
+        blend_tf(has_tf ? skin_w + (size_t)i * B : nullptr, Tp, B, tf);
+        lbs_apply(tf, g, p3, c6);
+        project_backward(cam, W, H, p3, c6, acc, dm, dc6);
+        // z = view row 2 . (p, 1) (project_gaussian): the expected depth's own path to the posed mean
+        dm[0] += cam.view[2] * gz; dm[1] += cam.view[6] * gz; dm[2] += cam.view[10] * gz;
+        lbs_backward_view<false>(tf, g, dm, dc6, nullptr, dxyz, ds, dR, dtf);
+        if (has_tf) {
+#pragma unroll
+            for (int b = 0; b < MGR_MAX_BONES; ++b) {
+                if (b < B) {
+                    const float* T = Tp + b * 16;
+                    float a = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) a += dtf[k] * T[k];
+                    dw[b] = a;
+                }
+            }
+        }
+        dop = acc[5];
+    }
+    const bool acc_out = accumulate != 0;
+    const bool lead = ok && vl == 0 && (grp_any || !acc_out);     // the lane that writes this Gaussian's rows
+    if (any_tf && d_w) {      // (workgroup-uniform branch around the DPP sums; only articulated rows own a d_w row)
+#pragma unroll
+        for (int b = 0; b < MGR_MAX_BONES; ++b) {
+            if (b < B) {
+                const float t = grp_sum<G>(dw[b]);
+                if (lead && has_tf) {
+                    float* o = d_w + (size_t)i * B + b;
+                    *o = acc_out ? *o + t : t;
+                }
+            }
+        }
+    }
+    {
+        const float sg = 1.0f / (1.0f + expf(-op_logit[i]));
+        const float o7[7] = {dxyz[0], dxyz[1], dxyz[2], ds[0] * g.s[0], ds[1] * g.s[1], ds[2] * g.s[2], dop * sg * (1.0f - sg)};
+        float t7[7], tR[9];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) t7[k] = grp_sum<G>(o7[k]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) tR[k] = grp_sum<G>(dR[k]);
+        if (lead) {
+            float drot[4];
+            quat_backward(g, tR, drot);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                d_xyz[3 * (size_t)i + k] = acc_out ? d_xyz[3 * (size_t)i + k] + t7[k] : t7[k];
+                d_ls[3 * (size_t)i + k] = acc_out ? d_ls[3 * (size_t)i + k] + t7[3 + k] : t7[3 + k];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d_rot[4 * (size_t)i + k] = acc_out ? d_rot[4 * (size_t)i + k] + drot[k] : drot[k];
+            d_op[i] = acc_out ? d_op[i] + t7[6] : t7[6];
+        }
+    }
+}
+
+extern "C" size_t mgr_views_maps_backward_workspace_bytes(int V, int N, int W, int H, int64_t cap) {
+    (void)W; (void)H;                 // (one record per (tile, Gaussian) pair; nothing is kept per pixel or per Gaussian)
+    if (V <= 0 || N < 0 || cap < 0) return 0;
+    return feat_scratch_layout(V, N, cap).geo;        // tags | records
+}
+
+extern "C" int mgr_views_maps_backward(int V, int N, int B, int n_articulated, int W, int H, const float* cams, const float* xyz,
+                                       const float* log_scale, const float* rot, const float* opacity_logit, const float* skin_w,
+                                       const float* transforms, const float* out_alpha, const float* out_depth,
+                                       const float* dL_dalpha, const float* dL_ddepth, int accumulate, float* d_xyz,
+                                       float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_skin_w,
+                                       const void* workspace, size_t workspace_bytes, int64_t cap, void* scratch,
+                                       size_t scratch_bytes, int flags, void* stream_) {
+    static const char* const who = "mgr_views_maps_backward";
+    hipStream_t stream = (hipStream_t)stream_;
+    if (V <= 0 || N < 0 || W <= 0 || H <= 0 || cap < 0 || cap > 0xFFFFFFF0ll) return mgr_fail(MGR_EINVAL, "%s: bad sizes", who);
+    if (!dL_dalpha && !dL_ddepth) return mgr_fail(MGR_EINVAL, "%s: no upstream gradient (dL_dalpha and dL_ddepth are both NULL)", who);
+    if ((dL_dalpha && !out_alpha) || (dL_ddepth && !out_depth) || !workspace || !scratch || !cams)
+        return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
+    if (N > 0 && (!xyz || !log_scale || !rot || !opacity_logit || !d_xyz || !d_log_scale || !d_rot || !d_opacity_logit ||
+                  (skin_w && (!transforms || !d_skin_w))))
+        return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
+    if (skin_w && (B <= 0 || B > MGR_MAX_BONES)) return mgr_fail(MGR_EINVAL, "%s: bad B", who);
+    if (skin_w && (n_articulated < 0 || n_articulated > N)) return mgr_fail(MGR_EINVAL, "%s: bad n_articulated", who);
+    const int gx = (W + 15) / 16, gy = (H + 15) / 16;
+    if (gx > 65535 || gy > 65535) return mgr_fail(MGR_EINVAL, "%s: image too large", who);
+    const MgrLayout L = mgr_layout(V, N, W, H, cap);
+    if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "%s: workspace too small for these sizes", who);
+    const FeatScratch S = feat_scratch_layout(V, N, cap);
+    if (scratch_bytes < S.geo) return mgr_fail(MGR_ENOMEM, "%s: scratch smaller than mgr_views_maps_backward_workspace_bytes", who);
+    const char* ws = (const char*)workspace;
+    MgrHeader h;
+    const int VT = V * gx * gy;
+    {
+        const int rc = feat_read_state(who, ws, L, V, N, W, H, cap, VT, stream, h);
+        if (rc != MGR_OK) return rc;
+    }
+    if (N == 0) return MGR_OK;
+    char* sc = (char*)scratch;
+    // a slot nobody writes must count as zero: the tags are cleared per call, the one launch tags with 1
+    MGR_HIP(hipMemsetAsync(sc + S.tag, 0, (size_t)(cap > 0 ? cap : 1) * 4, stream));
+
+    FeatBwdArgs a;
+    a.N = N; a.W = W; a.H = H; a.gx = gx; a.gy = gy; a.VT = VT;
+    a.n_queue = h.queue_len_i; a.cap = (uint32_t)cap;
+    a.tile_qrec = (const uint4*)(ws + L.tile_qrec);
+    a.sorted_gid = (const uint32_t*)(ws + L.sorted_gid);
+    a.grec = (const MgrGRec*)(ws + L.grec);
+    a.depth = (const float*)(ws + L.depth);
+    a.feat = nullptr; a.s_feat = 0; a.C = 0; a.c0 = 0; a.nc = 0;
+    a.with_z = dL_ddepth ? 1 : 0;                     // the depth is the launch's only channel: slot 0 of the records
+    a.out = out_depth; a.g_out = dL_ddepth; a.Cout = a.with_z;
+    a.out_alpha = dL_dalpha ? out_alpha : nullptr;
+    a.g_alpha = dL_dalpha;
+    a.rec = (float*)(sc + S.rec); a.tag = (uint32_t*)(sc + S.tag);
+    a.tagval = 1u;
+    {
+        MGR_PROF("k_blend_feat_bwd", stream);
+        hipLaunchKernelGGL(k_blend_feat_bwd<2>, dim3(FEAT_GRID), dim3(256), 0, stream, a);
+    }
+    MGR_LAUNCH_CHECK("k_blend_feat_bwd", stream, flags & MGR_BWD_CHECK);
+
+    const float* sw = (skin_w && n_articulated > 0) ? skin_w : nullptr;      // (no articulated Gaussian: the identity everywhere)
+    const int n_art = sw ? n_articulated : 0;
+    const int Gv = V <= 1 ? 1 : V <= 2 ? 2 : V <= 4 ? 4 : 8;
+    const size_t lds = (size_t)Gv * (MGR_CAM_FLOATS + (sw ? VM_TSTRIDE(B) : 0)) * sizeof(float);
+    const dim3 grid((unsigned)((N + VM_THREADS / Gv - 1) / (VM_THREADS / Gv)));
+    for (int v0 = 0; v0 < V; v0 += Gv) {
+        const int vc = V - v0 < Gv ? V - v0 : Gv;
+        const int accm = (accumulate || v0 > 0) ? 1 : 0;
+        MGR_PROF("k_views_feat_gather", stream);
+#define MGR_VM_LAUNCH(GG)                                                                                                         \
+    hipLaunchKernelGGL((k_views_feat_gather<GG>), grid, dim3(VM_THREADS), lds, stream, v0, vc, N, B, n_art, W, H, cams, xyz, log_scale, \
+                       rot, opacity_logit, sw, transforms, (const ushort4*)(ws + L.rect), (const uint32_t*)(ws + L.pair_off),    \
+                       (const uint32_t*)a.tag, (const float*)a.rec, (uint32_t)cap, a.with_z, accm, d_xyz, d_log_scale, d_rot,    \
+                       d_opacity_logit, d_skin_w)
+        if (Gv == 8) MGR_VM_LAUNCH(8);
+        else if (Gv == 4) MGR_VM_LAUNCH(4);
+        else if (Gv == 2) MGR_VM_LAUNCH(2);
+        else MGR_VM_LAUNCH(1);
+#undef MGR_VM_LAUNCH
+        MGR_LAUNCH_CHECK("k_views_feat_gather", stream, flags & MGR_BWD_CHECK);
+    }
+    return MGR_OK;
+}

@@ -23,7 +23,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import fused as fused_mod, ops, rasterizer
+from . import fused as fused_mod, losses, ops, rasterizer
 from . import _lib
 from ._lib import ManusHipError, check, lib, ptr, stream
 
@@ -544,14 +544,28 @@ class HipViewCompute:
       attach_list   that mapped list is built by the forward's last kernel (mgr_views_forward_attach_loss_list) instead of a
                     launch of its own.  MANUS_LOSS_LIST_ATTACH=0.
       overlap_loss  without target maps: the span list is built on a second stream while the forward blend runs (forward split
-                    at the blend, MGR_FWD_NO_BLEND / MGR_FWD_BLEND_ONLY).  MANUS_OVERLAP_LOSS=0."""
+                    at the blend, MGR_FWD_NO_BLEND / MGR_FWD_BLEND_ONLY).  MANUS_OVERLAP_LOSS=0.
+
+    Map supervision (`mask_targets`, `w_mask`, `depth_targets`, `w_depth`; plain attributes, settable after construction): with
+    `mask_targets` (V_all,H,W) and a non-zero weight the step adds, per view,
+        w_mask * mean|alpha - mask| + w_depth * mean(mask * |depth - depth_target|)
+    on the accumulated-opacity and expected-depth maps of the view (`rasterizer.blend_features`), on the scale convention of the
+    image term (`scale` * sum over the views).  The depth term needs `depth_targets` (V_all,H,W) as well.  Fused: feature render
+    on the step's lists, mgr_map_loss, mgr_views_maps_backward adding into the step's gradient buffers; modular: the same loss
+    through `rasterize_views_features` and `losses.map_loss` under autograd.  The output dict gains "loss_mask" / "loss_depth"
+    (the unweighted terms on that scale) and "loss" includes the weighted sum.  With a term on, the fused step fills its
+    gradient buffers in full every step (no MGR_BWD_OUTPUTS_KEPT), `last_active` is None, and grad2d / vis / radii stay the
+    COLOUR loss's statistics (the modular route's grad2d includes the map term: DESIGN.md section 9).  Not combined with
+    depth_cut, pose_grad or skin_grid_grad (ValueError).  With both weights zero or no mask the step is exactly the step without
+    these arguments."""
 
     # per-view target maps kept (130 KB per 1080p view)
     MAX_TARGET_MAPS = 4096
 
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
-                 persistent_grads=True, pose_grad=False, skin_grid_grad=False):
+                 persistent_grads=True, pose_grad=False, skin_grid_grad=False, mask_targets=None, w_mask=0.0, depth_targets=None,
+                 w_depth=0.0):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -566,6 +580,10 @@ class HipViewCompute:
         self._tmaps = {}                # per-view target maps (`_target_map`)
         self.targets = targets          # (V_all,3,H,W) on the GPU (a property: replacing it drops what was derived from it)
         self.cams = cam_table           # (V_all,40)
+        # -- map supervision (class docstring): (V_all,H,W) masks / depth targets and their weights
+        self._mask_targets = self._depth_targets = None
+        self._map_bufs = {}             # fused route: maps, their gradients and the scratch of the map chain, kept across steps
+        self.w_mask, self.w_depth = float(w_mask), float(w_depth)
         # -- model
         self.params = {k: v.detach().clone().requires_grad_(True) for k, v in scene["params"].items()}
         N = self.params["_xyz"].shape[0]
@@ -627,6 +645,60 @@ class HipViewCompute:
         # operator).  A Trainer sets it False on ITS compute object: no host sync, the forward leaves an overflow fence
         # that Trainer._run_step polls.  (The device-wide policy of rasterizer.set_sync_policy is left alone.)
         self.sync_check = True
+        self.mask_targets = mask_targets
+        self.depth_targets = depth_targets
+        self._map_terms()               # (the combinations a map term refuses)
+
+    def _map_target(self, t, what):
+        """A (V_all,H,W) float map on the step's device, or None; ValueError otherwise."""
+        if t is None:
+            return None
+        shape = (self.cams.shape[0], int(self.s["height"]), int(self.s["width"]))
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or not t.is_floating_point():
+            raise ValueError("%s must be a float tensor (V_all,H,W) = %s (got %s)" % (what, shape, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+        if t.device != self.cams.device:
+            raise ValueError("%s is on %s, the step's views are on %s" % (what, t.device, self.cams.device))
+        return t
+
+    @property
+    def mask_targets(self):
+        return self._mask_targets
+
+    @mask_targets.setter
+    def mask_targets(self, t):
+        self._mask_targets = self._map_target(t, "mask_targets")
+        self._drop_view_constants()
+
+    @property
+    def depth_targets(self):
+        return self._depth_targets
+
+    @depth_targets.setter
+    def depth_targets(self, t):
+        self._depth_targets = self._map_target(t, "depth_targets")
+        self._drop_view_constants()
+
+    def _map_terms(self):
+        """(mask term on, depth term on) of the step about to run; ValueError for a combination the map chain does not serve."""
+        if self._mask_targets is None:
+            return False, False
+        depth = self.w_depth != 0.0 and self._depth_targets is not None
+        mask = self.w_mask != 0.0
+        if mask or depth:
+            for name in ("depth_cut", "pose_grad", "skin_grid_grad"):
+                if getattr(self, name, False):
+                    # (the depth cut shortens the lists the maps are rendered on; the pose and grid gradients read the colour
+                    # backward's slots and active list, which the map term is not in)
+                    raise ValueError("a map term (mask_targets with w_mask / w_depth) cannot be combined with %s=True" % name)
+        return mask, depth
+
+    def _map_sel(self, sel, view_ids, depth):
+        """The step's views of the mask (and depth) targets, cached with the other per-view constants."""
+        if "masks" not in sel:
+            sel["masks"] = self._mask_targets[list(view_ids)].float().contiguous()
+        if depth and "depths" not in sel:
+            sel["depths"] = self._depth_targets[list(view_ids)].float().contiguous()
+        return sel["masks"], sel.get("depths") if depth else None
 
     @property
     def _pg_ws(self):      # (bench.py and the tests ask whether the selective fills are in use)
@@ -656,7 +728,7 @@ class HipViewCompute:
         when one of those tensors was replaced or written in place (torch version counter) they are rebuilt."""
         s = self.s
         tfm = s.get("transforms") if self.is_hand else None
-        stamp = tuple((id(t), t._version) if t is not None else None for t in (self._targets, s.get("bg"), self.cams, tfm))
+        stamp = tuple((id(t), t._version) if t is not None else None for t in (self._targets, s.get("bg"), self.cams, tfm, self._mask_targets, self._depth_targets))
         if stamp != self._const_stamp:
             if self._const_stamp is not None:
                 self._drop_view_constants()
@@ -724,8 +796,9 @@ class HipViewCompute:
             tf = torch.cat([tf, otf.expand(P, -1, -1)], dim=1)
         return pxyz, pcov, tf
 
-    def forward_views(self, view_ids, T=None):
-        """T: the bone transforms to pose with instead of the scene's (the pose-gradient step passes a leaf)."""
+    def forward_views(self, view_ids, T=None, maps=None):
+        """T: the bone transforms to pose with instead of the scene's (the pose-gradient step passes a leaf).  maps = (alpha,
+        depth) booleans: a fourth result, the differentiable maps of `rasterize_views_features`."""
         s, p, ops = self.s, self.params, self.ops
         sel = self._select(view_ids)
         cams = sel["cams"]
@@ -736,6 +809,10 @@ class HipViewCompute:
         col = ops.sh_colors(feats, p["_xyz"], tf, cams)
         N = p["_xyz"].shape[0]
         means2D = torch.zeros((V, N, 3), dtype=torch.float32, device=cams.device, requires_grad=True)
+        if maps is not None:
+            img, radii, extras = self.rz.rasterize_views_features(cams, pxyz, means2D, col, opac, pcov, s["bg"], s["width"], s["height"],
+                                                                  depth=bool(maps[1]), alpha=bool(maps[0]))
+            return img, radii, means2D, extras
         img, radii = self.rz.rasterize_views(cams, pxyz, means2D, col, opac, pcov, s["bg"], s["width"], s["height"])
         return img, radii, means2D
 
@@ -833,6 +910,7 @@ class HipViewCompute:
         kept = self._kept if (self.persistent_grads and not self.grad_arena and self.fused) else None
         if kept is not None:
             kept.begin(N, na, dev)
+        map_on = self._map_terms()
         w, B = self._skin_weights(p["_xyz"], na)
         if kept is not None:      # the image too is a kept buffer (MGR_FWD_IMAGE_KEPT)
             out = kept.get((V, 3, H, W), ("image", V, H, W), zeroed=False)
@@ -856,8 +934,9 @@ class HipViewCompute:
             if route != "overlap" and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
             loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
-            grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale)
-            active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"])
+            grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale, full_rows=any(map_on))
+            map_out = self._map_chain(ws, head, sel, view_ids, scale, map_on, grads, d_w) if any(map_on) else None
+            active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"], full_rows=any(map_on))
             d_grid = self._skin_grid_backward(head, p["_xyz"], d_w, active) if self.skin_grid_grad else None
             overflow = ws.buf[4:8].view(torch.int32)
         except BaseException:
@@ -873,6 +952,9 @@ class HipViewCompute:
         self.last_image, self.last_radii = out, radii
         self.last_active = active      # (device pointers into the workspace of this step: valid until the next forward on it)
         res = dict(grads=grads, grad2d=st_g, vis=st_v, radii=st_r, loss=loss, overflow=overflow)
+        if map_out is not None:
+            res["loss"] = loss + map_out[0]
+            res["loss_mask"], res["loss_depth"] = map_out[1], map_out[2]
         if d_T is not None:
             res["d_transforms"] = d_T
         if d_grid is not None:
@@ -972,9 +1054,46 @@ class HipViewCompute:
                                                 ptr(sums), ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_finish")
         return sums[2], g_img
 
-    def _backward(self, ws, fwd, g_img, scale):
+    def _map_chain(self, ws, head, sel, view_ids, scale, map_on, grads, d_w):
+        """The map terms of the fused step, behind the colour backward: feature render (C = 0) of alpha and, with the depth term,
+        the expected depth on the step's lists -> mgr_map_loss -> mgr_views_maps_backward ADDING to the leaf gradients and the
+        skin-weight gradient the colour backward has just written.  -> (weighted loss, mask term, depth term) on the step's
+        scale (`scale` * sum over the views).  A forward that overflowed its pair capacity leaves no complete lists: the chain
+        is skipped (zeros) -- the step's overflow word tells the caller to run it again."""
+        V, N, B, na, _, W, H = head[:7]
+        cams, xyz, ls, rot, op, w, T = head[7], head[9], head[10], head[11], head[12], head[15], head[16]
+        dev, L = self.device, lib()
+        masks, depths = self._map_sel(sel, view_ids, map_on[1])
+        key = (V, N, W, H, ws.cap, bool(map_on[1]))
+        mb = self._map_bufs.get(key)
+        if mb is None:
+            e = functools.partial(torch.empty, dtype=torch.float32, device=dev)
+            n_loss, n_scr = int(L.mgr_map_loss_workspace_bytes(V, H, W)), int(L.mgr_views_maps_backward_workspace_bytes(V, N, W, H, ws.cap))
+            mb = dict(alpha=e((V, H, W)), g_alpha=e((V, H, W)), depth=e((V, 1, H, W)) if map_on[1] else None,
+                      g_depth=e((V, 1, H, W)) if map_on[1] else None,
+                      loss_ws=torch.empty(n_loss, dtype=torch.uint8, device=dev), scratch=torch.empty(n_scr, dtype=torch.uint8, device=dev))
+            self._map_bufs = {key: mb}
+        sums = torch.empty(3, dtype=torch.float32, device=dev)
+        rc = L.mgr_raster_blend_features(V, N, 0, W, H, None, 0, None, int(map_on[1]), ptr(mb["depth"]), ptr(mb["alpha"]), ptr(ws.buf),
+                                         ws.nbytes, ws.cap, stream())
+        if rc == _lib.MGR_ESTATE and int(ws.buf[4:8].view(torch.int32).item()) != 0:
+            z = torch.zeros((), dtype=torch.float32, device=dev)
+            return z, z, z
+        check(rc, "mgr_raster_blend_features")
+        k = scale * V      # scale * sum over the views of a per-view mean = scale * V * the mean over all V H W elements
+        check(L.mgr_map_loss(V, H, W, ptr(mb["alpha"]), ptr(masks), ptr(mb["depth"]), ptr(depths), self.w_mask,
+                             self.w_depth if map_on[1] else 0.0, k, ptr(mb["g_alpha"]), ptr(mb["g_depth"]), ptr(sums), ptr(mb["loss_ws"]),
+                             mb["loss_ws"].numel(), stream()), "mgr_map_loss")
+        check(L.mgr_views_maps_backward(V, N, B, na, W, H, cams, xyz, ls, rot, op, w, T, ptr(mb["alpha"]), ptr(mb["depth"]),
+                                        ptr(mb["g_alpha"]), ptr(mb["g_depth"]), 1, ptr(grads["_xyz"]), ptr(grads["_scaling"]),
+                                        ptr(grads["_rotation"]), ptr(grads["_opacity"]), ptr(d_w), ptr(ws.buf), ws.nbytes, ws.cap,
+                                        ptr(mb["scratch"]), mb["scratch"].numel(), 0, stream()), "mgr_views_maps_backward")
+        return sums[2] * k, sums[0] * k, sums[1] * k
+
+    def _backward(self, ws, fwd, g_img, scale, full_rows=False):
         """mgr_views_backward into the kept buffers, the arena or fresh tensors: (leaf gradients, skin-weight gradient,
-        grad2d, vis, radii, dL/dtransforms or None)."""
+        grad2d, vis, radii, dL/dtransforms or None).  full_rows: every row is filled (a map term adds rows behind this call that
+        the library's row state does not know about)."""
         head, out, radii, kept = fwd
         V, N, B, na = head[:4]
         dev = self.device
@@ -986,7 +1105,7 @@ class HipViewCompute:
         d_w = e((na, B), "_skin_w") if na else None
         # the buffers are those of the previous backward on this very workspace, untouched since: the library may skip the
         # zero fill of the rows it knows to be zero (it checks that its row state is that call's)
-        bits = _lib.MGR_BWD_OUTPUTS_KEPT if (kept is not None and kept.grad_ws is ws and V <= 8) else 0
+        bits = _lib.MGR_BWD_OUTPUTS_KEPT if (kept is not None and kept.grad_ws is ws and V <= 8 and not full_rows) else 0
         self._kept.grad_ws = None
         args = (*head, ptr(radii), ptr(out), ptr(g_img), 1.0 / scale, *[ptr(g) for g in grads.values()],
                 ptr(d_w), ptr(st_g), ptr(st_v), ptr(st_r), ptr(ws.buf), ws.nbytes, ws.cap, bits)
@@ -1002,14 +1121,17 @@ class HipViewCompute:
             check(lib().mgr_views_backward(*args, stream()), "mgr_views_backward")
         if kept is not None:
             kept.handed_out(ws)
+            if full_rows:
+                kept.grad_ws = None
         return grads, d_w, st_g, st_v, st_r, d_T
 
-    def _skin_backward(self, ws, head, xyz, d_w, d_xyz):
+    def _skin_backward(self, ws, head, xyz, d_w, d_xyz, full_rows=False):
         """The backward's list of the Gaussians that received a gradient (device pointers: list, length; None beyond 8 views)
-        and, through it, d xyz += d w . d(trilinear weights)/d xyz (the leaf is used twice: gaussian_utils.py:167-196)."""
+        and, through it, d xyz += d w . d(trilinear weights)/d xyz (the leaf is used twice: gaussian_utils.py:167-196).
+        full_rows: no list, every articulated row (a map term wrote d_w rows outside the colour backward's list)."""
         V, N, _, na, _, W, H = head[:7]
         active = None
-        if V <= 8 and N > 0:
+        if V <= 8 and N > 0 and not full_rows:
             lst, cnt = ctypes.c_void_p(), ctypes.c_void_p()
             check(lib().mgr_views_active_list(ptr(ws.buf), V, N, W, H, ws.cap, ctypes.byref(lst), ctypes.byref(cnt)),
                   "mgr_views_active_list")
@@ -1018,7 +1140,7 @@ class HipViewCompute:
             return active
         s, sg = self.s, self.grid
         grid = (na, ptr(xyz), ptr(sg.data), sg.D, sg.H, sg.W, sg.B, sg.stride, ptr(s["grid_center"]), ptr(s["grid_scale"]), ptr(d_w), ptr(d_xyz))
-        if V <= 8:      # for the Gaussians that received a gradient only (the others' d_w rows are zero)
+        if active is not None:      # for the Gaussians that received a gradient only (the others' d_w rows are zero)
             check(lib().mgr_skin_weights_bwd_indexed(*grid, lst, cnt, N, stream()), "mgr_skin_weights_bwd_indexed")
         else:
             check(lib().mgr_skin_weights_bwd(*grid, 1, stream()), "mgr_skin_weights_bwd")
@@ -1043,15 +1165,30 @@ class HipViewCompute:
             v.grad = None
         sel = self._select(view_ids)
         T = sel["T"].detach().requires_grad_(True) if self.pose_grad else None     # a leaf for this step
-        img, radii, means2D = self.forward_views(view_ids, T=T)
+        map_on = self._map_terms()
         tgt = sel["targets"]
-        loss, g = self._image_loss(img, tgt, scale)
-        img.backward(g)
+        map_out = None
+        if any(map_on):
+            img, radii, means2D, extras = self.forward_views(view_ids, T=T, maps=(True, map_on[1]))
+            loss, g = self._image_loss(img, tgt, scale)
+            masks, depths = self._map_sel(sel, view_ids, map_on[1])
+            k = scale * len(view_ids)
+            ml, sums = losses.map_loss(extras["alpha"], masks, self.w_mask, extras["depth"] if map_on[1] else None, depths,
+                                       self.w_depth if map_on[1] else 0.0)
+            torch.autograd.backward([img, ml * k], [g, None])
+            map_out = (sums[2] * k, sums[0] * k, sums[1] * k)
+            loss = loss + map_out[0]
+        else:
+            img, radii, means2D = self.forward_views(view_ids, T=T)
+            loss, g = self._image_loss(img, tgt, scale)
+            img.backward(g)
         vis = radii > 0
         g2 = means2D.grad[..., :2].norm(dim=-1) * (1.0 / scale)
         res = dict(grads={n: v.grad for n, v in self.params.items()},
                    grad2d=(g2 * vis).sum(0), vis=vis.sum(0).float(),
                    radii=radii.max(dim=0).values, loss=loss)
+        if map_out is not None:
+            res["loss_mask"], res["loss_depth"] = map_out[1], map_out[2]
         if T is not None:
             res["d_transforms"] = T.grad
         if self.skin_grid_grad:

@@ -120,6 +120,28 @@ def rgb_ssim_loss(pred_image, gt_image, w_rgb=0.8, w_ssim=0.2):
     return _ImageLoss.apply(pred_image, gt_image, w_rgb, w_ssim) + w_ssim
 
 
+class _MapLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, alpha, mask, depth, depth_target, w_mask, w_depth):
+        sums, g_a, g_d = ops.map_loss_grad(alpha, mask, w_mask, depth, depth_target, w_depth, 1.0)
+        ctx.save_for_backward(g_a, g_d)
+        ctx.mark_non_differentiable(sums)
+        return sums[2].clone(), sums
+
+    @staticmethod
+    def backward(ctx, go, _g_sums):
+        g_a, g_d = ctx.saved_tensors
+        return g_a * go, None, (g_d * go if g_d is not None else None), None, None, None
+
+
+def map_loss(alpha, mask, w_mask=1.0, depth=None, depth_target=None, w_depth=0.0):
+    """Silhouette and depth supervision on the maps of `rasterizer.rasterize_views_features` (V,H,W), one kernel
+    (mgr_map_loss): w_mask * mean|alpha - mask| + w_depth * mean(mask * |depth - depth_target|), differentiable w.r.t. alpha
+    and depth.  `depth` is the expected, un-normalised depth of the feature render; the depth term is off without it.
+    Returns (loss, sums) with sums = [L_mask, L_depth, loss] detached.  No reference counterpart (its masks only prune)."""
+    return _MapLoss.apply(alpha, mask, depth, depth_target, float(w_mask), float(w_depth))
+
+
 class _IsotropicReg(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_scale, condition_number):

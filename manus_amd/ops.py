@@ -325,6 +325,32 @@ def l1_loss_grad(pred, target, scale=None):
     return s, g
 
 
+def map_loss_grad(alpha, mask, w_mask=1.0, depth=None, depth_target=None, w_depth=0.0, grad_scale=1.0):
+    """Silhouette and depth terms on (V,H,W) maps of the feature render (mgr_map_loss), value and gradient in one pass:
+    L_mask = mean|alpha - mask|, L_depth = mean(mask |depth - depth_target|) (off without `depth`).  Returns (sums, dL_dalpha,
+    dL_ddepth or None): sums = [L_mask, L_depth, w_mask L_mask + w_depth L_depth] (device tensor of 3 floats, without
+    grad_scale); the gradients are those of grad_scale * sums[2]."""
+    alpha, mask = f32c(alpha), f32c(mask)
+    if alpha.dim() != 3 or mask.shape != alpha.shape:
+        raise ManusHipError("map_loss: alpha and mask must be (V,H,W) maps of one shape (got %s, %s)" % (tuple(alpha.shape), tuple(mask.shape)))
+    if (depth is None) != (depth_target is None):
+        raise ManusHipError("map_loss: the depth term takes depth and depth_target together")
+    V, H, W = alpha.shape
+    g_d = None
+    if depth is not None:
+        depth, depth_target = f32c(depth), f32c(depth_target)
+        if depth.shape != alpha.shape or depth_target.shape != alpha.shape:
+            raise ManusHipError("map_loss: depth and depth_target must have the shape of alpha")
+        g_d = torch.empty_like(depth)
+    g_a = torch.empty_like(alpha)
+    sums = torch.empty(3, dtype=torch.float32, device=alpha.device)
+    nbytes = int(lib().mgr_map_loss_workspace_bytes(V, H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=alpha.device)
+    check(lib().mgr_map_loss(V, H, W, ptr(alpha), ptr(mask), ptr(depth), ptr(depth_target), float(w_mask), float(w_depth),
+                             float(grad_scale), ptr(g_a), ptr(g_d), ptr(sums), ptr(ws), nbytes, stream()), "mgr_map_loss")
+    return sums, g_a, g_d
+
+
 def image_loss_grad(pred, target, w_l1=0.8, w_ssim=0.2, grad_scale=1.0, loss_offset=0.0, bg=None, tile_start_ptr=None):
     """Fused L1 + SSIM image loss of the training step (loss_utils.py:22-97 as called at
     base.py:323-365), forward and backward, on (V,3,H,W) images.

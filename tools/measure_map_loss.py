@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Time the map supervision of the fused step (HipViewCompute(mask_targets=..., w_mask=...)).
+
+    python tools/measure_map_loss.py [--out FILE.json] [--quick]
+
+One process, HIP events, every shape warmed, median of 5 samples with min - max (each sample a batch of repeats), on the bench
+step (bench.py's scene and targets: 300k hand Gaussians, 8 views of 1920x1080, loss l1+ssim, targets = the model perturbed by
+1 %; mask targets = the alpha maps of that perturbed model):
+  * the step with the mask term off and on (and with the depth term as well), alternated;
+  * the three calls the term adds, alone, on the workspace of a step: mgr_raster_blend_features (C = 0, alpha),
+    mgr_map_loss, mgr_views_maps_backward (each call of the first and the last includes its blocking read of the header);
+  * the kernels' own times from the library's HIP-event profile (k_blend_feat, k_map_loss, k_blend_feat_bwd,
+    k_views_feat_gather).
+Needs a GPU; there is no fallback."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from measure_feature_render import timed  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true", help="small sizes (a rehearsal of the script, not a measurement)")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "measure_map_loss.py needs a GPU"
+    from manus_amd import _lib, rasterizer as rz
+    from manus_amd._lib import check, lib, ptr, stream
+    from manus_amd.engine import HipViewCompute
+    from manus_amd.synthetic import camera_table, make_scene
+    dev = "cuda:0"
+    V, N, W, H = (8, 300000, 1920, 1080) if not a.quick else (3, 5000, 96, 64)
+    scene = make_scene(n_gaussians=N, kind="hand", seed=0, n_cameras=V, width=W, height=H, device=dev,
+                       **({} if not a.quick else dict(grid_res=24, cam_radius=0.5, sigma_range=(2e-3, 8e-3))))
+    ct = camera_table(scene["cameras"], dev)
+    g = torch.Generator(device="cpu").manual_seed(123)
+    pert = dict(scene)
+    pert["params"] = {k: (v + 0.01 * v.abs().mean() * torch.randn(v.shape, generator=g).to(dev)) for k, v in scene["params"].items()}
+    ids = list(range(V))
+    with torch.no_grad():
+        hp = HipViewCompute(pert, torch.zeros((V, 3, H, W), device=dev), ct)
+        targets = hp.forward_views_fused(ids)[0].contiguous().clone()
+        m = rz.blend_features(depth=True, alpha=True, device=dev)
+        mask, dtgt = m["alpha"].clone(), m["depth"].clone()
+        del hp
+    rz.context(dev).clear()
+    res = {"device": torch.cuda.get_device_name(0), "sizes": dict(V=V, N=N, W=W, H=H), "step": {}, "calls": {}, "kernels": {}}
+    steps = {"off": HipViewCompute(scene, targets, ct, loss="l1+ssim"),
+             "mask": HipViewCompute(scene, targets, ct, loss="l1+ssim", mask_targets=mask, w_mask=0.1),
+             "mask+depth": HipViewCompute(scene, targets, ct, loss="l1+ssim", mask_targets=mask, w_mask=0.1, depth_targets=dtgt, w_depth=0.1)}
+    rep = 20 if not a.quick else 3
+    for key in ("off", "mask", "off_again", "mask+depth", "mask_again"):
+        hc = steps[key.replace("_again", "")]
+        res["step"][key] = timed(lambda: hc(ids, 1.0 / V), rep)
+        print("step %s" % key, json.dumps(res["step"][key]), flush=True)
+
+    # the three calls alone, on the workspace of a step of the "mask+depth" object
+    hc = steps["mask+depth"]
+    hc(ids, 1.0 / V)
+    torch.cuda.synchronize()
+    ws = rz.context(dev).last_ws
+    mb = next(iter(hc._map_bufs.values()))
+    p = {k: v.detach() for k, v in hc.params.items()}
+    w, B = hc._skin_weights(p["_xyz"], hc.n_art)
+    sel = hc._select(ids)
+    outs = [torch.zeros(s, device=dev) for s in ((N, 3), (N, 3), (N, 4), (N, 1), (hc.n_art, B))]
+    sums = torch.empty(3, device=dev)
+    L = lib()
+
+    def render(depth):
+        return lambda: check(L.mgr_raster_blend_features(V, N, 0, W, H, None, 0, None, int(depth), ptr(mb["depth"]) if depth else None,
+                                                         ptr(mb["alpha"]), ptr(ws.buf), ws.nbytes, ws.cap, stream()), "mgr_raster_blend_features")
+
+    def loss(depth):
+        return lambda: check(L.mgr_map_loss(V, H, W, ptr(mb["alpha"]), ptr(sel["masks"]), ptr(mb["depth"]) if depth else None,
+                                            ptr(sel["depths"]) if depth else None, 0.1, 0.1, 1.0, ptr(mb["g_alpha"]),
+                                            ptr(mb["g_depth"]) if depth else None, ptr(sums), ptr(mb["loss_ws"]), mb["loss_ws"].numel(), stream()),
+                             "mgr_map_loss")
+
+    def backward(depth):
+        return lambda: check(L.mgr_views_maps_backward(V, N, B, hc.n_art, W, H, ptr(sel["cams"]), ptr(p["_xyz"]), ptr(p["_scaling"]),
+                                                       ptr(p["_rotation"]), ptr(p["_opacity"].reshape(-1)), ptr(w), ptr(sel["T"]), ptr(mb["alpha"]),
+                                                       ptr(mb["depth"]) if depth else None, ptr(mb["g_alpha"]), ptr(mb["g_depth"]) if depth else None,
+                                                       1, *[ptr(t) for t in outs], ptr(ws.buf), ws.nbytes, ws.cap, ptr(mb["scratch"]),
+                                                       mb["scratch"].numel(), 0, stream()), "mgr_views_maps_backward")
+
+    res["calls"]["scratch_bytes"] = int(mb["scratch"].numel())
+    res["calls"]["workspace_bytes"] = int(ws.nbytes)
+    for key, fn in (("render_alpha", render(False)), ("render_alpha+depth", render(True)), ("map_loss_mask", loss(False)),
+                    ("map_loss_mask+depth", loss(True)), ("maps_backward_alpha", backward(False)), ("maps_backward_alpha+depth", backward(True)),
+                    ("maps_backward_alpha_again", backward(False))):
+        res["calls"][key] = timed(fn, 5 if not a.quick else 2)
+        print("call %s" % key, json.dumps(res["calls"][key]), flush=True)
+
+    # the kernels' own times (HIP events around every launch of the library)
+    for key in ("mask", "mask+depth"):
+        _lib.profile_enable(True)
+        _lib.profile_report()
+        for _ in range(5):
+            steps[key](ids, 1.0 / V)
+        rp = _lib.profile_report()
+        _lib.profile_enable(False)
+        res["kernels"][key] = {k: dict(launches=c, mean_ms=ms / max(c, 1)) for k, (c, ms) in rp.items()
+                               if k in ("k_blend_feat", "k_map_loss", "k_blend_feat_bwd", "k_views_feat_gather", "k_blend_bwd", "k_inst_bwd")}
+        print("kernels %s" % key, json.dumps(res["kernels"][key]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
