@@ -723,6 +723,37 @@ int mgr_map_loss(int V, int H, int W, const float* alpha, const float* mask, con
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Device frame store: the stored uint8 RGBA crops of a capture decoded into the float targets and masks of a step
+ * (manus_amd/frames.py; SequenceDataset.fetch_images, brics_dynamic.py:343-373, restated bit for bit).
+ *
+ * A target image is a constant of its view only on a still frame; a sequence draws new (action, frame, camera) items every
+ * step.  The crops of all items live in one device pool (`pool`, rows packed, each crop at a multiple of 16 bytes) and one
+ * call rewrites the rows `slot` of the caller's tables from them:
+ *   source pixel  the crop's value inside its bbox, (0,0,0,0) outside; the source frame is (H k) x (W k)
+ *   block mean    per channel the integer sum s of the k x k block, m = (2 s + k k) / (2 k k) in integers (numpy's
+ *                 floor(mean + 0.5), cv2's INTER_AREA for the factor 1/k on uint8)
+ *   composite     c' = m_c / 255.0, a' = m_a / 255.0 in fp64 (a table of constants: no division on the device),
+ *                 target = fp32(c' a' + bg (1.0 - a')), products and sum rounded one by one (no fma), mask = fp32(a')
+ * Only the rectangle (rx0, ry0, rx1, ry1) of OUTPUT pixels of a view is written: the whole image, or the union of the boxes of
+ * the old and the new crop when the caller knows what the slot held before (same background).  `views_host` is HOST memory:
+ * the records travel as kernel arguments, MGR_FRAMES_MAX_VIEWS per launch (a larger V is a loop over chunks).  No copy, no
+ * allocation on the device, no synchronisation.  masks may be NULL.  An empty crop (x1 == x0 or y1 == y0) gives background
+ * and a zero mask.
+ * MGR_EINVAL, before anything is launched: k < 1; a bbox outside [0, W k] x [0, H k] or reversed; an offset that is no multiple
+ * of 16; offset + crop bytes > pool_bytes; a rectangle outside the image; a slot outside [0, n_slots); two views of the call
+ * with one slot; a NULL pool with a non-empty crop. */
+#define MGR_FRAMES_MAX_VIEWS 16
+typedef struct {
+    int64_t offset;             /* byte offset of the crop in the pool, a multiple of 16 */
+    int32_t x0, y0, x1, y1;     /* bbox in SOURCE pixels; the crop is (y1 - y0, x1 - x0, 4) uint8 RGBA, rows packed */
+    int32_t rx0, ry0, rx1, ry1; /* rectangle of OUTPUT pixels to write */
+    float bg[3];                /* background colour */
+    int32_t slot;               /* row of targets / masks to write */
+} MgrFrameView;
+int mgr_frames_decode(int V, int H, int W, int k, const uint8_t* pool, int64_t pool_bytes, const MgrFrameView* views_host,
+                      float* targets /* (n_slots,3,H,W) */, float* masks /* (n_slots,H,W) or NULL */, int64_t n_slots, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimizer step and densification of the Gaussian parameter model
  * (src/models/gaussian.py:128-338).
  *

@@ -19,6 +19,7 @@ _LIB = None
 
 MGR_CAM_FLOATS = 40
 MGR_MAX_BONES = 32
+MGR_FRAMES_MAX_VIEWS = 16     # views per launch of mgr_frames_decode (the entry itself loops over larger calls)
 
 # The words of the rasterizer's ABI, value for value those of include/manus_hip.h (tests/test_abi_constants.py compares them).
 # Plain ints: the operator route is bound by host time, and enum.IntFlag arithmetic costs microseconds per operation.
@@ -33,6 +34,15 @@ MGR_TIERS_NEAR_SMALL_SHIFT, MGR_TIERS_NEAR_LARGE_SHIFT, MGR_TIERS_NEAR_MASK = 8,
 MGR_TIERS_BEYOND_SMALL_SHIFT, MGR_TIERS_BEYOND_SMALL_MASK = 24, 0x7F
 
 c_int, c_i64, c_f32, c_vp, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+
+
+class MgrFrameView(ctypes.Structure):
+    """One view of mgr_frames_decode (include/manus_hip.h): where its crop lies in the pool, its bbox in source pixels, the
+    rectangle of output pixels to write, the background colour and the row of the tables."""
+    _fields_ = [("offset", ctypes.c_int64), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
+                ("rx0", ctypes.c_int32), ("ry0", ctypes.c_int32), ("rx1", ctypes.c_int32), ("ry1", ctypes.c_int32),
+                ("bg", ctypes.c_float * 3), ("slot", ctypes.c_int32)]
+
 
 # name -> (restype, argtypes); must list every symbol of include/manus_hip.h
 SIGNATURES = {
@@ -129,6 +139,7 @@ SIGNATURES = {
                                             c_vp]),
     "mgr_map_loss_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_map_loss": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_frames_decode": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_i64, ctypes.POINTER(MgrFrameView), c_vp, c_vp, c_i64, c_vp]),
     "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_eval_triptych": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -460,24 +460,30 @@ class SequenceDataset(torch.utils.data.Dataset):
         return img
 
     # -- brics_dynamic.py:375-424 ---------------------------------------------------------------------------
-    def get_data_from_h5(self, index):
+    def get_data_from_h5(self, index, images=True):
+        """images=False: no image is read or composited (rgba is None) -- `view_batch` with a `frames.FrameStore`."""
         action, frame_id, cam_name = self.index_list[index]
         if cam_name is None:
             cams = list(np.random.default_rng().choice(self.cam_names, size=self.opts["rand_views_per_timestep"], replace=False))
         else:
             cams = [cam_name]
-        with open_sequence(self._path(action)) as file:
-            data = file.get("frames")[str(frame_id)]
-            rgba = np.array([self.fetch_images(data, c) for c in cams])
+        rgba = None
+        if images:
+            with open_sequence(self._path(action)) as file:
+                data = file.get("frames")[str(frame_id)]
+                rgba = np.array([self.fetch_images(data, c) for c in cams])
         cameras = self.all_cameras[[self.cam2idx[c] for c in cams]]
         return rgba, cameras, self.metadata_dict[action][str(frame_id)], [self.subject_id, action, frame_id, cams]
 
-    def fetch_data(self, index):
-        rgba, camera, md, info = self.get_data_from_h5(index)
+    def fetch_data(self, index, images=True):
+        rgba, camera, md, info = self.get_data_from_h5(index, images)
         rest, posed = Bones(**md["bones_rest"].__dict__), Bones(**md["bones_posed"].__dict__)   # (to_tensor converts in place)
-        return {"info": info, "rgb": to_tensor(rgba[..., :3]), "mask": to_tensor(rgba[..., 3:]), "camera": to_tensor(camera),
-                "scaling_modifier": 1.0, "bg_color": to_tensor(self.get_bg_color()), "bones_rest": to_tensor(rest),
-                "bones_posed": to_tensor(posed), "pose_latent": md["pose_latent"]}
+        out = {"info": info, "camera": to_tensor(camera),
+               "scaling_modifier": 1.0, "bg_color": to_tensor(self.get_bg_color()), "bones_rest": to_tensor(rest),
+               "bones_posed": to_tensor(posed), "pose_latent": md["pose_latent"]}
+        if images:
+            out["rgb"], out["mask"] = to_tensor(rgba[..., :3]), to_tensor(rgba[..., 3:])
+        return out
 
     # -- model initialisation (brics_dynamic.py:69-144) -------------------------------------------------------
     def _first_rest(self):
@@ -509,10 +515,20 @@ class SequenceDataset(torch.utils.data.Dataset):
         return mano_init.build_voxel_grid(self._first_rest(), self.mano_data, grid_boundary, res, ratio, offset, device)
 
     # -- hand-off to the engine --------------------------------------------------------------------------------
-    def view_batch(self, indices, device="cpu"):
+    def view_batch(self, indices, device="cpu", store=None):
         """Items -> what `engine.HipViewCompute` consumes for one step: targets (V,3,H,W), masks (V,H,W), the camera
         dicts, posed bone transforms (V,J,4,4) and keypoints (V,J+1,3) = first head + all tails
-        (hand_dynamic.py:199-204)."""
+        (hand_dynamic.py:199-204).  store: a `frames.FrameStore` over (at least) these items -- targets and masks are then
+        decoded on `device` from the store's crop pool (bit for bit the host path's; one background draw per item) and no
+        image is read, composited or copied on the host."""
+        if store is not None:
+            items = [self.fetch_data(i, images=False) for i in indices]
+            out = _skeleton_batch(items, device, camera_row=0)
+            V = len(items)
+            out["targets"] = torch.empty((V, 3, store.height, store.width), dtype=torch.float32, device=device)
+            out["masks"] = torch.empty((V, store.height, store.width), dtype=torch.float32, device=device)
+            store.decode(indices, np.stack([self.get_bg_color() for _ in items]), out["targets"], out["masks"], dirty=False)
+            return out
         items = [self.fetch_data(i) for i in indices]
         out = _skeleton_batch(items, device, camera_row=0)
         out["targets"] = torch.stack([it["rgb"][0].permute(2, 0, 1) for it in items]).to(device)

@@ -723,6 +723,13 @@ class HipViewCompute:
         self._tmaps.clear()
         self._const_stamp = None
 
+    def view_constants_changed(self):
+        """Someone wrote into `targets`, `mask_targets`, `depth_targets`, `cams` or the scene's transforms in a way torch's
+        version counters do not see (a kernel given the raw pointer: `frames.FrameStore`): everything derived from them is
+        rebuilt by the next step, and the depth-cut hints of the views rendered so far are dropped."""
+        self._drop_view_constants()
+        self._cut.new_generation()
+
     def _check_view_constants(self):
         """The target maps and the per-view-set gathers are functions of `targets`, `s["bg"]`, `cams` and the transforms:
         when one of those tensors was replaced or written in place (torch version counter) they are rebuilt."""
