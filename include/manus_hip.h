@@ -398,6 +398,36 @@ int mgr_views_maps_backward(int V, int N, int B, int n_articulated, int W, int H
                             float* d_opacity_logit, float* d_skin_w, const void* workspace, size_t workspace_bytes,
                             int64_t pair_capacity, void* scratch, size_t scratch_bytes, int flags, void* stream);
 
+/* mgr_views_maps_backward plus the map terms' gradient with respect to the pose: d_transforms (V,B,16) in the layout and
+ * conventions of mgr_views_backward_pose -- d_transforms[v][b][r][c] = sum_n skin_w[n][b] * dL/d(blended transform of Gaussian
+ * n in view v)[r][c] for r < 3, row 3 zero, the background transform a row like any other, the static rows of a composite
+ * contributing nothing.  The leading arguments are those of mgr_views_maps_backward, in its order.
+ *   accumulate_pose        0: every element of d_transforms is written (row 3 as zero; all-zero rows for a view in which
+ *                             nothing held a record);
+ *                          1: the result is added, as the last addition, to rows 0 .. 2 of what d_transforms holds and row 3 is
+ *                             left as it is -- on top of the d_transforms mgr_views_backward_pose wrote for the colour term
+ * Every other output is bit for bit that of mgr_views_maps_backward with the same arguments (they are written by the same
+ * kernels with the same arguments); the workspace is only read; the scratch contract is unchanged.  Behind the gather of every
+ * group of up to eight views one more kernel runs over the articulated Gaussians in the gather's lane layout: at most 1024
+ * workgroups, each taking the chunks x, x + gridDim.x, ... (gridDim.x = min(1024, chunks)) of 256 / Gv Gaussians (Gv = views per lane group: 1, 2, 4 or 8); a lane
+ * sums the records of its (view, Gaussian) again, recomputes dL/d(blended transform) in registers and parks it in LDS, the
+ * workgroup reduces the chunk in a fixed order and writes ONE partial of Gv x B x 12 floats into pose_workspace, and a fold kernel
+ * adds the partials in slot order.  No float atomics, bit-reproducible, nothing kept per (Gaussian, view).  With V > 8 every
+ * group of eight views writes (or adds to) its own rows.
+ * pose_workspace_bytes >= mgr_views_maps_pose_workspace_bytes(V, N, B) = min(1024, ceil(N / (256 / Gv))) x Gv x B x 12 x 4 bytes
+ * rounded up to 256 (at most 12.6 MB); 0 for non-positive sizes.  Its contents need not be initialised.
+ * Refused as mgr_views_maps_backward, and: MGR_EINVAL for skin_w == NULL or n_articulated <= 0 (nothing to differentiate) and for
+ * d_transforms or pose_workspace NULL; MGR_ENOMEM for a pose workspace below the size function.  On any refusal nothing is
+ * launched and no output is touched. */
+size_t mgr_views_maps_pose_workspace_bytes(int V, int N, int B);
+int mgr_views_maps_backward_pose(int V, int N, int B, int n_articulated, int W, int H, const float* cams, const float* xyz,
+                                 const float* log_scale, const float* rot, const float* opacity_logit, const float* skin_w,
+                                 const float* transforms, const float* out_alpha, const float* out_depth, const float* dL_dalpha,
+                                 const float* dL_ddepth, int accumulate, float* d_xyz, float* d_log_scale, float* d_rot,
+                                 float* d_opacity_logit, float* d_skin_w, const void* workspace, size_t workspace_bytes,
+                                 int64_t pair_capacity, void* scratch, size_t scratch_bytes, int flags, int accumulate_pose,
+                                 float* d_transforms, void* pose_workspace, size_t pose_workspace_bytes, void* stream);
+
 /* Device pointers (into the workspace) to the compacted list of Gaussians that received a gradient in the last
  * mgr_views_backward and to its length; V <= 8. */
 int mgr_views_active_list(void* workspace, int V, int N, int W, int H, int64_t pair_capacity, const uint32_t** list,
@@ -530,8 +560,13 @@ int mgr_skin_grid_adam(const int32_t* voxel, const float* grad, const uint32_t* 
                        float* grid, int grid_stride, int B, float* exp_avg, float* exp_avg_sq,
                        double lr, double beta1, double beta2, double eps, int step, int clamp, float clamp_min,
                        void* stream);
+/* mask[i] = 1 where row i of dL_dw (n,B) holds an entry != 0 (a NaN counts), else 0; every mask[0 .. n) is written.  With
+ * mgr_exchange_index behind it: the ascending list of the non-zero rows of a skin-weight gradient, the `index` of mgr_skin_grid_bwd
+ * where more than one backward added into dL_dw.  MGR_EINVAL (nothing launched): n < 0, B outside 1 .. MGR_MAX_BONES, a null
+ * pointer with n > 0. */
+int mgr_skin_rows_mask(int n, int B, const float* dL_dw, uint8_t* mask, void* stream);
 
-/* LBS for P poses.  transforms: (P,B,16) row-major 4x4 bone transforms
+/* LBS for P poses. transforms: (P,B,16) row-major 4x4 bone transforms
  * T_b = posed_b * inv(rest_b) (+ identity background).  skin_w (N,B) or NULL for
  * the static-object path (identity transform: posed = xyz, cov = Sigma).
  * Outputs: posed_xyz (P,N,3), posed_cov (P,N,6), tf (P,N,12) = rows 0..2 of the

@@ -70,6 +70,9 @@ SIGNATURES = {
                                         c_vp]),
     "mgr_views_maps_backward_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_i64]),
     "mgr_views_maps_backward": (c_int, [c_int] * 6 + [c_vp] * 11 + [c_int] + [c_vp] * 5 + [c_vp, c_sz, c_i64, c_vp, c_sz, c_int, c_vp]),
+    "mgr_views_maps_pose_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_views_maps_backward_pose": (c_int, [c_int] * 6 + [c_vp] * 11 + [c_int] + [c_vp] * 5 + [c_vp, c_sz, c_i64, c_vp, c_sz, c_int] +
+                                     [c_int, c_vp, c_vp, c_sz, c_vp]),
     "mgr_raster_record_bytes": (c_int, []),
     "mgr_raster_layout": (c_int, [c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_sz), c_int]),
     "mgr_raster_status_sync": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32), c_vp]),
@@ -92,6 +95,7 @@ SIGNATURES = {
                                   c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_vp]),
     "mgr_skin_grid_adam": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, c_int, c_int, c_f32, c_vp]),
+    "mgr_skin_rows_mask": (c_int, [c_int, c_int, c_vp, c_vp, c_vp]),
     "mgr_views_backward_run_lists": (c_int, [c_int]),
     "mgr_views_active_list": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "mgr_lbs_cov_fwd": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

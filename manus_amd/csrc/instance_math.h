@@ -546,3 +546,6 @@ __device__ __forceinline__ void pose_wg_store(int tid, int NV, int B, float* s_s
 // fixed order; v < v_count of the NV views a slot holds.
 int mgr_pose_fold(int v_first, int v_count, int NV, int B, const float* part, int n_slots, float* d_transforms,
                   hipStream_t stream);
+// The same with accumulate != 0: the sum is added (last) to what d_transforms holds in rows 0 .. 2; row 3 is left as it is.
+int mgr_pose_fold_acc(int v_first, int v_count, int NV, int B, const float* part, int n_slots, int accumulate, float* d_transforms,
+                      hipStream_t stream);

@@ -399,7 +399,10 @@ __global__ __launch_bounds__(256) void k_lbs_pose_part(int N, int B, int n_chunk
 
 // Second stage of both routes (mgr_pose_fold, instance_math.h).  Workgroup (b, v): thread 12 s + k adds the slots s, s + 21,
 // ... of element k of (v, b) in ascending order, thread k < 12 then the 21 slices in ascending order; row 3 is written as zero.
+// ACC (mgr_pose_fold_acc, the map backward's pose gradient on top of the colour backward's): the finished sum is added LAST to
+// what out holds, row 3 is left as it is.
 #define POSE_FOLD_SLICES 21
+template <bool ACC>
 __global__ __launch_bounds__(256) void k_pose_fold(int v_first, int NV, int B, const float* __restrict__ part, int n_slots,
                                                    float* __restrict__ out) {
     __shared__ float s_sum[POSE_FOLD_SLICES * 12];
@@ -414,20 +417,27 @@ __global__ __launch_bounds__(256) void k_pose_fold(int v_first, int NV, int B, c
         s_sum[s * 12 + k] = a;
     }
     __syncthreads();
-    if (tid < 16) {
+    if (tid < (ACC ? 12 : 16)) {
         float a = 0.f;
         if (tid < 12)
             for (int q = 0; q < POSE_FOLD_SLICES; ++q) a += s_sum[q * 12 + tid];
-        out[((size_t)(v_first + v) * B + b) * 16 + tid] = a;
+        float* o = out + ((size_t)(v_first + v) * B + b) * 16 + tid;
+        *o = ACC ? *o + a : a;
     }
+}
+
+int mgr_pose_fold_acc(int v_first, int v_count, int NV, int B, const float* part, int n_slots, int accumulate, float* d_transforms,
+                      hipStream_t stream) {
+    MGR_PROF("k_pose_fold", stream);
+    if (accumulate) hipLaunchKernelGGL(k_pose_fold<true>, dim3(B, v_count), dim3(256), 0, stream, v_first, NV, B, part, n_slots, d_transforms);
+    else hipLaunchKernelGGL(k_pose_fold<false>, dim3(B, v_count), dim3(256), 0, stream, v_first, NV, B, part, n_slots, d_transforms);
+    MGR_LAUNCH_CHECK("k_pose_fold", stream, 0);
+    return MGR_OK;
 }
 
 int mgr_pose_fold(int v_first, int v_count, int NV, int B, const float* part, int n_slots, float* d_transforms,
                   hipStream_t stream) {
-    MGR_PROF("k_pose_fold", stream);
-    hipLaunchKernelGGL(k_pose_fold, dim3(B, v_count), dim3(256), 0, stream, v_first, NV, B, part, n_slots, d_transforms);
-    MGR_LAUNCH_CHECK("k_pose_fold", stream, 0);
-    return MGR_OK;
+    return mgr_pose_fold_acc(v_first, v_count, NV, B, part, n_slots, 0, d_transforms, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -742,6 +742,9 @@ __global__ __launch_bounds__(VM_THREADS) void k_views_feat_gather(
     const float* const Tp = s_vm + vl * vstride + MGR_CAM_FLOATS;
 
     // the records of this (view, Gaussian), in slot order: [mean2D.x, .y, conic A, B, C, opacity] and dL/dz
+    // TWIN: k_views_feat_gather_pose below repeats this record walk, the camera unpack and the chain down to dtf by copy (the
+    // reason is at its head).  A change here to the record layout, the tag value, the slot clamp or the depth path goes there too;
+    // what would notice a drift is tests/test_gpu_map_pose.py's comparison of d_transforms with the operator route.
     float acc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float gz = 0.f;
     bool any = false;
@@ -844,20 +847,134 @@ __global__ __launch_bounds__(VM_THREADS) void k_views_feat_gather(
     }
 }
 
+// Pose gradient of the map backward (mgr_views_maps_backward_pose): dL/dT[v][b] = sum_n w[n][b] * dtf[n][v], the other contraction
+// of the dtf that k_views_feat_gather contracts with the bone transforms for d_skin_w.  A kernel of its own BEHIND the plain
+// gather, which keeps its argument list and its code and writes the leaf rows: restating the gather's lane work inside a second
+// kernel gave leaf rows that differ from k_views_feat_gather's in the last bit (the compiler contracts other multiply-adds
+// there), and the leaf outputs of the two entries must be the same bits.  So this kernel repeats only what dtf needs -- the
+// records of the lane's (view, Gaussian) in slot order, blend_tf / lbs_apply, project_backward, the depth's z row,
+// lbs_backward_view -- for the ARTICULATED Gaussians, and writes no leaf row.  The lane layout of k_pose_part_views
+// (raster_bwd.hip): lane = Gaussian_local * G + view_local; workgroup x stages the group's cameras and transforms once and takes
+// the chunks x, x + gridDim.x, ... of 256 / G Gaussians (gridDim.x <= MGR_POSE_MAX_WG); a lane that held records parks dtf and
+// its Gaussian index in LDS (MGR_POSE_REC words), pose_wg_lists / pose_wg_accumulate reduce the chunk per (view, bone) in lane
+// order, and the workgroup stores ONE partial of G x B x 12 floats (part + x * G * B * 12), which k_pose_fold adds in slot order.
+template <int G>
+__global__ __launch_bounds__(VM_THREADS) void k_views_feat_gather_pose(
+    int v_first, int v_count, int B, int n_art, int W, int H, const float* __restrict__ cams, const float* __restrict__ xyz,
+    const float* __restrict__ log_scale, const float* __restrict__ rot, const float* __restrict__ skin_w,
+    const float* __restrict__ transforms, const ushort4* __restrict__ rect, const uint32_t* __restrict__ pair_off,
+    const uint32_t* __restrict__ tag, const float* __restrict__ rec, uint32_t cap, int N, int with_z, int n_chunks,
+    float* __restrict__ part) {
+    constexpr int IPB = VM_THREADS / G;
+    extern __shared__ __align__(16) float s_vm[];        // G x (camera 40 | transforms VM_TSTRIDE(B))
+    __shared__ float s_rec[VM_THREADS * MGR_POSE_REC];
+    __shared__ unsigned char s_lst[G * VM_THREADS];
+    __shared__ int s_cnt[8], s_wc[8 * (VM_THREADS / 64)];
+    const int tid = threadIdx.x, vl = tid & (G - 1), il = tid / G;
+    const int vstride = MGR_CAM_FLOATS + VM_TSTRIDE(B);
+    for (int k = tid; k < G * MGR_CAM_FLOATS; k += VM_THREADS) {
+        const int g = k / MGR_CAM_FLOATS, e = k % MGR_CAM_FLOATS;
+        s_vm[g * vstride + e] = g < v_count ? cams[(size_t)(v_first + g) * MGR_CAM_FLOATS + e] : 0.f;
+    }
+    for (int k = tid; k < G * B * 16; k += VM_THREADS) {
+        const int g = k / (B * 16), e = k % (B * 16);
+        s_vm[g * vstride + MGR_CAM_FLOATS + e] = g < v_count ? transforms[(size_t)(v_first + g) * B * 16 + e] : 0.f;
+    }
+    __syncthreads();
+    const float* const Tp = s_vm + vl * vstride + MGR_CAM_FLOATS;
+    float pacc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pacc[k] = 0.f;
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {      // (workgroup-uniform trip count: barriers inside)
+        const int i = c * IPB + il;
+        // the records of this (view, Gaussian), in slot order (k_views_feat_gather's loop)
+        float acc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float gz = 0.f;
+        bool any = false;
+        if (i < n_art && vl < v_count) {
+            const size_t vi = (size_t)(v_first + vl) * N + i;
+            const ushort4 rc = rect[vi];
+            uint32_t cnt = (uint32_t)((rc.z - rc.x) * (rc.w - rc.y));
+            const uint32_t off = pair_off[vi];
+            if (cnt > 0 && off < cap) {
+                cnt = min(cnt, cap - off);
+                for (uint32_t s = 0; s < cnt; ++s) {
+                    if (tag[off + s] != 1u) continue;
+                    const float4* r = (const float4*)(rec + (size_t)(off + s) * FEAT_REC);
+                    const float4 r0 = r[0], r1 = r[1];
+                    acc[0] += r0.x; acc[1] += r0.y; acc[2] += r0.z; acc[3] += r0.w; acc[4] += r1.x; acc[5] += r1.y;
+                    gz += r1.z;
+                    any = true;
+                }
+            }
+        }
+        if (!with_z) gz = 0.f;
+        if (any) {
+            MgrCam cam;
+            {
+                const float* p = s_vm + vl * vstride;
+                cam.tanfovx = p[0];
+                cam.tanfovy = p[1];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    cam.view[k] = p[2 + k];
+                    cam.proj[k] = p[18 + k];
+                }
+                cam.campos[0] = p[34]; cam.campos[1] = p[35]; cam.campos[2] = p[36];
+            }
+            GaussCano g;
+            cano_load(xyz, log_scale, rot, i, g);
+            float dxyz[3] = {0.f, 0.f, 0.f}, ds[3] = {0.f, 0.f, 0.f};
+            float dR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float tf[12], p3[3], c6[6], dm[3], dc6[6], dtf[12];
+            blend_tf(skin_w + (size_t)i * B, Tp, B, tf);
+            lbs_apply(tf, g, p3, c6);
+            project_backward(cam, W, H, p3, c6, acc, dm, dc6);
+            dm[0] += cam.view[2] * gz; dm[1] += cam.view[6] * gz; dm[2] += cam.view[10] * gz;
+            lbs_backward_view<false>(tf, g, dm, dc6, nullptr, dxyz, ds, dR, dtf);      // (dxyz / ds / dR: by-products, not used)
+            float* r = s_rec + tid * MGR_POSE_REC;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) r[k] = dtf[k];
+            r[12] = __int_as_float(i);
+        }
+        pose_wg_lists<VM_THREADS>(tid, G, any ? vl : -1, s_lst, s_cnt, s_wc);
+        pose_wg_accumulate<VM_THREADS>(tid, G, B, s_rec, s_lst, s_cnt, skin_w, pacc);
+        __syncthreads();   // the next chunk's records
+    }
+    pose_wg_store<VM_THREADS>(tid, G, B, s_rec, pacc, part + (size_t)blockIdx.x * G * B * 12);
+}
+
 extern "C" size_t mgr_views_maps_backward_workspace_bytes(int V, int N, int W, int H, int64_t cap) {
     (void)W; (void)H;                 // (one record per (tile, Gaussian) pair; nothing is kept per pixel or per Gaussian)
     if (V <= 0 || N < 0 || cap < 0) return 0;
     return feat_scratch_layout(V, N, cap).geo;        // tags | records
 }
 
-extern "C" int mgr_views_maps_backward(int V, int N, int B, int n_articulated, int W, int H, const float* cams, const float* xyz,
-                                       const float* log_scale, const float* rot, const float* opacity_logit, const float* skin_w,
-                                       const float* transforms, const float* out_alpha, const float* out_depth,
-                                       const float* dL_dalpha, const float* dL_ddepth, int accumulate, float* d_xyz,
-                                       float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_skin_w,
-                                       const void* workspace, size_t workspace_bytes, int64_t cap, void* scratch,
-                                       size_t scratch_bytes, int flags, void* stream_) {
-    static const char* const who = "mgr_views_maps_backward";
+// Partial slots of the pose kernel: one per workgroup, at most MGR_POSE_MAX_WG (the workspace is sized for n_articulated = N)
+static int vm_pose_slots(int N, int Gv) {
+    const int ipb = VM_THREADS / Gv, chunks = N / ipb + (N % ipb != 0 ? 1 : 0);      // (no N + ipb - 1: N may be INT_MAX)
+    return chunks < MGR_POSE_MAX_WG ? chunks : MGR_POSE_MAX_WG;
+}
+extern "C" size_t mgr_views_maps_pose_workspace_bytes(int V, int N, int B) {
+    if (V <= 0 || N <= 0 || B <= 0) return 0;
+    const int Gv = V <= 1 ? 1 : V <= 2 ? 2 : V <= 4 ? 4 : 8;
+    return ((size_t)vm_pose_slots(N, Gv) * Gv * B * 12 * sizeof(float) + 255) & ~(size_t)255;
+}
+
+struct VmPose {      // mgr_views_maps_backward_pose: what it adds to mgr_views_maps_backward
+    int accumulate;
+    float* d_T;
+    void* ws;
+    size_t ws_bytes;
+};
+
+static int views_maps_backward_impl(const char* who, const VmPose* pose, int V, int N, int B, int n_articulated, int W, int H,
+                                    const float* cams, const float* xyz, const float* log_scale, const float* rot,
+                                    const float* opacity_logit, const float* skin_w, const float* transforms, const float* out_alpha,
+                                    const float* out_depth, const float* dL_dalpha, const float* dL_ddepth, int accumulate,
+                                    float* d_xyz, float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_skin_w,
+                                    const void* workspace, size_t workspace_bytes, int64_t cap, void* scratch,
+                                    size_t scratch_bytes, int flags, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (V <= 0 || N < 0 || W <= 0 || H <= 0 || cap < 0 || cap > 0xFFFFFFF0ll) return mgr_fail(MGR_EINVAL, "%s: bad sizes", who);
     if (!dL_dalpha && !dL_ddepth) return mgr_fail(MGR_EINVAL, "%s: no upstream gradient (dL_dalpha and dL_ddepth are both NULL)", who);
@@ -868,6 +985,13 @@ extern "C" int mgr_views_maps_backward(int V, int N, int B, int n_articulated, i
         return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
     if (skin_w && (B <= 0 || B > MGR_MAX_BONES)) return mgr_fail(MGR_EINVAL, "%s: bad B", who);
     if (skin_w && (n_articulated < 0 || n_articulated > N)) return mgr_fail(MGR_EINVAL, "%s: bad n_articulated", who);
+    if (pose) {
+        if (!skin_w || n_articulated <= 0)
+            return mgr_fail(MGR_EINVAL, "%s: no articulated Gaussians (skin_w NULL or n_articulated <= 0): nothing to differentiate", who);
+        if (!pose->d_T || !pose->ws) return mgr_fail(MGR_EINVAL, "%s: null pointer (d_transforms, pose_workspace)", who);
+        if (pose->ws_bytes < mgr_views_maps_pose_workspace_bytes(V, N, B))
+            return mgr_fail(MGR_ENOMEM, "%s: pose workspace smaller than mgr_views_maps_pose_workspace_bytes", who);
+    }
     const int gx = (W + 15) / 16, gy = (H + 15) / 16;
     if (gx > 65535 || gy > 65535) return mgr_fail(MGR_EINVAL, "%s: image too large", who);
     const MgrLayout L = mgr_layout(V, N, W, H, cap);
@@ -914,18 +1038,68 @@ extern "C" int mgr_views_maps_backward(int V, int N, int B, int n_articulated, i
     for (int v0 = 0; v0 < V; v0 += Gv) {
         const int vc = V - v0 < Gv ? V - v0 : Gv;
         const int accm = (accumulate || v0 > 0) ? 1 : 0;
-        MGR_PROF("k_views_feat_gather", stream);
+        {
+            MGR_PROF("k_views_feat_gather", stream);
 #define MGR_VM_LAUNCH(GG)                                                                                                         \
     hipLaunchKernelGGL((k_views_feat_gather<GG>), grid, dim3(VM_THREADS), lds, stream, v0, vc, N, B, n_art, W, H, cams, xyz, log_scale, \
                        rot, opacity_logit, sw, transforms, (const ushort4*)(ws + L.rect), (const uint32_t*)(ws + L.pair_off),    \
                        (const uint32_t*)a.tag, (const float*)a.rec, (uint32_t)cap, a.with_z, accm, d_xyz, d_log_scale, d_rot,    \
                        d_opacity_logit, d_skin_w)
-        if (Gv == 8) MGR_VM_LAUNCH(8);
-        else if (Gv == 4) MGR_VM_LAUNCH(4);
-        else if (Gv == 2) MGR_VM_LAUNCH(2);
-        else MGR_VM_LAUNCH(1);
+            if (Gv == 8) MGR_VM_LAUNCH(8);
+            else if (Gv == 4) MGR_VM_LAUNCH(4);
+            else if (Gv == 2) MGR_VM_LAUNCH(2);
+            else MGR_VM_LAUNCH(1);
 #undef MGR_VM_LAUNCH
+        }
         MGR_LAUNCH_CHECK("k_views_feat_gather", stream, flags & MGR_BWD_CHECK);
+        if (pose) {
+            // the pose gradient of this group's views: partials over the articulated Gaussians, then the fold that writes (or,
+            // accumulate_pose, adds to) the group's rows of d_transforms
+            const int ipb = VM_THREADS / Gv, n_chunks = (n_art + ipb - 1) / ipb, slots = vm_pose_slots(n_art, Gv);
+            {
+                MGR_PROF("k_views_feat_gather_pose", stream);
+#define MGR_VMP_LAUNCH(GG)                                                                                                        \
+    hipLaunchKernelGGL((k_views_feat_gather_pose<GG>), dim3((unsigned)slots), dim3(VM_THREADS), lds, stream, v0, vc, B, n_art, W, H,  \
+                       cams, xyz, log_scale, rot, sw, transforms, (const ushort4*)(ws + L.rect), (const uint32_t*)(ws + L.pair_off), \
+                       (const uint32_t*)a.tag, (const float*)a.rec, (uint32_t)cap, N, a.with_z, n_chunks, (float*)pose->ws)
+                if (Gv == 8) MGR_VMP_LAUNCH(8);
+                else if (Gv == 4) MGR_VMP_LAUNCH(4);
+                else if (Gv == 2) MGR_VMP_LAUNCH(2);
+                else MGR_VMP_LAUNCH(1);
+#undef MGR_VMP_LAUNCH
+            }
+            MGR_LAUNCH_CHECK("k_views_feat_gather_pose", stream, flags & MGR_BWD_CHECK);
+            const int rc = mgr_pose_fold_acc(v0, vc, Gv, B, (const float*)pose->ws, slots, pose->accumulate, pose->d_T, stream);
+            if (rc != MGR_OK) return rc;
+        }
     }
     return MGR_OK;
+}
+
+extern "C" int mgr_views_maps_backward(int V, int N, int B, int n_articulated, int W, int H, const float* cams, const float* xyz,
+                                       const float* log_scale, const float* rot, const float* opacity_logit, const float* skin_w,
+                                       const float* transforms, const float* out_alpha, const float* out_depth,
+                                       const float* dL_dalpha, const float* dL_ddepth, int accumulate, float* d_xyz,
+                                       float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_skin_w,
+                                       const void* workspace, size_t workspace_bytes, int64_t cap, void* scratch,
+                                       size_t scratch_bytes, int flags, void* stream) {
+    return views_maps_backward_impl("mgr_views_maps_backward", nullptr, V, N, B, n_articulated, W, H, cams, xyz, log_scale, rot,
+                                    opacity_logit, skin_w, transforms, out_alpha, out_depth, dL_dalpha, dL_ddepth, accumulate, d_xyz,
+                                    d_log_scale, d_rot, d_opacity_logit, d_skin_w, workspace, workspace_bytes, cap, scratch,
+                                    scratch_bytes, flags, stream);
+}
+
+extern "C" int mgr_views_maps_backward_pose(int V, int N, int B, int n_articulated, int W, int H, const float* cams, const float* xyz,
+                                            const float* log_scale, const float* rot, const float* opacity_logit,
+                                            const float* skin_w, const float* transforms, const float* out_alpha,
+                                            const float* out_depth, const float* dL_dalpha, const float* dL_ddepth, int accumulate,
+                                            float* d_xyz, float* d_log_scale, float* d_rot, float* d_opacity_logit, float* d_skin_w,
+                                            const void* workspace, size_t workspace_bytes, int64_t cap, void* scratch,
+                                            size_t scratch_bytes, int flags, int accumulate_pose, float* d_transforms,
+                                            void* pose_workspace, size_t pose_workspace_bytes, void* stream) {
+    const VmPose pose = {accumulate_pose, d_transforms, pose_workspace, pose_workspace_bytes};
+    return views_maps_backward_impl("mgr_views_maps_backward_pose", &pose, V, N, B, n_articulated, W, H, cams, xyz, log_scale, rot,
+                                    opacity_logit, skin_w, transforms, out_alpha, out_depth, dL_dalpha, dL_ddepth, accumulate, d_xyz,
+                                    d_log_scale, d_rot, d_opacity_logit, d_skin_w, workspace, workspace_bytes, cap, scratch,
+                                    scratch_bytes, flags, stream);
 }

@@ -438,3 +438,23 @@ extern "C" int mgr_skin_grid_adam(const int32_t* voxel, const float* grad, const
     MGR_LAUNCH_CHECK("k_sg_adam", stream, 0);
     return MGR_OK;
 }
+
+// mask[i] = 1 where row i of dL_dw (n,B) holds a non-zero entry (NaN != 0: a non-finite row is listed), else 0
+__global__ __launch_bounds__(256) void k_sg_rows_mask(int n, int B, const float* __restrict__ dL_dw, uint8_t* __restrict__ mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* r = dL_dw + (size_t)i * B;
+    bool any = false;
+    for (int c = 0; c < B; ++c) any = any || (r[c] != 0.0f);
+    mask[i] = any ? 1 : 0;
+}
+
+extern "C" int mgr_skin_rows_mask(int n, int B, const float* dL_dw, uint8_t* mask, void* stream_) {
+    if (n < 0 || B <= 0 || B > MGR_MAX_BONES) return mgr_fail(MGR_EINVAL, "mgr_skin_rows_mask: n < 0 or B outside 1 .. MGR_MAX_BONES");
+    if (n == 0) return MGR_OK;
+    if (!dL_dw || !mask) return mgr_fail(MGR_EINVAL, "mgr_skin_rows_mask: null pointer");
+    hipStream_t stream = (hipStream_t)stream_;
+    { MGR_PROF("k_sg_rows_mask", stream); hipLaunchKernelGGL(k_sg_rows_mask, dim3((unsigned)n / 256u + ((unsigned)n % 256u != 0u ? 1u : 0u)), dim3(256), 0, stream, n, B, dL_dw, mask); }
+    MGR_LAUNCH_CHECK("k_sg_rows_mask", stream, 0);
+    return MGR_OK;
+}

@@ -556,7 +556,9 @@ class HipViewCompute:
     (the unweighted terms on that scale) and "loss" includes the weighted sum.  With a term on, the fused step fills its
     gradient buffers in full every step (no MGR_BWD_OUTPUTS_KEPT), `last_active` is None, and grad2d / vis / radii stay the
     COLOUR loss's statistics (the modular route's grad2d includes the map term: DESIGN.md section 9).  Not combined with
-    depth_cut, pose_grad or skin_grid_grad (ValueError).  With both weights zero or no mask the step is exactly the step without
+    depth_cut (ValueError).  With pose_grad, "d_transforms" includes the map terms (fused: mgr_views_maps_backward_pose adds
+    them to the colour backward's); with skin_grid_grad, "d_skin_grid" is formed from the summed skin-weight gradient over its
+    non-zero rows (up to 8 views; all rows beyond).  With both weights zero or no mask the step is exactly the step without
     these arguments."""
 
     # per-view target maps kept (130 KB per 1080p view)
@@ -634,6 +636,8 @@ class HipViewCompute:
         self._kept = _KeptBuffers()
         self.grad_arena = None
         self._pose_ws = None            # partial slots of mgr_views_backward_pose (kept across steps)
+        self._map_pose_ws = None        # partial slots of mgr_views_maps_backward_pose (kept across steps)
+        self._sg_rows = None            # fused route, skin_grid_grad with a map term: mask / list / count / workspace of `_d_w_rows`
         # -- sh_storage "fp16" (BASELINE config 5): the fused kernels read an fp16 copy of _features_rest (96 B instead of
         # 180 B per Gaussian and view group); arithmetic, gradients and the optimizer's master copy stay fp32.  The copy
         # is refreshed lazily after the leaves changed (`mark_params_changed`).  The reference has no fp16 mode:
@@ -685,11 +689,13 @@ class HipViewCompute:
         depth = self.w_depth != 0.0 and self._depth_targets is not None
         mask = self.w_mask != 0.0
         if mask or depth:
-            for name in ("depth_cut", "pose_grad", "skin_grid_grad"):
-                if getattr(self, name, False):
-                    # (the depth cut shortens the lists the maps are rendered on; the pose and grid gradients read the colour
-                    # backward's slots and active list, which the map term is not in)
-                    raise ValueError("a map term (mask_targets with w_mask / w_depth) cannot be combined with %s=True" % name)
+            if getattr(self, "depth_cut", False):      # (the depth cut shortens the lists the maps are rendered on)
+                raise ValueError("a map term (mask_targets with w_mask / w_depth) cannot be combined with depth_cut=True")
+            for name in ("pose_grad", "skin_grid_grad"):
+                # (the constructor's refusal, asked again at the step: the flags are plain attributes)
+                if getattr(self, name, False) and not self.is_hand:
+                    raise ValueError("%s=True needs articulated Gaussians: a %r scene without a skin grid has none (asked with a map term on)"
+                                     % (name, self.kind))
         return mask, depth
 
     def _map_sel(self, sel, view_ids, depth):
@@ -942,9 +948,9 @@ class HipViewCompute:
                 ctx.fence(ws)
             loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
             grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale, full_rows=any(map_on))
-            map_out = self._map_chain(ws, head, sel, view_ids, scale, map_on, grads, d_w) if any(map_on) else None
+            map_out = self._map_chain(ws, head, sel, view_ids, scale, map_on, grads, d_w, d_T) if any(map_on) else None
             active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"], full_rows=any(map_on))
-            d_grid = self._skin_grid_backward(head, p["_xyz"], d_w, active) if self.skin_grid_grad else None
+            d_grid = self._skin_grid_backward(head, p["_xyz"], d_w, active, rows_of_d_w=any(map_on)) if self.skin_grid_grad else None
             overflow = ws.buf[4:8].view(torch.int32)
         except BaseException:
             # a call that failed between the loss's list and finish passes -- the forward included: its last kernel builds the
@@ -1061,12 +1067,14 @@ class HipViewCompute:
                                                 ptr(sums), ptr(lws), nbytes, stream()), "mgr_image_loss_tiles_finish")
         return sums[2], g_img
 
-    def _map_chain(self, ws, head, sel, view_ids, scale, map_on, grads, d_w):
+    def _map_chain(self, ws, head, sel, view_ids, scale, map_on, grads, d_w, d_T=None):
         """The map terms of the fused step, behind the colour backward: feature render (C = 0) of alpha and, with the depth term,
         the expected depth on the step's lists -> mgr_map_loss -> mgr_views_maps_backward ADDING to the leaf gradients and the
-        skin-weight gradient the colour backward has just written.  -> (weighted loss, mask term, depth term) on the step's
-        scale (`scale` * sum over the views).  A forward that overflowed its pair capacity leaves no complete lists: the chain
-        is skipped (zeros) -- the step's overflow word tells the caller to run it again."""
+        skin-weight gradient the colour backward has just written.  d_T (pose_grad): mgr_views_maps_backward_pose instead, which
+        also adds the map terms' pose gradient to the colour backward's d_transforms.  -> (weighted loss, mask term, depth term)
+        on the step's scale (`scale` * sum over the views).  A forward that overflowed its pair capacity leaves no complete
+        lists: the chain is skipped (zeros; d_T stays the colour term's) -- the step's overflow word tells the caller to run it
+        again."""
         V, N, B, na, _, W, H = head[:7]
         cams, xyz, ls, rot, op, w, T = head[7], head[9], head[10], head[11], head[12], head[15], head[16]
         dev, L = self.device, lib()
@@ -1091,10 +1099,17 @@ class HipViewCompute:
         check(L.mgr_map_loss(V, H, W, ptr(mb["alpha"]), ptr(masks), ptr(mb["depth"]), ptr(depths), self.w_mask,
                              self.w_depth if map_on[1] else 0.0, k, ptr(mb["g_alpha"]), ptr(mb["g_depth"]), ptr(sums), ptr(mb["loss_ws"]),
                              mb["loss_ws"].numel(), stream()), "mgr_map_loss")
-        check(L.mgr_views_maps_backward(V, N, B, na, W, H, cams, xyz, ls, rot, op, w, T, ptr(mb["alpha"]), ptr(mb["depth"]),
-                                        ptr(mb["g_alpha"]), ptr(mb["g_depth"]), 1, ptr(grads["_xyz"]), ptr(grads["_scaling"]),
-                                        ptr(grads["_rotation"]), ptr(grads["_opacity"]), ptr(d_w), ptr(ws.buf), ws.nbytes, ws.cap,
-                                        ptr(mb["scratch"]), mb["scratch"].numel(), 0, stream()), "mgr_views_maps_backward")
+        args = (V, N, B, na, W, H, cams, xyz, ls, rot, op, w, T, ptr(mb["alpha"]), ptr(mb["depth"]), ptr(mb["g_alpha"]), ptr(mb["g_depth"]), 1,
+                ptr(grads["_xyz"]), ptr(grads["_scaling"]), ptr(grads["_rotation"]), ptr(grads["_opacity"]), ptr(d_w), ptr(ws.buf),
+                ws.nbytes, ws.cap, ptr(mb["scratch"]), mb["scratch"].numel(), 0)
+        if d_T is not None:
+            nbytes = int(L.mgr_views_maps_pose_workspace_bytes(V, N, B))
+            if self._map_pose_ws is None or self._map_pose_ws.numel() < nbytes:
+                self._map_pose_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            check(L.mgr_views_maps_backward_pose(*args, 1, ptr(d_T), ptr(self._map_pose_ws), self._map_pose_ws.numel(), stream()),
+                  "mgr_views_maps_backward_pose")
+        else:
+            check(L.mgr_views_maps_backward(*args, stream()), "mgr_views_maps_backward")
         return sums[2] * k, sums[0] * k, sums[1] * k
 
     def _backward(self, ws, fwd, g_img, scale, full_rows=False):
@@ -1153,13 +1168,34 @@ class HipViewCompute:
             check(lib().mgr_skin_weights_bwd(*grid, 1, stream()), "mgr_skin_weights_bwd")
         return active
 
-    def _skin_grid_backward(self, head, xyz, d_w, active):
+    def _d_w_rows(self, d_w):
+        """(list, count) device pointers: the rows of d_w (na,B) that are not all zero, ascending -- the modular route's
+        `(w.grad != 0).any(1)`, formed on the device: a row mask (mgr_skin_rows_mask), then the exchange's ordered index of
+        a mask (mgr_exchange_index).  Deterministic: a scan, no atomics."""
+        na, B = d_w.shape
+        L, dev = lib(), d_w.device
+        r = self._sg_rows
+        if r is None or r["idx"].numel() != na or r["idx"].device != dev:
+            r = self._sg_rows = dict(mask=torch.empty(na, dtype=torch.uint8, device=dev), idx=torch.empty(na, dtype=torch.int32, device=dev),
+                                     count=torch.zeros(1, dtype=torch.int32, device=dev),
+                                     ws=torch.empty(L.mgr_exchange_index_workspace_bytes(na), dtype=torch.uint8, device=dev))
+        check(L.mgr_skin_rows_mask(na, B, ptr(d_w), ptr(r["mask"]), stream()), "mgr_skin_rows_mask")
+        check(L.mgr_exchange_index(na, ptr(r["mask"]), ptr(r["idx"]), ptr(r["count"]), ptr(r["ws"]), r["ws"].numel(), stream()), "mgr_exchange_index")
+        return ptr(r["idx"]), ptr(r["count"])
+
+    def _skin_grid_backward(self, head, xyz, d_w, active, rows_of_d_w=False):
         """Sparse dL/d(grid) from the skin-weight gradient the backward wrote: on the active list up to 8 views (the other
-        rows of d_w are zero), on all articulated rows beyond."""
+        rows of d_w are zero), on all articulated rows beyond.  rows_of_d_w (a map term added rows the active list does not
+        know): up to 8 views, on the list of the rows of the summed d_w that are not all zero -- SkinGridAdam steps every LISTED
+        voxel, so the list must be the modular route's."""
         V, N, _, na = head[:4]
         s = self.s
         lst, cnt = active if active is not None else (None, None)
         self.last_skin_w_grad = d_w
+        if rows_of_d_w and V <= 8 and na:
+            lst, cnt = self._d_w_rows(d_w)
+            return self.ops._skin_grid_grad(na, xyz, self.grid, s["grid_center"], s["grid_scale"], d_w, lst, cnt, na,
+                                            kept=self._sg_kept if self.persistent_grads else None)
         # (outputs and workspace kept across steps like the gradient buffers: "d_skin_grid" is valid until the next step)
         return self.ops._skin_grid_grad(na, xyz, self.grid, s["grid_center"], s["grid_scale"], d_w, lst, cnt, N if active is not None else na,
                                         kept=self._sg_kept if self.persistent_grads else None)
