@@ -758,6 +758,49 @@ int mgr_map_loss(int V, int H, int W, const float* alpha, const float* mask, con
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * LPIPS: the reference's fourth loss term, lpips.LPIPS(net="vgg") from start_lpips_iter on (base.py:333-341), and the
+ * LPIPS-AlexNet column of its validation CSV (loss_utils.py:111-117).  csrc/lpips.hip; convolutions on the fp32 matrix pipe.
+ *
+ *   x' = x mask (optional)   x'' = 2 x' - 1 (normalize != 0; the reference never passes it)   in = (x'' - shift) / scale
+ *   f_k: the five taps of the frozen backbone (net 0: VGG16 relu1_2, 2_2, 3_3, 4_3, 5_3; net 1: AlexNet's five ReLUs)
+ *   fh = f / (sqrt(sum_c f^2) + 1e-10)   s_k = mean_hw sum_c lin_k[c] (fh0 - fh1)^2   values[v] = sum_k s_k
+ * One deviation from autograd: a pixel whose tap features are all zero contributes a zero gradient (autograd: 0 * inf = NaN),
+ * the skip rule of a zero skin-weight sum above.
+ *
+ * Weights are user-supplied and frozen (no weight gradient): mgr_lpips_net_pack lays them out once into a caller-owned blob of
+ * mgr_lpips_net_bytes(net) bytes.  conv_w / conv_b / lin_w are HOST arrays of DEVICE pointers in layer order (13 or 5
+ * convolutions in torch's [Cout][Cin][KH][KW] layout, their biases, the 5 lin vectors of C_k floats).
+ *
+ * mgr_lpips: value and gradient in one pass, like mgr_map_loss.  pred / target (V,3,H,W), mask (V,H,W) or NULL (multiplies BOTH
+ * images), values (V).  dL_dpred (V,3,H,W) or NULL: the gradient of grad_scale * sum_v values[v] w.r.t. pred, written
+ * (accumulate = 0) or added to what is there (accumulate = 1); net 0 only.  Views run one after another on a workspace sized
+ * for one view (mgr_lpips_workspace_bytes; contents need not be initialised).  Spatial means are fp64 over a fixed tree, there
+ * are no float atomics: results are bit-reproducible, and V views equal V calls of one view bit for bit.
+ *
+ * mgr_lpips_layout: byte offsets into the workspace of, in order, pred's convolution outputs (post-ReLU; 13 / 5), the target's
+ * five taps, the two scratch buffers, the fp64 partials, and the total: n_conv + 9 entries; returns that count.  All are (C,h,w)
+ * fp32 of the LAST view of a call.
+ *
+ * Refused on the host, before any launch (-1 and mgr_last_error): net not 0 / 1, sizes at which the deepest tap has no pixel
+ * (or above 2^24 pixels), null pointers, blob_bytes != mgr_lpips_net_bytes, workspace too small (-2), net 1 with dL_dpred. */
+size_t mgr_lpips_net_bytes(int net);
+int mgr_lpips_net_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* blob,
+                       size_t blob_bytes, void* stream);
+size_t mgr_lpips_workspace_bytes(int net, int H, int W, int need_grad);
+int mgr_lpips_layout(int net, int H, int W, int need_grad, size_t* offsets, int n);
+int mgr_lpips(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob,
+              size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
+              void* workspace, size_t workspace_bytes, void* stream);
+/* One convolution of the LPIPS backbones on its own (tests, tools/measure_lpips.py; loss_utils.py:111-117 runs them inside the
+ * package): y = [relu](conv(x [gate > 0], w) + bias), w in torch's layout, packed into `scratch` (mgr_lpips_conv_scratch_bytes)
+ * on every call.  transposed != 0 runs the layer's data gradient instead: x and gate have Cout channels, y gets Cin (stride 1,
+ * 2 pad = K - 1, no bias).  Square kernels only. */
+size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW);
+int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                   const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
+                   void* stream);
+
+/* ------------------------------------------------------------------------
  * Device frame store: the stored uint8 RGBA crops of a capture decoded into the float targets and masks of a step
  * (manus_amd/frames.py; SequenceDataset.fetch_images, brics_dynamic.py:343-373, restated bit for bit).
  *

@@ -143,6 +143,13 @@ SIGNATURES = {
                                             c_vp]),
     "mgr_map_loss_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_map_loss": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_lpips_net_bytes": (c_sz, [c_int]),
+    "mgr_lpips_net_pack": (c_int, [c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_sz, c_vp]),
+    "mgr_lpips_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "mgr_lpips_layout": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_sz), c_int]),
+    "mgr_lpips": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_int, c_f32, c_vp, c_vp, c_int, c_vp, c_sz, c_vp]),
+    "mgr_lpips_conv_scratch_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "mgr_lpips_conv": (c_int, [c_int] * 8 + [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
     "mgr_frames_decode": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_i64, ctypes.POINTER(MgrFrameView), c_vp, c_vp, c_i64, c_vp]),
     "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

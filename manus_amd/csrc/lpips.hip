@@ -1,0 +1,702 @@
+// LPIPS (learned perceptual image patch similarity): the fourth term of the reference's hand loss (lpips.LPIPS(net="vgg"),
+// src/modules/base.py:333-341) and the LPIPS-AlexNet column of its validation CSV (src/utils/loss_utils.py:111-117), value and
+// gradient w.r.t. the first image in one call (mgr_lpips).
+//
+//   x' = x * mask (optional)        x'' = 2 x' - 1 (normalize)        in = (x'' - shift) / scale
+//   f_k = tap k of the frozen backbone (VGG16: relu1_2 .. relu5_3; AlexNet: its five ReLUs)
+//   fh  = f / (sqrt(sum_c f^2) + 1e-10)        s_k = mean_hw sum_c lin_k[c] (fh0 - fh1)^2        d = sum_k s_k
+//
+// k_lp_conv: implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.  Output channels are the accumulator rows, 32 pixels along x
+// the lanes' columns: A = packed weights [k][cout] (k = (ci, ky, kx)), B = the input patch.  A workgroup of four waves takes 64
+// output channels x 4 rows x 32 columns; wave w owns row w and two 32x32 accumulators.  Per chunk of input channels the halo
+// patch and the weight rows are staged in LDS once and reused by all KH KW taps.  The f32-input MFMA is bit for bit a k-ordered
+// fmaf chain: a chunk's sum is that chain from zero, and the chunk sums are added to the bias in chunk order, so an output
+// depends on the sizes alone, never on scheduling.  KH, KW, stride, pad, Cin, Cout, H, W are run-time
+// arguments (tile edges masked); K3 = true fixes 3x3 stride 1 pad 1 at compile time.  `gate` (same shape as the input) zeroes
+// the staged input where gate <= 0: the data gradient dX = conv(dY * [y > 0], W') runs on the same kernel with the flipped,
+// transposed weights W' that mgr_lpips_net_pack prepares.  The weights are frozen: there is no weight gradient.
+//
+// Spatial means travel as fp64 partials over a fixed tree (as k_map_loss does); no float atomics anywhere: bit-reproducible.
+//
+// One deviation from autograd: where a pixel's tap features are all zero, autograd through sqrt yields 0 * inf = NaN; here
+// that pixel contributes a zero gradient (the skip rule of a zero skin-weight sum, include/manus_hip.h).
+#include "mgr_common.h"
+
+typedef float lp_f16v __attribute__((ext_vector_type(16)));
+
+#define LP_T 256           // threads of every kernel of this file
+#define LP_TW 32           // output columns per workgroup of k_lp_conv (the MFMA's columns)
+#define LP_TH 4            // output rows per workgroup (one per wave)
+#define LP_TC 64           // output channels per workgroup (two MFMA row blocks)
+#define LP_LDS_BUDGET (64 * 1024)
+#define LP_MAX_CK 8
+#define LP_NTAP 5
+#define LP_MAX_OPS 20
+
+// ---------------------------------------------------------------------------
+// the two networks, as a host table
+// ---------------------------------------------------------------------------
+struct LpOp {
+    int conv;                 // 1: convolution + ReLU, 0: max-pool
+    int cin, cout, k, s, p;
+    int tap;                  // index of the tap this convolution's output is, or -1
+};
+
+static const LpOp LP_VGG[] = {
+    {1, 3, 64, 3, 1, 1, -1},    {1, 64, 64, 3, 1, 1, 0},    {0, 64, 64, 2, 2, 0, -1},   {1, 64, 128, 3, 1, 1, -1},
+    {1, 128, 128, 3, 1, 1, 1},  {0, 128, 128, 2, 2, 0, -1}, {1, 128, 256, 3, 1, 1, -1}, {1, 256, 256, 3, 1, 1, -1},
+    {1, 256, 256, 3, 1, 1, 2},  {0, 256, 256, 2, 2, 0, -1}, {1, 256, 512, 3, 1, 1, -1}, {1, 512, 512, 3, 1, 1, -1},
+    {1, 512, 512, 3, 1, 1, 3},  {0, 512, 512, 2, 2, 0, -1}, {1, 512, 512, 3, 1, 1, -1}, {1, 512, 512, 3, 1, 1, -1},
+    {1, 512, 512, 3, 1, 1, 4}};
+static const LpOp LP_ALEX[] = {{1, 3, 64, 11, 4, 2, 0},   {0, 64, 64, 3, 2, 0, -1},  {1, 64, 192, 5, 1, 2, 1}, {0, 192, 192, 3, 2, 0, -1},
+                               {1, 192, 384, 3, 1, 1, 2}, {1, 384, 256, 3, 1, 1, 3}, {1, 256, 256, 3, 1, 1, 4}};
+
+struct LpNet {
+    const LpOp* ops;
+    int n_ops, n_conv;
+    bool has_bwd;
+};
+
+static bool lp_net(int net, LpNet* n) {
+    if (net == 0) {
+        *n = {LP_VGG, (int)(sizeof(LP_VGG) / sizeof(LpOp)), 13, true};
+        return true;
+    }
+    if (net == 1) {
+        *n = {LP_ALEX, (int)(sizeof(LP_ALEX) / sizeof(LpOp)), 5, false};
+        return true;
+    }
+    return false;
+}
+
+static inline size_t lp_pad64(size_t c) { return (c + 63) & ~(size_t)63; }
+
+// the packed blob: per convolution [K][pad64(Cout)] forward weights, [pad64(Cout)] bias, (VGG) [Cout KH KW][pad64(Cin)] data-gradient
+// weights; then the five lin vectors
+struct LpBlob {
+    size_t w[13], b[13], wt[13], lin[LP_NTAP], total;
+};
+
+static LpBlob lp_blob(const LpNet& n) {
+    LpBlob B;
+    size_t o = 0;
+    int ci = 0;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (!op.conv) continue;
+        const size_t kk = (size_t)op.k * op.k;
+        B.w[ci] = o;  o += mgr_align((size_t)op.cin * kk * lp_pad64(op.cout) * 4);
+        B.b[ci] = o;  o += mgr_align(lp_pad64(op.cout) * 4);
+        B.wt[ci] = o;
+        if (n.has_bwd) o += mgr_align((size_t)op.cout * kk * lp_pad64(op.cin) * 4);
+        if (op.tap >= 0) { B.lin[op.tap] = o;  o += mgr_align((size_t)op.cout * 4); }
+        ++ci;
+    }
+    B.total = o;
+    return B;
+}
+
+// sizes of every op's output; false where some output has no pixel
+struct LpShape {
+    int h[LP_MAX_OPS], w[LP_MAX_OPS];
+};
+
+static bool lp_shapes(const LpNet& n, int H, int W, LpShape* S) {
+    int h = H, w = W;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (h + 2 * op.p < op.k || w + 2 * op.p < op.k) return false;
+        h = (h + 2 * op.p - op.k) / op.s + 1;
+        w = (w + 2 * op.p - op.k) / op.s + 1;
+        if (h < 1 || w < 1) return false;
+        S->h[i] = h;
+        S->w[i] = w;
+    }
+    return true;
+}
+
+// workspace: [pred's convolution outputs, in layer order][target's five taps][scratch A][scratch B][fp64 partials]
+struct LpLayout {
+    size_t act[13], tap[LP_NTAP], bufa, bufb, part, total;
+    size_t part_off[LP_NTAP + 1];      // in doubles: the slots of tap k are [part_off[k], part_off[k + 1])
+};
+
+static bool lp_layout(const LpNet& n, int H, int W, int need_grad, LpLayout* L) {
+    LpShape S;
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 24) || !lp_shapes(n, H, W, &S)) return false;
+    size_t o = 0, scratch = (size_t)3 * H * W;
+    int ci = 0;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        const size_t e = (size_t)op.cout * S.h[i] * S.w[i];
+        // scratch holds: the scaled image, every pool output, the target's convolution outputs that are no tap, and (with a
+        // gradient) the gradient w.r.t. any of them
+        if (!op.conv || op.tap < 0 || need_grad) scratch = scratch > e ? scratch : e;
+        if (op.conv) { L->act[ci++] = o;  o += mgr_align(e * 4); }
+    }
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (op.conv && op.tap >= 0) {
+            L->tap[op.tap] = o;  o += mgr_align((size_t)op.cout * S.h[i] * S.w[i] * 4);
+            L->part_off[op.tap + 1] = ((size_t)S.h[i] * S.w[i] + LP_T - 1) / LP_T;
+        }
+    }
+    L->part_off[0] = 0;
+    for (int k = 0; k < LP_NTAP; ++k) L->part_off[k + 1] += L->part_off[k];
+    L->bufa = o;  o += mgr_align(scratch * 4);
+    L->bufb = o;  o += mgr_align(scratch * 4);
+    L->part = o;  o += mgr_align(L->part_off[LP_NTAP] * 8);
+    L->total = o;
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// weight packing
+// ---------------------------------------------------------------------------
+// w: torch's [Cout][Cin][KH][KW].  fwd[(ci KK + t) CoP + co] = w[co][ci][t]; bwd[(co KK + (KK - 1 - t)) CiP + ci] = w[co][ci][t]
+// (the 180-degree flip of a square kernel is t -> KK - 1 - t); the padding columns are zero.
+__global__ __launch_bounds__(LP_T) void k_lp_pack(int Cout, int Cin, int KK, int CoP, int CiP, const float* __restrict__ w,
+                                                  const float* __restrict__ bias, float* __restrict__ fwd, float* __restrict__ bp,
+                                                  float* __restrict__ bwd) {
+    const size_t nf = (size_t)Cin * KK * CoP, nb = bwd ? (size_t)Cout * KK * CiP : 0;
+    const size_t stride = (size_t)gridDim.x * LP_T;
+    for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < nf; e += stride) {
+        const int co = (int)(e % CoP);
+        const size_t r = e / CoP;      // ci KK + t
+        fwd[e] = co < Cout ? w[(size_t)co * Cin * KK + r] : 0.f;
+    }
+    for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < nb; e += stride) {
+        const int ci = (int)(e % CiP);
+        const size_t r = e / CiP;
+        const int co = (int)(r / KK), t = KK - 1 - (int)(r % KK);
+        bwd[e] = ci < Cin ? w[((size_t)co * Cin + ci) * KK + t] : 0.f;
+    }
+    for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < (size_t)CoP; e += stride) bp[e] = e < (size_t)Cout ? bias[e] : 0.f;
+}
+
+__global__ __launch_bounds__(LP_T) void k_lp_copy(int n, const float* __restrict__ src, float* __restrict__ dst) {
+    const int e = blockIdx.x * LP_T + threadIdx.x;
+    if (e < n) dst[e] = src[e];
+}
+
+// ---------------------------------------------------------------------------
+// convolution
+// ---------------------------------------------------------------------------
+struct LpConvArgs {
+    int Cin, Cout, CoP, H, W, Ho, Wo, KH, KW, stride, pad, CK, relu;
+    const float *x, *gate, *wp, *bias;
+    float* y;
+};
+
+template <bool K3>
+__global__ __launch_bounds__(LP_T) void k_lp_conv(const LpConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lp_smem[];
+    const int KH = K3 ? 3 : a.KH, KW = K3 ? 3 : a.KW, st = K3 ? 1 : a.stride, pad = K3 ? 1 : a.pad;
+    const int KK = KH * KW;
+    const int PH = (LP_TH - 1) * st + KH, PW = (LP_TW - 1) * st + KW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+    const int ox0 = blockIdx.x * LP_TW, oy0 = blockIdx.y * LP_TH, co0 = blockIdx.z * LP_TC;
+    const int ix0 = ox0 * st - pad, iy0 = oy0 * st - pad;
+    const bool two = a.Cout - co0 > 32;           // the second block of 32 output channels holds any (workgroup-uniform)
+    float* sW = lp_smem;                                     // [2 ceil(CK KK / 2)][64]
+    float* sX = lp_smem + (size_t)((a.CK * KK + 1) & ~1) * LP_TC;      // [CK][PH][PW]
+
+    lp_f16v acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        acc0[r] = a.bias ? a.bias[co0 + row] : 0.f;
+        acc1[r] = a.bias ? a.bias[co0 + 32 + row] : 0.f;       // (the bias is padded to CoP, a multiple of 64)
+    }
+
+    for (int ci0 = 0; ci0 < a.Cin; ci0 += a.CK) {
+        const int ckn = min(a.CK, a.Cin - ci0), Kc = ckn * KK, Kce = (Kc + 1) & ~1;
+        // the weight rows of this chunk, [k][64 output channels]; an odd tail row is zero
+        for (int e = tid; e < Kce * LP_TC; e += LP_T) {
+            const int kk = e >> 6, c = e & 63;
+            sW[e] = kk < Kc ? a.wp[((size_t)ci0 * KK + kk) * a.CoP + co0 + c] : 0.f;
+        }
+        // the halo patch, zero outside the image and where the gate is not positive
+        const int pn = ckn * PH * PW;
+        for (int e = tid; e < pn; e += LP_T) {
+            const int px = e % PW, q = e / PW, py = q % PH, ci = q / PH;
+            const int ix = ix0 + px, iy = iy0 + py;
+            float v = 0.f;
+            if (ix >= 0 && ix < a.W && iy >= 0 && iy < a.H) {
+                const size_t g = ((size_t)(ci0 + ci) * a.H + iy) * a.W + ix;
+                v = a.x[g];
+                if (a.gate && !(a.gate[g] > 0.f)) v = 0.f;
+            }
+            sX[e] = v;
+        }
+        __syncthreads();
+        // lanes 0-31 take k = 2 j, lanes 32-63 k = 2 j + 1; (ci, ky, kx) advance by two taps per step
+        int kx = half, ky = 0, ci = 0;
+        while (kx >= KW) { kx -= KW; ++ky; }
+        while (ky >= KH) { ky -= KH; ++ci; }
+        const float* xrow = sX + (wave * st) * PW + col * st;
+        // the chunk's own sum starts at zero and is added to the total once: a blocked sum, whose rounding error grows with
+        // the chunk length plus the number of chunks instead of with Cin KH KW (4608 terms in VGG's deepest layers)
+        lp_f16v c0, c1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c0[r] = c1[r] = 0.f;
+        for (int kk = half; kk < Kce; kk += 2) {
+            const float b = ci < ckn ? xrow[(ci * PH + ky) * PW + kx] : 0.f;
+            const float w0 = sW[kk * LP_TC + col];
+            c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w0, b, c0, 0, 0, 0);
+            if (two) {
+                const float w1 = sW[kk * LP_TC + 32 + col];
+                c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1, b, c1, 0, 0, 0);
+            }
+            kx += 2;
+            while (kx >= KW) { kx -= KW; ++ky; }
+            while (ky >= KH) { ky -= KH; ++ci; }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc0[r] += c0[r];
+            acc1[r] += c1[r];
+        }
+        __syncthreads();
+    }
+
+    const int ox = ox0 + col, oy = oy0 + wave;
+    if (ox < a.Wo && oy < a.Ho) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int c0 = co0 + row, c1 = c0 + 32;
+            float v0 = acc0[r], v1 = acc1[r];
+            if (a.relu) {
+                v0 = v0 < 0.f ? 0.f : v0;
+                v1 = v1 < 0.f ? 0.f : v1;
+            }
+            if (c0 < a.Cout) a.y[((size_t)c0 * a.Ho + oy) * a.Wo + ox] = v0;
+            if (two && c1 < a.Cout) a.y[((size_t)c1 * a.Ho + oy) * a.Wo + ox] = v1;
+        }
+    }
+}
+
+static int lp_conv_ck(int Cin, int KH, int KW, int stride, size_t* lds) {
+    const size_t PH = (size_t)(LP_TH - 1) * stride + KH, PW = (size_t)(LP_TW - 1) * stride + KW, KK = (size_t)KH * KW;
+    int ck = Cin < LP_MAX_CK ? Cin : LP_MAX_CK;
+    for (;; --ck) {
+        *lds = ((((size_t)ck * KK + 1) & ~(size_t)1) * LP_TC + (size_t)ck * PH * PW) * 4;
+        if (*lds <= LP_LDS_BUDGET || ck == 1) break;
+    }
+    return ck;
+}
+
+// y (Cout, Ho, Wo) = [relu](conv(x * [gate > 0], w) + bias); wp: [Cin KH KW][CoP] packed, bias: [CoP] or null
+static int lp_conv(hipStream_t stream, const char* name, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
+                   const float* x, const float* gate, const float* wp, const float* bias, int relu, float* y) {
+    LpConvArgs a;
+    a.Cin = Cin; a.Cout = Cout; a.CoP = (int)lp_pad64(Cout); a.H = H; a.W = W;
+    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.relu = relu;
+    a.x = x; a.gate = gate; a.wp = wp; a.bias = bias; a.y = y;
+    size_t lds;
+    a.CK = lp_conv_ck(Cin, KH, KW, stride, &lds);
+    if (lds > 150 * 1024) return mgr_fail(MGR_EINVAL, "k_lp_conv: kernel window too large for LDS");
+    const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (Cout + LP_TC - 1) / LP_TC);
+    if (grid.y > 65535u || grid.z > 65535u) return mgr_fail(MGR_EINVAL, "k_lp_conv: image too large");
+    MGR_PROF(name, stream);
+    if (KH == 3 && KW == 3 && stride == 1 && pad == 1) {
+        hipLaunchKernelGGL(k_lp_conv<true>, grid, dim3(LP_T), lds, stream, a);
+    } else {
+        if (lds > 64 * 1024) {
+            static bool raised = false;
+            if (!raised) {
+                MGR_HIP(hipFuncSetAttribute((const void*)k_lp_conv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                raised = true;
+            }
+        }
+        hipLaunchKernelGGL(k_lp_conv<false>, grid, dim3(LP_T), lds, stream, a);
+    }
+    MGR_LAUNCH_CHECK(name, stream, 0);
+    return MGR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// scaling layer, pools
+// ---------------------------------------------------------------------------
+__constant__ float LP_SHIFT[3] = {-0.030f, -0.088f, -0.188f};
+__constant__ float LP_SCALE[3] = {0.458f, 0.448f, 0.450f};
+
+// out (3, H, W) = ((x * mask) [* 2 - 1] - shift) / scale
+__global__ __launch_bounds__(LP_T) void k_lp_scale(int HW, const float* __restrict__ x, const float* __restrict__ mask, int normalize,
+                                                   float* __restrict__ out) {
+    const int p = blockIdx.x * LP_T + threadIdx.x;
+    if (p >= HW) return;
+    const float m = mask ? mask[p] : 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = x[(size_t)c * HW + p];
+        if (mask) v *= m;
+        if (normalize) v = 2.f * v - 1.f;
+        out[(size_t)c * HW + p] = (v - LP_SHIFT[c]) / LP_SCALE[c];
+    }
+}
+
+// dL/dx = g / scale [* 2] [* mask], written or added
+__global__ __launch_bounds__(LP_T) void k_lp_scale_bwd(int HW, const float* __restrict__ g, const float* __restrict__ mask, int normalize,
+                                                       int accumulate, float* __restrict__ dx) {
+    const int p = blockIdx.x * LP_T + threadIdx.x;
+    if (p >= HW) return;
+    const float m = mask ? mask[p] : 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = g[(size_t)c * HW + p] / LP_SCALE[c];
+        if (normalize) v *= 2.f;
+        if (mask) v *= m;
+        const size_t e = (size_t)c * HW + p;
+        dx[e] = accumulate ? dx[e] + v : v;
+    }
+}
+
+// max-pool k x k stride 2 (floor): the FIRST maximum in row-major window order, as torch
+__global__ __launch_bounds__(LP_T) void k_lp_pool(int C, int H, int W, int Ho, int Wo, int k, const float* __restrict__ x,
+                                                  float* __restrict__ y) {
+    const size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x;
+    if (e >= (size_t)C * Ho * Wo) return;
+    const int ox = (int)(e % Wo), oy = (int)((e / Wo) % Ho);
+    const size_t c = e / ((size_t)Wo * Ho);
+    const float* src = x + (c * H + 2 * oy) * W + 2 * ox;
+    float m = src[0];
+    for (int dy = 0; dy < k; ++dy)
+        for (int dx = 0; dx < k; ++dx) {
+            const float v = src[dy * W + dx];
+            if (v > m) m = v;
+        }
+    y[e] = m;
+}
+
+// 2 x 2 stride 2 backward: one thread per INPUT element; the winner is recomputed from the stored input
+__global__ __launch_bounds__(LP_T) void k_lp_pool2_bwd(int C, int H, int W, int Ho, int Wo, const float* __restrict__ x,
+                                                       const float* __restrict__ gy, float* __restrict__ gx) {
+    const size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x;
+    if (e >= (size_t)C * H * W) return;
+    const int ix = (int)(e % W), iy = (int)((e / W) % H);
+    const size_t c = e / ((size_t)W * H);
+    const int ox = ix >> 1, oy = iy >> 1;
+    float g = 0.f;
+    if (ox < Wo && oy < Ho) {
+        const float* src = x + (c * H + 2 * oy) * W + 2 * ox;
+        float m = src[0];
+        int win = 0;
+        if (src[1] > m) { m = src[1]; win = 1; }
+        if (src[W] > m) { m = src[W]; win = 2; }
+        if (src[W + 1] > m) { m = src[W + 1]; win = 3; }
+        if (win == ((iy & 1) << 1 | (ix & 1))) g = gy[(c * Ho + oy) * Wo + ox];
+    }
+    gx[e] = g;
+}
+
+// ---------------------------------------------------------------------------
+// head
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double lp_block_sum(double a, double* s_red, int tid) {
+    s_red[tid] = a;
+    __syncthreads();
+#pragma unroll
+    for (int h = LP_T / 2; h > 0; h >>= 1) {
+        if (tid < h) s_red[tid] += s_red[tid + h];
+        __syncthreads();
+    }
+    return s_red[0];
+}
+
+// one thread per pixel of a tap: sum_c lin[c] (f0 / n0 - f1 / n1)^2 into the workgroup's fp64 partial; with g: the gradient of
+// gs * (that sum) w.r.t. f0, written (add = 0) or added (add = 1).  A pixel whose f0 is all zero contributes no gradient.
+__global__ __launch_bounds__(LP_T) void k_lp_head(int C, int HW, const float* __restrict__ f0, const float* __restrict__ f1,
+                                                  const float* __restrict__ lin, float gs, float* __restrict__ g, int add,
+                                                  double* __restrict__ part) {
+    __shared__ double s_red[LP_T];
+    const int tid = threadIdx.x, p = blockIdx.x * LP_T + tid;
+    double val = 0.0;
+    if (p < HW) {
+        float s0 = 0.f, s1 = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float a = f0[(size_t)c * HW + p], b = f1[(size_t)c * HW + p];
+            s0 = fmaf(a, a, s0);
+            s1 = fmaf(b, b, s1);
+        }
+        const float r0 = sqrtf(s0), n0 = r0 + 1e-10f, n1 = sqrtf(s1) + 1e-10f;
+        float v = 0.f, dot = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float a = f0[(size_t)c * HW + p], b = f1[(size_t)c * HW + p];
+            const float d = a / n0 - b / n1, l = lin[c];
+            v = fmaf(l, d * d, v);
+            dot = fmaf(2.f * l * d, a, dot);
+        }
+        val = (double)v;
+        if (g) {
+            // u = f0 / n0, n0 = r0 + eps: dL/df0[c] = gu[c] / n0 - (sum_c' gu[c'] f0[c']) f0[c] / (n0^2 r0), gu = 2 gs lin (u - v)
+            const float k2 = r0 > 0.f ? dot / (n0 * n0 * r0) : 0.f;
+            for (int c = 0; c < C; ++c) {
+                const size_t e = (size_t)c * HW + p;
+                const float a = f0[e], b = f1[e];
+                const float d = a / n0 - b / n1;
+                const float t = r0 > 0.f ? gs * (2.f * lin[c] * d / n0 - k2 * a) : 0.f;
+                g[e] = add ? g[e] + t : t;
+            }
+        }
+    }
+    const double tot = lp_block_sum(val, s_red, tid);
+    if (tid == 0) part[blockIdx.x] = tot;
+}
+
+struct LpFoldArgs {
+    int off[LP_NTAP + 1];
+    double inv[LP_NTAP];
+};
+
+// values[v] = sum_k (sum of tap k's partials) / (H_k W_k): thread t adds slots t, t + 256, ... in ascending order, fixed tree
+__global__ __launch_bounds__(LP_T) void k_lp_fold(const LpFoldArgs a, const double* __restrict__ part, float* __restrict__ value) {
+    __shared__ double s_red[LP_T];
+    const int tid = threadIdx.x;
+    double d = 0.0;
+    for (int k = 0; k < LP_NTAP; ++k) {
+        double s = 0.0;
+        for (int i = a.off[k] + tid; i < a.off[k + 1]; i += LP_T) s += part[i];
+        const double tot = lp_block_sum(s, s_red, tid);
+        __syncthreads();
+        d += tot * a.inv[k];
+    }
+    if (tid == 0) *value = (float)d;
+}
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+extern "C" size_t mgr_lpips_net_bytes(int net) {
+    LpNet n;
+    if (!lp_net(net, &n)) return 0;
+    return lp_blob(n).total;
+}
+
+extern "C" int mgr_lpips_net_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* blob,
+                                  size_t blob_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LpNet n;
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: net must be 0 (vgg) or 1 (alex)");
+    if (!conv_w || !conv_b || !lin_w || !blob) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: null pointer");
+    const LpBlob B = lp_blob(n);
+    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: blob_bytes is not mgr_lpips_net_bytes(net)");
+    for (int i = 0; i < n.n_conv; ++i)
+        if (!conv_w[i] || !conv_b[i]) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: null weight or bias pointer");
+    for (int k = 0; k < LP_NTAP; ++k)
+        if (!lin_w[k]) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: null lin pointer");
+    char* base = (char*)blob;
+    int ci = 0;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (!op.conv) continue;
+        const int KK = op.k * op.k, CoP = (int)lp_pad64(op.cout), CiP = (int)lp_pad64(op.cin);
+        const size_t nf = (size_t)op.cin * KK * CoP;
+        const unsigned nb = (unsigned)((nf + LP_T - 1) / LP_T < 4096 ? (nf + LP_T - 1) / LP_T : 4096);
+        hipLaunchKernelGGL(k_lp_pack, dim3(nb), dim3(LP_T), 0, stream, op.cout, op.cin, KK, CoP, CiP, conv_w[ci], conv_b[ci],
+                           (float*)(base + B.w[ci]), (float*)(base + B.b[ci]), n.has_bwd ? (float*)(base + B.wt[ci]) : (float*)nullptr);
+        MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
+        if (op.tap >= 0) {
+            hipLaunchKernelGGL(k_lp_copy, dim3((op.cout + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, op.cout, lin_w[op.tap],
+                               (float*)(base + B.lin[op.tap]));
+            MGR_LAUNCH_CHECK("k_lp_copy", stream, 0);
+        }
+        ++ci;
+    }
+    return MGR_OK;
+}
+
+extern "C" size_t mgr_lpips_workspace_bytes(int net, int H, int W, int need_grad) {
+    LpNet n;
+    LpLayout L;
+    if (!lp_net(net, &n) || !lp_layout(n, H, W, need_grad, &L)) return 0;
+    return L.total;
+}
+
+extern "C" int mgr_lpips_layout(int net, int H, int W, int need_grad, size_t* offsets, int n_off) {
+    LpNet n;
+    LpLayout L;
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: net must be 0 (vgg) or 1 (alex)");
+    if (!lp_layout(n, H, W, need_grad, &L)) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: image too small for the deepest tap (or too large)");
+    const int need = n.n_conv + LP_NTAP + 4;
+    if (!offsets || n_off < need) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: offsets holds fewer than n_conv + 9 entries");
+    int j = 0;
+    for (int i = 0; i < n.n_conv; ++i) offsets[j++] = L.act[i];
+    for (int k = 0; k < LP_NTAP; ++k) offsets[j++] = L.tap[k];
+    offsets[j++] = L.bufa;
+    offsets[j++] = L.bufb;
+    offsets[j++] = L.part;
+    offsets[j++] = L.total;
+    return need;
+}
+
+extern "C" int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                              const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
+                              void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || KH != KW || stride < 1 || pad < 0 || H + 2 * pad < KH || W + 2 * pad < KW)
+        return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: bad sizes");
+    if (!x || !w || !y || !scratch) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: null pointer");
+    if (transposed && (stride != 1 || 2 * pad != KH - 1)) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: the data gradient needs stride 1 and a same-size pad");
+    if (transposed && bias) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: the data gradient takes no bias");
+    const int KK = KH * KW, CoP = (int)lp_pad64(Cout), CiP = (int)lp_pad64(Cin);
+    // scratch: [forward pack][bias pack][data-gradient pack]
+    const size_t o_f = 0, o_b = mgr_align((size_t)Cin * KK * CoP * 4), o_t = o_b + mgr_align((size_t)CoP * 4),
+                 tot = o_t + mgr_align((size_t)Cout * KK * CiP * 4);
+    if (scratch_bytes < tot) return mgr_fail(MGR_ENOMEM, "mgr_lpips_conv: scratch too small");
+    char* base = (char*)scratch;
+    // w is [Cout][Cin][KH][KW]; transposed: the layer is used backwards, x has Cout channels and y gets Cin
+    const float* bsrc = bias ? bias : w;        // (k_lp_pack reads Cout values; unused where bias is null)
+    hipLaunchKernelGGL(k_lp_pack, dim3(256), dim3(LP_T), 0, stream, Cout, Cin, KK, CoP, CiP, w, bsrc, (float*)(base + o_f),
+                       (float*)(base + o_b), (float*)(base + o_t));
+    MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
+    if (transposed)
+        return lp_conv(stream, "k_lp_conv_bwd", Cout, Cin, H, W, KH, KW, 1, pad, x, gate, (const float*)(base + o_t), nullptr, relu, y);
+    return lp_conv(stream, "k_lp_conv", Cin, Cout, H, W, KH, KW, stride, pad, x, gate, (const float*)(base + o_f),
+                   bias ? (const float*)(base + o_b) : nullptr, relu, y);
+}
+
+extern "C" size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW) {
+    if (Cin < 1 || Cout < 1 || KH < 1 || KW < 1) return 0;
+    const size_t KK = (size_t)KH * KW;
+    return mgr_align((size_t)Cin * KK * lp_pad64(Cout) * 4) + mgr_align(lp_pad64(Cout) * 4) + mgr_align((size_t)Cout * KK * lp_pad64(Cin) * 4);
+}
+
+// forward of one image: scaled image -> sb, then the ops; a convolution writes to its slot of `store` (by convolution index)
+// where that is not null, else to the scratch buffer its input is not in
+static int lp_forward(hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, const LpShape& S, int H, int W,
+                      const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb) {
+    const int HW = H * W;
+    hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, sb);
+    MGR_LAUNCH_CHECK("k_lp_scale", stream, 0);
+    const float* cur = sb;
+    int h = H, w = W, ci = 0;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        float* out;
+        if (op.conv) {
+            out = store[ci] ? store[ci] : (cur == sa ? sb : sa);
+            const int rc = lp_conv(stream, "k_lp_conv", op.cin, op.cout, h, w, op.k, op.k, op.s, op.p, cur, nullptr,
+                                   (const float*)(blob + B.w[ci]), (const float*)(blob + B.b[ci]), 1, out);
+            if (rc != MGR_OK) return rc;
+            ++ci;
+        } else {
+            out = cur == sa ? sb : sa;
+            const size_t ne = (size_t)op.cout * S.h[i] * S.w[i];
+            hipLaunchKernelGGL(k_lp_pool, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, op.cout, h, w, S.h[i], S.w[i],
+                               op.k, cur, out);
+            MGR_LAUNCH_CHECK("k_lp_pool", stream, 0);
+        }
+        cur = out;
+        h = S.h[i];
+        w = S.w[i];
+    }
+    return MGR_OK;
+}
+
+extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob_,
+                         size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LpNet n;
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips: net must be 0 (vgg) or 1 (alex)");
+    if (V <= 0 || H <= 0 || W <= 0) return mgr_fail(MGR_EINVAL, "mgr_lpips: bad sizes");
+    if (!pred || !target || !blob_ || !values || !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips: null pointer");
+    if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "mgr_lpips: the AlexNet network is forward only (dL_dpred must be null)");
+    const int need_grad = dL_dpred != nullptr;
+    LpLayout L;
+    LpShape S;
+    if (!lp_layout(n, H, W, need_grad, &L) || !lp_shapes(n, H, W, &S))
+        return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small for the deepest tap to have one pixel (or above 2^24 pixels)");
+    const LpBlob B = lp_blob(n);
+    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips: blob_bytes is not mgr_lpips_net_bytes(net)");
+    if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_lpips: workspace smaller than mgr_lpips_workspace_bytes");
+    const char* blob = (const char*)blob_;
+    char* ws = (char*)workspace;
+    float *sa = (float*)(ws + L.bufa), *sb = (float*)(ws + L.bufb);
+    double* part = (double*)(ws + L.part);
+    float *act[13], *tgt[13];
+    int tap_conv[LP_NTAP], tap_op[LP_NTAP], conv_op[13];
+    {
+        int ci = 0;
+        for (int i = 0; i < n.n_ops; ++i) {
+            const LpOp& op = n.ops[i];
+            if (!op.conv) continue;
+            act[ci] = (float*)(ws + L.act[ci]);
+            tgt[ci] = op.tap >= 0 ? (float*)(ws + L.tap[op.tap]) : nullptr;
+            if (op.tap >= 0) { tap_conv[op.tap] = ci;  tap_op[op.tap] = i; }
+            conv_op[ci] = i;
+            ++ci;
+        }
+    }
+    LpFoldArgs fa;
+    for (int k = 0; k <= LP_NTAP; ++k) fa.off[k] = (int)L.part_off[k];
+    for (int k = 0; k < LP_NTAP; ++k) fa.inv[k] = 1.0 / ((double)S.h[tap_op[k]] * S.w[tap_op[k]]);
+    const size_t img = (size_t)3 * H * W, px = (size_t)H * W;
+
+    for (int v = 0; v < V; ++v) {
+        const float* mk = mask ? mask + v * px : nullptr;
+        int rc = lp_forward(stream, n, B, blob, S, H, W, target + v * img, mk, normalize, tgt, sa, sb);
+        if (rc != MGR_OK) return rc;
+        rc = lp_forward(stream, n, B, blob, S, H, W, pred + v * img, mk, normalize, act, sa, sb);
+        if (rc != MGR_OK) return rc;
+        if (!need_grad) {
+            MGR_PROF("k_lp_head", stream);
+            for (int k = 0; k < LP_NTAP; ++k) {
+                const int i = tap_op[k], hw = S.h[i] * S.w[i];
+                hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
+                                   (const float*)act[tap_conv[k]], (const float*)tgt[tap_conv[k]], (const float*)(blob + B.lin[k]), 0.f,
+                                   (float*)nullptr, 0, part + L.part_off[k]);
+                MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
+            }
+        } else {
+            // from the deepest tap down: g holds dL/d(post-ReLU output) of the current op
+            float *g = sa, *o = sb;
+            bool have = false;       // g holds a gradient from deeper layers
+            int h_in, w_in;
+            for (int i = n.n_ops - 1; i >= 0; --i) {
+                const LpOp& op = n.ops[i];
+                h_in = i ? S.h[i - 1] : H;
+                w_in = i ? S.w[i - 1] : W;
+                if (op.conv) {
+                    int ci = 0;
+                    for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
+                    if (op.tap >= 0) {
+                        const int hw = S.h[i] * S.w[i], k = op.tap;
+                        const float gs = (float)((double)grad_scale * fa.inv[k]);
+                        MGR_PROF("k_lp_head", stream);
+                        hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, op.cout, hw, (const float*)act[ci],
+                                           (const float*)tgt[ci], (const float*)(blob + B.lin[k]), gs, g, have ? 1 : 0,
+                                           part + L.part_off[k]);
+                        MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
+                        have = true;
+                    }
+                    // dL/d(input) = conv(g * [y > 0], W')
+                    rc = lp_conv(stream, "k_lp_conv_bwd", op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1, op.p, g, act[ci],
+                                 (const float*)(blob + B.wt[ci]), nullptr, 0, o);
+                    if (rc != MGR_OK) return rc;
+                } else {
+                    // the pool's input is the previous convolution's stored output
+                    int ci = -1;
+                    for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
+                    const size_t ne = (size_t)op.cin * h_in * w_in;
+                    MGR_PROF("k_lp_pool2_bwd", stream);
+                    hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, op.cin, h_in, w_in,
+                                       S.h[i], S.w[i], (const float*)act[ci], (const float*)g, o);
+                    MGR_LAUNCH_CHECK("k_lp_pool2_bwd", stream, 0);
+                }
+                float* t = g;  g = o;  o = t;
+            }
+            (void)conv_op;
+            const int HW = H * W;
+            hipLaunchKernelGGL(k_lp_scale_bwd, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, (const float*)g, mk, normalize,
+                               accumulate, dL_dpred + v * img);
+            MGR_LAUNCH_CHECK("k_lp_scale_bwd", stream, 0);
+        }
+        hipLaunchKernelGGL(k_lp_fold, dim3(1), dim3(LP_T), 0, stream, fa, (const double*)part, values + v);
+        MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
+    }
+    return MGR_OK;
+}

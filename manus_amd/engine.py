@@ -210,8 +210,11 @@ class ViewShardedStep:
         dev = out["grad2d"].device
         radii = out["radii"].to(torch.int32)
         if not packed:
-            return dict(grads=out["grads"], grad2d=out["grad2d"], vis=out["vis"], radii=radii, loss=out["loss"],
-                        overflow=out.get("overflow"))
+            res = dict(grads=out["grads"], grad2d=out["grad2d"], vis=out["vis"], radii=radii, loss=out["loss"],
+                       overflow=out.get("overflow"))
+            if "loss_lpips" in out:
+                res["loss_lpips"] = out["loss_lpips"]
+            return res
         if self._store is None or self._store.device != dev:
             self._alloc(dev)
         st, n_g = self._store, N * GRAD_WIDTH
@@ -559,6 +562,14 @@ class HipViewCompute:
     depth_cut (ValueError).  With pose_grad, "d_transforms" includes the map terms (fused: mgr_views_maps_backward_pose adds
     them to the colour backward's); with skin_grid_grad, "d_skin_grid" is formed from the summed skin-weight gradient over its
     non-zero rows (up to 8 views; all rows beyond).  With both weights zero or no mask the step is exactly the step without
+    these arguments.
+
+    LPIPS (`lpips`, `w_lpips`, `lpips_on`; plain attributes): with a VGG `manus_amd.lpips.LPIPS` and a non-zero weight the step
+    adds scale * w_lpips * sum over the views of d(render_v, target_v), the reference's lpips_loss term (base.py:333-341), on the
+    scale of the image loss and the map terms.  Its gradient travels through the image on both routes (mgr_lpips adds it to
+    dL/dimage before the backward), so grad2d / vis see the term, unlike the map terms.  `lpips_on` gates it per step (a Trainer
+    sets it from start_lpips_iter); the output dict gains "loss_lpips" (the unweighted term on that scale) and `last_lpips`
+    holds it (None with the term off).  Off -- no network, weight zero or lpips_on False -- the step is exactly the step without
     these arguments."""
 
     # per-view target maps kept (130 KB per 1080p view)
@@ -567,7 +578,7 @@ class HipViewCompute:
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
                  persistent_grads=True, pose_grad=False, skin_grid_grad=False, mask_targets=None, w_mask=0.0, depth_targets=None,
-                 w_depth=0.0):
+                 w_depth=0.0, lpips=None, w_lpips=0.0):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -586,6 +597,11 @@ class HipViewCompute:
         self._mask_targets = self._depth_targets = None
         self._map_bufs = {}             # fused route: maps, their gradients and the scratch of the map chain, kept across steps
         self.w_mask, self.w_depth = float(w_mask), float(w_depth)
+        # -- LPIPS term (class docstring)
+        if lpips is not None and getattr(lpips, "net", None) != "vgg":
+            raise ValueError("lpips: the training term takes a VGG manus_amd.lpips.LPIPS (the AlexNet network is forward only)")
+        self.lpips, self.w_lpips, self.lpips_on = lpips, float(w_lpips), True
+        self.last_lpips = None
         # -- model
         self.params = {k: v.detach().clone().requires_grad_(True) for k, v in scene["params"].items()}
         N = self.params["_xyz"].shape[0]
@@ -856,6 +872,17 @@ class HipViewCompute:
         k = self.loss_weight * scale / img[0].numel()
         return k, self.w_ssim * self.loss_weight * scale * img.shape[0]
 
+    def _lpips_term(self, img, tgt, scale, g_img):
+        """The LPIPS term of the step: mgr_lpips ADDS the gradient of scale * w_lpips * sum_v d_v to g_img (V,3,H,W) and returns
+        scale * sum_v d_v; None with the term off.  On the fused route g_img is unwritten under empty background tiles (the image
+        loss leaves it so); the backward never reads there, so adding to whatever it holds is harmless."""
+        self.last_lpips = None
+        if self.lpips is None or self.w_lpips == 0.0 or not self.lpips_on:
+            return None
+        vals, _ = self.lpips.values_grad(img.detach(), tgt, need_grad=True, grad_scale=scale * self.w_lpips, out_grad=g_img, accumulate=True)
+        self.last_lpips = vals.sum() * scale
+        return self.last_lpips
+
     def _image_loss(self, img, tgt, scale, tiles=None):
         """(loss value, dL/dimg) of scale * sum over the views of the per-view image loss.  tiles = (bg, device address
         of the tile-list offsets of the forward that rendered img): spans under empty tiles are not read (ops.image_loss_grad)."""
@@ -946,7 +973,9 @@ class HipViewCompute:
                                 sync_check=self.sync_check, defer_fence=True)
             if route != "overlap" and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
+            given = g_img is not None
             loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
+            lp = None if given else self._lpips_term(out, sel["targets"], scale, g_img)
             grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale, full_rows=any(map_on))
             map_out = self._map_chain(ws, head, sel, view_ids, scale, map_on, grads, d_w, d_T) if any(map_on) else None
             active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"], full_rows=any(map_on))
@@ -968,6 +997,9 @@ class HipViewCompute:
         if map_out is not None:
             res["loss"] = loss + map_out[0]
             res["loss_mask"], res["loss_depth"] = map_out[1], map_out[2]
+        if lp is not None:
+            res["loss"] = res["loss"] + self.w_lpips * lp
+            res["loss_lpips"] = lp
         if d_T is not None:
             res["d_transforms"] = d_T
         if d_grid is not None:
@@ -1214,6 +1246,7 @@ class HipViewCompute:
         if any(map_on):
             img, radii, means2D, extras = self.forward_views(view_ids, T=T, maps=(True, map_on[1]))
             loss, g = self._image_loss(img, tgt, scale)
+            lp = self._lpips_term(img, tgt, scale, g)
             masks, depths = self._map_sel(sel, view_ids, map_on[1])
             k = scale * len(view_ids)
             ml, sums = losses.map_loss(extras["alpha"], masks, self.w_mask, extras["depth"] if map_on[1] else None, depths,
@@ -1224,6 +1257,7 @@ class HipViewCompute:
         else:
             img, radii, means2D = self.forward_views(view_ids, T=T)
             loss, g = self._image_loss(img, tgt, scale)
+            lp = self._lpips_term(img, tgt, scale, g)
             img.backward(g)
         vis = radii > 0
         g2 = means2D.grad[..., :2].norm(dim=-1) * (1.0 / scale)
@@ -1232,6 +1266,9 @@ class HipViewCompute:
                    radii=radii.max(dim=0).values, loss=loss)
         if map_out is not None:
             res["loss_mask"], res["loss_depth"] = map_out[1], map_out[2]
+        if lp is not None:
+            res["loss"] = res["loss"] + self.w_lpips * lp
+            res["loss_lpips"] = lp
         if T is not None:
             res["d_transforms"] = T.grad
         if self.skin_grid_grad:
@@ -1309,13 +1346,16 @@ class Trainer:
 
     def __init__(self, compute, n_views, extent, opts=None, spatial_lr_scale=1.0, rank=0, world_size=1, group=None,
                  bg_white=True, kind=None, compact_allreduce=False, sharded_adam=False, view_weights=None, depth_cut=False,
-                 sort_rows=False, persistent_grads=True):
+                 sort_rows=False, persistent_grads=True, start_lpips_iter=1000):
         # sharded_adam (world_size > 1): reduce-scatter of the gradients -> every rank takes the Adam step on the 1/world
         # of the parameter elements it owns -> all-gather of the parameters.  The same bytes on the wire as the
         # all-reduce (which is a reduce-scatter followed by an all-gather), 1/world of the optimizer work per rank.
         # sort_rows: after a densification / pruning has rebuilt the tensors, put the rows in Z-order of their positions
         # (GaussianOptimizer.sort_rows: the same model up to the permutation; every rank computes the same one)
         self.sort_rows = bool(sort_rows)
+        # start_lpips_iter: the LPIPS term of the compute object (if it has a network) is on from this global step
+        # (base.py:334, scripts/train/train_hands.sh:40)
+        self.start_lpips_iter = int(start_lpips_iter)
         # persistent_grads (one rank): the compute object keeps the gradient buffers (HipViewCompute's own default): the
         # tensors in a step's `out["grads"]` are overwritten by the next step -- the optimizer has consumed them by then
         # (see train_step).  False: fresh tensors every step.
@@ -1396,14 +1436,16 @@ class Trainer:
             self.stepper.all_gather_params(self.opt.mflat)
             self.stepper.all_gather_params(self.opt.vflat)
 
-    def validate(self, view_ids, masks=None, validator=None, group=8):
+    def validate(self, view_ids, masks=None, validator=None, group=8, lpips=None):
         """The validation pass over the views `view_ids` of the compute object (validation_step / on_validation_epoch_end,
         src/modules/base.py:112-188): rendered under no_grad with `forward_views` in groups of `group` views (the group
         size of `HipViewCompute.pairs_per_view`), compared with `compute.targets` by `ops.eval_views` / `ops.eval_triptych`
         on the whole group, ONE host synchronisation per group (the read-back of its metrics; the render runs fenced and
         is rendered again with more room should its pairs not have fitted).  masks: (len(view_ids),H,W), possibly fractional, or None
         (ones).  validator: a `validation.Validator` that receives every view (metrics, its share of the group's render
-        time, triptych); the caller brackets the pass with its start() / end(global_step).
+        time, triptych); the caller brackets the pass with its start() / end(global_step).  lpips: a `manus_amd.lpips.LPIPS`
+        (the reference's is AlexNet, loss_utils.py:19): its per-view value on the masked images, render * mask against
+        target * mask, goes to the validator's CSV column and to the result's "lpips" list.
 
         Returns dict(psnr, ssim: per-view lists; psnr_mean, ssim_mean; render_time: seconds from the start of each
         group's render to the end of its last kernel, summed (two events on the stream: the group's host work included,
@@ -1429,7 +1471,7 @@ class Trainer:
         if any(key[1] != n_now for key in self._val_ctx.pool):      # a densification changed N: the old workspaces are of no use
             self._val_ctx.clear()
         saved_cache, saved_stamp = c._cache, c._const_stamp
-        psnrs, ssims, images, render_time = [], [], [], 0.0
+        psnrs, ssims, lps, images, render_time = [], [], [], [], 0.0
         self._rz._CONTEXTS[idx] = self._val_ctx
         try:
             with torch.no_grad():
@@ -1445,7 +1487,10 @@ class Trainer:
                         sq, ss, gmax = ops.eval_views(img, tgt, m)
                         trip = ops.eval_triptych(img, tgt, gmax)
                         n = float(img[0].numel())
-                        both = torch.stack([psnr_from_sums(sq, n), ss / n]).cpu()      # the group's one synchronisation
+                        rows = [psnr_from_sums(sq, n), ss / n]
+                        if lpips is not None:
+                            rows.append(lpips.values_grad(img, tgt, m, need_grad=False)[0])
+                        both = torch.stack(rows).cpu()      # the group's one synchronisation
                         try:
                             self._val_ctx.poll()                # the render's fence (long complete): did its pairs fit?
                             break
@@ -1456,18 +1501,24 @@ class Trainer:
                     render_time += dt
                     psnrs += both[0].tolist()
                     ssims += both[1].tolist()
+                    if lpips is not None:
+                        lps += both[2].tolist()
                     images.append(trip)
                     if validator is not None:
                         host = trip.cpu().numpy()
                         for j in range(len(part)):
-                            validator.add(float(both[0, j]), float(both[1, j]), dt / len(part), host[j])
+                            validator.add(float(both[0, j]), float(both[1, j]), dt / len(part), host[j],
+                                          lpips=float(both[2, j]) if lpips is not None else None)
         finally:
             self._rz._CONTEXTS[idx] = train_ctx
             c._cache, c._const_stamp = saved_cache, saved_stamp
         import numpy as np
-        return dict(psnr=psnrs, ssim=ssims, psnr_mean=float(np.mean(psnrs)) if psnrs else float("nan"),
-                    ssim_mean=float(np.mean(ssims)) if ssims else float("nan"), render_time=render_time,
-                    images=torch.cat(images) if images else None)
+        res = dict(psnr=psnrs, ssim=ssims, psnr_mean=float(np.mean(psnrs)) if psnrs else float("nan"),
+                   ssim_mean=float(np.mean(ssims)) if ssims else float("nan"), render_time=render_time,
+                   images=torch.cat(images) if images else None)
+        if lpips is not None:
+            res["lpips"] = lps
+        return res
 
     def train_step(self, views=None):
         """One optimisation step; returns the step's output dict (loss, statistics) plus "changed".
@@ -1478,6 +1529,8 @@ class Trainer:
         next call; clone what is logged or compared across steps (or construct the Trainer with persistent_grads=False).
         Writing into them is safe (HipViewCompute notices by the tensors' version counters and refills them in full)."""
         o, gs = self.opt.opts, self.global_step
+        if getattr(self.compute, "lpips", None) is not None:
+            self.compute.lpips_on = gs >= self.start_lpips_iter
         out = self._run_step()
         if not self.density_enabled:     # composite: render + reduce + Adam only (see __init__)
             self.opt.update_learning_rate(gs)

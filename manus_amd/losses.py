@@ -142,6 +142,15 @@ def map_loss(alpha, mask, w_mask=1.0, depth=None, depth_target=None, w_depth=0.0
     return _MapLoss.apply(alpha, mask, depth, depth_target, float(w_mask), float(w_depth))
 
 
+def lpips_loss(pred, ref, net):
+    """lpips_loss(pred, ref) of loss_utils.py:111-117 (and the term of loss_func, base.py:333-341): pred (H,W,3), ref (1,H,W,3),
+    `net` a `manus_amd.lpips.LPIPS` (the reference keeps its network in a module global); the mean of the distances,
+    differentiable w.r.t. pred with a VGG network."""
+    pred = pred[None].permute(0, 3, 1, 2)
+    ref = ref.permute(0, 3, 1, 2)
+    return net(pred, ref).mean()
+
+
 class _IsotropicReg(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_scale, condition_number):

@@ -11,9 +11,10 @@ Mirrors `BaseTrainingModule.validation_step` / `on_validation_epoch_start` / `on
 
 `engine.Trainer.validate` is the batched form (V views per launch chain, straight from the rasterizer's layout).
 
-Not reproduced: LPIPS (its network weights are not part of this package) -- the `lpips` column of the
-CSV is written as an EMPTY field so that the file keeps the reference's six columns; and the `.ply` dump of
-`dump_gaussians` for the first validation batch.
+LPIPS (loss_utils.py:19, 111-117; base.py:149): its network weights are not part of this package.  With a user-supplied
+`manus_amd.lpips.LPIPS` (`Trainer.validate(..., lpips=...)`, `Validator.add(..., lpips=...)`) the `lpips` column of the CSV
+holds the mean of the per-view values on the masked images; without one it is written as an EMPTY field so that the file
+keeps the reference's six columns.  Not reproduced: the `.ply` dump of `dump_gaussians` for the first validation batch.
 
 NaN pixels: numpy's float -> uint8 cast of NaN is undefined; here a NaN render or ground-truth pixel is written as
 byte 0 in its panel.  That is this package's definition, not the reference's.
@@ -100,10 +101,13 @@ class Validator:
         """on_validation_epoch_start"""
         os.makedirs(self.val_results_dir, exist_ok=True)
         self.val_images, self.psnr_vals, self.ssim_vals, self.render_time = [], [], [], []
+        self.lpips_vals = []
 
-    def add(self, psnr, ssim, render_time, image=None):
+    def add(self, psnr, ssim, render_time, image=None, lpips=None):
         """One validated view: its metrics (numbers or 0-dim tensors), the wall-clock seconds of its render and its
-        (3H,W,3) uint8 triptych (tensor or array; None: no image kept)."""
+        (3H,W,3) uint8 triptych (tensor or array; None: no image kept).  lpips: the view's LPIPS value, or None (no network)."""
+        if lpips is not None:
+            self.lpips_vals.append(_scalar(lpips))
         self.psnr_vals.append(_scalar(psnr))
         self.ssim_vals.append(_scalar(ssim))
         self.render_time.append(float(render_time))
@@ -114,8 +118,9 @@ class Validator:
 
     def end(self, global_step):
         """on_validation_epoch_end: append `name, step, psnr, ssim, lpips, rendering_time` (the header first when the file
-        is new; `lpips` empty, see the module docstring) and save the triptychs.  Returns the row."""
-        row = [self.exp_name, int(global_step), np.mean(self.psnr_vals), np.mean(self.ssim_vals), "", np.mean(self.render_time)]
+        is new; `lpips` empty without values, see the module docstring) and save the triptychs.  Returns the row."""
+        lp = np.mean(self.lpips_vals) if getattr(self, "lpips_vals", None) else ""
+        row = [self.exp_name, int(global_step), np.mean(self.psnr_vals), np.mean(self.ssim_vals), lp, np.mean(self.render_time)]
         csv_path = os.path.join(self.val_results_dir, "val_results.csv")
         new = not os.path.exists(csv_path)
         with open(csv_path, "a") as f:

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Time the LPIPS term (csrc/lpips.hip, manus_amd/lpips.py).
+
+    python tools/measure_lpips.py [--out FILE.json] [--quick]
+
+One process, HIP events, every shape warmed, median of 5 samples with min - max (each sample a batch of repeats).  Stand-in
+weights (seeded randn * sqrt(2 / fan_in)): no weight file ships, and the convolutions are dense, so their time does not depend
+on the values.
+  * every VGG convolution alone (mgr_lpips_conv: one launch of the weight pack + k_lp_conv; the pack's own time is reported
+    next to it and subtracted) at 1280x720 and 1920x1080, one view: time and achieved TF/s (2 Cin Cout 9 Ho Wo flop), and the
+    ratio to the 122 TF of an untuned fp32-MFMA GEMM at 4096^3;
+  * the whole call (mgr_lpips, VGG, one view) forward only and with the gradient, and AlexNet forward only;
+  * the bench step (bench.py's scene and targets: 300k hand Gaussians, 8 views of 1920x1080, loss l1+ssim) with the term off
+    and on.
+Needs a GPU; there is no fallback."""
+import argparse
+import json
+import math
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from measure_feature_render import timed  # noqa: E402
+
+GEMM_TF = 122.0      # untuned LDS-tiled mfma_f32_32x32x2f32 GEMM at 4096^3 on this device class
+
+
+def stand_in(net, dev):
+    from manus_amd.lpips import CONV_INDEX, CONV_SHAPE, LPIPS, TAP_CHANNELS
+    g = torch.Generator().manual_seed(0)
+    sd, lin = {}, {}
+    for i, (co, ci, k) in zip(CONV_INDEX[net], CONV_SHAPE[net]):
+        sd["features.%d.weight" % i] = torch.randn((co, ci, k, k), generator=g) * math.sqrt(2.0 / (ci * k * k))
+        sd["features.%d.bias" % i] = torch.randn(co, generator=g)
+    for k, c in enumerate(TAP_CHANNELS[net]):
+        lin["lin%d.model.1.weight" % k] = torch.randn((1, c, 1, 1), generator=g).abs()
+    return LPIPS.from_state_dicts(sd, lin, net=net, device=dev), sd
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true", help="small sizes (a rehearsal of the script, not a measurement)")
+    ap.add_argument("--no-step", action="store_true", help="skip the bench step")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "measure_lpips.py needs a GPU"
+    from manus_amd._lib import check, lib, ptr, stream
+    from manus_amd.lpips import CONV_INDEX, CONV_SHAPE
+    dev = "cuda:0"
+    res = {"device": torch.cuda.get_device_name(0), "conv": {}, "call": {}, "step": {}}
+    vgg, sd = stand_in("vgg", dev)
+    alex, _ = stand_in("alex", dev)
+    sizes = [(1280, 720), (1920, 1080)] if not a.quick else [(96, 64)]
+    pools_before = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4)
+    L = lib()
+    for W, H in sizes:
+        rows, total_ms, total_flop = [], 0.0, 0.0
+        for li, (i, (co, ci, k)) in enumerate(zip(CONV_INDEX["vgg"], CONV_SHAPE["vgg"])):
+            h, w = H >> pools_before[li], W >> pools_before[li]
+            x = torch.randn((ci, h, w), device=dev)
+            wt, b = sd["features.%d.weight" % i].to(dev), sd["features.%d.bias" % i].to(dev)
+            y = torch.empty((co, h, w), device=dev)
+            n = int(L.mgr_lpips_conv_scratch_bytes(ci, co, 3, 3))
+            scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+            t_all = timed(lambda: check(L.mgr_lpips_conv(ci, co, h, w, 3, 3, 1, 1, ptr(x), None, ptr(wt), ptr(b), 1, 0, ptr(y), ptr(scratch), n,
+                                                         stream()), "mgr_lpips_conv"), 3)
+            # the pack alone: the same call on a 1x32 image (one workgroup row of the convolution)
+            xs, ys = torch.randn((ci, 1, 32), device=dev), torch.empty((co, 1, 32), device=dev)
+            t_pack = timed(lambda: check(L.mgr_lpips_conv(ci, co, 1, 32, 3, 3, 1, 1, ptr(xs), None, ptr(wt), ptr(b), 1, 0, ptr(ys), ptr(scratch), n,
+                                                          stream()), "mgr_lpips_conv"), 3)
+            ms = t_all["median_ms"] - t_pack["median_ms"]
+            flop = 2.0 * ci * co * 9 * h * w
+            row = dict(layer=i, cin=ci, cout=co, h=h, w=w, ms=ms, ms_with_pack=t_all["median_ms"], min_ms=t_all["min_ms"], max_ms=t_all["max_ms"],
+                       pack_ms=t_pack["median_ms"], tflops=flop / (ms * 1e9), ratio_to_gemm=flop / (ms * 1e9) / GEMM_TF)
+            rows.append(row)
+            total_ms += ms
+            total_flop += flop
+            print("conv %dx%d" % (W, H), json.dumps(row), flush=True)
+        res["conv"]["%dx%d" % (W, H)] = dict(layers=rows, total_ms=total_ms, tflops=total_flop / (total_ms * 1e9),
+                                             ratio_to_gemm=total_flop / (total_ms * 1e9) / GEMM_TF)
+        print("conv %dx%d total" % (W, H), total_ms, "ms", total_flop / (total_ms * 1e9), "TF/s", flush=True)
+        pred, target = torch.rand((1, 3, H, W), device=dev), torch.rand((1, 3, H, W), device=dev)
+        for key, fn in (("vgg_forward", lambda: vgg.values_grad(pred, target, need_grad=False)),
+                        ("vgg_value_and_gradient", lambda: vgg.values_grad(pred, target, need_grad=True)),
+                        ("alex_forward", lambda: alex.values_grad(pred, target, need_grad=False))):
+            res["call"]["%s %dx%d" % (key, W, H)] = timed(fn, 2)
+            print("call %s %dx%d" % (key, W, H), json.dumps(res["call"]["%s %dx%d" % (key, W, H)]), flush=True)
+        res["call"]["workspace_bytes %dx%d" % (W, H)] = int(L.mgr_lpips_workspace_bytes(0, H, W, 1))
+
+    if not a.no_step:
+        from manus_amd import rasterizer as rz
+        from manus_amd.engine import HipViewCompute
+        from manus_amd.synthetic import camera_table, make_scene
+        V, N, W, H = (8, 300000, 1920, 1080) if not a.quick else (3, 5000, 96, 64)
+        scene = make_scene(n_gaussians=N, kind="hand", seed=0, n_cameras=V, width=W, height=H, device=dev,
+                           **({} if not a.quick else dict(grid_res=24, cam_radius=0.5, sigma_range=(2e-3, 8e-3))))
+        ct = camera_table(scene["cameras"], dev)
+        g = torch.Generator(device="cpu").manual_seed(123)
+        pert = dict(scene)
+        pert["params"] = {k: (v + 0.01 * v.abs().mean() * torch.randn(v.shape, generator=g).to(dev)) for k, v in scene["params"].items()}
+        ids = list(range(V))
+        with torch.no_grad():
+            hp = HipViewCompute(pert, torch.zeros((V, 3, H, W), device=dev), ct)
+            targets = hp.forward_views_fused(ids)[0].contiguous().clone()
+            del hp
+        rz.context(dev).clear()
+        steps = {"off": HipViewCompute(scene, targets, ct, loss="l1+ssim"),
+                 "on": HipViewCompute(scene, targets, ct, loss="l1+ssim", lpips=vgg, w_lpips=0.1)}
+        for key in ("off", "on", "off_again", "on_again"):
+            hc = steps[key.replace("_again", "")]
+            res["step"][key] = timed(lambda: hc(ids, 1.0 / V), 20 if key.startswith("off") and not a.quick else 2)
+            print("step %s" % key, json.dumps(res["step"][key]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
