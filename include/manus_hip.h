@@ -759,7 +759,8 @@ int mgr_map_loss(int V, int H, int W, const float* alpha, const float* mask, con
 
 /* ------------------------------------------------------------------------
  * LPIPS: the reference's fourth loss term, lpips.LPIPS(net="vgg") from start_lpips_iter on (base.py:333-341), and the
- * LPIPS-AlexNet column of its validation CSV (loss_utils.py:111-117).  csrc/lpips.hip; convolutions on the fp32 matrix pipe.
+ * LPIPS-AlexNet column of its validation CSV (loss_utils.py:111-117).  csrc/lpips.hip; convolutions on the fp32 matrix pipe, or
+ * (the *_op entries with operands = MGR_LPIPS_BF16) on the bf16 matrix pipe.
  *
  *   x' = x mask (optional)   x'' = 2 x' - 1 (normalize != 0; the reference never passes it)   in = (x'' - shift) / scale
  *   f_k: the five taps of the frozen backbone (net 0: VGG16 relu1_2, 2_2, 3_3, 4_3, 5_3; net 1: AlexNet's five ReLUs)
@@ -799,6 +800,27 @@ size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW);
 int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
                    const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
                    void* stream);
+/* The operand mode: the entries above with a trailing `operands`.  MGR_LPIPS_F32 is the entries above, bit for bit (they are
+ * calls of these).  MGR_LPIPS_BF16: in every convolution of the call, forward and data gradient, the two matrix operands --
+ * the input value AFTER the ReLU gate and the zero padding, and the weight -- are rounded to bf16 (round to nearest even) and
+ * their products are summed in fp32 on v_mfma_f32_32x32x16_bf16.  Everything else is as above: fp32 bias, ReLU, fp32 stored
+ * activations (the gates of the data gradient come from them), the workspace and mgr_lpips_layout (neither depends on the
+ * mode), scaling layer, pools, heads, fp64 spatial means, accumulate, grad_scale.  The summation order inside a bf16 MFMA is
+ * the hardware's, so this mode promises no k-ordered chain; it keeps the rest: no atomics, results depend on the sizes alone,
+ * two runs give equal bits, V views equal V calls of one view.  The packed blob differs in size and layout between the modes:
+ * a blob packed for one is refused by the other (blob_bytes).  Also refused on the host: operands other than 0 / 1 (the *_bytes
+ * entries return 0), and everything the entries above refuse. */
+enum { MGR_LPIPS_F32 = 0, MGR_LPIPS_BF16 = 1 };
+size_t mgr_lpips_net_bytes_op(int net, int operands);
+int mgr_lpips_net_pack_op(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* blob,
+                          size_t blob_bytes, void* stream, int operands);
+int mgr_lpips_op(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob,
+                 size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
+                 void* workspace, size_t workspace_bytes, void* stream, int operands);
+size_t mgr_lpips_conv_scratch_bytes_op(int Cin, int Cout, int KH, int KW, int operands);
+int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                      const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
+                      void* stream, int operands);
 
 /* ------------------------------------------------------------------------
  * Device frame store: the stored uint8 RGBA crops of a capture decoded into the float targets and masks of a step

@@ -16,6 +16,14 @@
 // the staged input where gate <= 0: the data gradient dX = conv(dY * [y > 0], W') runs on the same kernel with the flipped,
 // transposed weights W' that mgr_lpips_net_pack prepares.  The weights are frozen: there is no weight gradient.
 //
+// k_lp_conv16 (operands = MGR_LPIPS_BF16): the same workgroup tile and epilogue on v_mfma_f32_32x32x16_bf16.  The two MFMA
+// operands -- the staged input AFTER the gate and the halo zeroing, and the weight -- are rounded to bf16 (round to nearest
+// even) and the products are summed in fp32.  k is ordered (tap, input channel): the patch is staged as bf16
+// [py][px][channel], the weights are pre-packed by k_lp_pack16 as bf16 [tap][channel / 8][cout][8], so every fragment is one
+// 16-byte LDS read.  Bias, ReLU, the stored fp32 activations and everything outside the convolutions are as in fp32 mode.
+// The summation order inside a bf16 MFMA is the hardware's: there is no k-ordered chain, but still no atomics, and an output
+// depends on the sizes alone.  The chunk sums are blocked as above.
+//
 // Spatial means travel as fp64 partials over a fixed tree (as k_map_loss does); no float atomics anywhere: bit-reproducible.
 //
 // One deviation from autograd: where a pixel's tap features are all zero, autograd through sqrt yields 0 * inf = NaN; here
@@ -23,6 +31,7 @@
 #include "mgr_common.h"
 
 typedef float lp_f16v __attribute__((ext_vector_type(16)));
+typedef __bf16 lp_bf8 __attribute__((ext_vector_type(8)));
 
 #define LP_T 256           // threads of every kernel of this file
 #define LP_TW 32           // output columns per workgroup of k_lp_conv (the MFMA's columns)
@@ -30,6 +39,8 @@ typedef float lp_f16v __attribute__((ext_vector_type(16)));
 #define LP_TC 64           // output channels per workgroup (two MFMA row blocks)
 #define LP_LDS_BUDGET (64 * 1024)
 #define LP_MAX_CK 8
+#define LP16_CK 32         // input channels per chunk of k_lp_conv16 (a multiple of 8)
+#define LP16_XPAD 16       // bytes of padding per staged pixel of k_lp_conv16: 80- / 48-byte pixels are conflict-free for 16-byte reads
 #define LP_NTAP 5
 #define LP_MAX_OPS 20
 
@@ -70,14 +81,20 @@ static bool lp_net(int net, LpNet* n) {
 }
 
 static inline size_t lp_pad64(size_t c) { return (c + 63) & ~(size_t)63; }
+static inline size_t lp_pad8(size_t c) { return (c + 7) & ~(size_t)7; }
+static inline bool lp_operands_ok(int operands) { return operands == MGR_LPIPS_F32 || operands == MGR_LPIPS_BF16; }
+// bytes of one packed weight set: fp32 [K][pad64(Cout)], bf16 [taps][pad8(Cin) / 8][pad64(Cout)][8]
+static inline size_t lp_wbytes(int operands, size_t cin, size_t kk, size_t cout) {
+    return operands == MGR_LPIPS_BF16 ? kk * lp_pad8(cin) * lp_pad64(cout) * 2 : cin * kk * lp_pad64(cout) * 4;
+}
 
 // the packed blob: per convolution [K][pad64(Cout)] forward weights, [pad64(Cout)] bias, (VGG) [Cout KH KW][pad64(Cin)] data-gradient
-// weights; then the five lin vectors
+// weights; then the five lin vectors.  In bf16 mode the two weight sets are bf16 in k_lp_pack16's layout, the rest is fp32.
 struct LpBlob {
     size_t w[13], b[13], wt[13], lin[LP_NTAP], total;
 };
 
-static LpBlob lp_blob(const LpNet& n) {
+static LpBlob lp_blob(const LpNet& n, int operands) {
     LpBlob B;
     size_t o = 0;
     int ci = 0;
@@ -85,10 +102,10 @@ static LpBlob lp_blob(const LpNet& n) {
         const LpOp& op = n.ops[i];
         if (!op.conv) continue;
         const size_t kk = (size_t)op.k * op.k;
-        B.w[ci] = o;  o += mgr_align((size_t)op.cin * kk * lp_pad64(op.cout) * 4);
+        B.w[ci] = o;  o += mgr_align(lp_wbytes(operands, op.cin, kk, op.cout));
         B.b[ci] = o;  o += mgr_align(lp_pad64(op.cout) * 4);
         B.wt[ci] = o;
-        if (n.has_bwd) o += mgr_align((size_t)op.cout * kk * lp_pad64(op.cin) * 4);
+        if (n.has_bwd) o += mgr_align(lp_wbytes(operands, op.cout, kk, op.cin));
         if (op.tap >= 0) { B.lin[op.tap] = o;  o += mgr_align((size_t)op.cout * 4); }
         ++ci;
     }
@@ -318,6 +335,238 @@ static int lp_conv(hipStream_t stream, const char* name, int Cin, int Cout, int 
 }
 
 // ---------------------------------------------------------------------------
+// convolution with bf16 operands
+// ---------------------------------------------------------------------------
+// w: torch's [Cout][Cin][KH][KW].  With NBi = pad8(Cin) / 8, NBo = pad8(Cout) / 8:
+//   fwd[((t NBi + ci / 8) CoP + co) 8 + ci % 8] = bf16(w[co][ci][t])
+//   bwd[((t NBo + co / 8) CiP + ci) 8 + co % 8] = bf16(w[co][ci][KK - 1 - t])        (the layer used backwards: k runs over co)
+// zero wherever ci >= Cin or co >= Cout; the bias stays fp32.
+__global__ __launch_bounds__(LP_T) void k_lp_pack16(int Cout, int Cin, int KK, int CoP, int CiP, const float* __restrict__ w,
+                                                    const float* __restrict__ bias, __bf16* __restrict__ fwd, float* __restrict__ bp,
+                                                    __bf16* __restrict__ bwd) {
+    const int NBi = (Cin + 7) >> 3, NBo = (Cout + 7) >> 3;
+    const size_t nf = (size_t)KK * NBi * CoP * 8, nb = bwd ? (size_t)KK * NBo * CiP * 8 : 0;
+    const size_t stride = (size_t)gridDim.x * LP_T;
+    for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < nf; e += stride) {
+        const int j = (int)(e & 7), co = (int)((e >> 3) % CoP);
+        const size_t r = (e >> 3) / CoP;      // t NBi + ci / 8
+        const int ci = (int)(r % NBi) * 8 + j, t = (int)(r / NBi);
+        fwd[e] = (__bf16)(co < Cout && ci < Cin ? w[((size_t)co * Cin + ci) * KK + t] : 0.f);
+    }
+    for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < nb; e += stride) {
+        const int j = (int)(e & 7), ci = (int)((e >> 3) % CiP);
+        const size_t r = (e >> 3) / CiP;
+        const int co = (int)(r % NBo) * 8 + j, t = KK - 1 - (int)(r / NBo);
+        bwd[e] = (__bf16)(co < Cout && ci < Cin ? w[((size_t)co * Cin + ci) * KK + t] : 0.f);
+    }
+    for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < (size_t)CoP; e += stride) bp[e] = e < (size_t)Cout ? bias[e] : 0.f;
+}
+
+struct LpConv16Args {
+    int Cin, Cout, CoP, NB, H, W, Ho, Wo, KH, KW, stride, pad, CK, KYN, relu;       // NB = pad8(Cin) / 8
+    const float *x, *gate, *bias;
+    const lp_bf8* wp;
+    float* y;
+};
+
+// A chunk is CK input channels (a multiple of 8) times KYN kernel rows (all of them for 3x3).  Its k runs over q = (tap, block
+// of 8 channels); one MFMA takes q = 2 m (lanes 0-31) and q = 2 m + 1 (lanes 32-63), an odd tail is zero.
+template <bool K3>
+__global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_smem16[];
+    const int KH = K3 ? 3 : a.KH, KW = K3 ? 3 : a.KW, st = K3 ? 1 : a.stride, pad = K3 ? 1 : a.pad, KYN = K3 ? 3 : a.KYN;
+    const int PW = (LP_TW - 1) * st + KW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+    const int ox0 = blockIdx.x * LP_TW, oy0 = blockIdx.y * LP_TH, co0 = blockIdx.z * LP_TC;
+    const int ix0 = ox0 * st - pad, iy0 = oy0 * st - pad;
+    const bool two = a.Cout - co0 > 32;
+    const int XS = a.CK * 2 + LP16_XPAD;                      // bytes per staged pixel
+    lp_bf8* sW = (lp_bf8*)lp_smem16;                          // [q][64 output channels] of 8 bf16
+    unsigned char* sX = lp_smem16 + (size_t)KYN * KW * (a.CK >> 3) * LP_TC * 16;       // [py][px] of XS bytes: CK bf16, padding
+
+    lp_f16v acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        acc0[r] = a.bias ? a.bias[co0 + row] : 0.f;
+        acc1[r] = a.bias ? a.bias[co0 + 32 + row] : 0.f;
+    }
+    lp_bf8 zero;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) zero[j] = (__bf16)0.f;
+
+    for (int ci0 = 0; ci0 < 8 * a.NB; ci0 += a.CK) {
+        const int nb = min(a.CK, 8 * a.NB - ci0) >> 3;
+        for (int ky0 = 0; ky0 < KH; ky0 += KYN) {
+            const int kyn = min(KYN, KH - ky0), Q = kyn * KW * nb, PH = (LP_TH - 1) * st + kyn;
+            if (K3 && nb == 4) {
+                // the hot shape: fixed trip counts and unconditional loads from clamped addresses, so that all loads of a
+                // chunk are in flight together instead of one latency per iteration
+#pragma unroll
+                for (int it = 0; it < 9; ++it) {
+                    const int e = tid + it * LP_T, c = e & 63, q = e >> 6;        // q = 4 t + cb
+                    sW[e] = a.wp[((size_t)(q >> 2) * a.NB + (ci0 >> 3) + (q & 3)) * a.CoP + co0 + c];
+                }
+                constexpr int NP = (LP_TH + 2) * (LP_TW + 2);
+#pragma unroll
+                for (int it = 0; it < (4 * NP + LP_T - 1) / LP_T; ++it) {
+                    const int e = tid + it * LP_T, cb = e / NP, p = e - cb * NP, py = p / (LP_TW + 2), px = p - py * (LP_TW + 2);
+                    const int ix = ix0 + px, iy = iy0 + py;
+                    const bool in = ix >= 0 && ix < a.W && iy >= 0 && iy < a.H;
+                    const size_t gp = (size_t)min(max(iy, 0), a.H - 1) * a.W + min(max(ix, 0), a.W - 1);
+                    float f[8], gt[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const size_t g = (size_t)min(ci0 + cb * 8 + j, a.Cin - 1) * a.H * a.W + gp;
+                        f[j] = a.x[g];
+                        gt[j] = a.gate ? a.gate[g] : 1.f;
+                    }
+                    lp_bf8 v;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = (__bf16)(in && ci0 + cb * 8 + j < a.Cin && gt[j] > 0.f ? f[j] : 0.f);
+                    if (e < 4 * NP) *(lp_bf8*)(sX + p * (LP16_CK * 2 + LP16_XPAD) + cb * 16) = v;
+                }
+            } else {
+                for (int e = tid; e < Q * LP_TC; e += LP_T) {
+                    const int c = e & 63, q = e >> 6, t = q / nb, cb = q - t * nb;
+                    sW[e] = a.wp[((size_t)(ky0 * KW + t) * a.NB + (ci0 >> 3) + cb) * a.CoP + co0 + c];
+                }
+                // the halo patch of kernel rows [ky0, ky0 + kyn): gated, zero outside the image and past Cin, THEN rounded
+                const int np = PH * PW;
+                for (int e = tid; e < nb * np; e += LP_T) {
+                    const int cb = e / np, p = e - cb * np, py = p / PW, px = p - py * PW;
+                    const int ix = ix0 + px, iy = iy0 + ky0 + py;
+                    const bool in = ix >= 0 && ix < a.W && iy >= 0 && iy < a.H;
+                    lp_bf8 v;
+    #pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int c = ci0 + cb * 8 + j;
+                        float f = 0.f;
+                        if (in && c < a.Cin) {
+                            const size_t g = ((size_t)c * a.H + iy) * a.W + ix;
+                            f = a.x[g];
+                            if (a.gate && !(a.gate[g] > 0.f)) f = 0.f;
+                        }
+                        v[j] = (__bf16)f;
+                    }
+                    *(lp_bf8*)(sX + p * XS + cb * 16) = v;
+                }
+            }
+            __syncthreads();
+            const unsigned char* xl = sX + ((wave * st) * PW + col * st) * XS;
+            lp_f16v c0, c1;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c0[r] = c1[r] = 0.f;
+            if (K3 && nb == 4) {
+                // the hot shape: 32 channels, 9 taps, every offset a constant
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+#pragma unroll
+                    for (int pp = 0; pp < 2; ++pp) {
+                        const int cb = 2 * pp + half;
+                        const lp_bf8 b = *(const lp_bf8*)(xl + ((t / 3) * (LP_TW + 2) + t % 3) * (LP16_CK * 2 + LP16_XPAD) + cb * 16);
+                        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sW[(t * 4 + cb) * LP_TC + col], b, c0, 0, 0, 0);
+                        if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sW[(t * 4 + cb) * LP_TC + 32 + col], b, c1, 0, 0, 0);
+                    }
+                }
+            } else {
+                int cb = half, kx = 0, ky = 0;
+                while (cb >= nb) { cb -= nb;  if (++kx == KW) { kx = 0; ++ky; } }
+                for (int q = half; q < Q + half; q += 2) {
+                    lp_bf8 b = zero, w0 = zero, w1 = zero;
+                    if (q < Q) {
+                        b = *(const lp_bf8*)(xl + (ky * PW + kx) * XS + cb * 16);
+                        w0 = sW[q * LP_TC + col];
+                        if (two) w1 = sW[q * LP_TC + 32 + col];
+                    }
+                    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b, c0, 0, 0, 0);
+                    if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b, c1, 0, 0, 0);
+                    cb += 2;
+                    while (cb >= nb) { cb -= nb;  if (++kx == KW) { kx = 0; ++ky; } }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                acc0[r] += c0[r];
+                acc1[r] += c1[r];
+            }
+            __syncthreads();
+        }
+    }
+
+    const int ox = ox0 + col, oy = oy0 + wave;
+    if (ox < a.Wo && oy < a.Ho) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int c0 = co0 + row, c1 = c0 + 32;
+            float v0 = acc0[r], v1 = acc1[r];
+            if (a.relu) {
+                v0 = v0 < 0.f ? 0.f : v0;
+                v1 = v1 < 0.f ? 0.f : v1;
+            }
+            if (c0 < a.Cout) a.y[((size_t)c0 * a.Ho + oy) * a.Wo + ox] = v0;
+            if (two && c1 < a.Cout) a.y[((size_t)c1 * a.Ho + oy) * a.Wo + ox] = v1;
+        }
+    }
+}
+
+static size_t lp_conv16_lds(int ck, int kyn, int KW, int stride) {
+    const size_t PH = (size_t)(LP_TH - 1) * stride + kyn, PW = (size_t)(LP_TW - 1) * stride + KW;
+    return (size_t)kyn * KW * (ck >> 3) * LP_TC * 16 + PH * PW * (ck * 2 + LP16_XPAD);
+}
+
+// the chunk: the most channels (32, 16, 8) and then the most kernel rows that fit the LDS budget; 8 channels of one row if none does
+static void lp_conv16_chunk(int Cin, int KH, int KW, int stride, int* ck, int* kyn, size_t* lds) {
+    const int cmax = (int)lp_pad8(Cin) < LP16_CK ? (int)lp_pad8(Cin) : LP16_CK;
+    for (int c = cmax; c >= 8; c = c > 16 ? 16 : c - 8)
+        for (int r = KH; r >= 1; --r)
+            if (lp_conv16_lds(c, r, KW, stride) <= LP_LDS_BUDGET) {
+                *ck = c;  *kyn = r;  *lds = lp_conv16_lds(c, r, KW, stride);
+                return;
+            }
+    *ck = 8;  *kyn = 1;  *lds = lp_conv16_lds(8, 1, KW, stride);
+}
+
+// as lp_conv, on bf16 operands; wp: k_lp_pack16's layout
+static int lp_conv16(hipStream_t stream, const char* name, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
+                     const float* x, const float* gate, const void* wp, const float* bias, int relu, float* y) {
+    LpConv16Args a;
+    a.Cin = Cin; a.Cout = Cout; a.CoP = (int)lp_pad64(Cout); a.NB = (int)(lp_pad8(Cin) >> 3); a.H = H; a.W = W;
+    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.relu = relu;
+    a.x = x; a.gate = gate; a.wp = (const lp_bf8*)wp; a.bias = bias; a.y = y;
+    size_t lds;
+    lp_conv16_chunk(Cin, KH, KW, stride, &a.CK, &a.KYN, &lds);
+    if (lds > 150 * 1024) return mgr_fail(MGR_EINVAL, "k_lp_conv16: kernel window too large for LDS");
+    const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (Cout + LP_TC - 1) / LP_TC);
+    if (grid.y > 65535u || grid.z > 65535u) return mgr_fail(MGR_EINVAL, "k_lp_conv16: image too large");
+    MGR_PROF(name, stream);
+    if (KH == 3 && KW == 3 && stride == 1 && pad == 1) {
+        hipLaunchKernelGGL(k_lp_conv16<true>, grid, dim3(LP_T), lds, stream, a);
+    } else {
+        if (lds > 64 * 1024) {
+            static bool raised = false;
+            if (!raised) {
+                MGR_HIP(hipFuncSetAttribute((const void*)k_lp_conv16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                raised = true;
+            }
+        }
+        hipLaunchKernelGGL(k_lp_conv16<false>, grid, dim3(LP_T), lds, stream, a);
+    }
+    MGR_LAUNCH_CHECK(name, stream, 0);
+    return MGR_OK;
+}
+
+// one convolution in the call's operand mode
+static int lp_conv_op(int operands, hipStream_t stream, const char* name, const char* name16, int Cin, int Cout, int H, int W, int KH,
+                      int KW, int stride, int pad, const float* x, const float* gate, const void* wp, const float* bias, int relu,
+                      float* y) {
+    if (operands == MGR_LPIPS_BF16) return lp_conv16(stream, name16, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, wp, bias, relu, y);
+    return lp_conv(stream, name, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, (const float*)wp, bias, relu, y);
+}
+
+// ---------------------------------------------------------------------------
 // scaling layer, pools
 // ---------------------------------------------------------------------------
 __constant__ float LP_SHIFT[3] = {-0.030f, -0.088f, -0.188f};
@@ -469,20 +718,24 @@ __global__ __launch_bounds__(LP_T) void k_lp_fold(const LpFoldArgs a, const doub
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
-extern "C" size_t mgr_lpips_net_bytes(int net) {
+extern "C" size_t mgr_lpips_net_bytes_op(int net, int operands) {
     LpNet n;
-    if (!lp_net(net, &n)) return 0;
-    return lp_blob(n).total;
+    if (!lp_net(net, &n) || !lp_operands_ok(operands)) return 0;
+    return lp_blob(n, operands).total;
 }
 
-extern "C" int mgr_lpips_net_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* blob,
-                                  size_t blob_bytes, void* stream_) {
+extern "C" size_t mgr_lpips_net_bytes(int net) { return mgr_lpips_net_bytes_op(net, MGR_LPIPS_F32); }
+
+extern "C" int mgr_lpips_net_pack_op(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w,
+                                     void* blob, size_t blob_bytes, void* stream_, int operands) {
     hipStream_t stream = (hipStream_t)stream_;
     LpNet n;
     if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: net must be 0 (vgg) or 1 (alex)");
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: operands must be 0 (fp32) or 1 (bf16)");
     if (!conv_w || !conv_b || !lin_w || !blob) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: null pointer");
-    const LpBlob B = lp_blob(n);
-    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: blob_bytes is not mgr_lpips_net_bytes(net)");
+    const LpBlob B = lp_blob(n, operands);
+    if (blob_bytes != B.total)
+        return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
     for (int i = 0; i < n.n_conv; ++i)
         if (!conv_w[i] || !conv_b[i]) return mgr_fail(MGR_EINVAL, "mgr_lpips_net_pack: null weight or bias pointer");
     for (int k = 0; k < LP_NTAP; ++k)
@@ -495,9 +748,17 @@ extern "C" int mgr_lpips_net_pack(int net, const float* const* conv_w, const flo
         const int KK = op.k * op.k, CoP = (int)lp_pad64(op.cout), CiP = (int)lp_pad64(op.cin);
         const size_t nf = (size_t)op.cin * KK * CoP;
         const unsigned nb = (unsigned)((nf + LP_T - 1) / LP_T < 4096 ? (nf + LP_T - 1) / LP_T : 4096);
-        hipLaunchKernelGGL(k_lp_pack, dim3(nb), dim3(LP_T), 0, stream, op.cout, op.cin, KK, CoP, CiP, conv_w[ci], conv_b[ci],
-                           (float*)(base + B.w[ci]), (float*)(base + B.b[ci]), n.has_bwd ? (float*)(base + B.wt[ci]) : (float*)nullptr);
-        MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
+        if (operands == MGR_LPIPS_BF16) {
+            hipLaunchKernelGGL(k_lp_pack16, dim3(nb), dim3(LP_T), 0, stream, op.cout, op.cin, KK, CoP, CiP, conv_w[ci], conv_b[ci],
+                               (__bf16*)(base + B.w[ci]), (float*)(base + B.b[ci]),
+                               n.has_bwd ? (__bf16*)(base + B.wt[ci]) : (__bf16*)nullptr);
+            MGR_LAUNCH_CHECK("k_lp_pack16", stream, 0);
+        } else {
+            hipLaunchKernelGGL(k_lp_pack, dim3(nb), dim3(LP_T), 0, stream, op.cout, op.cin, KK, CoP, CiP, conv_w[ci], conv_b[ci],
+                               (float*)(base + B.w[ci]), (float*)(base + B.b[ci]),
+                               n.has_bwd ? (float*)(base + B.wt[ci]) : (float*)nullptr);
+            MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
+        }
         if (op.tap >= 0) {
             hipLaunchKernelGGL(k_lp_copy, dim3((op.cout + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, op.cout, lin_w[op.tap],
                                (float*)(base + B.lin[op.tap]));
@@ -506,6 +767,11 @@ extern "C" int mgr_lpips_net_pack(int net, const float* const* conv_w, const flo
         ++ci;
     }
     return MGR_OK;
+}
+
+extern "C" int mgr_lpips_net_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* blob,
+                                  size_t blob_bytes, void* stream) {
+    return mgr_lpips_net_pack_op(net, conv_w, conv_b, lin_w, blob, blob_bytes, stream, MGR_LPIPS_F32);
 }
 
 extern "C" size_t mgr_lpips_workspace_bytes(int net, int H, int W, int need_grad) {
@@ -532,10 +798,11 @@ extern "C" int mgr_lpips_layout(int net, int H, int W, int need_grad, size_t* of
     return need;
 }
 
-extern "C" int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
-                              const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
-                              void* stream_) {
+extern "C" int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                                 const float* w, const float* bias, int relu, int transposed, float* y, void* scratch,
+                                 size_t scratch_bytes, void* stream_, int operands) {
     hipStream_t stream = (hipStream_t)stream_;
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: operands must be 0 (fp32) or 1 (bf16)");
     if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || KH != KW || stride < 1 || pad < 0 || H + 2 * pad < KH || W + 2 * pad < KW)
         return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: bad sizes");
     if (!x || !w || !y || !scratch) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: null pointer");
@@ -543,30 +810,48 @@ extern "C" int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, i
     if (transposed && bias) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: the data gradient takes no bias");
     const int KK = KH * KW, CoP = (int)lp_pad64(Cout), CiP = (int)lp_pad64(Cin);
     // scratch: [forward pack][bias pack][data-gradient pack]
-    const size_t o_f = 0, o_b = mgr_align((size_t)Cin * KK * CoP * 4), o_t = o_b + mgr_align((size_t)CoP * 4),
-                 tot = o_t + mgr_align((size_t)Cout * KK * CiP * 4);
+    const size_t o_f = 0, o_b = mgr_align(lp_wbytes(operands, Cin, KK, Cout)), o_t = o_b + mgr_align((size_t)CoP * 4),
+                 tot = o_t + mgr_align(lp_wbytes(operands, Cout, KK, Cin));
     if (scratch_bytes < tot) return mgr_fail(MGR_ENOMEM, "mgr_lpips_conv: scratch too small");
     char* base = (char*)scratch;
     // w is [Cout][Cin][KH][KW]; transposed: the layer is used backwards, x has Cout channels and y gets Cin
     const float* bsrc = bias ? bias : w;        // (k_lp_pack reads Cout values; unused where bias is null)
-    hipLaunchKernelGGL(k_lp_pack, dim3(256), dim3(LP_T), 0, stream, Cout, Cin, KK, CoP, CiP, w, bsrc, (float*)(base + o_f),
-                       (float*)(base + o_b), (float*)(base + o_t));
-    MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
+    if (operands == MGR_LPIPS_BF16) {
+        hipLaunchKernelGGL(k_lp_pack16, dim3(256), dim3(LP_T), 0, stream, Cout, Cin, KK, CoP, CiP, w, bsrc, (__bf16*)(base + o_f),
+                           (float*)(base + o_b), (__bf16*)(base + o_t));
+        MGR_LAUNCH_CHECK("k_lp_pack16", stream, 0);
+    } else {
+        hipLaunchKernelGGL(k_lp_pack, dim3(256), dim3(LP_T), 0, stream, Cout, Cin, KK, CoP, CiP, w, bsrc, (float*)(base + o_f),
+                           (float*)(base + o_b), (float*)(base + o_t));
+        MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
+    }
     if (transposed)
-        return lp_conv(stream, "k_lp_conv_bwd", Cout, Cin, H, W, KH, KW, 1, pad, x, gate, (const float*)(base + o_t), nullptr, relu, y);
-    return lp_conv(stream, "k_lp_conv", Cin, Cout, H, W, KH, KW, stride, pad, x, gate, (const float*)(base + o_f),
-                   bias ? (const float*)(base + o_b) : nullptr, relu, y);
+        return lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", Cout, Cin, H, W, KH, KW, 1, pad, x, gate, base + o_t, nullptr,
+                          relu, y);
+    return lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", Cin, Cout, H, W, KH, KW, stride, pad, x, gate, base + o_f,
+                      bias ? (const float*)(base + o_b) : nullptr, relu, y);
+}
+
+extern "C" int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                              const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
+                              void* stream) {
+    return mgr_lpips_conv_op(Cin, Cout, H, W, KH, KW, stride, pad, x, gate, w, bias, relu, transposed, y, scratch, scratch_bytes, stream,
+                             MGR_LPIPS_F32);
+}
+
+extern "C" size_t mgr_lpips_conv_scratch_bytes_op(int Cin, int Cout, int KH, int KW, int operands) {
+    if (Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || !lp_operands_ok(operands)) return 0;
+    const size_t KK = (size_t)KH * KW;
+    return mgr_align(lp_wbytes(operands, Cin, KK, Cout)) + mgr_align(lp_pad64(Cout) * 4) + mgr_align(lp_wbytes(operands, Cout, KK, Cin));
 }
 
 extern "C" size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW) {
-    if (Cin < 1 || Cout < 1 || KH < 1 || KW < 1) return 0;
-    const size_t KK = (size_t)KH * KW;
-    return mgr_align((size_t)Cin * KK * lp_pad64(Cout) * 4) + mgr_align(lp_pad64(Cout) * 4) + mgr_align((size_t)Cout * KK * lp_pad64(Cin) * 4);
+    return mgr_lpips_conv_scratch_bytes_op(Cin, Cout, KH, KW, MGR_LPIPS_F32);
 }
 
 // forward of one image: scaled image -> sb, then the ops; a convolution writes to its slot of `store` (by convolution index)
 // where that is not null, else to the scratch buffer its input is not in
-static int lp_forward(hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, const LpShape& S, int H, int W,
+static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, const LpShape& S, int H, int W,
                       const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb) {
     const int HW = H * W;
     hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, sb);
@@ -578,8 +863,8 @@ static int lp_forward(hipStream_t stream, const LpNet& n, const LpBlob& B, const
         float* out;
         if (op.conv) {
             out = store[ci] ? store[ci] : (cur == sa ? sb : sa);
-            const int rc = lp_conv(stream, "k_lp_conv", op.cin, op.cout, h, w, op.k, op.k, op.s, op.p, cur, nullptr,
-                                   (const float*)(blob + B.w[ci]), (const float*)(blob + B.b[ci]), 1, out);
+            const int rc = lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", op.cin, op.cout, h, w, op.k, op.k, op.s, op.p, cur,
+                                      nullptr, blob + B.w[ci], (const float*)(blob + B.b[ci]), 1, out);
             if (rc != MGR_OK) return rc;
             ++ci;
         } else {
@@ -596,12 +881,13 @@ static int lp_forward(hipStream_t stream, const LpNet& n, const LpBlob& B, const
     return MGR_OK;
 }
 
-extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob_,
-                         size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
-                         void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob_,
+                            size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
+                            void* workspace, size_t workspace_bytes, void* stream_, int operands) {
     hipStream_t stream = (hipStream_t)stream_;
     LpNet n;
     if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips: net must be 0 (vgg) or 1 (alex)");
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips: operands must be 0 (fp32) or 1 (bf16)");
     if (V <= 0 || H <= 0 || W <= 0) return mgr_fail(MGR_EINVAL, "mgr_lpips: bad sizes");
     if (!pred || !target || !blob_ || !values || !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips: null pointer");
     if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "mgr_lpips: the AlexNet network is forward only (dL_dpred must be null)");
@@ -610,8 +896,8 @@ extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const 
     LpShape S;
     if (!lp_layout(n, H, W, need_grad, &L) || !lp_shapes(n, H, W, &S))
         return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small for the deepest tap to have one pixel (or above 2^24 pixels)");
-    const LpBlob B = lp_blob(n);
-    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips: blob_bytes is not mgr_lpips_net_bytes(net)");
+    const LpBlob B = lp_blob(n, operands);
+    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
     if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_lpips: workspace smaller than mgr_lpips_workspace_bytes");
     const char* blob = (const char*)blob_;
     char* ws = (char*)workspace;
@@ -638,9 +924,9 @@ extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const 
 
     for (int v = 0; v < V; ++v) {
         const float* mk = mask ? mask + v * px : nullptr;
-        int rc = lp_forward(stream, n, B, blob, S, H, W, target + v * img, mk, normalize, tgt, sa, sb);
+        int rc = lp_forward(operands, stream, n, B, blob, S, H, W, target + v * img, mk, normalize, tgt, sa, sb);
         if (rc != MGR_OK) return rc;
-        rc = lp_forward(stream, n, B, blob, S, H, W, pred + v * img, mk, normalize, act, sa, sb);
+        rc = lp_forward(operands, stream, n, B, blob, S, H, W, pred + v * img, mk, normalize, act, sa, sb);
         if (rc != MGR_OK) return rc;
         if (!need_grad) {
             MGR_PROF("k_lp_head", stream);
@@ -674,8 +960,8 @@ extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const 
                         have = true;
                     }
                     // dL/d(input) = conv(g * [y > 0], W')
-                    rc = lp_conv(stream, "k_lp_conv_bwd", op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1, op.p, g, act[ci],
-                                 (const float*)(blob + B.wt[ci]), nullptr, 0, o);
+                    rc = lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1, op.p,
+                                    g, act[ci], blob + B.wt[ci], nullptr, 0, o);
                     if (rc != MGR_OK) return rc;
                 } else {
                     // the pool's input is the previous convolution's stored output
@@ -699,4 +985,11 @@ extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const 
         MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
     }
     return MGR_OK;
+}
+
+extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob,
+                         size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    return mgr_lpips_op(net, V, H, W, pred, target, mask, blob, blob_bytes, normalize, grad_scale, values, dL_dpred, accumulate, workspace,
+                        workspace_bytes, stream, MGR_LPIPS_F32);
 }

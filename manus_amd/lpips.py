@@ -6,14 +6,19 @@ No weight file ships with this package and none is fetched: the user supplies to
 (keys `features.{i}.weight` / `features.{i}.bias`) and the `lpips` package's `weights/v0.1/{vgg,alex}.pth` (keys
 `lin{k}.model.1.weight`, shape (1,C,1,1)); INTEGRATION.md says where.  The weights are frozen.  GPU tensors only; there is
 no CPU fallback.
+
+`operands="bf16"` runs every convolution, forward and data gradient, on the bf16 matrix pipe: input values and weights are
+rounded to bf16 (round to nearest even), the products summed in fp32; everything else stays fp32 (include/manus_hip.h).  The
+default, "fp32", is the k-ordered fp32 chain.
 """
 import ctypes
 
 import torch
 
-from ._lib import ManusHipError, check, f32c, lib, ptr, stream
+from ._lib import MGR_LPIPS_BF16, MGR_LPIPS_F32, ManusHipError, check, f32c, lib, ptr, stream
 
 NETS = {"vgg": 0, "alex": 1}
+OPERANDS = {"fp32": MGR_LPIPS_F32, "bf16": MGR_LPIPS_BF16}
 # torchvision `features` indices of the convolutions, (Cout, Cin, K) of each, and the tap channels
 CONV_INDEX = {"vgg": (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28), "alex": (0, 3, 6, 8, 10)}
 CONV_SHAPE = {"vgg": ((64, 3, 3), (64, 64, 3), (128, 64, 3), (128, 128, 3), (256, 128, 3), (256, 256, 3), (256, 256, 3), (512, 256, 3),
@@ -22,6 +27,12 @@ CONV_SHAPE = {"vgg": ((64, 3, 3), (64, 64, 3), (128, 64, 3), (128, 128, 3), (256
 TAP_CHANNELS = {"vgg": (64, 128, 256, 512, 512), "alex": (64, 192, 384, 256, 256)}
 # which convolution (in layer order) each tap is the output of
 TAP_CONV = {"vgg": (1, 3, 6, 9, 12), "alex": (0, 1, 2, 3, 4)}
+
+
+def _operands(operands, who):
+    if operands not in OPERANDS:
+        raise ManusHipError("%s: operands must be 'fp32' or 'bf16' (got %r)" % (who, operands))
+    return OPERANDS[operands]
 
 
 def _ptr_array(tensors):
@@ -60,18 +71,20 @@ class _Lpips(torch.autograd.Function):
 class LPIPS:
     """`lpips.LPIPS(net=...)` in eval mode with frozen weights.  Build with `from_state_dicts` or `load`."""
 
-    def __init__(self, net="vgg"):
+    def __init__(self, net="vgg", operands="fp32"):
         if net not in NETS:
             raise ManusHipError("LPIPS: net must be 'vgg' or 'alex' (got %r)" % (net,))
+        self._op = _operands(operands, "LPIPS")
         self.net = net
+        self.operands = operands
         self.blob = None
         self._ws = None
 
     # ---- weights
     @classmethod
-    def from_state_dicts(cls, backbone_sd, lin_sd, net="vgg", device="cuda"):
+    def from_state_dicts(cls, backbone_sd, lin_sd, net="vgg", device="cuda", operands="fp32"):
         """backbone_sd: torchvision's `vgg16` / `alexnet` state dict; lin_sd: the lpips package's linear layers."""
-        self = cls(net)
+        self = cls(net, operands)
         ws, bs, lins = [], [], []
         for i, (co, ci, k) in zip(CONV_INDEX[net], CONV_SHAPE[net]):
             for kind, shape, out in (("weight", (co, ci, k, k), ws), ("bias", (co,), bs)):
@@ -92,20 +105,21 @@ class LPIPS:
             lins.append(t)
         dev = torch.device(device)
         ws, bs, lins = ([f32c(t.detach().to(dev)) for t in grp] for grp in (ws, bs, lins))
-        nbytes = int(lib().mgr_lpips_net_bytes(NETS[net]))
+        nbytes = int(lib().mgr_lpips_net_bytes_op(NETS[net], self._op))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         for t in ws + bs + lins:
             ptr(t)      # (raises for CPU tensors: there is no CPU fallback)
-        check(lib().mgr_lpips_net_pack(NETS[net], _ptr_array(ws), _ptr_array(bs), _ptr_array(lins), ptr(blob), nbytes, stream()),
-              "mgr_lpips_net_pack")
+        check(lib().mgr_lpips_net_pack_op(NETS[net], _ptr_array(ws), _ptr_array(bs), _ptr_array(lins), ptr(blob), nbytes, stream(),
+                                          self._op), "mgr_lpips_net_pack_op")
         torch.cuda.current_stream().synchronize()       # the sources may die now
         self.blob = blob
         return self
 
     @classmethod
-    def load(cls, backbone_path, lin_path, net="vgg", device="cuda"):
+    def load(cls, backbone_path, lin_path, net="vgg", device="cuda", operands="fp32"):
         """torch.load of the two user-supplied files (see the module docstring)."""
-        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu"), torch.load(lin_path, map_location="cpu"), net, device)
+        return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu"), torch.load(lin_path, map_location="cpu"), net, device,
+                                    operands)
 
     # ---- the call
     def workspace(self, H, W, need_grad):
@@ -137,9 +151,9 @@ class LPIPS:
                 raise ManusHipError("LPIPS: out_grad must be fp32 of pred's shape")
         ws = self.workspace(H, W, need_grad)
         vals = torch.empty(V, dtype=torch.float32, device=pred.device)
-        check(lib().mgr_lpips(NETS[self.net], V, H, W, ptr(pred), ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
-                              int(bool(normalize)), float(grad_scale), ptr(vals), ptr(g), int(bool(accumulate)), ptr(ws), ws.numel(),
-                              stream()), "mgr_lpips")
+        check(lib().mgr_lpips_op(NETS[self.net], V, H, W, ptr(pred), ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
+                                 int(bool(normalize)), float(grad_scale), ptr(vals), ptr(g), int(bool(accumulate)), ptr(ws), ws.numel(),
+                                 stream(), self._op), "mgr_lpips_op")
         return vals, g
 
     def __call__(self, in0, in1, normalize=False):
@@ -149,8 +163,9 @@ class LPIPS:
         return _Lpips.apply(in0, in1, self, bool(normalize))
 
 
-def conv2d(x, w, bias=None, stride=1, pad=0, relu=True, gate=None, transposed=False):
-    """One convolution of the backbones on its own (`mgr_lpips_conv`; tests and tools).  x (Cin,H,W), w (Cout,Cin,K,K)."""
+def conv2d(x, w, bias=None, stride=1, pad=0, relu=True, gate=None, transposed=False, operands="fp32"):
+    """One convolution of the backbones on its own (`mgr_lpips_conv_op`; tests and tools).  x (Cin,H,W), w (Cout,Cin,K,K)."""
+    op = _operands(operands, "conv2d")
     x, w = f32c(x), f32c(w)
     co, ci, kh, kw = w.shape
     cx, H, W = x.shape
@@ -158,9 +173,9 @@ def conv2d(x, w, bias=None, stride=1, pad=0, relu=True, gate=None, transposed=Fa
         raise ManusHipError("conv2d: x has %d channels" % cx)
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     y = torch.empty((ci if transposed else co, Ho, Wo), dtype=torch.float32, device=x.device)
-    n = int(lib().mgr_lpips_conv_scratch_bytes(ci, co, kh, kw))
+    n = int(lib().mgr_lpips_conv_scratch_bytes_op(ci, co, kh, kw, op))
     scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
-    check(lib().mgr_lpips_conv(ci, co, H, W, kh, kw, int(stride), int(pad), ptr(x), ptr(None if gate is None else f32c(gate)), ptr(w),
-                               ptr(None if bias is None else f32c(bias)), int(bool(relu)), int(bool(transposed)), ptr(y), ptr(scratch), n,
-                               stream()), "mgr_lpips_conv")
+    check(lib().mgr_lpips_conv_op(ci, co, H, W, kh, kw, int(stride), int(pad), ptr(x), ptr(None if gate is None else f32c(gate)), ptr(w),
+                                  ptr(None if bias is None else f32c(bias)), int(bool(relu)), int(bool(transposed)), ptr(y), ptr(scratch),
+                                  n, stream(), op), "mgr_lpips_conv_op")
     return y

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Time the LPIPS term (csrc/lpips.hip, manus_amd/lpips.py).
 
-    python tools/measure_lpips.py [--out FILE.json] [--quick]
+    python tools/measure_lpips.py [--out FILE.json] [--quick] [--operands bf16]
 
 One process, HIP events, every shape warmed, median of 5 samples with min - max (each sample a batch of repeats).  Stand-in
 weights (seeded randn * sqrt(2 / fan_in)): no weight file ships, and the convolutions are dense, so their time does not depend
 on the values.
-  * every VGG convolution alone (mgr_lpips_conv: one launch of the weight pack + k_lp_conv; the pack's own time is reported
+With --operands bf16 every row of the three tables is run in BOTH operand modes, fp32 first, in this one process (a bf16 time
+is only ever read beside the fp32 time of the same run); the result's "modes" then has both, and "speedup" their ratios.
+  * every VGG convolution alone (mgr_lpips_conv_op: one launch of the weight pack + k_lp_conv; the pack's own time is reported
     next to it and subtracted) at 1280x720 and 1920x1080, one view: time and achieved TF/s (2 Cin Cout 9 Ho Wo flop), and the
     ratio to the 122 TF of an untuned fp32-MFMA GEMM at 4096^3;
   * the whole call (mgr_lpips, VGG, one view) forward only and with the gradient, and AlexNet forward only;
@@ -27,7 +29,7 @@ from measure_feature_render import timed  # noqa: E402
 GEMM_TF = 122.0      # untuned LDS-tiled mfma_f32_32x32x2f32 GEMM at 4096^3 on this device class
 
 
-def stand_in(net, dev):
+def stand_in(net, dev, operands="fp32"):
     from manus_amd.lpips import CONV_INDEX, CONV_SHAPE, LPIPS, TAP_CHANNELS
     g = torch.Generator().manual_seed(0)
     sd, lin = {}, {}
@@ -36,7 +38,7 @@ def stand_in(net, dev):
         sd["features.%d.bias" % i] = torch.randn(co, generator=g)
     for k, c in enumerate(TAP_CHANNELS[net]):
         lin["lin%d.model.1.weight" % k] = torch.randn((1, c, 1, 1), generator=g).abs()
-    return LPIPS.from_state_dicts(sd, lin, net=net, device=dev), sd
+    return LPIPS.from_state_dicts(sd, lin, net=net, device=dev, operands=operands), sd
 
 
 def main():
@@ -44,50 +46,58 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="small sizes (a rehearsal of the script, not a measurement)")
     ap.add_argument("--no-step", action="store_true", help="skip the bench step")
+    ap.add_argument("--operands", default="fp32", choices=("fp32", "bf16"), help="bf16: measure both modes, fp32 beside bf16")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "measure_lpips.py needs a GPU"
     from manus_amd._lib import check, lib, ptr, stream
-    from manus_amd.lpips import CONV_INDEX, CONV_SHAPE
+    from manus_amd.lpips import CONV_INDEX, CONV_SHAPE, OPERANDS
     dev = "cuda:0"
-    res = {"device": torch.cuda.get_device_name(0), "conv": {}, "call": {}, "step": {}}
-    vgg, sd = stand_in("vgg", dev)
-    alex, _ = stand_in("alex", dev)
+    modes = ("fp32",) if a.operands == "fp32" else ("fp32", "bf16")
+    res = {"device": torch.cuda.get_device_name(0), "modes": {m: {"conv": {}, "call": {}, "step": {}} for m in modes}}
+    nets = {m: (stand_in("vgg", dev, m), stand_in("alex", dev, m)[0]) for m in modes}
     sizes = [(1280, 720), (1920, 1080)] if not a.quick else [(96, 64)]
     pools_before = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4)
     L = lib()
     for W, H in sizes:
-        rows, total_ms, total_flop = [], 0.0, 0.0
+        rows, total_ms, total_flop = {m: [] for m in modes}, dict.fromkeys(modes, 0.0), 0.0
         for li, (i, (co, ci, k)) in enumerate(zip(CONV_INDEX["vgg"], CONV_SHAPE["vgg"])):
             h, w = H >> pools_before[li], W >> pools_before[li]
+            sd = nets["fp32"][0][1]
             x = torch.randn((ci, h, w), device=dev)
             wt, b = sd["features.%d.weight" % i].to(dev), sd["features.%d.bias" % i].to(dev)
             y = torch.empty((co, h, w), device=dev)
-            n = int(L.mgr_lpips_conv_scratch_bytes(ci, co, 3, 3))
-            scratch = torch.empty(n, dtype=torch.uint8, device=dev)
-            t_all = timed(lambda: check(L.mgr_lpips_conv(ci, co, h, w, 3, 3, 1, 1, ptr(x), None, ptr(wt), ptr(b), 1, 0, ptr(y), ptr(scratch), n,
-                                                         stream()), "mgr_lpips_conv"), 3)
-            # the pack alone: the same call on a 1x32 image (one workgroup row of the convolution)
             xs, ys = torch.randn((ci, 1, 32), device=dev), torch.empty((co, 1, 32), device=dev)
-            t_pack = timed(lambda: check(L.mgr_lpips_conv(ci, co, 1, 32, 3, 3, 1, 1, ptr(xs), None, ptr(wt), ptr(b), 1, 0, ptr(ys), ptr(scratch), n,
-                                                          stream()), "mgr_lpips_conv"), 3)
-            ms = t_all["median_ms"] - t_pack["median_ms"]
             flop = 2.0 * ci * co * 9 * h * w
-            row = dict(layer=i, cin=ci, cout=co, h=h, w=w, ms=ms, ms_with_pack=t_all["median_ms"], min_ms=t_all["min_ms"], max_ms=t_all["max_ms"],
-                       pack_ms=t_pack["median_ms"], tflops=flop / (ms * 1e9), ratio_to_gemm=flop / (ms * 1e9) / GEMM_TF)
-            rows.append(row)
-            total_ms += ms
             total_flop += flop
-            print("conv %dx%d" % (W, H), json.dumps(row), flush=True)
-        res["conv"]["%dx%d" % (W, H)] = dict(layers=rows, total_ms=total_ms, tflops=total_flop / (total_ms * 1e9),
-                                             ratio_to_gemm=total_flop / (total_ms * 1e9) / GEMM_TF)
-        print("conv %dx%d total" % (W, H), total_ms, "ms", total_flop / (total_ms * 1e9), "TF/s", flush=True)
+            for m in modes:
+                op = OPERANDS[m]
+                n = int(L.mgr_lpips_conv_scratch_bytes_op(ci, co, 3, 3, op))
+                scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+                t_all = timed(lambda: check(L.mgr_lpips_conv_op(ci, co, h, w, 3, 3, 1, 1, ptr(x), None, ptr(wt), ptr(b), 1, 0, ptr(y), ptr(scratch),
+                                                                n, stream(), op), "mgr_lpips_conv_op"), 3)
+                # the pack alone: the same call on a 1x32 image (one workgroup row of the convolution)
+                t_pack = timed(lambda: check(L.mgr_lpips_conv_op(ci, co, 1, 32, 3, 3, 1, 1, ptr(xs), None, ptr(wt), ptr(b), 1, 0, ptr(ys),
+                                                                 ptr(scratch), n, stream(), op), "mgr_lpips_conv_op"), 3)
+                ms = t_all["median_ms"] - t_pack["median_ms"]
+                row = dict(layer=i, cin=ci, cout=co, h=h, w=w, ms=ms, ms_with_pack=t_all["median_ms"], min_ms=t_all["min_ms"],
+                           max_ms=t_all["max_ms"], pack_ms=t_pack["median_ms"], tflops=flop / (ms * 1e9),
+                           ratio_to_gemm=flop / (ms * 1e9) / GEMM_TF)
+                rows[m].append(row)
+                total_ms[m] += ms
+                print("conv %s %dx%d" % (m, W, H), json.dumps(row), flush=True)
         pred, target = torch.rand((1, 3, H, W), device=dev), torch.rand((1, 3, H, W), device=dev)
-        for key, fn in (("vgg_forward", lambda: vgg.values_grad(pred, target, need_grad=False)),
-                        ("vgg_value_and_gradient", lambda: vgg.values_grad(pred, target, need_grad=True)),
-                        ("alex_forward", lambda: alex.values_grad(pred, target, need_grad=False))):
-            res["call"]["%s %dx%d" % (key, W, H)] = timed(fn, 2)
-            print("call %s %dx%d" % (key, W, H), json.dumps(res["call"]["%s %dx%d" % (key, W, H)]), flush=True)
-        res["call"]["workspace_bytes %dx%d" % (W, H)] = int(L.mgr_lpips_workspace_bytes(0, H, W, 1))
+        for m in modes:
+            (vgg, _), alex = nets[m]
+            r = res["modes"][m]
+            r["conv"]["%dx%d" % (W, H)] = dict(layers=rows[m], total_ms=total_ms[m], tflops=total_flop / (total_ms[m] * 1e9),
+                                               ratio_to_gemm=total_flop / (total_ms[m] * 1e9) / GEMM_TF)
+            print("conv %s %dx%d total" % (m, W, H), total_ms[m], "ms", total_flop / (total_ms[m] * 1e9), "TF/s", flush=True)
+            for key, fn in (("vgg_forward", lambda: vgg.values_grad(pred, target, need_grad=False)),
+                            ("vgg_value_and_gradient", lambda: vgg.values_grad(pred, target, need_grad=True)),
+                            ("alex_forward", lambda: alex.values_grad(pred, target, need_grad=False))):
+                r["call"]["%s %dx%d" % (key, W, H)] = timed(fn, 2)
+                print("call %s %s %dx%d" % (m, key, W, H), json.dumps(r["call"]["%s %dx%d" % (key, W, H)]), flush=True)
+            r["call"]["workspace_bytes %dx%d" % (W, H)] = int(L.mgr_lpips_workspace_bytes(0, H, W, 1))
 
     if not a.no_step:
         from manus_amd import rasterizer as rz
@@ -106,12 +116,21 @@ def main():
             targets = hp.forward_views_fused(ids)[0].contiguous().clone()
             del hp
         rz.context(dev).clear()
-        steps = {"off": HipViewCompute(scene, targets, ct, loss="l1+ssim"),
-                 "on": HipViewCompute(scene, targets, ct, loss="l1+ssim", lpips=vgg, w_lpips=0.1)}
-        for key in ("off", "on", "off_again", "on_again"):
-            hc = steps[key.replace("_again", "")]
-            res["step"][key] = timed(lambda: hc(ids, 1.0 / V), 20 if key.startswith("off") and not a.quick else 2)
-            print("step %s" % key, json.dumps(res["step"][key]), flush=True)
+        off = HipViewCompute(scene, targets, ct, loss="l1+ssim")
+        for m in modes:
+            steps = {"off": off, "on": HipViewCompute(scene, targets, ct, loss="l1+ssim", lpips=nets[m][0][0], w_lpips=0.1)}
+            for key in ("off", "on", "off_again", "on_again"):
+                hc = steps[key.replace("_again", "")]
+                res["modes"][m]["step"][key] = timed(lambda: hc(ids, 1.0 / V), 20 if key.startswith("off") and not a.quick else 2)
+                print("step %s %s" % (m, key), json.dumps(res["modes"][m]["step"][key]), flush=True)
+    if len(modes) == 2:
+        f, h16 = res["modes"]["fp32"], res["modes"]["bf16"]
+        res["speedup"] = {"conv": {sz: [dict(layer=a_["layer"], cin=a_["cin"], cout=a_["cout"], fp32_ms=a_["ms"], bf16_ms=b_["ms"],
+                                             ratio=a_["ms"] / b_["ms"]) for a_, b_ in zip(f["conv"][sz]["layers"], h16["conv"][sz]["layers"])]
+                                        for sz in f["conv"]},
+                          "call": {k: f["call"][k]["median_ms"] / h16["call"][k]["median_ms"] for k in f["call"] if not k.startswith("workspace")},
+                          "step": {k: f["step"][k]["median_ms"] / h16["step"][k]["median_ms"] for k in f["step"]}}
+        print("speedup", json.dumps(res["speedup"]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
