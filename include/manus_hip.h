@@ -822,6 +822,41 @@ int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW, int strid
                       const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
                       void* stream, int operands);
 
+/* LPIPS on a per-view window (the mgr_lpips_roi* entries).  The windowed distance of view v with the rectangle rects[v] =
+ * (x0, y0, w, h) in frame pixels is the LPIPS OF THE TWO CROPS: mgr_lpips_op on contiguous (3,h,w) copies of that rectangle of
+ * pred and target (and of mask), with the crop's own zero padding at its edges and its own spatial means, bit for bit.  It is
+ * NOT the full-frame value restricted to a region (no halo).  The scaling kernels read and write the rectangle of the pitched
+ * frame directly; the convolutions run on (h, w).  Gradient: inside the rectangle the crop's gradient, written or (accumulate
+ * = 1) added with one fp32 add; outside it 0 (accumulate = 0, the same launch writes the whole frame) or untouched (accumulate
+ * = 1).  A rectangle with w == 0 or h == 0 is an empty view: value 0, no gradient, a zero-filled frame with accumulate = 0.
+ *
+ * rects: HOST (V,4) ints.  grad_scales: HOST array of V floats, one per view (may be NULL without dL_dpred).  pred / target
+ * (V,3,H,W), mask (V,H,W) or NULL: the frames.  target_taps: NULL, or a HOST array of V DEVICE pointers, each NULL ("compute
+ * this view's target") or mgr_lpips_taps_bytes(net, h, w) bytes that mgr_lpips_roi_taps_op filled for that view's rectangle,
+ * target, mask, normalize and operand mode: the view's target forward is skipped and the result is bit for bit the call
+ * without (the taps are the same kernels' output).  With taps for every non-empty view, target may be NULL.  The workspace is
+ * the largest view's: mgr_lpips_roi_workspace_bytes = the maximum of mgr_lpips_workspace_bytes over the non-empty rectangles
+ * (0 where one is refused).  mgr_lpips_roi_taps_op: the target forward of ONE view's window (target_v (3,H,W), mask_v (H,W) or
+ * NULL) into taps_out: the five taps (C_k,h_k,w_k) fp32, each at a multiple of 256 bytes, in tap order; its workspace is
+ * mgr_lpips_workspace_bytes(net, h, w, 0).
+ *
+ * Refused on the host before any launch (outputs untouched): a rectangle not inside the frame, negative sizes, a non-empty
+ * rectangle at which the deepest tap has no pixel (what mgr_lpips refuses for an image of that size), null pointers (a
+ * non-empty view with neither target nor taps included), net 1 with dL_dpred, wrong blob_bytes, a workspace too small (-2),
+ * H above 65535. */
+size_t mgr_lpips_roi_workspace_bytes(int net, int V, const int* rects, int need_grad);
+size_t mgr_lpips_taps_bytes(int net, int h, int w);
+int mgr_lpips_roi_taps_op(int net, int H, int W, const int* rect, const float* target_v, const float* mask_v, const void* blob,
+                          size_t blob_bytes, int normalize, float* taps_out, void* workspace, size_t workspace_bytes, void* stream,
+                          int operands);
+int mgr_lpips_roi_op(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                     const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
+                     int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream,
+                     int operands);
+int mgr_lpips_roi(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                  const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
+                  int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Device frame store: the stored uint8 RGBA crops of a capture decoded into the float targets and masks of a step
  * (manus_amd/frames.py; SequenceDataset.fetch_images, brics_dynamic.py:343-373, restated bit for bit).

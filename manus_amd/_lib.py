@@ -157,6 +157,14 @@ SIGNATURES = {
                              c_int]),
     "mgr_lpips_conv_scratch_bytes_op": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "mgr_lpips_conv_op": (c_int, [c_int] * 8 + [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_sz, c_vp, c_int]),
+    "mgr_lpips_roi_workspace_bytes": (c_sz, [c_int, c_int, ctypes.POINTER(c_int), c_int]),
+    "mgr_lpips_taps_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_lpips_roi_taps_op": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_sz, c_int, c_vp, c_vp, c_sz, c_vp,
+                                      c_int]),
+    "mgr_lpips_roi_op": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_sz, c_int,
+                                 ctypes.POINTER(c_f32), c_vp, c_vp, c_int, ctypes.POINTER(c_vp), c_vp, c_sz, c_vp, c_int]),
+    "mgr_lpips_roi": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_sz, c_int,
+                              ctypes.POINTER(c_f32), c_vp, c_vp, c_int, ctypes.POINTER(c_vp), c_vp, c_sz, c_vp]),
     "mgr_frames_decode": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_i64, ctypes.POINTER(MgrFrameView), c_vp, c_vp, c_i64, c_vp]),
     "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -24,6 +24,13 @@
 // The summation order inside a bf16 MFMA is the hardware's: there is no k-ordered chain, but still no atomics, and an output
 // depends on the sizes alone.  The chunk sums are blocked as above.
 //
+// Windows (mgr_lpips_roi_op): the chain runs on the contiguous (3,h,w) copy of a per-view rectangle of the (3,H,W) frame.  Only the
+// scaling kernels know about the frame: k_lp_scale_win reads the rectangle of the pitched frame (and mask), k_lp_scale_bwd_win
+// adds the gradient into the rectangle, or writes the whole frame with zeros outside it; the arithmetic per element is
+// k_lp_scale's, so a window is the call on .contiguous() crops bit for bit -- the crop's own zero padding and spatial means, not
+// the full-frame value restricted to a region.  mgr_lpips_roi_taps_op leaves the target tower's five taps of a window in a
+// caller's buffer; a call given it skips that tower (same kernels, same bits).  k_lp_conv / k_lp_conv16 are untouched.
+//
 // Spatial means travel as fp64 partials over a fixed tree (as k_map_loss does); no float atomics anywhere: bit-reproducible.
 //
 // One deviation from autograd: where a pixel's tap features are all zero, autograd through sqrt yields 0 * inf = NaN; here
@@ -603,6 +610,58 @@ __global__ __launch_bounds__(LP_T) void k_lp_scale_bwd(int HW, const float* __re
     }
 }
 
+// The window of a frame.  A windowed view runs the chain on the contiguous (3, h, w) copy of the rectangle (x0, y0, w, h) of its
+// (3, FH, FW) frame: these two kernels are k_lp_scale / k_lp_scale_bwd with a pitch and an origin, the arithmetic per element
+// unchanged, so a window equals the call on .contiguous() crops bit for bit.  Lanes run along x (coalesced rows), no atomics.
+struct LpWin {
+    int FH, FW, x0, y0;
+};
+
+// grid (ceil(w / LP_T), h).  out (3, h, w) = k_lp_scale of x[:, y0 : y0 + h, x0 : x0 + w] (and of that rectangle of the mask)
+__global__ __launch_bounds__(LP_T) void k_lp_scale_win(int w, int h, const LpWin f, const float* __restrict__ x,
+                                                       const float* __restrict__ mask, int normalize, float* __restrict__ out) {
+    const int cx = blockIdx.x * LP_T + threadIdx.x, cy = blockIdx.y;
+    if (cx >= w || cy >= h) return;
+    const size_t FP = (size_t)f.FH * f.FW, HW = (size_t)h * w;
+    const size_t sp = (size_t)(f.y0 + cy) * f.FW + f.x0 + cx, p = (size_t)cy * w + cx;
+    const float m = mask ? mask[sp] : 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = x[c * FP + sp];
+        if (mask) v *= m;
+        if (normalize) v = 2.f * v - 1.f;
+        out[c * HW + p] = (v - LP_SHIFT[c]) / LP_SCALE[c];
+    }
+}
+
+// accumulate = 1: grid (ceil(w / LP_T), h), the rectangle's value is added (one fp32 add) to the rectangle of dx (3, FH, FW) and
+// the rest of the frame is not touched.  accumulate = 0: grid (ceil(FW / LP_T), FH), ONE launch writes the whole frame, the
+// value inside the rectangle and 0 outside (w = 0 or h = 0: a zero fill; g is not read).
+__global__ __launch_bounds__(LP_T) void k_lp_scale_bwd_win(int w, int h, const LpWin f, const float* __restrict__ g,
+                                                           const float* __restrict__ mask, int normalize, int accumulate,
+                                                           float* __restrict__ dx) {
+    const int t = blockIdx.x * LP_T + threadIdx.x;
+    const int gx = accumulate ? f.x0 + t : t, gy = accumulate ? f.y0 + (int)blockIdx.y : (int)blockIdx.y;
+    if (gx >= f.FW || gy >= f.FH) return;
+    const int cx = gx - f.x0, cy = gy - f.y0;
+    const bool in = cx >= 0 && cx < w && cy >= 0 && cy < h;
+    if (accumulate && !in) return;
+    const size_t FP = (size_t)f.FH * f.FW, HW = (size_t)h * w;
+    const size_t sp = (size_t)gy * f.FW + gx, p = in ? (size_t)cy * w + cx : 0;
+    const float m = (mask && in) ? mask[sp] : 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = 0.f;
+        if (in) {
+            v = g[c * HW + p] / LP_SCALE[c];
+            if (normalize) v *= 2.f;
+            if (mask) v *= m;
+        }
+        const size_t e = c * FP + sp;
+        dx[e] = accumulate ? __fadd_rn(dx[e], v) : v;
+    }
+}
+
 // max-pool k x k stride 2 (floor): the FIRST maximum in row-major window order, as torch
 __global__ __launch_bounds__(LP_T) void k_lp_pool(int C, int H, int W, int Ho, int Wo, int k, const float* __restrict__ x,
                                                   float* __restrict__ y) {
@@ -852,10 +911,16 @@ extern "C" size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW
 // forward of one image: scaled image -> sb, then the ops; a convolution writes to its slot of `store` (by convolution index)
 // where that is not null, else to the scratch buffer its input is not in
 static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, const LpShape& S, int H, int W,
-                      const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb) {
+                      const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb,
+                      const LpWin* win = nullptr) {
     const int HW = H * W;
-    hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, sb);
-    MGR_LAUNCH_CHECK("k_lp_scale", stream, 0);
+    if (win) {      // img / mask are the frame: (H, W) is the rectangle at win's origin
+        hipLaunchKernelGGL(k_lp_scale_win, dim3((W + LP_T - 1) / LP_T, H), dim3(LP_T), 0, stream, W, H, *win, img, mask, normalize, sb);
+        MGR_LAUNCH_CHECK("k_lp_scale_win", stream, 0);
+    } else {
+        hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, sb);
+        MGR_LAUNCH_CHECK("k_lp_scale", stream, 0);
+    }
     const float* cur = sb;
     int h = H, w = W, ci = 0;
     for (int i = 0; i < n.n_ops; ++i) {
@@ -881,6 +946,110 @@ static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const Lp
     return MGR_OK;
 }
 
+// one view of a call, validated by the caller: the two forwards (the target's only where `taps` is null), the heads, the
+// gradient chain and the fold into *value.  win = null: pred / target / mask / dL are contiguous (3,H,W) / (H,W) images;
+// else they are the view's frames and (H, W) is the rectangle at win's origin.  taps: the target's five taps as
+// mgr_lpips_roi_taps_op left them (the workspace's tap region, in its layout), or null.
+static int lp_view(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, int H, int W, const LpWin* win,
+                   const float* pred, const float* target, const float* mk, const float* taps, int normalize, float grad_scale,
+                   float* value, float* dL, int accumulate, char* ws) {
+    const int need_grad = dL != nullptr;
+    LpLayout L;
+    LpShape S;
+    if (!lp_layout(n, H, W, need_grad, &L) || !lp_shapes(n, H, W, &S)) return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small");
+    float *sa = (float*)(ws + L.bufa), *sb = (float*)(ws + L.bufb);
+    double* part = (double*)(ws + L.part);
+    float *act[13], *tgt[13];
+    int tap_conv[LP_NTAP], tap_op[LP_NTAP];
+    {
+        int ci = 0;
+        for (int i = 0; i < n.n_ops; ++i) {
+            const LpOp& op = n.ops[i];
+            if (!op.conv) continue;
+            act[ci] = (float*)(ws + L.act[ci]);
+            tgt[ci] = nullptr;
+            if (op.tap >= 0) {
+                tgt[ci] = taps ? (float*)((const char*)taps + (L.tap[op.tap] - L.tap[0])) : (float*)(ws + L.tap[op.tap]);
+                tap_conv[op.tap] = ci;
+                tap_op[op.tap] = i;
+            }
+            ++ci;
+        }
+    }
+    LpFoldArgs fa;
+    for (int k = 0; k <= LP_NTAP; ++k) fa.off[k] = (int)L.part_off[k];
+    for (int k = 0; k < LP_NTAP; ++k) fa.inv[k] = 1.0 / ((double)S.h[tap_op[k]] * S.w[tap_op[k]]);
+
+    int rc;
+    if (!taps) {
+        rc = lp_forward(operands, stream, n, B, blob, S, H, W, target, mk, normalize, tgt, sa, sb, win);
+        if (rc != MGR_OK) return rc;
+    }
+    rc = lp_forward(operands, stream, n, B, blob, S, H, W, pred, mk, normalize, act, sa, sb, win);
+    if (rc != MGR_OK) return rc;
+    if (!need_grad) {
+        MGR_PROF("k_lp_head", stream);
+        for (int k = 0; k < LP_NTAP; ++k) {
+            const int i = tap_op[k], hw = S.h[i] * S.w[i];
+            hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
+                               (const float*)act[tap_conv[k]], (const float*)tgt[tap_conv[k]], (const float*)(blob + B.lin[k]), 0.f,
+                               (float*)nullptr, 0, part + L.part_off[k]);
+            MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
+        }
+    } else {
+        // from the deepest tap down: g holds dL/d(post-ReLU output) of the current op
+        float *g = sa, *o = sb;
+        bool have = false;       // g holds a gradient from deeper layers
+        int h_in, w_in;
+        for (int i = n.n_ops - 1; i >= 0; --i) {
+            const LpOp& op = n.ops[i];
+            h_in = i ? S.h[i - 1] : H;
+            w_in = i ? S.w[i - 1] : W;
+            if (op.conv) {
+                int ci = 0;
+                for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
+                if (op.tap >= 0) {
+                    const int hw = S.h[i] * S.w[i], k = op.tap;
+                    const float gs = (float)((double)grad_scale * fa.inv[k]);
+                    MGR_PROF("k_lp_head", stream);
+                    hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, op.cout, hw, (const float*)act[ci],
+                                       (const float*)tgt[ci], (const float*)(blob + B.lin[k]), gs, g, have ? 1 : 0,
+                                       part + L.part_off[k]);
+                    MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
+                    have = true;
+                }
+                // dL/d(input) = conv(g * [y > 0], W')
+                rc = lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1, op.p,
+                                g, act[ci], blob + B.wt[ci], nullptr, 0, o);
+                if (rc != MGR_OK) return rc;
+            } else {
+                // the pool's input is the previous convolution's stored output
+                int ci = -1;
+                for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
+                const size_t ne = (size_t)op.cin * h_in * w_in;
+                MGR_PROF("k_lp_pool2_bwd", stream);
+                hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, op.cin, h_in, w_in,
+                                   S.h[i], S.w[i], (const float*)act[ci], (const float*)g, o);
+                MGR_LAUNCH_CHECK("k_lp_pool2_bwd", stream, 0);
+            }
+            float* t = g;  g = o;  o = t;
+        }
+        if (win) {
+            const dim3 grid = accumulate ? dim3((W + LP_T - 1) / LP_T, H) : dim3((win->FW + LP_T - 1) / LP_T, win->FH);
+            hipLaunchKernelGGL(k_lp_scale_bwd_win, grid, dim3(LP_T), 0, stream, W, H, *win, (const float*)g, mk, normalize, accumulate, dL);
+            MGR_LAUNCH_CHECK("k_lp_scale_bwd_win", stream, 0);
+        } else {
+            const int HW = H * W;
+            hipLaunchKernelGGL(k_lp_scale_bwd, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, (const float*)g, mk, normalize,
+                               accumulate, dL);
+            MGR_LAUNCH_CHECK("k_lp_scale_bwd", stream, 0);
+        }
+    }
+    hipLaunchKernelGGL(k_lp_fold, dim3(1), dim3(LP_T), 0, stream, fa, (const double*)part, value);
+    MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
+    return MGR_OK;
+}
+
 extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob_,
                             size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
                             void* workspace, size_t workspace_bytes, void* stream_, int operands) {
@@ -893,96 +1062,17 @@ extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, con
     if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "mgr_lpips: the AlexNet network is forward only (dL_dpred must be null)");
     const int need_grad = dL_dpred != nullptr;
     LpLayout L;
-    LpShape S;
-    if (!lp_layout(n, H, W, need_grad, &L) || !lp_shapes(n, H, W, &S))
+    if (!lp_layout(n, H, W, need_grad, &L))
         return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small for the deepest tap to have one pixel (or above 2^24 pixels)");
     const LpBlob B = lp_blob(n, operands);
     if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
     if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_lpips: workspace smaller than mgr_lpips_workspace_bytes");
-    const char* blob = (const char*)blob_;
-    char* ws = (char*)workspace;
-    float *sa = (float*)(ws + L.bufa), *sb = (float*)(ws + L.bufb);
-    double* part = (double*)(ws + L.part);
-    float *act[13], *tgt[13];
-    int tap_conv[LP_NTAP], tap_op[LP_NTAP], conv_op[13];
-    {
-        int ci = 0;
-        for (int i = 0; i < n.n_ops; ++i) {
-            const LpOp& op = n.ops[i];
-            if (!op.conv) continue;
-            act[ci] = (float*)(ws + L.act[ci]);
-            tgt[ci] = op.tap >= 0 ? (float*)(ws + L.tap[op.tap]) : nullptr;
-            if (op.tap >= 0) { tap_conv[op.tap] = ci;  tap_op[op.tap] = i; }
-            conv_op[ci] = i;
-            ++ci;
-        }
-    }
-    LpFoldArgs fa;
-    for (int k = 0; k <= LP_NTAP; ++k) fa.off[k] = (int)L.part_off[k];
-    for (int k = 0; k < LP_NTAP; ++k) fa.inv[k] = 1.0 / ((double)S.h[tap_op[k]] * S.w[tap_op[k]]);
     const size_t img = (size_t)3 * H * W, px = (size_t)H * W;
-
     for (int v = 0; v < V; ++v) {
-        const float* mk = mask ? mask + v * px : nullptr;
-        int rc = lp_forward(operands, stream, n, B, blob, S, H, W, target + v * img, mk, normalize, tgt, sa, sb);
+        const int rc = lp_view(operands, stream, n, B, (const char*)blob_, H, W, nullptr, pred + v * img, target + v * img,
+                               mask ? mask + v * px : nullptr, nullptr, normalize, grad_scale, values + v,
+                               dL_dpred ? dL_dpred + v * img : nullptr, accumulate, (char*)workspace);
         if (rc != MGR_OK) return rc;
-        rc = lp_forward(operands, stream, n, B, blob, S, H, W, pred + v * img, mk, normalize, act, sa, sb);
-        if (rc != MGR_OK) return rc;
-        if (!need_grad) {
-            MGR_PROF("k_lp_head", stream);
-            for (int k = 0; k < LP_NTAP; ++k) {
-                const int i = tap_op[k], hw = S.h[i] * S.w[i];
-                hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
-                                   (const float*)act[tap_conv[k]], (const float*)tgt[tap_conv[k]], (const float*)(blob + B.lin[k]), 0.f,
-                                   (float*)nullptr, 0, part + L.part_off[k]);
-                MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
-            }
-        } else {
-            // from the deepest tap down: g holds dL/d(post-ReLU output) of the current op
-            float *g = sa, *o = sb;
-            bool have = false;       // g holds a gradient from deeper layers
-            int h_in, w_in;
-            for (int i = n.n_ops - 1; i >= 0; --i) {
-                const LpOp& op = n.ops[i];
-                h_in = i ? S.h[i - 1] : H;
-                w_in = i ? S.w[i - 1] : W;
-                if (op.conv) {
-                    int ci = 0;
-                    for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
-                    if (op.tap >= 0) {
-                        const int hw = S.h[i] * S.w[i], k = op.tap;
-                        const float gs = (float)((double)grad_scale * fa.inv[k]);
-                        MGR_PROF("k_lp_head", stream);
-                        hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, op.cout, hw, (const float*)act[ci],
-                                           (const float*)tgt[ci], (const float*)(blob + B.lin[k]), gs, g, have ? 1 : 0,
-                                           part + L.part_off[k]);
-                        MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
-                        have = true;
-                    }
-                    // dL/d(input) = conv(g * [y > 0], W')
-                    rc = lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1, op.p,
-                                    g, act[ci], blob + B.wt[ci], nullptr, 0, o);
-                    if (rc != MGR_OK) return rc;
-                } else {
-                    // the pool's input is the previous convolution's stored output
-                    int ci = -1;
-                    for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
-                    const size_t ne = (size_t)op.cin * h_in * w_in;
-                    MGR_PROF("k_lp_pool2_bwd", stream);
-                    hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, op.cin, h_in, w_in,
-                                       S.h[i], S.w[i], (const float*)act[ci], (const float*)g, o);
-                    MGR_LAUNCH_CHECK("k_lp_pool2_bwd", stream, 0);
-                }
-                float* t = g;  g = o;  o = t;
-            }
-            (void)conv_op;
-            const int HW = H * W;
-            hipLaunchKernelGGL(k_lp_scale_bwd, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, (const float*)g, mk, normalize,
-                               accumulate, dL_dpred + v * img);
-            MGR_LAUNCH_CHECK("k_lp_scale_bwd", stream, 0);
-        }
-        hipLaunchKernelGGL(k_lp_fold, dim3(1), dim3(LP_T), 0, stream, fa, (const double*)part, values + v);
-        MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
     }
     return MGR_OK;
 }
@@ -992,4 +1082,135 @@ extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const 
                          void* workspace, size_t workspace_bytes, void* stream) {
     return mgr_lpips_op(net, V, H, W, pred, target, mask, blob, blob_bytes, normalize, grad_scale, values, dL_dpred, accumulate, workspace,
                         workspace_bytes, stream, MGR_LPIPS_F32);
+}
+
+// ---------------------------------------------------------------------------
+// the windowed call
+// ---------------------------------------------------------------------------
+// 0: empty, 1: fine, < 0: refused (-1 negative size, -2 outside the frame, -3 too small for the deepest tap or too large)
+static int lp_rect_check(const LpNet& n, int H, int W, const int* r, int need_grad, LpLayout* L) {
+    const long long x0 = r[0], y0 = r[1], w = r[2], h = r[3];
+    if (w < 0 || h < 0) return -1;
+    if (w == 0 || h == 0) return 0;
+    if (x0 < 0 || y0 < 0 || x0 + w > W || y0 + h > H) return -2;
+    return lp_layout(n, (int)h, (int)w, need_grad, L) ? 1 : -3;
+}
+
+static int lp_rect_fail(const char* who, int rc) {
+    return mgr_fail(MGR_EINVAL, "%s: %s", who,
+                    rc == -1 ? "a rectangle has a negative size"
+                             : rc == -2 ? "a rectangle is not inside the frame"
+                                        : "a rectangle is too small for the deepest tap to have one pixel (or above 2^24 pixels)");
+}
+
+extern "C" size_t mgr_lpips_roi_workspace_bytes(int net, int V, const int* rects, int need_grad) {
+    LpNet n;
+    if (!lp_net(net, &n) || V <= 0 || !rects) return 0;
+    size_t need = 0;
+    for (int v = 0; v < V; ++v) {
+        const int* r = rects + 4 * v;
+        if (r[2] == 0 || r[3] == 0) continue;
+        LpLayout L;
+        if (r[2] < 0 || r[3] < 0 || !lp_layout(n, r[3], r[2], need_grad, &L)) return 0;
+        need = need > L.total ? need : L.total;
+    }
+    return need;
+}
+
+extern "C" size_t mgr_lpips_taps_bytes(int net, int h, int w) {
+    LpNet n;
+    LpLayout L;
+    if (!lp_net(net, &n) || !lp_layout(n, h, w, 0, &L)) return 0;
+    return L.bufa - L.tap[0];
+}
+
+extern "C" int mgr_lpips_roi_taps_op(int net, int H, int W, const int* rect, const float* target_v, const float* mask_v, const void* blob_,
+                                     size_t blob_bytes, int normalize, float* taps_out, void* workspace, size_t workspace_bytes,
+                                     void* stream_, int operands) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LpNet n;
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: net must be 0 (vgg) or 1 (alex)");
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: operands must be 0 (fp32) or 1 (bf16)");
+    if (H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: bad sizes");
+    if (!rect || !target_v || !blob_ || !taps_out || !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: null pointer");
+    LpLayout L;
+    const int ok = lp_rect_check(n, H, W, rect, 0, &L);
+    if (ok < 0) return lp_rect_fail("mgr_lpips_roi_taps", ok);
+    if (ok == 0) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: an empty rectangle has no taps");
+    const LpBlob B = lp_blob(n, operands);
+    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
+    if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_lpips_roi_taps: workspace smaller than mgr_lpips_workspace_bytes(net, h, w, 0)");
+    LpShape S;
+    lp_shapes(n, rect[3], rect[2], &S);
+    float* tgt[13];
+    int ci = 0;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (!op.conv) continue;
+        tgt[ci++] = op.tap >= 0 ? (float*)((char*)taps_out + (L.tap[op.tap] - L.tap[0])) : nullptr;
+    }
+    const LpWin win = {H, W, rect[0], rect[1]};
+    char* ws = (char*)workspace;
+    return lp_forward(operands, stream, n, B, (const char*)blob_, S, rect[3], rect[2], target_v, mask_v, normalize, tgt, (float*)(ws + L.bufa),
+                      (float*)(ws + L.bufb), &win);
+}
+
+extern "C" int mgr_lpips_roi_op(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                                const void* blob_, size_t blob_bytes, int normalize, const float* grad_scales, float* values,
+                                float* dL_dpred, int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes,
+                                void* stream_, int operands) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LpNet n;
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: net must be 0 (vgg) or 1 (alex)");
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: operands must be 0 (fp32) or 1 (bf16)");
+    if (V <= 0 || H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: bad sizes");
+    if (!rects || !pred || !blob_ || !values || (dL_dpred && !grad_scales)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: null pointer");
+    if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: the AlexNet network is forward only (dL_dpred must be null)");
+    const int need_grad = dL_dpred != nullptr;
+    // every view is judged before the first launch
+    size_t need = 0;
+    for (int v = 0; v < V; ++v) {
+        LpLayout L;
+        const int ok = lp_rect_check(n, H, W, rects + 4 * v, need_grad, &L);
+        if (ok < 0) return lp_rect_fail("mgr_lpips_roi", ok);
+        if (ok == 0) continue;
+        if (!target && !(target_taps && target_taps[v]))
+            return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: null pointer (a view has neither a target nor cached taps)");
+        need = need > L.total ? need : L.total;
+    }
+    const LpBlob B = lp_blob(n, operands);
+    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
+    if (need && !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: null pointer");
+    if (workspace_bytes < need) return mgr_fail(MGR_ENOMEM, "mgr_lpips_roi: workspace smaller than mgr_lpips_roi_workspace_bytes");
+    const size_t img = (size_t)3 * H * W, px = (size_t)H * W;
+    for (int v = 0; v < V; ++v) {
+        const int* r = rects + 4 * v;
+        float* dL = dL_dpred ? dL_dpred + v * img : nullptr;
+        if (r[2] == 0 || r[3] == 0) {
+            // an empty view: the value is 0 (a fold over no partials); no gradient, and a written frame is zero
+            LpFoldArgs fa = {};
+            hipLaunchKernelGGL(k_lp_fold, dim3(1), dim3(LP_T), 0, stream, fa, (const double*)nullptr, values + v);
+            MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
+            if (dL && !accumulate) {
+                const LpWin win = {H, W, 0, 0};
+                hipLaunchKernelGGL(k_lp_scale_bwd_win, dim3((W + LP_T - 1) / LP_T, H), dim3(LP_T), 0, stream, 0, 0, win,
+                                   (const float*)nullptr, (const float*)nullptr, 0, 0, dL);
+                MGR_LAUNCH_CHECK("k_lp_scale_bwd_win", stream, 0);
+            }
+            continue;
+        }
+        const LpWin win = {H, W, r[0], r[1]};
+        const int rc = lp_view(operands, stream, n, B, (const char*)blob_, r[3], r[2], &win, pred + v * img,
+                               target ? target + v * img : nullptr, mask ? mask + v * px : nullptr, target_taps ? target_taps[v] : nullptr,
+                               normalize, need_grad ? grad_scales[v] : 0.f, values + v, dL, accumulate, (char*)workspace);
+        if (rc != MGR_OK) return rc;
+    }
+    return MGR_OK;
+}
+
+extern "C" int mgr_lpips_roi(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                             const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
+                             int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream) {
+    return mgr_lpips_roi_op(net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values, dL_dpred, accumulate,
+                            target_taps, workspace, workspace_bytes, stream, MGR_LPIPS_F32);
 }

@@ -20,6 +20,7 @@ import ctypes
 import functools
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -570,7 +571,20 @@ class HipViewCompute:
     dL/dimage before the backward), so grad2d / vis see the term, unlike the map terms.  `lpips_on` gates it per step (a Trainer
     sets it from start_lpips_iter); the output dict gains "loss_lpips" (the unweighted term on that scale) and `last_lpips`
     holds it (None with the term off).  Off -- no network, weight zero or lpips_on False -- the step is exactly the step without
-    these arguments."""
+    these arguments.
+
+    LPIPS windows (`lpips_rects`, `lpips_norm`, `lpips_cache_targets`; plain attributes): `lpips_rects` is a HOST table (V_all,4)
+    of ints x0, y0, w, h indexed by view id like `targets` (the caller's, or `frames.FrameStore.load_step(lpips_rects=True)`'s;
+    never found on the device); with it view v's term is the LPIPS of the CROPS of render and target at its rectangle
+    (`LPIPS.values_grad(rects=)`: the crop's own zero padding and spatial means, not the full-frame value restricted to the
+    region), only the rectangle is convolved (times: DESIGN.md section 6), and the gradient is zero outside it.  An empty rectangle turns a
+    view's term off.  `lpips_norm`: "frame" (default) multiplies view v's value and gradient by (w h) / (W H), which keeps
+    `w_lpips` on the scale of the full-frame term -- an APPROXIMATION: the full-frame spatial mean is diluted by the background
+    where both images agree, but the crop's padding and the features near its edge differ from the frame's; "window" applies no
+    factor (full-frame rects then give the step without rects, bit for bit).  `lpips_cache_targets` True keeps the target
+    tower's taps of the step's view set beside the other per-view constants (`LPIPS.target_taps`; same bits, the target
+    tower skipped, 122 floats per window pixel and view of memory): dropped with them -- `view_constants_changed()`, a version-counter
+    change of `targets` -- and on new rects.  None (default): exactly the step above."""
 
     # per-view target maps kept (130 KB per 1080p view)
     MAX_TARGET_MAPS = 4096
@@ -578,7 +592,7 @@ class HipViewCompute:
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
                  persistent_grads=True, pose_grad=False, skin_grid_grad=False, mask_targets=None, w_mask=0.0, depth_targets=None,
-                 w_depth=0.0, lpips=None, w_lpips=0.0):
+                 w_depth=0.0, lpips=None, w_lpips=0.0, lpips_rects=None, lpips_norm="frame", lpips_cache_targets=False):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -602,6 +616,9 @@ class HipViewCompute:
             raise ValueError("lpips: the training term takes a VGG manus_amd.lpips.LPIPS (the AlexNet network is forward only)")
         self.lpips, self.w_lpips, self.lpips_on = lpips, float(w_lpips), True
         self.last_lpips = None
+        if lpips_norm not in ("frame", "window"):
+            raise ValueError("lpips_norm must be 'frame' or 'window' (got %r)" % (lpips_norm,))
+        self.lpips_rects, self.lpips_norm, self.lpips_cache_targets = lpips_rects, lpips_norm, bool(lpips_cache_targets)
         # -- model
         self.params = {k: v.detach().clone().requires_grad_(True) for k, v in scene["params"].items()}
         N = self.params["_xyz"].shape[0]
@@ -872,16 +889,51 @@ class HipViewCompute:
         k = self.loss_weight * scale / img[0].numel()
         return k, self.w_ssim * self.loss_weight * scale * img.shape[0]
 
-    def _lpips_term(self, img, tgt, scale, g_img):
+    def _lpips_term(self, img, tgt, scale, g_img, sel=None, view_ids=None):
         """The LPIPS term of the step: mgr_lpips ADDS the gradient of scale * w_lpips * sum_v d_v to g_img (V,3,H,W) and returns
         scale * sum_v d_v; None with the term off.  On the fused route g_img is unwritten under empty background tiles (the image
-        loss leaves it so); the backward never reads there, so adding to whatever it holds is harmless."""
+        loss leaves it so); the backward never reads there, so adding to whatever it holds is harmless.  With `lpips_rects` the
+        views are windowed (class docstring): d_v is the crops' distance times the view's norm factor."""
         self.last_lpips = None
         if self.lpips is None or self.w_lpips == 0.0 or not self.lpips_on:
             return None
-        vals, _ = self.lpips.values_grad(img.detach(), tgt, need_grad=True, grad_scale=scale * self.w_lpips, out_grad=g_img, accumulate=True)
+        if self.lpips_rects is None:
+            vals, _ = self.lpips.values_grad(img.detach(), tgt, need_grad=True, grad_scale=scale * self.w_lpips, out_grad=g_img, accumulate=True)
+            self.last_lpips = vals.sum() * scale
+            return self.last_lpips
+        win = self._lpips_window(sel, view_ids, tgt)
+        k = scale * self.w_lpips
+        vals, _ = self.lpips.values_grad(img.detach(), tgt, need_grad=True, out_grad=g_img, accumulate=True, rects=win["rects"],
+                                         grad_scales=[k] * len(view_ids) if win["factors"] is None else [k * f for f in win["factors"]],
+                                         target_taps=win["taps"])
+        if win["factors"] is not None:
+            vals = vals * win["factors_dev"]
         self.last_lpips = vals.sum() * scale
         return self.last_lpips
+
+    def _lpips_window(self, sel, view_ids, tgt):
+        """The windows of the step's views, kept with the other per-view constants of the view set: their rects, the norm
+        factors (w h) / (W H) of lpips_norm = "frame" (host floats and a device vector; None for "window") and, with
+        lpips_cache_targets, the target tower's taps.  Rebuilt when the rects of these views, the norm, the network or the
+        cache switch differ from what the entry was built with; dropped with `sel` by `_drop_view_constants`."""
+        if self.lpips_norm not in ("frame", "window"):
+            raise ValueError("lpips_norm must be 'frame' or 'window' (got %r)" % (self.lpips_norm,))
+        table = np.asarray(self.lpips_rects)
+        if table.ndim != 2 or table.shape != (self.cams.shape[0], 4):
+            raise ValueError("lpips_rects must be (V_all,4) = (%d,4) host ints x0, y0, w, h (got %s)" % (self.cams.shape[0], table.shape))
+        rects = np.ascontiguousarray(table[list(view_ids)].astype(np.int32))
+        cache = bool(self.lpips_cache_targets)
+        key = (rects.tobytes(), self.lpips_norm, id(self.lpips), cache)
+        win = sel.get("lpips")
+        if win is None or win["key"] != key:
+            factors = factors_dev = None
+            if self.lpips_norm == "frame":
+                area = float(int(self.s["width"]) * int(self.s["height"]))
+                factors = [float(int(r[2]) * int(r[3])) / area for r in rects]
+                factors_dev = torch.tensor(factors, dtype=torch.float32, device=self.device)
+            win = sel["lpips"] = dict(key=key, rects=rects, factors=factors, factors_dev=factors_dev,
+                                      taps=self.lpips.target_taps(tgt, rects) if cache else None)
+        return win
 
     def _image_loss(self, img, tgt, scale, tiles=None):
         """(loss value, dL/dimg) of scale * sum over the views of the per-view image loss.  tiles = (bg, device address
@@ -975,7 +1027,7 @@ class HipViewCompute:
                 ctx.fence(ws)
             given = g_img is not None
             loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
-            lp = None if given else self._lpips_term(out, sel["targets"], scale, g_img)
+            lp = None if given else self._lpips_term(out, sel["targets"], scale, g_img, sel, view_ids)
             grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale, full_rows=any(map_on))
             map_out = self._map_chain(ws, head, sel, view_ids, scale, map_on, grads, d_w, d_T) if any(map_on) else None
             active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"], full_rows=any(map_on))
@@ -1246,7 +1298,7 @@ class HipViewCompute:
         if any(map_on):
             img, radii, means2D, extras = self.forward_views(view_ids, T=T, maps=(True, map_on[1]))
             loss, g = self._image_loss(img, tgt, scale)
-            lp = self._lpips_term(img, tgt, scale, g)
+            lp = self._lpips_term(img, tgt, scale, g, sel, view_ids)
             masks, depths = self._map_sel(sel, view_ids, map_on[1])
             k = scale * len(view_ids)
             ml, sums = losses.map_loss(extras["alpha"], masks, self.w_mask, extras["depth"] if map_on[1] else None, depths,
@@ -1257,7 +1309,7 @@ class HipViewCompute:
         else:
             img, radii, means2D = self.forward_views(view_ids, T=T)
             loss, g = self._image_loss(img, tgt, scale)
-            lp = self._lpips_term(img, tgt, scale, g)
+            lp = self._lpips_term(img, tgt, scale, g, sel, view_ids)
             img.backward(g)
         vis = radii > 0
         g2 = means2D.grad[..., :2].norm(dim=-1) * (1.0 / scale)

@@ -225,6 +225,20 @@ class FrameStore:
         if len(self._state) > 65536:      # (tables long gone: forget them all, the next writes are whole images)
             self._state = dict(new_state)
 
+    # -- LPIPS windows ---------------------------------------------------------------------------------------------------
+    def lpips_rects(self, items, margin=16, net="vgg"):
+        """(len(items),4) int32 x0, y0, w, h: every item's bbox in output pixels (`out_rect`), grown by `margin`, clamped to the
+        frame and brought to the network's minimum size (`lpips.fit_rects`) -- the windows of `HipViewCompute.lpips_rects`.  An
+        empty bbox gives an empty rectangle.  Host arithmetic only."""
+        from .lpips import fit_rects
+        rects = []
+        for it in items:
+            if int(it) not in self.row:
+                raise KeyError("item %r is not in the frame store" % (it,))
+            x0, y0, x1, y1 = out_rect(self.bboxes[self.row[int(it)]], self.k)
+            rects.append((x0, y0, x1 - x0, y1 - y0))
+        return fit_rects(np.asarray(rects, np.int64).reshape(-1, 4), self.height, self.width, net, margin)
+
     # -- one step of a compute object -----------------------------------------------------------------------------------
     def _compute_bg(self, compute):
         """The three floats of the compute object's background colour (read back once per tensor version)."""
@@ -234,12 +248,14 @@ class FrameStore:
             self._bg_host = (key, np.asarray(bg.detach().cpu(), np.float32).reshape(3))
         return self._bg_host[1]
 
-    def load_step(self, compute, items, slots=None, masks=False):
+    def load_step(self, compute, items, slots=None, masks=False, lpips_rects=False):
         """Point the rows `slots` (default 0 .. len(items) - 1) of an `engine.HipViewCompute` at the dataset items `items`:
         their targets decoded into `compute.targets`, their masks into `compute.mask_targets` (when that is set; masks=True
         allocates a zero table and sets it when it is not), their camera rows into `compute.cams`, their bone transforms (and
         posed transforms, keypoints, camera dicts, pruning masks where the scene holds them) into the scene's tables, all in
-        place; the compute object is told, so its next step rebuilds what it derives from them."""
+        place; the compute object is told, so its next step rebuilds what it derives from them.  lpips_rects=True also writes
+        the slots' rows of `compute.lpips_rects` with the items' windows (`lpips_rects(items)`), allocating a table of full-frame
+        rectangles first when the compute object has none."""
         if self.cam_rows is None:
             raise ValueError("load_step needs the camera rows and poses of a store built by FrameStore.from_dataset")
         items = [int(i) for i in items]
@@ -267,4 +283,12 @@ class FrameStore:
             s["masks"].index_copy_(0, slots_t, mt.index_select(0, slots_t).to(s["masks"].dtype))
         if mt is not compute.mask_targets:
             compute.mask_targets = mt
+        if lpips_rects:
+            table = compute.lpips_rects
+            if table is None:
+                table = np.tile(np.asarray([0, 0, self.width, self.height], np.int32), (int(compute.targets.shape[0]), 1))
+            else:
+                table = np.array(table, dtype=np.int32).reshape(-1, 4)
+            table[slots] = self.lpips_rects(items)
+            compute.lpips_rects = table
         compute.view_constants_changed()

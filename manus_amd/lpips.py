@@ -10,9 +10,17 @@ no CPU fallback.
 `operands="bf16"` runs every convolution, forward and data gradient, on the bf16 matrix pipe: input values and weights are
 rounded to bf16 (round to nearest even), the products summed in fp32; everything else stays fp32 (include/manus_hip.h).  The
 default, "fp32", is the k-ordered fp32 chain.
+
+Windows (`values_grad(rects=)`, `target_taps`, `fit_rects`): the distance of view v on the rectangle rects[v] = (x0, y0, w, h)
+of its frame is the LPIPS of the two crops -- the plain call on contiguous copies of that rectangle, bit for bit, with the
+crop's own zero padding and spatial means -- not the full-frame value restricted to a region.  Only the window is convolved
+(DESIGN.md section 6 has the times: below about 768^2 they fall more slowly than the area).  A target is a constant of its view: `target_taps` keeps the target tower's five taps of
+a window, and a call given them skips that tower (the same bits).
 """
 import ctypes
+import functools
 
+import numpy as np
 import torch
 
 from ._lib import MGR_LPIPS_BF16, MGR_LPIPS_F32, ManusHipError, check, f32c, lib, ptr, stream
@@ -50,6 +58,76 @@ def layout(net, H, W, need_grad=True):
     v = list(buf)
     return {"act": v[:n_conv], "tap": v[n_conv:n_conv + 5], "scratch": (v[n_conv + 5], v[n_conv + 6]), "part": v[n_conv + 7],
             "total": v[n_conv + 8]}
+
+
+@functools.lru_cache(maxsize=None)
+def min_size(net):
+    """The smallest height (= width) at which the deepest tap of `net` has a pixel, asked of the library's layer tables."""
+    m = 1
+    while not lib().mgr_lpips_workspace_bytes(NETS[net], m, m, 0):
+        m += 1
+    return m
+
+
+def _rects(rects, V=None):
+    """(V,4) int32 host array of x0, y0, w, h."""
+    r = np.ascontiguousarray(np.asarray(rects, dtype=np.int64).reshape(-1, 4).astype(np.int32))
+    if V is not None and r.shape[0] != V:
+        raise ManusHipError("LPIPS: rects must be (V,4) = (%d,4) ints (got %s)" % (V, r.shape))
+    return r
+
+
+def _fit_span(a, n, margin, m, F):
+    """The span [a, a + n) grown by `margin`, clamped to [0, F), then grown (evenly, shifted at a border) to m pixels."""
+    lo, hi = max(a - margin, 0), min(a + n + margin, F)
+    if hi <= lo:
+        return 0, 0
+    if hi - lo < m:
+        lo = min(max(lo - (m - (hi - lo)) // 2, 0), F - m)
+        hi = lo + m
+    return lo, hi - lo
+
+
+def fit_rects(rects, H, W, net, margin=0):
+    """Rectangles (x0, y0, w, h) made fit for a windowed call on an H x W frame: every non-empty one grown by `margin` on all
+    sides, clamped to the frame, then grown or shifted inside the frame to the network's minimum size (`min_size`).  An empty
+    rectangle (w or h zero, or nothing left inside the frame) comes back as (0,0,0,0).  Pure host arithmetic; (V,4) int32.
+    ValueError for a negative size or margin, or a frame smaller than the minimum."""
+    m = min_size(net)
+    if H < m or W < m:
+        raise ValueError("fit_rects: a %dx%d frame is smaller than the %dx%d minimum of the %s network" % (W, H, m, m, net))
+    if margin < 0:
+        raise ValueError("fit_rects: negative margin")
+    src = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    out = np.zeros(src.shape, np.int32)
+    for j, (x0, y0, w, h) in enumerate(src.tolist()):
+        if w < 0 or h < 0:
+            raise ValueError("fit_rects: rectangle %d has a negative size" % j)
+        if w == 0 or h == 0:
+            continue
+        fx, fw = _fit_span(x0, w, int(margin), m, W)
+        fy, fh = _fit_span(y0, h, int(margin), m, H)
+        if fw and fh:
+            out[j] = (fx, fy, fw, fh)
+    return out
+
+
+class TargetTaps:
+    """The target tower's five taps of each view's window (`LPIPS.target_taps`): one device buffer per view (None for an empty
+    view), and what they were built with -- a call with other rects, frame size, network, operand mode or normalize / mask
+    flags refuses them."""
+
+    def __init__(self, bufs, rects, frame, net, operands, normalize, masked):
+        self.bufs, self.rects, self.frame = bufs, rects, frame
+        self.net, self.operands, self.normalize, self.masked = net, operands, bool(normalize), bool(masked)
+
+    @property
+    def nbytes(self):
+        return sum(int(b.numel()) for b in self.bufs if b is not None)
+
+    def matches(self, rects, frame, net, operands, normalize, masked):
+        return (self.frame == frame and self.net == net and self.operands == operands and self.normalize == bool(normalize)
+                and self.masked == bool(masked) and self.rects.shape == rects.shape and bool((self.rects == rects).all()))
 
 
 class _Lpips(torch.autograd.Function):
@@ -131,11 +209,28 @@ class LPIPS:
             self._ws = torch.empty(n, dtype=torch.uint8, device=self.blob.device)
         return self._ws
 
-    def values_grad(self, pred, target, mask=None, normalize=False, need_grad=True, grad_scale=1.0, out_grad=None, accumulate=False):
+    def _grow(self, n):
+        if self._ws is None or self._ws.numel() < n or self._ws.device != self.blob.device:
+            self._ws = torch.empty(max(int(n), 1), dtype=torch.uint8, device=self.blob.device)
+        return self._ws
+
+    def values_grad(self, pred, target, mask=None, normalize=False, need_grad=True, grad_scale=1.0, out_grad=None, accumulate=False,
+                    rects=None, grad_scales=None, target_taps=None):
         """values (V,) and the gradient of grad_scale * sum(values) w.r.t. pred (V,3,H,W) in one pass (`mgr_lpips`).  `out_grad`:
-        write (or, with accumulate, add) the gradient there instead of a new tensor."""
+        write (or, with accumulate, add) the gradient there instead of a new tensor.
+
+        rects: (V,4) host ints x0, y0, w, h -- the windowed call (`mgr_lpips_roi_op`, module docstring): view v is the LPIPS of
+        the crops at rects[v]; its gradient is the crop's inside the rectangle and, outside it, zero (or, with accumulate,
+        untouched).  An empty rectangle gives the value 0 and no gradient.  grad_scales: V floats, one per view, instead of the
+        one grad_scale.  target_taps: a `TargetTaps` of `target_taps(...)` on the same rects, mask and flags: the target tower
+        is skipped, `target` may then be None.  rects=None is the plain call."""
         if self.blob is None:
             raise ManusHipError("LPIPS: no weights (build with LPIPS.from_state_dicts or LPIPS.load)")
+        if rects is not None:
+            return self._values_grad_roi(pred, target, mask, normalize, need_grad, grad_scale, out_grad, accumulate, rects, grad_scales,
+                                         target_taps)
+        if grad_scales is not None or target_taps is not None:
+            raise ManusHipError("LPIPS: grad_scales and target_taps belong to the windowed call (rects=)")
         pred, target = f32c(pred), f32c(target)
         if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != target.shape:
             raise ManusHipError("LPIPS: images are (N,3,H,W), both of one shape (got %s, %s)" % (tuple(pred.shape), tuple(target.shape)))
@@ -155,6 +250,73 @@ class LPIPS:
                                  int(bool(normalize)), float(grad_scale), ptr(vals), ptr(g), int(bool(accumulate)), ptr(ws), ws.numel(),
                                  stream(), self._op), "mgr_lpips_op")
         return vals, g
+
+    def _frames(self, pred, target, mask):
+        """The checked frames of a windowed call: (pred, target or None, mask or None, V, H, W)."""
+        pred = f32c(pred)
+        if pred.dim() != 4 or pred.shape[1] != 3:
+            raise ManusHipError("LPIPS: images are (N,3,H,W) (got %s)" % (tuple(pred.shape),))
+        if target is not None:
+            target = f32c(target)
+            if target.shape != pred.shape:
+                raise ManusHipError("LPIPS: images are (N,3,H,W), both of one shape (got %s, %s)" % (tuple(pred.shape), tuple(target.shape)))
+        V, _, H, W = pred.shape
+        if mask is not None:
+            mask = f32c(mask)
+            if tuple(mask.shape) != (V, H, W):
+                raise ManusHipError("LPIPS: mask must be (N,H,W)")
+        return pred, target, mask, V, H, W
+
+    def _values_grad_roi(self, pred, target, mask, normalize, need_grad, grad_scale, out_grad, accumulate, rects, grad_scales, taps):
+        if target is None and taps is None:
+            raise ManusHipError("LPIPS: a windowed call needs target or target_taps")
+        pred, target, mask, V, H, W = self._frames(pred, target, mask)
+        rects = _rects(rects, V)
+        tap_ptrs = None
+        if taps is not None:
+            if not isinstance(taps, TargetTaps) or not taps.matches(rects, (H, W), self.net, self.operands, normalize, mask is not None):
+                raise ManusHipError("LPIPS: target_taps were built with other rects, frame size, network, operand mode or normalize / "
+                                    "mask flags than this call's")
+            tap_ptrs = (ctypes.c_void_p * V)(*[None if b is None else ptr(b) for b in taps.bufs])
+        scales = [float(grad_scale)] * V if grad_scales is None else [float(x) for x in grad_scales]
+        if len(scales) != V:
+            raise ManusHipError("LPIPS: grad_scales must hold one float per view")
+        g = None
+        if need_grad:
+            g = out_grad if out_grad is not None else torch.empty_like(pred)
+            if g.shape != pred.shape or g.dtype != torch.float32:
+                raise ManusHipError("LPIPS: out_grad must be fp32 of pred's shape")
+        rp = rects.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        # (0 where a rectangle is refused: the call below says which and why)
+        ws = self._grow(lib().mgr_lpips_roi_workspace_bytes(NETS[self.net], V, rp, int(bool(need_grad))))
+        vals = torch.empty(V, dtype=torch.float32, device=pred.device)
+        check(lib().mgr_lpips_roi_op(NETS[self.net], V, H, W, rp, ptr(pred), ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
+                                     int(bool(normalize)), (ctypes.c_float * V)(*scales), ptr(vals), ptr(g), int(bool(accumulate)),
+                                     tap_ptrs, ptr(ws), ws.numel(), stream(), self._op), "mgr_lpips_roi_op")
+        return vals, g
+
+    def target_taps(self, target, rects, mask=None, normalize=False):
+        """The target tower's taps of every view's window (`mgr_lpips_roi_taps_op`), for `values_grad(target_taps=)`: a
+        `TargetTaps` holding mgr_lpips_taps_bytes per non-empty view.  target (V,3,H,W), mask (V,H,W) or None, rects (V,4)."""
+        if self.blob is None:
+            raise ManusHipError("LPIPS: no weights (build with LPIPS.from_state_dicts or LPIPS.load)")
+        target, _, mask, V, H, W = self._frames(target, None, mask)
+        rects = _rects(rects, V)
+        net, bufs = NETS[self.net], []
+        for v in range(V):
+            x0, y0, w, h = (int(t) for t in rects[v])
+            if w == 0 or h == 0:
+                bufs.append(None)
+                continue
+            # (0 bytes where the rectangle is refused: the call says why)
+            buf = torch.empty(max(int(lib().mgr_lpips_taps_bytes(net, h, w)), 1), dtype=torch.uint8, device=target.device)
+            ws = self._grow(lib().mgr_lpips_workspace_bytes(net, h, w, 0))
+            check(lib().mgr_lpips_roi_taps_op(net, H, W, rects[v].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(target[v]),
+                                              None if mask is None else ptr(mask[v]), ptr(self.blob), self.blob.numel(),
+                                              int(bool(normalize)), ptr(buf), ptr(ws), ws.numel(), stream(), self._op),
+                  "mgr_lpips_roi_taps_op")
+            bufs.append(buf)
+        return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None)
 
     def __call__(self, in0, in1, normalize=False):
         """d(in0, in1) of shape (N,1,1,1) for (N,3,H,W) images, differentiable in in0 (VGG only)."""
