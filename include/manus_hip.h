@@ -645,6 +645,42 @@ int mgr_pack_camera(float tanfovx, float tanfovy, const float* view16, const flo
                     float* out40, void* stream);
 int mgr_bone_transforms(int B, int background, const float* posed, const float* rest, float* out, void* stream);
 
+/* Pose chain on the device (csrc/pose.hip; manus_amd/pose.py: PoseRefiner).  No reference counterpart: the reference's
+ * config names src.models.pose_optimizer, which was never released.  A per-frame, per-bone correction rotvec / trans (F,B,3)
+ * of the posed bone matrices, in the bone's local frame:
+ *     T[v,b] = (posed[v,b] @ [[exp(rotvec[f,b]), trans[f,b]], [0,0,0,1]]) @ inv(rest[b])
+ * exp = Rodrigues, R = I + a K + b K^2 with a = sin(th)/th, b = (1 - cos th)/th^2, and for t = |r|^2 < 1e-6 the series
+ * a = 1 - t/6 + t^2/120, b = 1/2 - t/24 (pose._exp_so3).  The inverse and the last product are those of mgr_bone_transforms
+ * (same elimination, same summation order): a zero correction, or no correction, gives its bits.  fp32, one thread per small
+ * matrix, one or two workgroups per launch, no workspace, no atomics.  All pointers are DEVICE pointers; posed is
+ * (V_all,B,4,4) and transforms (V_all,B+1,4,4), the tables of all views, rest (B,4,4); view_rows[k] (int32) is the row of
+ * those tables the step's position k shows, frame_of_view[k] (int32) its row of rotvec / trans -- outside [0,F) (-1 for
+ * validation views): no correction.  The caller vouches for view_rows lying inside the tables.
+ * Every entry refuses, before any launch and with mgr_last_error() naming it: a NULL pointer (gathered alone may be NULL),
+ * V, B or U below 1, B > MGR_MAX_BONES, F < 1.
+ *
+ * mgr_pose_apply: T of the positions k < V into transforms[view_rows[k], 0..B-1], the identity into row B; the same B+1
+ *   rows into gathered[k] (V,B+1,4,4), the contiguous copy the fused kernels read, when it is given.  Rows of views not
+ *   listed are not touched.
+ * mgr_pose_backward: d_transforms (V,B+1,4,4) by position (the step's "d_transforms").  Per position and bone
+ *   dC = posed[v,b]^T dT inv(rest[b])^T; d_trans = dC[:3,3]; d_rotvec = the vector-Jacobian product of exp at rotvec[f,b]
+ *   with dC[:3,:3], the series branch differentiated as a series (da/dt = -1/6 + t/60, db/dt = -1/24).  Row u of d_rotvec /
+ *   d_trans (U,B,3) is the sum over the positions with frame_of_view[k] == frames_listed[u], in ascending k by ONE thread per
+ *   (u, bone): deterministic.  A listed frame without a view (or outside [0,F)) gets zeros; positions whose frame is not
+ *   listed contribute nothing.
+ * mgr_pose_adam: the row Adam of mgr_skin_grid_adam (torch.optim.SparseAdam: parameters and moments of the listed rows only,
+ *   bias correction of the global `step` >= 1) on the rows frames_listed[u] (distinct, inside the tables: the caller's to
+ *   ensure; negative entries are skipped) of rotvec / trans and their moments m_r, v_r, m_t, v_t (F,B,3), from d_rotvec /
+ *   d_trans (U,B,3).  Separate learning rates, no clamp. */
+int mgr_pose_apply(int V, int B, int F, const int32_t* view_rows, const int32_t* frame_of_view, const float* posed,
+                   const float* rest, const float* rotvec, const float* trans, float* transforms, float* gathered, void* stream);
+int mgr_pose_backward(int V, int B, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                      const int32_t* frame_of_view, const float* posed, const float* rest, const float* rotvec,
+                      const float* trans, const float* d_transforms, float* d_rotvec, float* d_trans, void* stream);
+int mgr_pose_adam(int U, int B, const int32_t* frames_listed, const float* d_rotvec, const float* d_trans, float* rotvec,
+                  float* trans, float* m_r, float* v_r, float* m_t, float* v_t, double lr_rot, double lr_trans, double beta1,
+                  double beta2, double eps, int step, void* stream);
+
 /* uv = (K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
 int mgr_project_points(int N, const float* xyz, const float* K9, const float* E12, float* uv,
                        void* stream);

@@ -115,6 +115,9 @@ SIGNATURES = {
                                  c_vp]),
     "mgr_pack_camera": (c_int, [c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_bone_transforms": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "mgr_pose_apply": (c_int, [c_int, c_int, c_int] + [c_vp] * 8 + [c_vp]),
+    "mgr_pose_backward": (c_int, [c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_vp]),
+    "mgr_pose_adam": (c_int, [c_int, c_int] + [c_vp] * 9 + [ctypes.c_double] * 5 + [c_int, c_vp]),
     "mgr_project_points": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_dilate_mask": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "mgr_points_outside_mask": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),

@@ -11,6 +11,7 @@
 //   SH colour      src/utils/gaussian_utils.py:431-449; src/utils/sh_utils.py:57-104
 //   projection     src/utils/transforms.py:304-311
 //   L1 loss        src/utils/loss_utils.py:22-27
+#include "bone_math.h"
 #include "instance_math.h"
 #include "skin_tri.h"
 
@@ -870,60 +871,19 @@ extern "C" int mgr_pack_camera(float tanfovx, float tanfovy, const float* view16
 }
 
 // One thread per bone: T_b = posed_b @ inv(rest_b), the inverse by Gauss-Jordan elimination with partial pivoting in fp32
-// (the operation count and pivoting of the LU route torch.linalg.inv takes; results agree with it to fp32 roundoff).
-// A singular rest matrix gives non-finite entries, like the reference's inverse raising would stop the step.
+// (bone_math.h: the device functions are shared with the pose chain of pose.hip, which must reproduce these bits).
 __global__ __launch_bounds__(64) void k_bone_transforms(int B, int background, const float* __restrict__ posed,
                                                         const float* __restrict__ rest, float* __restrict__ out) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B + (background ? 1 : 0)) return;
     float* o = out + (size_t)b * 16;
     if (b >= B) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) o[k] = (k % 5 == 0) ? 1.f : 0.f;
+        bone_identity(o);
         return;
     }
     float a[4][8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            a[r][c] = rest[(size_t)b * 16 + r * 4 + c];
-            a[r][4 + c] = r == c ? 1.f : 0.f;
-        }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        float best = fabsf(a[c][c]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (r > c && fabsf(a[r][c]) > best) { best = fabsf(a[r][c]); piv = r; }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (r == piv && r != c) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { const float t = a[c][k]; a[c][k] = a[r][k]; a[r][k] = t; }
-            }
-        const float inv = 1.0f / a[c][c];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) a[c][k] *= inv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (r != c) {
-                const float f = a[r][c];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) a[r][k] -= f * a[c][k];
-            }
-    }
-    const float* p = posed + (size_t)b * 16;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc += p[r * 4 + k] * a[k][4 + c];
-            o[r * 4 + c] = acc;
-        }
+    bone_invert(rest + (size_t)b * 16, a);
+    bone_mul_inverse(posed + (size_t)b * 16, a, o);
 }
 
 extern "C" int mgr_bone_transforms(int B, int background, const float* posed, const float* rest, float* out, void* stream_) {

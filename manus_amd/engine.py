@@ -213,8 +213,10 @@ class ViewShardedStep:
         if not packed:
             res = dict(grads=out["grads"], grad2d=out["grad2d"], vis=out["vis"], radii=radii, loss=out["loss"],
                        overflow=out.get("overflow"))
-            if "loss_lpips" in out:
-                res["loss_lpips"] = out["loss_lpips"]
+            # (one rank, nothing to reduce: what the compute object returned beside the reduced quantities travels as it is)
+            for name in ("loss_lpips", "d_transforms", "d_skin_grid", "loss_mask", "loss_depth"):
+                if name in out:
+                    res[name] = out[name]
             return res
         if self._store is None or self._store.device != dev:
             self._alloc(dev)
@@ -767,6 +769,29 @@ class HipViewCompute:
         version counters do not see (a kernel given the raw pointer: `frames.FrameStore`): everything derived from them is
         rebuilt by the next step, and the depth-cut hints of the views rendered so far are dropped."""
         self._drop_view_constants()
+        self._cut.new_generation()
+
+    def gathered_transforms(self, view_ids):
+        """The contiguous (len(view_ids),B+1,4,4) copy of the transforms the kernels read for exactly this view set, when one is
+        cached and still valid; else None (the next step gathers it from the table)."""
+        if not self.is_hand:
+            return None
+        self._check_view_constants()
+        c = self._cache.get(tuple(view_ids))
+        return None if c is None else c.get("T")
+
+    def transforms_changed(self, written=None):
+        """ONLY the scene's transforms moved, written through a raw pointer (`pose.PoseRefiner.apply`): the gathered transforms
+        of the cached view set are refreshed from the table -- unless it is the view set `written`, whose gathered copy
+        (`gathered_transforms`) the writer has filled itself -- and the depth-cut hints of the views rendered so far are
+        dropped.  Everything that depends on the targets alone is kept: the gathered targets and cameras, target maps, mask and
+        depth gathers, LPIPS windows and the cached target taps.  (`view_constants_changed()` drops all of it.)"""
+        if self.is_hand:
+            self._check_view_constants()
+            skip = None if written is None else tuple(written)
+            for key, c in self._cache.items():
+                if key != skip and c.get("T") is not None:
+                    c["T"].copy_(self.s["transforms"][list(key)])
         self._cut.new_generation()
 
     def _check_view_constants(self):
@@ -1380,6 +1405,36 @@ class HipViewCompute:
         return out
 
 
+class FrameSchedule:
+    """Which items of a `frames.FrameStore` a step looks at: epoch e is a permutation of the store's items drawn from
+    numpy.random.default_rng((seed, e)) ("shuffle") or their stored order ("sequential"), consumed `views_per_step` at a time; a
+    tail shorter than that is dropped.  `items(step)` is a pure function of (seed, step).  The reference trains one shuffled
+    (frame, view) per step (its DataLoader shuffles the items); this is that order, batched build-side."""
+
+    def __init__(self, store, views_per_step, seed=0, order="shuffle"):
+        if order not in ("shuffle", "sequential"):
+            raise ValueError("order must be 'shuffle' or 'sequential' (got %r)" % (order,))
+        self.store, self.views_per_step, self.seed, self.order = store, int(views_per_step), int(seed), order
+        self.pool = [int(i) for i in store.items]
+        if self.views_per_step < 1 or len(self.pool) < self.views_per_step:
+            raise ValueError("FrameSchedule: %d items cannot fill a step of %d views" % (len(self.pool), self.views_per_step))
+        self.steps_per_epoch = len(self.pool) // self.views_per_step
+        self._epoch = None          # (e, its item list)
+
+    def epoch(self, e):
+        """The items of epoch e in the order they are consumed (the dropped tail included)."""
+        if self._epoch is None or self._epoch[0] != e:
+            import numpy as np
+            n = len(self.pool)
+            perm = np.arange(n) if self.order == "sequential" else np.random.default_rng((self.seed, int(e))).permutation(n)
+            self._epoch = (e, [self.pool[int(j)] for j in perm])
+        return list(self._epoch[1])
+
+    def items(self, step):
+        e, k = divmod(int(step), self.steps_per_epoch)
+        return self.epoch(e)[k * self.views_per_step:(k + 1) * self.views_per_step]
+
+
 class Trainer:
     """One optimisation step in the reference's order (src/modules/hand_dynamic.py:230-282 + Lightning's hooks):
 
@@ -1394,11 +1449,42 @@ class Trainer:
     synchronisation; every step is fenced (`rasterizer.poll`: waits for the forward only) and re-run with a larger
     pair capacity if it overflowed, so no update is ever made from a truncated image.
     Multi-GPU: every rank must draw the same split noise, so rank 0's is broadcast; the pruning masks are OR-ed
-    over the ranks; max_radii2D is MAX-reduced before it is consumed."""
+    over the ranks; max_radii2D is MAX-reduced before it is consumed.
+
+    Drawn frames and pose refinement (one rank; both None: exactly the step above on the fixed views 0 .. n_views - 1).
+    frames: a `FrameSchedule` of n_views views per step -- before the step, the rows 0 .. n_views - 1 of the compute object's
+    tables are pointed at `frames.items(global_step)` (`FrameStore.load_step`; `last_items` keeps the list).  pose: a
+    `pose.PoseRefiner` -- at the global steps g >= pose_from_iter with (g - pose_from_iter) % pose_every == 0 the corrected
+    transforms of the step's frames are written before the step (`PoseRefiner.apply`) and the corrections take their own Adam
+    step on `out["d_transforms"]` behind the Gaussians' optimizer step (`PoseRefiner.step`); a re-run after an overflow uses
+    the same items and transforms.  Without `frames`, pose_frames gives the frame row of each of the fixed views.  On a step
+    at which the corrections are NOT applied (before pose_from_iter, between pose_every steps) the two modes differ: with
+    `frames`, `load_step` has just written the items' UNCORRECTED transforms, so the Gaussians train on those; on a fixed view
+    set the table keeps the transforms of the last `apply`.  The pruning tests (`compute.prune_views`) keep testing against the
+    DATASET's keypoints, not the corrected ones; their masks and cameras are those of the drawn items
+    (`load_step(scene_masks=True)`), with or without a mask table on the compute object."""
 
     def __init__(self, compute, n_views, extent, opts=None, spatial_lr_scale=1.0, rank=0, world_size=1, group=None,
                  bg_white=True, kind=None, compact_allreduce=False, sharded_adam=False, view_weights=None, depth_cut=False,
-                 sort_rows=False, persistent_grads=True, start_lpips_iter=1000):
+                 sort_rows=False, persistent_grads=True, start_lpips_iter=1000, frames=None, pose=None, pose_from_iter=0,
+                 pose_every=1, pose_frames=None):
+        if frames is not None:
+            if world_size > 1:
+                raise ValueError("Trainer(frames=...) needs world_size == 1: the frame pool is one rank's")
+            if frames.views_per_step != n_views:
+                raise ValueError("Trainer: the schedule draws %d views per step, n_views is %d" % (frames.views_per_step, n_views))
+        if pose is not None:
+            if not getattr(compute, "pose_grad", False):
+                raise ValueError("Trainer(pose=...) needs a compute object with pose_grad=True (its step returns d_transforms)")
+            if world_size > 1:
+                raise ValueError("Trainer(pose=...) needs world_size == 1: d_transforms is not reduced across ranks")
+            if int(pose_every) < 1:
+                raise ValueError("pose_every must be at least 1")
+            if frames is None and (pose_frames is None or len(pose_frames) != n_views):
+                raise ValueError("Trainer(pose=...) without frames needs pose_frames: one frame row per view of the fixed set")
+        self.frames, self.pose, self.pose_from_iter, self.pose_every = frames, pose, int(pose_from_iter), int(pose_every)
+        self.pose_frames = None if pose_frames is None else [int(f) for f in pose_frames]
+        self.last_items = None          # with frames: the dataset items of the last step
         # sharded_adam (world_size > 1): reduce-scatter of the gradients -> every rank takes the Adam step on the 1/world
         # of the parameter elements it owns -> all-gather of the parameters.  The same bytes on the wire as the
         # all-reduce (which is a reduce-scatter followed by an all-gather), 1/world of the optimizer work per rank.
@@ -1572,6 +1658,22 @@ class Trainer:
             res["lpips"] = lps
         return res
 
+    def _point_views(self, gs):
+        """Before the step at global step gs: the drawn items into the compute object's rows, then the pose corrections into
+        its transforms.  -> (view ids, frame rows) when the corrections were applied (they take their step behind this one's
+        backward), else None."""
+        c, ids = self.compute, list(self.stepper.local_views)
+        if self.frames is not None:
+            self.last_items = self.frames.items(gs)
+            # (scene_masks: without a mask table the pruning masks of the scene still follow the drawn items)
+            self.frames.store.load_step(c, self.last_items, masks=c.mask_targets is not None, lpips_rects=c.lpips_rects is not None,
+                                        scene_masks=True)
+        if self.pose is None or gs < self.pose_from_iter or (gs - self.pose_from_iter) % self.pose_every != 0:
+            return None
+        rows = self.pose.frames_of(self.frames.store, self.last_items) if self.frames is not None else self.pose_frames
+        self.pose.apply(c, ids, rows)
+        return ids, rows
+
     def train_step(self, views=None):
         """One optimisation step; returns the step's output dict (loss, statistics) plus "changed".
         views: optional list of per-view dicts for the pruning tests (default: `compute.prune_views`).
@@ -1583,6 +1685,7 @@ class Trainer:
         o, gs = self.opt.opts, self.global_step
         if getattr(self.compute, "lpips", None) is not None:
             self.compute.lpips_on = gs >= self.start_lpips_iter
+        posed_step = self._point_views(gs) if (self.frames is not None or self.pose is not None) else None
         out = self._run_step()
         if not self.density_enabled:     # composite: render + reduce + Adam only (see __init__)
             self.opt.update_learning_rate(gs)
@@ -1594,6 +1697,8 @@ class Trainer:
                 self.opt.step(out["grads"])
             if hasattr(self.compute, "mark_params_changed"):
                 self.compute.mark_params_changed()
+            if posed_step is not None:
+                self.pose.step(out["d_transforms"], *posed_step)
             self.global_step += 1
             out["changed"] = False
             return out
@@ -1647,6 +1752,8 @@ class Trainer:
             self.opt.step(out["grads"])   # skips the groups replaced above (all of them after a densify / prune)
         if hasattr(self.compute, "mark_params_changed"):
             self.compute.mark_params_changed()
+        if posed_step is not None:
+            self.pose.step(out["d_transforms"], *posed_step)
         self.global_step += 1
         if resized:
             self.compute.set_params(self.opt.parameters(), None)

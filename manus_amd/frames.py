@@ -61,6 +61,7 @@ class FrameStore:
     height, width, k    output size and the block size of the resize (source frame = output size times k)
     cam_rows (n,40), transforms (n,J+1,4,4), posed (n,J,4,4), keypoints (n,J+1,3)    on the device, only from `from_dataset`: the
               per-item camera rows and poses `load_step` copies into a compute object's tables
+    frame_keys    per row the (action, frame_id) of the item, host, only from `from_dataset`
     """
 
     def __init__(self, pool, offsets, bboxes, height, width, k=1, items=None):
@@ -72,7 +73,9 @@ class FrameStore:
         self.row = {it: j for j, it in enumerate(self.items)}
         self.cam_rows = self.transforms = self.posed = self.keypoints = None
         self.cameras = None          # per row the camera dict of the dataset (host)
+        self.frame_keys = None       # per row the (action, frame_id) of the item (host; `from_dataset`): the rows of `pose.PoseRefiner`
         self._state = {}             # (targets.data_ptr(), slot) -> (weak reference to the table, rectangle, background, masks pointer)
+        self._scene_masks = None     # (targets.data_ptr(), float table): masks decoded for a scene's pruning masks alone (`load_step(scene_masks=True)`)
         self._bg_host = None         # (id, version) of a compute object's background tensor and its three floats
         if len(self.offsets) != len(self.items) or len(self.bboxes) != len(self.items):
             raise ValueError("offsets, bboxes and items must have one entry per crop")
@@ -142,6 +145,7 @@ class FrameStore:
             tfs.append(T.bone_transforms(p, it["bones_rest"].transforms.cpu().float()))
             keyp.append(sk["keypoints"][0].float())
         st.cameras = cams
+        st.frame_keys = [tuple(ds.index_list[i][:2]) for i in indices]
         if indices:
             st.cam_rows = torch.stack(cam_rows).to(device)
             st.transforms, st.posed, st.keypoints = torch.stack(tfs).to(device), torch.stack(posed).to(device), torch.stack(keyp).to(device)
@@ -248,14 +252,17 @@ class FrameStore:
             self._bg_host = (key, np.asarray(bg.detach().cpu(), np.float32).reshape(3))
         return self._bg_host[1]
 
-    def load_step(self, compute, items, slots=None, masks=False, lpips_rects=False):
+    def load_step(self, compute, items, slots=None, masks=False, lpips_rects=False, scene_masks=False):
         """Point the rows `slots` (default 0 .. len(items) - 1) of an `engine.HipViewCompute` at the dataset items `items`:
         their targets decoded into `compute.targets`, their masks into `compute.mask_targets` (when that is set; masks=True
         allocates a zero table and sets it when it is not), their camera rows into `compute.cams`, their bone transforms (and
         posed transforms, keypoints, camera dicts, pruning masks where the scene holds them) into the scene's tables, all in
         place; the compute object is told, so its next step rebuilds what it derives from them.  lpips_rects=True also writes
         the slots' rows of `compute.lpips_rects` with the items' windows (`lpips_rects(items)`), allocating a table of full-frame
-        rectangles first when the compute object has none."""
+        rectangles first when the compute object has none.  scene_masks=True: when the compute object has NO mask table but the
+        scene holds pruning masks (`s["masks"]`, what `HipViewCompute.prune_views` hands the pruning tests), the items' masks are
+        decoded into a table the store keeps and copied into the scene's rows all the same -- the mask loss term stays off --,
+        so that a pruning test never meets a drawn item's camera with another item's mask."""
         if self.cam_rows is None:
             raise ValueError("load_step needs the camera rows and poses of a store built by FrameStore.from_dataset")
         items = [int(i) for i in items]
@@ -264,6 +271,17 @@ class FrameStore:
         mt = compute.mask_targets
         if mt is None and masks:
             mt = torch.zeros((compute.targets.shape[0], self.height, self.width), dtype=torch.float32, device=compute.targets.device)
+        if mt is None and scene_masks and torch.is_tensor(s.get("masks")) and \
+                tuple(s["masks"].shape) == (int(compute.targets.shape[0]), self.height, self.width):
+            key = compute.targets.data_ptr()
+            if self._scene_masks is None or self._scene_masks[0] != key or self._scene_masks[1].device != compute.targets.device \
+                    or self._scene_masks[1].shape != s["masks"].shape:
+                self._scene_masks = (key, torch.zeros(tuple(s["masks"].shape), dtype=torch.float32, device=compute.targets.device))
+                self.invalidate(compute.targets)      # (a new masks table: the next decode writes whole images)
+            mt = self._scene_masks[1]
+            decoded_for_scene = True
+        else:
+            decoded_for_scene = False
         self.decode(items, self._compute_bg(compute), compute.targets, mt, slots)
         dev = compute.cams.device
         rows_t = torch.tensor([self.row[i] for i in items], dtype=torch.long, device=dev)
@@ -281,7 +299,7 @@ class FrameStore:
                 s["cameras"][slot] = self.cameras[self.row[i]]
         if mt is not None and torch.is_tensor(s.get("masks")) and s["masks"] is not mt and s["masks"].shape == mt.shape:
             s["masks"].index_copy_(0, slots_t, mt.index_select(0, slots_t).to(s["masks"].dtype))
-        if mt is not compute.mask_targets:
+        if mt is not compute.mask_targets and not decoded_for_scene:
             compute.mask_targets = mt
         if lpips_rects:
             table = compute.lpips_rects

@@ -1,10 +1,16 @@
 """Pose refinement on top of the pose gradient (`HipViewCompute(pose_grad=True)`, `ops.lbs_cov` with a differentiable
 `transforms`): a per-frame, per-bone correction of the posed bone matrices and the chain rule from dL/d(bone transforms) back
-to them.  Plain host torch on B small matrices.
+to them.
+
+Two forms of the same chain.  `PoseCorrection` / `pose_backward` are plain host torch on B small matrices under autograd: the
+form the tests check against, and what validation and contact renders call.  `PoseRefiner` is the chain on the device (csrc/pose.hip: apply,
+backward, row Adam; three launches per step, no autograd graph, no read-back), which `engine.Trainer(pose=...)` schedules.
 
 No reference counterpart: the reference's config/model/pose_optimizer.yaml names `src.models.pose_optimizer`, which was
-never released.  `Trainer` does not schedule pose refinement; a caller drives it (tests/test_gpu_pose_grad.py)."""
+never released."""
 import torch
+
+from ._lib import MGR_MAX_BONES, check, lib, ptr, stream
 
 
 def _exp_so3(r):
@@ -51,3 +57,155 @@ def pose_backward(d_transforms, posed, rest, background=True):
         raise ValueError("pose_backward: %s transforms for %s posed matrices" % (tuple(dT.shape), tuple(posed.shape)))
     inv_t = torch.linalg.inv(rest.to(device=dT.device, dtype=posed.dtype)).transpose(-1, -2)
     return dT.to(posed.dtype) @ inv_t
+
+
+class PoseRefiner:
+    """The correction tables of `PoseCorrection` -- rotvec and trans (F,B,3), zero at the start -- kept, applied, differentiated
+    and stepped on the device (mgr_pose_apply / mgr_pose_backward / mgr_pose_adam).
+
+    frame_keys: the (action, frame_id) pairs the rows stand for, e.g. those of `SequenceDataset.index_list` (its triples are
+    accepted, the camera is ignored; repeats count once, in first-seen order).  rest (B,4,4): the rest matrices of the bones.
+    The optimizer is the row Adam of `optim.SkinGridAdam` (torch.optim.SparseAdam's semantics: only the frames a step shows
+    move, the bias correction uses the global count `steps`), with a rate each for rotations and translations and no clamp;
+    the moments are allocated at the first step.
+
+        frames = refiner.frames_of(store, items)             # one row per view, -1: no correction
+        refiner.apply(compute, view_ids, frames)             # corrected transforms into the compute object's tables
+        out = compute(view_ids, scale)                       # HipViewCompute(pose_grad=True)
+        refiner.step(out["d_transforms"], view_ids, frames)"""
+
+    def __init__(self, frame_keys, n_bones, rest, lr_rot, lr_trans, betas=(0.9, 0.999), eps=1e-8, device=None):
+        self.frame_keys = list(dict.fromkeys((k[0], k[1]) for k in frame_keys))
+        self.row = {k: j for j, k in enumerate(self.frame_keys)}
+        F, B = len(self.frame_keys), int(n_bones)
+        if F < 1:
+            raise ValueError("PoseRefiner needs at least one frame")
+        if not 1 <= B <= MGR_MAX_BONES:
+            raise ValueError("PoseRefiner: n_bones must be 1 .. %d (got %d)" % (MGR_MAX_BONES, B))
+        rest = torch.as_tensor(rest)
+        self.device = torch.device(device if device is not None else rest.device)
+        if tuple(rest.shape) != (B, 4, 4):
+            raise ValueError("PoseRefiner: rest must be (%d,4,4) (got %s)" % (B, tuple(rest.shape)))
+        self.rest = rest.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.n_frames, self.n_bones = F, B
+        self.lr_rot, self.lr_trans = float(lr_rot), float(lr_trans)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.rotvec = torch.zeros((F, B, 3), dtype=torch.float32, device=self.device)
+        self.trans = torch.zeros((F, B, 3), dtype=torch.float32, device=self.device)
+        self.m_r = self.v_r = self.m_t = self.v_t = None
+        self.steps = 0
+        self.last_grad = None           # (frames listed, d_rotvec (U,B,3), d_trans (U,B,3)) of the last step
+        self._posed = None              # the posed table of the compute object last applied to
+        self._lists = {}                # (view ids, frames) -> their device lists
+
+    # -- host lists ------------------------------------------------------------------------------------------------------
+    def frames_of(self, store, items):
+        """The rows of the dataset items `items` of a `frames.FrameStore` built by `from_dataset`; -1 (no correction) for an
+        item whose frame is not among `frame_keys`."""
+        if getattr(store, "frame_keys", None) is None:
+            raise ValueError("frames_of needs the frame keys of a store built by FrameStore.from_dataset")
+        return [self.row.get(store.frame_keys[store.row[int(i)]], -1) for i in items]
+
+    def _device_lists(self, view_ids, frames):
+        """(view rows, frame of view, frames listed: int32 device tensors; the listed frames on the host) of one step.  The
+        host drew the views, so the unique frames are listed here, ascending: nothing is read back from the device."""
+        key = (tuple(int(v) for v in view_ids), tuple(int(f) for f in frames))
+        if len(key[0]) != len(key[1]) or not key[0]:
+            raise ValueError("PoseRefiner: one frame row per view, at least one view (got %d views, %d frames)" % (len(key[0]), len(key[1])))
+        ent = self._lists.get(key)
+        if ent is None:
+            if any(f >= self.n_frames for f in key[1]):
+                raise ValueError("PoseRefiner: a frame row beyond the %d frames" % self.n_frames)
+            if min(key[0]) < 0:
+                raise ValueError("PoseRefiner: negative view id")
+            listed = sorted({f for f in key[1] if f >= 0})
+            # the three lists in one host buffer and one copy (pinned and asynchronous where the host allows it): a shuffled
+            # schedule brings a new key almost every step
+            V, U = len(key[0]), len(listed)
+            host = torch.tensor(list(key[0]) + list(key[1]) + listed, dtype=torch.int32)
+            if self.device.type == "cuda":
+                try:
+                    host = host.pin_memory()
+                except RuntimeError:
+                    pass
+            buf = host.to(self.device, non_blocking=True)
+            ent = (buf[:V], buf[V:2 * V], buf[2 * V:] if U else None, listed, host)      # (host: alive until the copy has run)
+            if len(self._lists) >= 256:
+                self._lists.clear()
+            self._lists[key] = ent
+        return ent
+
+    # -- the three launches -----------------------------------------------------------------------------------------------
+    def apply(self, compute, view_ids, frames):
+        """Corrected bone transforms of the views `view_ids` (frame rows `frames`, -1: uncorrected) from `compute.s["posed"]`
+        into `compute.s["transforms"]`, and into the gathered copy of that view set when the compute object holds one; then
+        `compute.transforms_changed()`.  Rows of other views stay as they are."""
+        s, B = compute.s, self.n_bones
+        posed, tfm = s.get("posed"), s.get("transforms")
+        if not torch.is_tensor(posed) or not torch.is_tensor(tfm):
+            raise ValueError("PoseRefiner.apply: the scene holds no posed / transforms tables")
+        n_all = tfm.shape[0]
+        if tuple(posed.shape) != (n_all, B, 4, 4) or tuple(tfm.shape) != (n_all, B + 1, 4, 4) or posed.dtype != torch.float32 \
+                or tfm.dtype != torch.float32:
+            raise ValueError("PoseRefiner.apply: posed %s / transforms %s are not the float32 tables (V,%d,4,4) / (V,%d,4,4)"
+                             % (tuple(posed.shape), tuple(tfm.shape), B, B + 1))
+        rows, fov = self._device_lists(view_ids, frames)[:2]
+        if max(int(v) for v in view_ids) >= n_all:
+            raise ValueError("PoseRefiner.apply: a view id beyond the %d views of the tables" % n_all)
+        gathered = compute.gathered_transforms(view_ids)
+        check(lib().mgr_pose_apply(len(view_ids), B, self.n_frames, ptr(rows), ptr(fov), ptr(posed), ptr(self.rest), ptr(self.rotvec),
+                                   ptr(self.trans), ptr(tfm), ptr(gathered), stream()), "mgr_pose_apply")
+        self._posed = posed
+        compute.transforms_changed(written=view_ids if gathered is not None else None)
+
+    def step(self, d_transforms, view_ids, frames):
+        """One Adam step of the frames the views show, from the step's `out["d_transforms"]` (len(view_ids),B+1,4,4) at the
+        transforms the last `apply` wrote.  Views with frame -1 contribute nothing; with no frame at all nothing happens."""
+        if self._posed is None:
+            raise ValueError("PoseRefiner.step before apply")
+        B, V = self.n_bones, len(view_ids)
+        if tuple(d_transforms.shape) != (V, B + 1, 4, 4) or d_transforms.dtype != torch.float32:
+            raise ValueError("PoseRefiner.step: d_transforms %s is not float32 (%d,%d,4,4)" % (tuple(d_transforms.shape), V, B + 1))
+        rows, fov, listed_t, listed = self._device_lists(view_ids, frames)[:4]
+        if not listed:
+            return
+        U = len(listed)
+        if self.m_r is None:
+            self.m_r, self.v_r, self.m_t, self.v_t = (torch.zeros_like(self.rotvec) for _ in range(4))
+        g_r = torch.empty((U, B, 3), dtype=torch.float32, device=self.device)
+        g_t = torch.empty((U, B, 3), dtype=torch.float32, device=self.device)
+        L = lib()
+        check(L.mgr_pose_backward(V, B, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self._posed), ptr(self.rest),
+                                  ptr(self.rotvec), ptr(self.trans), ptr(d_transforms), ptr(g_r), ptr(g_t), stream()), "mgr_pose_backward")
+        self.steps += 1
+        check(L.mgr_pose_adam(U, B, ptr(listed_t), ptr(g_r), ptr(g_t), ptr(self.rotvec), ptr(self.trans), ptr(self.m_r), ptr(self.v_r),
+                              ptr(self.m_t), ptr(self.v_t), self.lr_rot, self.lr_trans, self.betas[0], self.betas[1], self.eps, self.steps,
+                              stream()), "mgr_pose_adam")
+        self.last_grad = (listed, g_r, g_t)
+
+    # -- state --------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        return dict(frame_keys=list(self.frame_keys), steps=self.steps, rotvec=self.rotvec.clone(), trans=self.trans.clone(),
+                    **{k: (getattr(self, k).clone() if getattr(self, k) is not None else None) for k in ("m_r", "v_r", "m_t", "v_t")})
+
+    def load_state_dict(self, state):
+        if [tuple(k) for k in state["frame_keys"]] != self.frame_keys:
+            raise ValueError("PoseRefiner.load_state_dict: the state is of other frames")
+        for k in ("rotvec", "trans"):
+            if tuple(state[k].shape) != tuple(self.rotvec.shape):
+                raise ValueError("PoseRefiner.load_state_dict: %s %s, expected %s" % (k, tuple(state[k].shape), tuple(self.rotvec.shape)))
+            getattr(self, k).copy_(state[k])
+        for k in ("m_r", "v_r", "m_t", "v_t"):
+            t = state.get(k)
+            setattr(self, k, None if t is None else t.detach().to(device=self.device, dtype=torch.float32).clone().contiguous())
+        self.steps = int(state["steps"])
+
+    def as_module(self):
+        """A `PoseCorrection` on the SAME storage (its parameters see every later step): what validation and contact renders
+        pose with, `module(posed, frame)`.  Just above the series threshold (|r|^2 in [1e-6, ~1e-5]) the module's fp32
+        `_exp_so3` forms (1 - cos th) / th^2 with up to 2.7 % error where the kernel takes it from sin^2(th / 2): the two
+        rotations differ by about 1e-8 there, the rounding of the host form, not another function."""
+        m = PoseCorrection(self.n_frames, self.n_bones, device=self.device)
+        m.rotvec = torch.nn.Parameter(self.rotvec, requires_grad=False)
+        m.trans = torch.nn.Parameter(self.trans, requires_grad=False)
+        return m
