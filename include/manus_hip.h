@@ -893,6 +893,40 @@ int mgr_lpips_roi(int net, int V, int H, int W, const int* rects, const float* p
                   const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
                   int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A step's equal-size windows in one batched call (the mgr_lpips_roi*_batch* entries).  mgr_lpips_roi_batch_op batches
+ * mgr_lpips_roi_op: the same arguments and a trailing max_batch, the same refusals, and bit for bit the same values and
+ * gradient frames -- in every kernel an output depends on the sizes alone, so the batch coordinate changes no sum.  On the host,
+ * before the first launch, the non-empty views are grouped by (w, h) in ascending view order and every group is cut into chunks
+ * of at most min(max_batch, LP_MAX_BATCH) views; the chunks run in the order of their first view, and a chunk of G views is ONE
+ * chain of launches: the convolutions carry (batch, output-channel block) in blockIdx.z, the scaling kernels a per-launch
+ * table of (view, x0, y0), the head one grid row and the fold one workgroup per view.  Empty views are handled as in
+ * mgr_lpips_roi_op.  A chunk's target tower runs, batched among themselves, for those of its views that have no cached taps.
+ *
+ * Workspace of a chunk of G views: the one-view layout (mgr_lpips_layout) with every region G times as long, batch-major --
+ * view b of a buffer of e elements sits at b e.  mgr_lpips_roi_batch_workspace_bytes is the largest chunk's; with max_batch = 1
+ * it is mgr_lpips_roi_workspace_bytes and the call is the sequential one.
+ *
+ * mgr_lpips_roi_taps_batch_op batches mgr_lpips_roi_taps_op over the V views of a call: target (V,3,H,W), mask (V,H,W) or NULL,
+ * rects HOST (V,4), taps_out a HOST array of V DEVICE pointers (mgr_lpips_taps_bytes(net, h, w) bytes each; ignored, and
+ * normally NULL, for an empty view).  Every view's buffer ends up exactly as mgr_lpips_roi_taps_op leaves it.  Its workspace is
+ * mgr_lpips_roi_batch_workspace_bytes(net, V, rects, 0, max_batch).
+ *
+ * Refused in addition to what the sequential entries refuse, on the host before any launch (no buffer touched): max_batch < 1
+ * (-1; the size query returns 0), a workspace below the batched size (-2), a non-empty view of the taps build without a buffer. */
+#define LP_MAX_BATCH 16 /* the most views of one launch: keeps the per-launch tables well inside the kernel-argument space */
+size_t mgr_lpips_roi_batch_workspace_bytes(int net, int V, const int* rects, int need_grad, int max_batch);
+int mgr_lpips_roi_taps_batch_op(int net, int V, int H, int W, const int* rects, const float* target, const float* mask, const void* blob,
+                                size_t blob_bytes, int normalize, float* const* taps_out, int max_batch, void* workspace,
+                                size_t workspace_bytes, void* stream, int operands);
+int mgr_lpips_roi_batch_op(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                           const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
+                           int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream,
+                           int operands, int max_batch);
+int mgr_lpips_roi_batch(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                        const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
+                        int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream,
+                        int max_batch);
+
 /* ------------------------------------------------------------------------
  * Device frame store: the stored uint8 RGBA crops of a capture decoded into the float targets and masks of a step
  * (manus_amd/frames.py; SequenceDataset.fetch_images, brics_dynamic.py:343-373, restated bit for bit).

@@ -29,13 +29,22 @@
 // adds the gradient into the rectangle, or writes the whole frame with zeros outside it; the arithmetic per element is
 // k_lp_scale's, so a window is the call on .contiguous() crops bit for bit -- the crop's own zero padding and spatial means, not
 // the full-frame value restricted to a region.  mgr_lpips_roi_taps_op leaves the target tower's five taps of a window in a
-// caller's buffer; a call given it skips that tower (same kernels, same bits).  k_lp_conv / k_lp_conv16 are untouched.
+// caller's buffer; a call given it skips that tower (same kernels, same bits).
+//
+// Batches (mgr_lpips_roi_batch_op, mgr_lpips_roi_taps_batch_op): the views of a call that share a window size run as chunks of at
+// most LP_MAX_BATCH views, one chain of launches per chunk, on a workspace with every region G times as long, batch-major.  The
+// convolutions carry (batch, output-channel block) in blockIdx.z and offset x / gate / y by their own Cin H W and Cout Ho Wo;
+// pools run on G C channels; the scaling kernels take a per-launch table of (view, x0, y0), the head per-view target pointers
+// and scales, the fold one workgroup per view.  No sum changes: a batched call is the sequential call bit for bit, and every
+// other call of this file is the batch of one view.
 //
 // Spatial means travel as fp64 partials over a fixed tree (as k_map_loss does); no float atomics anywhere: bit-reproducible.
 //
 // One deviation from autograd: where a pixel's tap features are all zero, autograd through sqrt yields 0 * inf = NaN; here
 // that pixel contributes a zero gradient (the skip rule of a zero skin-weight sum, include/manus_hip.h).
 #include "mgr_common.h"
+
+#include <vector>
 
 typedef float lp_f16v __attribute__((ext_vector_type(16)));
 typedef __bf16 lp_bf8 __attribute__((ext_vector_type(8)));
@@ -140,12 +149,14 @@ static bool lp_shapes(const LpNet& n, int H, int W, LpShape* S) {
 }
 
 // workspace: [pred's convolution outputs, in layer order][target's five taps][scratch A][scratch B][fp64 partials]
+// A chunk of G equal-size views (the batched entries) has every region G times as long, batch-major: view b of a buffer of e
+// elements sits at b e, view b's partials at b part_off[LP_NTAP].  G = 1 is the one-view layout.
 struct LpLayout {
     size_t act[13], tap[LP_NTAP], bufa, bufb, part, total;
     size_t part_off[LP_NTAP + 1];      // in doubles: the slots of tap k are [part_off[k], part_off[k + 1])
 };
 
-static bool lp_layout(const LpNet& n, int H, int W, int need_grad, LpLayout* L) {
+static bool lp_layout(const LpNet& n, int H, int W, int need_grad, LpLayout* L, size_t G = 1) {
     LpShape S;
     if (H < 1 || W < 1 || (long long)H * W > (1ll << 24) || !lp_shapes(n, H, W, &S)) return false;
     size_t o = 0, scratch = (size_t)3 * H * W;
@@ -156,20 +167,20 @@ static bool lp_layout(const LpNet& n, int H, int W, int need_grad, LpLayout* L) 
         // scratch holds: the scaled image, every pool output, the target's convolution outputs that are no tap, and (with a
         // gradient) the gradient w.r.t. any of them
         if (!op.conv || op.tap < 0 || need_grad) scratch = scratch > e ? scratch : e;
-        if (op.conv) { L->act[ci++] = o;  o += mgr_align(e * 4); }
+        if (op.conv) { L->act[ci++] = o;  o += mgr_align(G * e * 4); }
     }
     for (int i = 0; i < n.n_ops; ++i) {
         const LpOp& op = n.ops[i];
         if (op.conv && op.tap >= 0) {
-            L->tap[op.tap] = o;  o += mgr_align((size_t)op.cout * S.h[i] * S.w[i] * 4);
+            L->tap[op.tap] = o;  o += mgr_align(G * op.cout * S.h[i] * S.w[i] * 4);
             L->part_off[op.tap + 1] = ((size_t)S.h[i] * S.w[i] + LP_T - 1) / LP_T;
         }
     }
     L->part_off[0] = 0;
     for (int k = 0; k < LP_NTAP; ++k) L->part_off[k + 1] += L->part_off[k];
-    L->bufa = o;  o += mgr_align(scratch * 4);
-    L->bufb = o;  o += mgr_align(scratch * 4);
-    L->part = o;  o += mgr_align(L->part_off[LP_NTAP] * 8);
+    L->bufa = o;  o += mgr_align(G * scratch * 4);
+    L->bufb = o;  o += mgr_align(G * scratch * 4);
+    L->part = o;  o += mgr_align(G * L->part_off[LP_NTAP] * 8);
     L->total = o;
     return true;
 }
@@ -206,8 +217,9 @@ __global__ __launch_bounds__(LP_T) void k_lp_copy(int n, const float* __restrict
 // ---------------------------------------------------------------------------
 // convolution
 // ---------------------------------------------------------------------------
+// blockIdx.z = batch NZ + (block of 64 output channels); view b's x / gate sit at b Cin H W, its y at b Cout Ho Wo
 struct LpConvArgs {
-    int Cin, Cout, CoP, H, W, Ho, Wo, KH, KW, stride, pad, CK, relu;
+    int Cin, Cout, CoP, H, W, Ho, Wo, KH, KW, stride, pad, CK, relu, NZ;
     const float *x, *gate, *wp, *bias;
     float* y;
 };
@@ -219,9 +231,14 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv(const LpConvArgs a) {
     const int KK = KH * KW;
     const int PH = (LP_TH - 1) * st + KH, PW = (LP_TW - 1) * st + KW;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-    const int ox0 = blockIdx.x * LP_TW, oy0 = blockIdx.y * LP_TH, co0 = blockIdx.z * LP_TC;
+    const int zb = blockIdx.z / a.NZ;
+    const int ox0 = blockIdx.x * LP_TW, oy0 = blockIdx.y * LP_TH, co0 = (blockIdx.z - zb * a.NZ) * LP_TC;
     const int ix0 = ox0 * st - pad, iy0 = oy0 * st - pad;
     const bool two = a.Cout - co0 > 32;           // the second block of 32 output channels holds any (workgroup-uniform)
+    const size_t xoff = (size_t)zb * a.Cin * a.H * a.W;
+    const float* ax = a.x + xoff;
+    const float* agate = a.gate ? a.gate + xoff : nullptr;
+    float* ay = a.y + (size_t)zb * a.Cout * a.Ho * a.Wo;
     float* sW = lp_smem;                                     // [2 ceil(CK KK / 2)][64]
     float* sX = lp_smem + (size_t)((a.CK * KK + 1) & ~1) * LP_TC;      // [CK][PH][PW]
 
@@ -248,8 +265,8 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv(const LpConvArgs a) {
             float v = 0.f;
             if (ix >= 0 && ix < a.W && iy >= 0 && iy < a.H) {
                 const size_t g = ((size_t)(ci0 + ci) * a.H + iy) * a.W + ix;
-                v = a.x[g];
-                if (a.gate && !(a.gate[g] > 0.f)) v = 0.f;
+                v = ax[g];
+                if (agate && !(agate[g] > 0.f)) v = 0.f;
             }
             sX[e] = v;
         }
@@ -295,8 +312,8 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv(const LpConvArgs a) {
                 v0 = v0 < 0.f ? 0.f : v0;
                 v1 = v1 < 0.f ? 0.f : v1;
             }
-            if (c0 < a.Cout) a.y[((size_t)c0 * a.Ho + oy) * a.Wo + ox] = v0;
-            if (two && c1 < a.Cout) a.y[((size_t)c1 * a.Ho + oy) * a.Wo + ox] = v1;
+            if (c0 < a.Cout) ay[((size_t)c0 * a.Ho + oy) * a.Wo + ox] = v0;
+            if (two && c1 < a.Cout) ay[((size_t)c1 * a.Ho + oy) * a.Wo + ox] = v1;
         }
     }
 }
@@ -312,7 +329,7 @@ static int lp_conv_ck(int Cin, int KH, int KW, int stride, size_t* lds) {
 }
 
 // y (Cout, Ho, Wo) = [relu](conv(x * [gate > 0], w) + bias); wp: [Cin KH KW][CoP] packed, bias: [CoP] or null
-static int lp_conv(hipStream_t stream, const char* name, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
+static int lp_conv(hipStream_t stream, const char* name, int G, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
                    const float* x, const float* gate, const float* wp, const float* bias, int relu, float* y) {
     LpConvArgs a;
     a.Cin = Cin; a.Cout = Cout; a.CoP = (int)lp_pad64(Cout); a.H = H; a.W = W;
@@ -322,7 +339,8 @@ static int lp_conv(hipStream_t stream, const char* name, int Cin, int Cout, int 
     size_t lds;
     a.CK = lp_conv_ck(Cin, KH, KW, stride, &lds);
     if (lds > 150 * 1024) return mgr_fail(MGR_EINVAL, "k_lp_conv: kernel window too large for LDS");
-    const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (Cout + LP_TC - 1) / LP_TC);
+    a.NZ = (Cout + LP_TC - 1) / LP_TC;
+    const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (unsigned)(G * a.NZ));
     if (grid.y > 65535u || grid.z > 65535u) return mgr_fail(MGR_EINVAL, "k_lp_conv: image too large");
     MGR_PROF(name, stream);
     if (KH == 3 && KW == 3 && stride == 1 && pad == 1) {
@@ -370,7 +388,7 @@ __global__ __launch_bounds__(LP_T) void k_lp_pack16(int Cout, int Cin, int KK, i
 }
 
 struct LpConv16Args {
-    int Cin, Cout, CoP, NB, H, W, Ho, Wo, KH, KW, stride, pad, CK, KYN, relu;       // NB = pad8(Cin) / 8
+    int Cin, Cout, CoP, NB, H, W, Ho, Wo, KH, KW, stride, pad, CK, KYN, relu, NZ;       // NB = pad8(Cin) / 8; NZ as in LpConvArgs
     const float *x, *gate, *bias;
     const lp_bf8* wp;
     float* y;
@@ -384,9 +402,14 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
     const int KH = K3 ? 3 : a.KH, KW = K3 ? 3 : a.KW, st = K3 ? 1 : a.stride, pad = K3 ? 1 : a.pad, KYN = K3 ? 3 : a.KYN;
     const int PW = (LP_TW - 1) * st + KW;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-    const int ox0 = blockIdx.x * LP_TW, oy0 = blockIdx.y * LP_TH, co0 = blockIdx.z * LP_TC;
+    const int zb = blockIdx.z / a.NZ;
+    const int ox0 = blockIdx.x * LP_TW, oy0 = blockIdx.y * LP_TH, co0 = (blockIdx.z - zb * a.NZ) * LP_TC;
     const int ix0 = ox0 * st - pad, iy0 = oy0 * st - pad;
     const bool two = a.Cout - co0 > 32;
+    const size_t xoff = (size_t)zb * a.Cin * a.H * a.W;
+    const float* ax = a.x + xoff;
+    const float* agate = a.gate ? a.gate + xoff : nullptr;
+    float* ay = a.y + (size_t)zb * a.Cout * a.Ho * a.Wo;
     const int XS = a.CK * 2 + LP16_XPAD;                      // bytes per staged pixel
     lp_bf8* sW = (lp_bf8*)lp_smem16;                          // [q][64 output channels] of 8 bf16
     unsigned char* sX = lp_smem16 + (size_t)KYN * KW * (a.CK >> 3) * LP_TC * 16;       // [py][px] of XS bytes: CK bf16, padding
@@ -425,8 +448,8 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const size_t g = (size_t)min(ci0 + cb * 8 + j, a.Cin - 1) * a.H * a.W + gp;
-                        f[j] = a.x[g];
-                        gt[j] = a.gate ? a.gate[g] : 1.f;
+                        f[j] = ax[g];
+                        gt[j] = agate ? agate[g] : 1.f;
                     }
                     lp_bf8 v;
 #pragma unroll
@@ -451,8 +474,8 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
                         float f = 0.f;
                         if (in && c < a.Cin) {
                             const size_t g = ((size_t)c * a.H + iy) * a.W + ix;
-                            f = a.x[g];
-                            if (a.gate && !(a.gate[g] > 0.f)) f = 0.f;
+                            f = ax[g];
+                            if (agate && !(agate[g] > 0.f)) f = 0.f;
                         }
                         v[j] = (__bf16)f;
                     }
@@ -512,8 +535,8 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
                 v0 = v0 < 0.f ? 0.f : v0;
                 v1 = v1 < 0.f ? 0.f : v1;
             }
-            if (c0 < a.Cout) a.y[((size_t)c0 * a.Ho + oy) * a.Wo + ox] = v0;
-            if (two && c1 < a.Cout) a.y[((size_t)c1 * a.Ho + oy) * a.Wo + ox] = v1;
+            if (c0 < a.Cout) ay[((size_t)c0 * a.Ho + oy) * a.Wo + ox] = v0;
+            if (two && c1 < a.Cout) ay[((size_t)c1 * a.Ho + oy) * a.Wo + ox] = v1;
         }
     }
 }
@@ -536,7 +559,7 @@ static void lp_conv16_chunk(int Cin, int KH, int KW, int stride, int* ck, int* k
 }
 
 // as lp_conv, on bf16 operands; wp: k_lp_pack16's layout
-static int lp_conv16(hipStream_t stream, const char* name, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
+static int lp_conv16(hipStream_t stream, const char* name, int G, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
                      const float* x, const float* gate, const void* wp, const float* bias, int relu, float* y) {
     LpConv16Args a;
     a.Cin = Cin; a.Cout = Cout; a.CoP = (int)lp_pad64(Cout); a.NB = (int)(lp_pad8(Cin) >> 3); a.H = H; a.W = W;
@@ -546,7 +569,8 @@ static int lp_conv16(hipStream_t stream, const char* name, int Cin, int Cout, in
     size_t lds;
     lp_conv16_chunk(Cin, KH, KW, stride, &a.CK, &a.KYN, &lds);
     if (lds > 150 * 1024) return mgr_fail(MGR_EINVAL, "k_lp_conv16: kernel window too large for LDS");
-    const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (Cout + LP_TC - 1) / LP_TC);
+    a.NZ = (Cout + LP_TC - 1) / LP_TC;
+    const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (unsigned)(G * a.NZ));
     if (grid.y > 65535u || grid.z > 65535u) return mgr_fail(MGR_EINVAL, "k_lp_conv16: image too large");
     MGR_PROF(name, stream);
     if (KH == 3 && KW == 3 && stride == 1 && pad == 1) {
@@ -565,12 +589,12 @@ static int lp_conv16(hipStream_t stream, const char* name, int Cin, int Cout, in
     return MGR_OK;
 }
 
-// one convolution in the call's operand mode
-static int lp_conv_op(int operands, hipStream_t stream, const char* name, const char* name16, int Cin, int Cout, int H, int W, int KH,
-                      int KW, int stride, int pad, const float* x, const float* gate, const void* wp, const float* bias, int relu,
+// one convolution, of G views that sit batch-major in x / gate / y, in the call's operand mode
+static int lp_conv_op(int operands, hipStream_t stream, const char* name, const char* name16, int G, int Cin, int Cout, int H, int W,
+                      int KH, int KW, int stride, int pad, const float* x, const float* gate, const void* wp, const float* bias, int relu,
                       float* y) {
-    if (operands == MGR_LPIPS_BF16) return lp_conv16(stream, name16, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, wp, bias, relu, y);
-    return lp_conv(stream, name, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, (const float*)wp, bias, relu, y);
+    if (operands == MGR_LPIPS_BF16) return lp_conv16(stream, name16, G, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, wp, bias, relu, y);
+    return lp_conv(stream, name, G, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, (const float*)wp, bias, relu, y);
 }
 
 // ---------------------------------------------------------------------------
@@ -613,18 +637,24 @@ __global__ __launch_bounds__(LP_T) void k_lp_scale_bwd(int HW, const float* __re
 // The window of a frame.  A windowed view runs the chain on the contiguous (3, h, w) copy of the rectangle (x0, y0, w, h) of its
 // (3, FH, FW) frame: these two kernels are k_lp_scale / k_lp_scale_bwd with a pitch and an origin, the arithmetic per element
 // unchanged, so a window equals the call on .contiguous() crops bit for bit.  Lanes run along x (coalesced rows), no atomics.
+// The table of a launch: entry j (blockIdx.z) is the window (x0[j], y0[j], w, h) of frame view[j] of x / mask / dx, which are
+// the (V, 3, FH, FW) / (V, FH, FW) frames; its contiguous copy is slot j of out / g.  w and h are shared by the launch.
 struct LpWin {
-    int FH, FW, x0, y0;
+    int FH, FW;
+    int view[LP_MAX_BATCH], x0[LP_MAX_BATCH], y0[LP_MAX_BATCH];
 };
 
-// grid (ceil(w / LP_T), h).  out (3, h, w) = k_lp_scale of x[:, y0 : y0 + h, x0 : x0 + w] (and of that rectangle of the mask)
+// grid (ceil(w / LP_T), h, entries).  out[j] (3, h, w) = k_lp_scale of x[view, :, y0 : y0 + h, x0 : x0 + w] (and of that rectangle
+// of the mask)
 __global__ __launch_bounds__(LP_T) void k_lp_scale_win(int w, int h, const LpWin f, const float* __restrict__ x,
                                                        const float* __restrict__ mask, int normalize, float* __restrict__ out) {
-    const int cx = blockIdx.x * LP_T + threadIdx.x, cy = blockIdx.y;
+    const int cx = blockIdx.x * LP_T + threadIdx.x, cy = blockIdx.y, j = blockIdx.z;
     if (cx >= w || cy >= h) return;
     const size_t FP = (size_t)f.FH * f.FW, HW = (size_t)h * w;
-    const size_t sp = (size_t)(f.y0 + cy) * f.FW + f.x0 + cx, p = (size_t)cy * w + cx;
-    const float m = mask ? mask[sp] : 1.f;
+    const size_t sp = (size_t)(f.y0[j] + cy) * f.FW + f.x0[j] + cx, p = (size_t)cy * w + cx;
+    x += (size_t)f.view[j] * 3 * FP;
+    out += (size_t)j * 3 * HW;
+    const float m = mask ? mask[(size_t)f.view[j] * FP + sp] : 1.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float v = x[c * FP + sp];
@@ -636,19 +666,23 @@ __global__ __launch_bounds__(LP_T) void k_lp_scale_win(int w, int h, const LpWin
 
 // accumulate = 1: grid (ceil(w / LP_T), h), the rectangle's value is added (one fp32 add) to the rectangle of dx (3, FH, FW) and
 // the rest of the frame is not touched.  accumulate = 0: grid (ceil(FW / LP_T), FH), ONE launch writes the whole frame, the
-// value inside the rectangle and 0 outside (w = 0 or h = 0: a zero fill; g is not read).
+// value inside the rectangle and 0 outside (w = 0 or h = 0: a zero fill; g is not read).  grid.z: the table's entries, every
+// one its own frame of dx.
 __global__ __launch_bounds__(LP_T) void k_lp_scale_bwd_win(int w, int h, const LpWin f, const float* __restrict__ g,
                                                            const float* __restrict__ mask, int normalize, int accumulate,
                                                            float* __restrict__ dx) {
-    const int t = blockIdx.x * LP_T + threadIdx.x;
-    const int gx = accumulate ? f.x0 + t : t, gy = accumulate ? f.y0 + (int)blockIdx.y : (int)blockIdx.y;
+    const int t = blockIdx.x * LP_T + threadIdx.x, j = blockIdx.z;
+    const int x0 = f.x0[j], y0 = f.y0[j];
+    const int gx = accumulate ? x0 + t : t, gy = accumulate ? y0 + (int)blockIdx.y : (int)blockIdx.y;
     if (gx >= f.FW || gy >= f.FH) return;
-    const int cx = gx - f.x0, cy = gy - f.y0;
+    const int cx = gx - x0, cy = gy - y0;
     const bool in = cx >= 0 && cx < w && cy >= 0 && cy < h;
     if (accumulate && !in) return;
     const size_t FP = (size_t)f.FH * f.FW, HW = (size_t)h * w;
     const size_t sp = (size_t)gy * f.FW + gx, p = in ? (size_t)cy * w + cx : 0;
-    const float m = (mask && in) ? mask[sp] : 1.f;
+    g += (size_t)j * 3 * HW;
+    dx += (size_t)f.view[j] * 3 * FP;
+    const float m = (mask && in) ? mask[(size_t)f.view[j] * FP + sp] : 1.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float v = 0.f;
@@ -716,11 +750,23 @@ __device__ __forceinline__ double lp_block_sum(double a, double* s_red, int tid)
 
 // one thread per pixel of a tap: sum_c lin[c] (f0 / n0 - f1 / n1)^2 into the workgroup's fp64 partial; with g: the gradient of
 // gs * (that sum) w.r.t. f0, written (add = 0) or added (add = 1).  A pixel whose f0 is all zero contributes no gradient.
-__global__ __launch_bounds__(LP_T) void k_lp_head(int C, int HW, const float* __restrict__ f0, const float* __restrict__ f1,
-                                                  const float* __restrict__ lin, float gs, float* __restrict__ g, int add,
-                                                  double* __restrict__ part) {
+// blockIdx.y is the view of the chunk: f0 and g are batch-major, f1 (cached taps live in a buffer per view) and gs (the view's
+// grad_scale / (H_k W_k)) come per view, and view b's partials start at b part_stride.
+struct LpHeadArgs {
+    const float* f1[LP_MAX_BATCH];
+    float gs[LP_MAX_BATCH];
+};
+
+__global__ __launch_bounds__(LP_T) void k_lp_head(int C, int HW, const float* __restrict__ f0, const LpHeadArgs t,
+                                                  const float* __restrict__ lin, float* __restrict__ g, int add,
+                                                  double* __restrict__ part, int part_stride) {
     __shared__ double s_red[LP_T];
-    const int tid = threadIdx.x, p = blockIdx.x * LP_T + tid;
+    const int tid = threadIdx.x, p = blockIdx.x * LP_T + tid, vb = blockIdx.y;
+    const float* __restrict__ f1 = t.f1[vb];
+    const float gs = t.gs[vb];
+    f0 += (size_t)vb * C * HW;
+    if (g) g += (size_t)vb * C * HW;
+    part += (size_t)vb * part_stride;
     double val = 0.0;
     if (p < HW) {
         float s0 = 0.f, s1 = 0.f;
@@ -757,12 +803,15 @@ __global__ __launch_bounds__(LP_T) void k_lp_head(int C, int HW, const float* __
 struct LpFoldArgs {
     int off[LP_NTAP + 1];
     double inv[LP_NTAP];
+    int view[LP_MAX_BATCH];       // workgroup b folds the partials at b off[LP_NTAP] into value[view[b]]
 };
 
 // values[v] = sum_k (sum of tap k's partials) / (H_k W_k): thread t adds slots t, t + 256, ... in ascending order, fixed tree
 __global__ __launch_bounds__(LP_T) void k_lp_fold(const LpFoldArgs a, const double* __restrict__ part, float* __restrict__ value) {
     __shared__ double s_red[LP_T];
     const int tid = threadIdx.x;
+    part += (size_t)blockIdx.x * a.off[LP_NTAP];
+    value += a.view[blockIdx.x];
     double d = 0.0;
     for (int k = 0; k < LP_NTAP; ++k) {
         double s = 0.0;
@@ -885,9 +934,9 @@ extern "C" int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW
         MGR_LAUNCH_CHECK("k_lp_pack", stream, 0);
     }
     if (transposed)
-        return lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", Cout, Cin, H, W, KH, KW, 1, pad, x, gate, base + o_t, nullptr,
-                          relu, y);
-    return lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", Cin, Cout, H, W, KH, KW, stride, pad, x, gate, base + o_f,
+        return lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", 1, Cout, Cin, H, W, KH, KW, 1, pad, x, gate, base + o_t,
+                          nullptr, relu, y);
+    return lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", 1, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, base + o_f,
                       bias ? (const float*)(base + o_b) : nullptr, relu, y);
 }
 
@@ -908,14 +957,15 @@ extern "C" size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW
     return mgr_lpips_conv_scratch_bytes_op(Cin, Cout, KH, KW, MGR_LPIPS_F32);
 }
 
-// forward of one image: scaled image -> sb, then the ops; a convolution writes to its slot of `store` (by convolution index)
-// where that is not null, else to the scratch buffer its input is not in
+// forward of G images: scaled images -> sb, then the ops; a convolution writes to its slot of `store` (by convolution index)
+// where that is not null, else to the scratch buffer its input is not in.  Every buffer is batch-major.  win = null: G = 1 and
+// img / mask are one contiguous (3,H,W) / (H,W) image; else they are the frames and (H, W) is the size of win's G rectangles.
 static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, const LpShape& S, int H, int W,
-                      const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb,
+                      int G, const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb,
                       const LpWin* win = nullptr) {
     const int HW = H * W;
-    if (win) {      // img / mask are the frame: (H, W) is the rectangle at win's origin
-        hipLaunchKernelGGL(k_lp_scale_win, dim3((W + LP_T - 1) / LP_T, H), dim3(LP_T), 0, stream, W, H, *win, img, mask, normalize, sb);
+    if (win) {
+        hipLaunchKernelGGL(k_lp_scale_win, dim3((W + LP_T - 1) / LP_T, H, G), dim3(LP_T), 0, stream, W, H, *win, img, mask, normalize, sb);
         MGR_LAUNCH_CHECK("k_lp_scale_win", stream, 0);
     } else {
         hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, sb);
@@ -928,15 +978,16 @@ static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const Lp
         float* out;
         if (op.conv) {
             out = store[ci] ? store[ci] : (cur == sa ? sb : sa);
-            const int rc = lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", op.cin, op.cout, h, w, op.k, op.k, op.s, op.p, cur,
+            const int rc = lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", G, op.cin, op.cout, h, w, op.k, op.k, op.s, op.p, cur,
                                       nullptr, blob + B.w[ci], (const float*)(blob + B.b[ci]), 1, out);
             if (rc != MGR_OK) return rc;
             ++ci;
         } else {
+            // a per-channel kernel: the G views are G cout channels
             out = cur == sa ? sb : sa;
-            const size_t ne = (size_t)op.cout * S.h[i] * S.w[i];
-            hipLaunchKernelGGL(k_lp_pool, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, op.cout, h, w, S.h[i], S.w[i],
-                               op.k, cur, out);
+            const size_t ne = (size_t)G * op.cout * S.h[i] * S.w[i];
+            hipLaunchKernelGGL(k_lp_pool, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, G * op.cout, h, w, S.h[i],
+                               S.w[i], op.k, cur, out);
             MGR_LAUNCH_CHECK("k_lp_pool", stream, 0);
         }
         cur = out;
@@ -946,20 +997,38 @@ static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const Lp
     return MGR_OK;
 }
 
-// one view of a call, validated by the caller: the two forwards (the target's only where `taps` is null), the heads, the
-// gradient chain and the fold into *value.  win = null: pred / target / mask / dL are contiguous (3,H,W) / (H,W) images;
-// else they are the view's frames and (H, W) is the rectangle at win's origin.  taps: the target's five taps as
-// mgr_lpips_roi_taps_op left them (the workspace's tap region, in its layout), or null.
-static int lp_view(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, int H, int W, const LpWin* win,
-                   const float* pred, const float* target, const float* mk, const float* taps, int normalize, float grad_scale,
-                   float* value, float* dL, int accumulate, char* ws) {
+// G equal-size views of a call (one chunk; G = 1 in the plain and the sequential windowed call), validated by the caller: the
+// two forwards (the target's only for the views whose `taps` entry is null, batched among themselves), the heads, the gradient
+// chain and the folds into values[view].  The workspace is lp_layout's of G.  win = null: G = 1 and pred / target / mk / dL /
+// values are that view's contiguous images and value; else they are the call's frames and (H, W) is the size of win's
+// rectangles.  taps[b]: view b's five target taps as mgr_lpips_roi_taps_op left them (in the one-view layout), or null.
+static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, int H, int W, int G,
+                    const LpWin* win, const float* pred, const float* target, const float* mk, const float* const* taps, int normalize,
+                    const float* grad_scale, float* values, float* dL, int accumulate, char* ws) {
     const int need_grad = dL != nullptr;
-    LpLayout L;
+    LpLayout L, L1;
     LpShape S;
-    if (!lp_layout(n, H, W, need_grad, &L) || !lp_shapes(n, H, W, &S)) return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small");
+    if (!lp_layout(n, H, W, need_grad, &L, (size_t)G) || !lp_layout(n, H, W, need_grad, &L1) || !lp_shapes(n, H, W, &S))
+        return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small");
     float *sa = (float*)(ws + L.bufa), *sb = (float*)(ws + L.bufb);
     double* part = (double*)(ws + L.part);
+    const int part_stride = (int)L.part_off[LP_NTAP];
+    // the views whose target tower runs: slot j of the workspace's tap regions is view tw.view[j]
+    LpWin tw = {};
+    int slot[LP_MAX_BATCH], GT = 0;
+    if (win) {
+        tw.FH = win->FH;
+        tw.FW = win->FW;
+    }
+    for (int b = 0; b < G; ++b) {
+        slot[b] = -1;
+        if (taps && taps[b]) continue;
+        slot[b] = GT;
+        if (win) { tw.view[GT] = win->view[b];  tw.x0[GT] = win->x0[b];  tw.y0[GT] = win->y0[b]; }
+        ++GT;
+    }
     float *act[13], *tgt[13];
+    LpHeadArgs ha[LP_NTAP];
     int tap_conv[LP_NTAP], tap_op[LP_NTAP];
     {
         int ci = 0;
@@ -969,31 +1038,43 @@ static int lp_view(int operands, hipStream_t stream, const LpNet& n, const LpBlo
             act[ci] = (float*)(ws + L.act[ci]);
             tgt[ci] = nullptr;
             if (op.tap >= 0) {
-                tgt[ci] = taps ? (float*)((const char*)taps + (L.tap[op.tap] - L.tap[0])) : (float*)(ws + L.tap[op.tap]);
+                tgt[ci] = (float*)(ws + L.tap[op.tap]);
+                const size_t e = (size_t)op.cout * S.h[i] * S.w[i];
+                for (int b = 0; b < LP_MAX_BATCH; ++b) {
+                    ha[op.tap].f1[b] = nullptr;
+                    ha[op.tap].gs[b] = 0.f;
+                    if (b >= G) continue;
+                    ha[op.tap].f1[b] = slot[b] < 0 ? (const float*)((const char*)taps[b] + (L1.tap[op.tap] - L1.tap[0]))
+                                                   : tgt[ci] + (size_t)slot[b] * e;
+                }
                 tap_conv[op.tap] = ci;
                 tap_op[op.tap] = i;
             }
             ++ci;
         }
     }
-    LpFoldArgs fa;
+    LpFoldArgs fa = {};
     for (int k = 0; k <= LP_NTAP; ++k) fa.off[k] = (int)L.part_off[k];
     for (int k = 0; k < LP_NTAP; ++k) fa.inv[k] = 1.0 / ((double)S.h[tap_op[k]] * S.w[tap_op[k]]);
+    for (int b = 0; b < G; ++b) fa.view[b] = win ? win->view[b] : 0;
+    if (need_grad)
+        for (int k = 0; k < LP_NTAP; ++k)
+            for (int b = 0; b < G; ++b) ha[k].gs[b] = (float)((double)grad_scale[b] * fa.inv[k]);
 
     int rc;
-    if (!taps) {
-        rc = lp_forward(operands, stream, n, B, blob, S, H, W, target, mk, normalize, tgt, sa, sb, win);
+    if (GT) {
+        rc = lp_forward(operands, stream, n, B, blob, S, H, W, GT, target, mk, normalize, tgt, sa, sb, win ? &tw : nullptr);
         if (rc != MGR_OK) return rc;
     }
-    rc = lp_forward(operands, stream, n, B, blob, S, H, W, pred, mk, normalize, act, sa, sb, win);
+    rc = lp_forward(operands, stream, n, B, blob, S, H, W, G, pred, mk, normalize, act, sa, sb, win);
     if (rc != MGR_OK) return rc;
     if (!need_grad) {
         MGR_PROF("k_lp_head", stream);
         for (int k = 0; k < LP_NTAP; ++k) {
             const int i = tap_op[k], hw = S.h[i] * S.w[i];
-            hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
-                               (const float*)act[tap_conv[k]], (const float*)tgt[tap_conv[k]], (const float*)(blob + B.lin[k]), 0.f,
-                               (float*)nullptr, 0, part + L.part_off[k]);
+            hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
+                               (const float*)act[tap_conv[k]], ha[k], (const float*)(blob + B.lin[k]), (float*)nullptr, 0,
+                               part + L.part_off[k], part_stride);
             MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
         }
     } else {
@@ -1010,32 +1091,31 @@ static int lp_view(int operands, hipStream_t stream, const LpNet& n, const LpBlo
                 for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
                 if (op.tap >= 0) {
                     const int hw = S.h[i] * S.w[i], k = op.tap;
-                    const float gs = (float)((double)grad_scale * fa.inv[k]);
                     MGR_PROF("k_lp_head", stream);
-                    hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, op.cout, hw, (const float*)act[ci],
-                                       (const float*)tgt[ci], (const float*)(blob + B.lin[k]), gs, g, have ? 1 : 0,
-                                       part + L.part_off[k]);
+                    hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, op.cout, hw,
+                                       (const float*)act[ci], ha[k], (const float*)(blob + B.lin[k]), g, have ? 1 : 0,
+                                       part + L.part_off[k], part_stride);
                     MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
                     have = true;
                 }
                 // dL/d(input) = conv(g * [y > 0], W')
-                rc = lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1, op.p,
-                                g, act[ci], blob + B.wt[ci], nullptr, 0, o);
+                rc = lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", G, op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1,
+                                op.p, g, act[ci], blob + B.wt[ci], nullptr, 0, o);
                 if (rc != MGR_OK) return rc;
             } else {
                 // the pool's input is the previous convolution's stored output
                 int ci = -1;
                 for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
-                const size_t ne = (size_t)op.cin * h_in * w_in;
+                const size_t ne = (size_t)G * op.cin * h_in * w_in;
                 MGR_PROF("k_lp_pool2_bwd", stream);
-                hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, op.cin, h_in, w_in,
+                hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, G * op.cin, h_in, w_in,
                                    S.h[i], S.w[i], (const float*)act[ci], (const float*)g, o);
                 MGR_LAUNCH_CHECK("k_lp_pool2_bwd", stream, 0);
             }
             float* t = g;  g = o;  o = t;
         }
         if (win) {
-            const dim3 grid = accumulate ? dim3((W + LP_T - 1) / LP_T, H) : dim3((win->FW + LP_T - 1) / LP_T, win->FH);
+            const dim3 grid = accumulate ? dim3((W + LP_T - 1) / LP_T, H, G) : dim3((win->FW + LP_T - 1) / LP_T, win->FH, G);
             hipLaunchKernelGGL(k_lp_scale_bwd_win, grid, dim3(LP_T), 0, stream, W, H, *win, (const float*)g, mk, normalize, accumulate, dL);
             MGR_LAUNCH_CHECK("k_lp_scale_bwd_win", stream, 0);
         } else {
@@ -1045,7 +1125,7 @@ static int lp_view(int operands, hipStream_t stream, const LpNet& n, const LpBlo
             MGR_LAUNCH_CHECK("k_lp_scale_bwd", stream, 0);
         }
     }
-    hipLaunchKernelGGL(k_lp_fold, dim3(1), dim3(LP_T), 0, stream, fa, (const double*)part, value);
+    hipLaunchKernelGGL(k_lp_fold, dim3(G), dim3(LP_T), 0, stream, fa, (const double*)part, values);
     MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
     return MGR_OK;
 }
@@ -1069,9 +1149,9 @@ extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, con
     if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_lpips: workspace smaller than mgr_lpips_workspace_bytes");
     const size_t img = (size_t)3 * H * W, px = (size_t)H * W;
     for (int v = 0; v < V; ++v) {
-        const int rc = lp_view(operands, stream, n, B, (const char*)blob_, H, W, nullptr, pred + v * img, target + v * img,
-                               mask ? mask + v * px : nullptr, nullptr, normalize, grad_scale, values + v,
-                               dL_dpred ? dL_dpred + v * img : nullptr, accumulate, (char*)workspace);
+        const int rc = lp_views(operands, stream, n, B, (const char*)blob_, H, W, 1, nullptr, pred + v * img, target + v * img,
+                                mask ? mask + v * px : nullptr, nullptr, normalize, &grad_scale, values + v,
+                                dL_dpred ? dL_dpred + v * img : nullptr, accumulate, (char*)workspace);
         if (rc != MGR_OK) return rc;
     }
     return MGR_OK;
@@ -1103,18 +1183,67 @@ static int lp_rect_fail(const char* who, int rc) {
                                         : "a rectangle is too small for the deepest tap to have one pixel (or above 2^24 pixels)");
 }
 
-extern "C" size_t mgr_lpips_roi_workspace_bytes(int net, int V, const int* rects, int need_grad) {
-    LpNet n;
-    if (!lp_net(net, &n) || V <= 0 || !rects) return 0;
-    size_t need = 0;
+// The chunks of a windowed call: the non-empty views grouped by (w, h) in ascending view order, every group cut into runs of at
+// most `cap` views; the chunks stand in the order of their first view.  cap = 1: one chunk per non-empty view.
+struct LpChunk {
+    int w, h, n;
+    int view[LP_MAX_BATCH];
+};
+
+static void lp_chunks(int V, const int* rects, int cap, std::vector<LpChunk>* out) {
+    out->clear();
     for (int v = 0; v < V; ++v) {
-        const int* r = rects + 4 * v;
-        if (r[2] == 0 || r[3] == 0) continue;
+        const int w = rects[4 * v + 2], h = rects[4 * v + 3];
+        if (w <= 0 || h <= 0) continue;
+        LpChunk* c = nullptr;
+        if (cap > 1)
+            for (size_t j = out->size(); j-- > 0;)
+                if ((*out)[j].w == w && (*out)[j].h == h) {        // the group's last chunk: the only one that may have room
+                    if ((*out)[j].n < cap) c = &(*out)[j];
+                    break;
+                }
+        if (!c) {
+            out->push_back(LpChunk{w, h, 0, {}});
+            c = &out->back();
+        }
+        c->view[c->n++] = v;
+    }
+}
+
+static inline int lp_batch_cap(int max_batch) { return max_batch < LP_MAX_BATCH ? max_batch : LP_MAX_BATCH; }
+
+// the largest chunk's workspace; 0 where a rectangle is refused
+static size_t lp_chunks_bytes(const LpNet& n, const std::vector<LpChunk>& chunks, int need_grad) {
+    size_t need = 0;
+    for (const LpChunk& c : chunks) {
         LpLayout L;
-        if (r[2] < 0 || r[3] < 0 || !lp_layout(n, r[3], r[2], need_grad, &L)) return 0;
+        if (!lp_layout(n, c.h, c.w, need_grad, &L, (size_t)c.n)) return 0;
         need = need > L.total ? need : L.total;
     }
     return need;
+}
+
+static size_t lp_roi_bytes(const LpNet& n, int V, const int* rects, int need_grad, int cap) {
+    for (int v = 0; v < V; ++v) {
+        const int* r = rects + 4 * v;
+        if (r[2] == 0 || r[3] == 0) continue;
+        if (r[2] < 0 || r[3] < 0) return 0;
+    }
+    std::vector<LpChunk> chunks;
+    lp_chunks(V, rects, cap, &chunks);
+    return lp_chunks_bytes(n, chunks, need_grad);
+}
+
+extern "C" size_t mgr_lpips_roi_workspace_bytes(int net, int V, const int* rects, int need_grad) {
+    LpNet n;
+    if (!lp_net(net, &n) || V <= 0 || !rects) return 0;
+    return lp_roi_bytes(n, V, rects, need_grad, 1);
+}
+
+extern "C" size_t mgr_lpips_roi_batch_workspace_bytes(int net, int V, const int* rects, int need_grad, int max_batch) {
+    LpNet n;
+    if (!lp_net(net, &n) || V <= 0 || !rects || max_batch < 1) return 0;
+    return lp_roi_bytes(n, V, rects, need_grad, lp_batch_cap(max_batch));
 }
 
 extern "C" size_t mgr_lpips_taps_bytes(int net, int h, int w) {
@@ -1122,6 +1251,59 @@ extern "C" size_t mgr_lpips_taps_bytes(int net, int h, int w) {
     LpLayout L;
     if (!lp_net(net, &n) || !lp_layout(n, h, w, 0, &L)) return 0;
     return L.bufa - L.tap[0];
+}
+
+// view b's n floats at src + b n -> dst[b] + off (the taps of a chunk leave the batch-major workspace for the views' buffers)
+struct LpTapOut {
+    float* dst[LP_MAX_BATCH];
+};
+
+__global__ __launch_bounds__(LP_T) void k_lp_taps_out(size_t n, const float* __restrict__ src, const LpTapOut t, size_t off) {
+    const size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x;
+    if (e < n) t.dst[blockIdx.y][off + e] = src[(size_t)blockIdx.y * n + e];
+}
+
+// the target tower of one chunk into its views' tap buffers; one view writes them directly (the one-view entry), more go through
+// the workspace's batch-major tap regions
+static int lp_taps_chunk(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, int H, int W, const int* rects,
+                         const LpChunk& c, const float* target, const float* mask, int normalize, float* const* taps_out, char* ws) {
+    LpLayout L, L1;
+    LpShape S;
+    lp_layout(n, c.h, c.w, 0, &L, (size_t)c.n);
+    lp_layout(n, c.h, c.w, 0, &L1);
+    lp_shapes(n, c.h, c.w, &S);
+    LpWin win = {};
+    win.FH = H;
+    win.FW = W;
+    for (int b = 0; b < c.n; ++b) {
+        win.view[b] = c.view[b];
+        win.x0[b] = rects[4 * c.view[b]];
+        win.y0[b] = rects[4 * c.view[b] + 1];
+    }
+    float* tgt[13];
+    int ci = 0;
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (!op.conv) continue;
+        tgt[ci] = nullptr;
+        if (op.tap >= 0)
+            tgt[ci] = c.n == 1 ? (float*)((char*)taps_out[c.view[0]] + (L1.tap[op.tap] - L1.tap[0])) : (float*)(ws + L.tap[op.tap]);
+        ++ci;
+    }
+    const int rc = lp_forward(operands, stream, n, B, blob, S, c.h, c.w, c.n, target, mask, normalize, tgt, (float*)(ws + L.bufa),
+                              (float*)(ws + L.bufb), &win);
+    if (rc != MGR_OK || c.n == 1) return rc;
+    LpTapOut to = {};
+    for (int b = 0; b < c.n; ++b) to.dst[b] = taps_out[c.view[b]];
+    for (int i = 0; i < n.n_ops; ++i) {
+        const LpOp& op = n.ops[i];
+        if (!op.conv || op.tap < 0) continue;
+        const size_t e = (size_t)op.cout * S.h[i] * S.w[i];
+        hipLaunchKernelGGL(k_lp_taps_out, dim3((unsigned)((e + LP_T - 1) / LP_T), c.n), dim3(LP_T), 0, stream, e,
+                           (const float*)(ws + L.tap[op.tap]), to, (L1.tap[op.tap] - L1.tap[0]) / 4);
+        MGR_LAUNCH_CHECK("k_lp_taps_out", stream, 0);
+    }
+    return MGR_OK;
 }
 
 extern "C" int mgr_lpips_roi_taps_op(int net, int H, int W, const int* rect, const float* target_v, const float* mask_v, const void* blob_,
@@ -1140,72 +1322,120 @@ extern "C" int mgr_lpips_roi_taps_op(int net, int H, int W, const int* rect, con
     const LpBlob B = lp_blob(n, operands);
     if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
     if (workspace_bytes < L.total) return mgr_fail(MGR_ENOMEM, "mgr_lpips_roi_taps: workspace smaller than mgr_lpips_workspace_bytes(net, h, w, 0)");
-    LpShape S;
-    lp_shapes(n, rect[3], rect[2], &S);
-    float* tgt[13];
-    int ci = 0;
-    for (int i = 0; i < n.n_ops; ++i) {
-        const LpOp& op = n.ops[i];
-        if (!op.conv) continue;
-        tgt[ci++] = op.tap >= 0 ? (float*)((char*)taps_out + (L.tap[op.tap] - L.tap[0])) : nullptr;
-    }
-    const LpWin win = {H, W, rect[0], rect[1]};
-    char* ws = (char*)workspace;
-    return lp_forward(operands, stream, n, B, (const char*)blob_, S, rect[3], rect[2], target_v, mask_v, normalize, tgt, (float*)(ws + L.bufa),
-                      (float*)(ws + L.bufb), &win);
+    const LpChunk c = {rect[2], rect[3], 1, {}};
+    return lp_taps_chunk(operands, stream, n, B, (const char*)blob_, H, W, rect, c, target_v, mask_v, normalize, &taps_out, (char*)workspace);
 }
 
-extern "C" int mgr_lpips_roi_op(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
-                                const void* blob_, size_t blob_bytes, int normalize, const float* grad_scales, float* values,
-                                float* dL_dpred, int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes,
-                                void* stream_, int operands) {
+extern "C" int mgr_lpips_roi_taps_batch_op(int net, int V, int H, int W, const int* rects, const float* target, const float* mask,
+                                           const void* blob_, size_t blob_bytes, int normalize, float* const* taps_out, int max_batch,
+                                           void* workspace, size_t workspace_bytes, void* stream_, int operands) {
     hipStream_t stream = (hipStream_t)stream_;
     LpNet n;
-    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: net must be 0 (vgg) or 1 (alex)");
-    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: operands must be 0 (fp32) or 1 (bf16)");
-    if (V <= 0 || H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: bad sizes");
-    if (!rects || !pred || !blob_ || !values || (dL_dpred && !grad_scales)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: null pointer");
-    if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: the AlexNet network is forward only (dL_dpred must be null)");
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: net must be 0 (vgg) or 1 (alex)");
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: operands must be 0 (fp32) or 1 (bf16)");
+    if (V <= 0 || H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: bad sizes");
+    if (max_batch < 1) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: max_batch must be at least 1");
+    if (!rects || !target || !blob_ || !taps_out) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: null pointer");
+    for (int v = 0; v < V; ++v) {
+        LpLayout L;
+        const int ok = lp_rect_check(n, H, W, rects + 4 * v, 0, &L);
+        if (ok < 0) return lp_rect_fail("mgr_lpips_roi_taps_batch", ok);
+        if (ok && !taps_out[v]) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: null pointer (a non-empty view has no tap buffer)");
+    }
+    const LpBlob B = lp_blob(n, operands);
+    if (blob_bytes != B.total)
+        return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
+    std::vector<LpChunk> chunks;
+    lp_chunks(V, rects, lp_batch_cap(max_batch), &chunks);
+    const size_t need = lp_chunks_bytes(n, chunks, 0);
+    if (need && !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: null pointer");
+    if (workspace_bytes < need)
+        return mgr_fail(MGR_ENOMEM, "mgr_lpips_roi_taps_batch: workspace smaller than mgr_lpips_roi_batch_workspace_bytes(.., 0, max_batch)");
+    for (const LpChunk& c : chunks) {
+        // the one-view entry takes the view's own frame: chunk views index the call's frames here
+        const int rc = lp_taps_chunk(operands, stream, n, B, (const char*)blob_, H, W, rects, c, target, mask, normalize, taps_out,
+                                     (char*)workspace);
+        if (rc != MGR_OK) return rc;
+    }
+    return MGR_OK;
+}
+
+// the windowed call, sequential (cap = 1) or batched
+static int lp_roi_run(const char* who, int net, int V, int H, int W, const int* rects, const float* pred, const float* target,
+                      const float* mask, const void* blob_, size_t blob_bytes, int normalize, const float* grad_scales, float* values,
+                      float* dL_dpred, int accumulate, const float* const* target_taps, int max_batch, void* workspace,
+                      size_t workspace_bytes, hipStream_t stream, int operands) {
+    LpNet n;
+    if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "%s: net must be 0 (vgg) or 1 (alex)", who);
+    if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "%s: operands must be 0 (fp32) or 1 (bf16)", who);
+    if (V <= 0 || H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "%s: bad sizes", who);
+    if (max_batch < 1) return mgr_fail(MGR_EINVAL, "%s: max_batch must be at least 1", who);
+    if (!rects || !pred || !blob_ || !values || (dL_dpred && !grad_scales)) return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
+    if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "%s: the AlexNet network is forward only (dL_dpred must be null)", who);
     const int need_grad = dL_dpred != nullptr;
     // every view is judged before the first launch
-    size_t need = 0;
     for (int v = 0; v < V; ++v) {
         LpLayout L;
         const int ok = lp_rect_check(n, H, W, rects + 4 * v, need_grad, &L);
-        if (ok < 0) return lp_rect_fail("mgr_lpips_roi", ok);
+        if (ok < 0) return lp_rect_fail(who, ok);
         if (ok == 0) continue;
         if (!target && !(target_taps && target_taps[v]))
-            return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: null pointer (a view has neither a target nor cached taps)");
-        need = need > L.total ? need : L.total;
+            return mgr_fail(MGR_EINVAL, "%s: null pointer (a view has neither a target nor cached taps)", who);
     }
     const LpBlob B = lp_blob(n, operands);
-    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
-    if (need && !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi: null pointer");
-    if (workspace_bytes < need) return mgr_fail(MGR_ENOMEM, "mgr_lpips_roi: workspace smaller than mgr_lpips_roi_workspace_bytes");
-    const size_t img = (size_t)3 * H * W, px = (size_t)H * W;
+    if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "%s: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode", who);
+    std::vector<LpChunk> chunks;
+    lp_chunks(V, rects, lp_batch_cap(max_batch), &chunks);
+    const size_t need = lp_chunks_bytes(n, chunks, need_grad);
+    if (need && !workspace) return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
+    if (workspace_bytes < need) return mgr_fail(MGR_ENOMEM, "%s: workspace smaller than %s_workspace_bytes", who, who);
+    const size_t img = (size_t)3 * H * W;
+    size_t next = 0;
     for (int v = 0; v < V; ++v) {
         const int* r = rects + 4 * v;
-        float* dL = dL_dpred ? dL_dpred + v * img : nullptr;
         if (r[2] == 0 || r[3] == 0) {
             // an empty view: the value is 0 (a fold over no partials); no gradient, and a written frame is zero
+            float* dL = dL_dpred ? dL_dpred + v * img : nullptr;
             LpFoldArgs fa = {};
             hipLaunchKernelGGL(k_lp_fold, dim3(1), dim3(LP_T), 0, stream, fa, (const double*)nullptr, values + v);
             MGR_LAUNCH_CHECK("k_lp_fold", stream, 0);
             if (dL && !accumulate) {
-                const LpWin win = {H, W, 0, 0};
+                LpWin win = {};
+                win.FH = H;
+                win.FW = W;
                 hipLaunchKernelGGL(k_lp_scale_bwd_win, dim3((W + LP_T - 1) / LP_T, H), dim3(LP_T), 0, stream, 0, 0, win,
                                    (const float*)nullptr, (const float*)nullptr, 0, 0, dL);
                 MGR_LAUNCH_CHECK("k_lp_scale_bwd_win", stream, 0);
             }
             continue;
         }
-        const LpWin win = {H, W, r[0], r[1]};
-        const int rc = lp_view(operands, stream, n, B, (const char*)blob_, r[3], r[2], &win, pred + v * img,
-                               target ? target + v * img : nullptr, mask ? mask + v * px : nullptr, target_taps ? target_taps[v] : nullptr,
-                               normalize, need_grad ? grad_scales[v] : 0.f, values + v, dL, accumulate, (char*)workspace);
+        if (next >= chunks.size() || chunks[next].view[0] != v) continue;       // a later view of a chunk that has run
+        const LpChunk& c = chunks[next++];
+        LpWin win = {};
+        win.FH = H;
+        win.FW = W;
+        const float* taps[LP_MAX_BATCH];
+        float gs[LP_MAX_BATCH];
+        for (int b = 0; b < c.n; ++b) {
+            win.view[b] = c.view[b];
+            win.x0[b] = rects[4 * c.view[b]];
+            win.y0[b] = rects[4 * c.view[b] + 1];
+            taps[b] = target_taps ? target_taps[c.view[b]] : nullptr;
+            gs[b] = need_grad ? grad_scales[c.view[b]] : 0.f;
+        }
+        const int rc = lp_views(operands, stream, n, B, (const char*)blob_, c.h, c.w, c.n, &win, pred, target, mask, taps, normalize, gs,
+                                values, dL_dpred, accumulate, (char*)workspace);
         if (rc != MGR_OK) return rc;
     }
     return MGR_OK;
+}
+
+extern "C" int mgr_lpips_roi_op(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                                const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values,
+                                float* dL_dpred, int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes,
+                                void* stream, int operands) {
+    return lp_roi_run("mgr_lpips_roi", net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values, dL_dpred,
+                      accumulate, target_taps, 1, workspace, workspace_bytes, (hipStream_t)stream, operands);
 }
 
 extern "C" int mgr_lpips_roi(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
@@ -1213,4 +1443,20 @@ extern "C" int mgr_lpips_roi(int net, int V, int H, int W, const int* rects, con
                              int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream) {
     return mgr_lpips_roi_op(net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values, dL_dpred, accumulate,
                             target_taps, workspace, workspace_bytes, stream, MGR_LPIPS_F32);
+}
+
+extern "C" int mgr_lpips_roi_batch_op(int net, int V, int H, int W, const int* rects, const float* pred, const float* target,
+                                      const float* mask, const void* blob, size_t blob_bytes, int normalize, const float* grad_scales,
+                                      float* values, float* dL_dpred, int accumulate, const float* const* target_taps, void* workspace,
+                                      size_t workspace_bytes, void* stream, int operands, int max_batch) {
+    return lp_roi_run("mgr_lpips_roi_batch", net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values,
+                      dL_dpred, accumulate, target_taps, max_batch, workspace, workspace_bytes, (hipStream_t)stream, operands);
+}
+
+extern "C" int mgr_lpips_roi_batch(int net, int V, int H, int W, const int* rects, const float* pred, const float* target,
+                                   const float* mask, const void* blob, size_t blob_bytes, int normalize, const float* grad_scales,
+                                   float* values, float* dL_dpred, int accumulate, const float* const* target_taps, void* workspace,
+                                   size_t workspace_bytes, void* stream, int max_batch) {
+    return mgr_lpips_roi_batch_op(net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values, dL_dpred,
+                                  accumulate, target_taps, workspace, workspace_bytes, stream, MGR_LPIPS_F32, max_batch);
 }

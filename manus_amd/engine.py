@@ -586,7 +586,10 @@ class HipViewCompute:
     factor (full-frame rects then give the step without rects, bit for bit).  `lpips_cache_targets` True keeps the target
     tower's taps of the step's view set beside the other per-view constants (`LPIPS.target_taps`; same bits, the target
     tower skipped, 122 floats per window pixel and view of memory): dropped with them -- `view_constants_changed()`, a version-counter
-    change of `targets` -- and on new rects.  None (default): exactly the step above."""
+    change of `targets` -- and on new rects.  None (default): exactly the step above.  `lpips_batch` (a plain attribute like the
+    others): the most views per launch of the windowed term and of the cached taps build (`LPIPS.values_grad(batch=)`,
+    `LPIPS.target_taps(batch=)`): views whose rectangles share a size run as one chain of launches, the same bits (so it is no
+    part of the window cache's key); `FrameStore.lpips_fit` gives a drawn step such rectangles.  0 (default) is the step above."""
 
     # per-view target maps kept (130 KB per 1080p view)
     MAX_TARGET_MAPS = 4096
@@ -594,7 +597,8 @@ class HipViewCompute:
     def __init__(self, scene, targets, cam_table, loss_weight=1.0, fused=True, loss="l1", w_rgb=0.8, w_ssim=0.2,
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
                  persistent_grads=True, pose_grad=False, skin_grid_grad=False, mask_targets=None, w_mask=0.0, depth_targets=None,
-                 w_depth=0.0, lpips=None, w_lpips=0.0, lpips_rects=None, lpips_norm="frame", lpips_cache_targets=False):
+                 w_depth=0.0, lpips=None, w_lpips=0.0, lpips_rects=None, lpips_norm="frame", lpips_cache_targets=False,
+                 lpips_batch=0):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -621,6 +625,7 @@ class HipViewCompute:
         if lpips_norm not in ("frame", "window"):
             raise ValueError("lpips_norm must be 'frame' or 'window' (got %r)" % (lpips_norm,))
         self.lpips_rects, self.lpips_norm, self.lpips_cache_targets = lpips_rects, lpips_norm, bool(lpips_cache_targets)
+        self.lpips_batch = int(lpips_batch)
         # -- model
         self.params = {k: v.detach().clone().requires_grad_(True) for k, v in scene["params"].items()}
         N = self.params["_xyz"].shape[0]
@@ -930,7 +935,7 @@ class HipViewCompute:
         k = scale * self.w_lpips
         vals, _ = self.lpips.values_grad(img.detach(), tgt, need_grad=True, out_grad=g_img, accumulate=True, rects=win["rects"],
                                          grad_scales=[k] * len(view_ids) if win["factors"] is None else [k * f for f in win["factors"]],
-                                         target_taps=win["taps"])
+                                         target_taps=win["taps"], batch=self.lpips_batch)
         if win["factors"] is not None:
             vals = vals * win["factors_dev"]
         self.last_lpips = vals.sum() * scale
@@ -957,7 +962,7 @@ class HipViewCompute:
                 factors = [float(int(r[2]) * int(r[3])) / area for r in rects]
                 factors_dev = torch.tensor(factors, dtype=torch.float32, device=self.device)
             win = sel["lpips"] = dict(key=key, rects=rects, factors=factors, factors_dev=factors_dev,
-                                      taps=self.lpips.target_taps(tgt, rects) if cache else None)
+                                      taps=self.lpips.target_taps(tgt, rects, batch=self.lpips_batch) if cache else None)
         return win
 
     def _image_loss(self, img, tgt, scale, tiles=None):

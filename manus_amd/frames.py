@@ -77,6 +77,7 @@ class FrameStore:
         self._state = {}             # (targets.data_ptr(), slot) -> (weak reference to the table, rectangle, background, masks pointer)
         self._scene_masks = None     # (targets.data_ptr(), float table): masks decoded for a scene's pruning masks alone (`load_step(scene_masks=True)`)
         self._bg_host = None         # (id, version) of a compute object's background tensor and its three floats
+        self.lpips_fit = None        # keywords of `lpips_rects` for `load_step(lpips_rects=True)`, e.g. dict(margin=16, quantum=32, common=True)
         if len(self.offsets) != len(self.items) or len(self.bboxes) != len(self.items):
             raise ValueError("offsets, bboxes and items must have one entry per crop")
         if (self.offsets % ALIGN).any():
@@ -230,10 +231,11 @@ class FrameStore:
             self._state = dict(new_state)
 
     # -- LPIPS windows ---------------------------------------------------------------------------------------------------
-    def lpips_rects(self, items, margin=16, net="vgg"):
+    def lpips_rects(self, items, margin=16, net="vgg", quantum=0, common=False):
         """(len(items),4) int32 x0, y0, w, h: every item's bbox in output pixels (`out_rect`), grown by `margin`, clamped to the
         frame and brought to the network's minimum size (`lpips.fit_rects`) -- the windows of `HipViewCompute.lpips_rects`.  An
-        empty bbox gives an empty rectangle.  Host arithmetic only."""
+        empty bbox gives an empty rectangle.  quantum / common: `fit_rects`' -- sides rounded up to a multiple of the quantum,
+        one size for the whole set -- for a batched term (`HipViewCompute.lpips_batch`).  Host arithmetic only."""
         from .lpips import fit_rects
         rects = []
         for it in items:
@@ -241,7 +243,7 @@ class FrameStore:
                 raise KeyError("item %r is not in the frame store" % (it,))
             x0, y0, x1, y1 = out_rect(self.bboxes[self.row[int(it)]], self.k)
             rects.append((x0, y0, x1 - x0, y1 - y0))
-        return fit_rects(np.asarray(rects, np.int64).reshape(-1, 4), self.height, self.width, net, margin)
+        return fit_rects(np.asarray(rects, np.int64).reshape(-1, 4), self.height, self.width, net, margin, quantum, common)
 
     # -- one step of a compute object -----------------------------------------------------------------------------------
     def _compute_bg(self, compute):
@@ -258,7 +260,8 @@ class FrameStore:
         allocates a zero table and sets it when it is not), their camera rows into `compute.cams`, their bone transforms (and
         posed transforms, keypoints, camera dicts, pruning masks where the scene holds them) into the scene's tables, all in
         place; the compute object is told, so its next step rebuilds what it derives from them.  lpips_rects=True also writes
-        the slots' rows of `compute.lpips_rects` with the items' windows (`lpips_rects(items)`), allocating a table of full-frame
+        the slots' rows of `compute.lpips_rects` with the items' windows (`lpips_rects(items, **self.lpips_fit)`; the store's
+        `lpips_fit` is None, today's rows, or a dict of margin / net / quantum / common), allocating a table of full-frame
         rectangles first when the compute object has none.  scene_masks=True: when the compute object has NO mask table but the
         scene holds pruning masks (`s["masks"]`, what `HipViewCompute.prune_views` hands the pruning tests), the items' masks are
         decoded into a table the store keeps and copied into the scene's rows all the same -- the mask loss term stays off --,
@@ -307,6 +310,6 @@ class FrameStore:
                 table = np.tile(np.asarray([0, 0, self.width, self.height], np.int32), (int(compute.targets.shape[0]), 1))
             else:
                 table = np.array(table, dtype=np.int32).reshape(-1, 4)
-            table[slots] = self.lpips_rects(items)
+            table[slots] = self.lpips_rects(items, **(self.lpips_fit or {}))
             compute.lpips_rects = table
         compute.view_constants_changed()

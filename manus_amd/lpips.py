@@ -16,6 +16,11 @@ of its frame is the LPIPS of the two crops -- the plain call on contiguous copie
 crop's own zero padding and spatial means -- not the full-frame value restricted to a region.  Only the window is convolved
 (DESIGN.md section 6 has the times: below about 768^2 they fall more slowly than the area).  A target is a constant of its view: `target_taps` keeps the target tower's five taps of
 a window, and a call given them skips that tower (the same bits).
+
+Batches (`values_grad(rects=, batch=B)`, `target_taps(batch=B)`): with B >= 2 the views of a call that share a window size run
+as chunks of at most min(B, LP_MAX_BATCH) views, one chain of launches per chunk (`mgr_lpips_roi_batch_op`), bit for bit the
+sequential call; the kept workspace grows to the largest chunk's.  `fit_rects(quantum=, common=)` gives a view set windows of a
+shared size -- larger windows, and so other values than the tight ones.  The default, batch=0, is the sequential call.
 """
 import ctypes
 import functools
@@ -23,7 +28,7 @@ import functools
 import numpy as np
 import torch
 
-from ._lib import MGR_LPIPS_BF16, MGR_LPIPS_F32, ManusHipError, check, f32c, lib, ptr, stream
+from ._lib import LP_MAX_BATCH, MGR_LPIPS_BF16, MGR_LPIPS_F32, ManusHipError, check, f32c, lib, ptr, stream
 
 NETS = {"vgg": 0, "alex": 1}
 OPERANDS = {"fp32": MGR_LPIPS_F32, "bf16": MGR_LPIPS_BF16}
@@ -88,16 +93,30 @@ def _fit_span(a, n, margin, m, F):
     return lo, hi - lo
 
 
-def fit_rects(rects, H, W, net, margin=0):
+def _widen_span(a, n, to, F):
+    """The span [a, a + n) of a frame side F widened to min(to, F) pixels: grown to the right, shifted left at the border."""
+    to = min(int(to), F)
+    return min(a, F - to), to
+
+
+def fit_rects(rects, H, W, net, margin=0, quantum=0, common=False):
     """Rectangles (x0, y0, w, h) made fit for a windowed call on an H x W frame: every non-empty one grown by `margin` on all
     sides, clamped to the frame, then grown or shifted inside the frame to the network's minimum size (`min_size`).  An empty
     rectangle (w or h zero, or nothing left inside the frame) comes back as (0,0,0,0).  Pure host arithmetic; (V,4) int32.
-    ValueError for a negative size or margin, or a frame smaller than the minimum."""
+    ValueError for a negative size, margin or quantum, or a frame smaller than the minimum.
+
+    For a batched call (`values_grad(batch=)`), which groups views by window size: quantum > 0 then rounds w and h up to a
+    multiple of `quantum`, capped at the frame's side; common=True then gives every non-empty rectangle the largest w and the
+    largest h of the set, so that the whole set is one group.  Either keeps the origin and shifts the rectangle at the right /
+    bottom border so that it stays inside the frame and contains the rectangle fitted so far.  Both off is the fitting above."""
     m = min_size(net)
     if H < m or W < m:
         raise ValueError("fit_rects: a %dx%d frame is smaller than the %dx%d minimum of the %s network" % (W, H, m, m, net))
     if margin < 0:
         raise ValueError("fit_rects: negative margin")
+    if quantum < 0:
+        raise ValueError("fit_rects: negative quantum")
+    quantum = int(quantum)
     src = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
     out = np.zeros(src.shape, np.int32)
     for j, (x0, y0, w, h) in enumerate(src.tolist()):
@@ -108,8 +127,26 @@ def fit_rects(rects, H, W, net, margin=0):
         fx, fw = _fit_span(x0, w, int(margin), m, W)
         fy, fh = _fit_span(y0, h, int(margin), m, H)
         if fw and fh:
+            if quantum > 0:
+                fx, fw = _widen_span(fx, fw, -(-fw // quantum) * quantum, W)
+                fy, fh = _widen_span(fy, fh, -(-fh // quantum) * quantum, H)
             out[j] = (fx, fy, fw, fh)
+    if common and out[:, 2].any():
+        cw, ch = int(out[:, 2].max()), int(out[:, 3].max())
+        for j in range(out.shape[0]):
+            if out[j, 2]:
+                fx, fw = _widen_span(int(out[j, 0]), int(out[j, 2]), cw, W)
+                fy, fh = _widen_span(int(out[j, 1]), int(out[j, 3]), ch, H)
+                out[j] = (fx, fy, fw, fh)
     return out
+
+
+def _batch(batch, who):
+    """The `batch` keyword as the C ABI's max_batch: 0 (and 1) is the sequential call."""
+    b = int(batch)
+    if b < 0:
+        raise ManusHipError("%s: batch must be 0 (sequential) or the most views per launch (got %r)" % (who, batch))
+    return b
 
 
 class TargetTaps:
@@ -215,7 +252,7 @@ class LPIPS:
         return self._ws
 
     def values_grad(self, pred, target, mask=None, normalize=False, need_grad=True, grad_scale=1.0, out_grad=None, accumulate=False,
-                    rects=None, grad_scales=None, target_taps=None):
+                    rects=None, grad_scales=None, target_taps=None, batch=0):
         """values (V,) and the gradient of grad_scale * sum(values) w.r.t. pred (V,3,H,W) in one pass (`mgr_lpips`).  `out_grad`:
         write (or, with accumulate, add) the gradient there instead of a new tensor.
 
@@ -223,12 +260,17 @@ class LPIPS:
         the crops at rects[v]; its gradient is the crop's inside the rectangle and, outside it, zero (or, with accumulate,
         untouched).  An empty rectangle gives the value 0 and no gradient.  grad_scales: V floats, one per view, instead of the
         one grad_scale.  target_taps: a `TargetTaps` of `target_taps(...)` on the same rects, mask and flags: the target tower
-        is skipped, `target` may then be None.  rects=None is the plain call."""
+        is skipped, `target` may then be None.  rects=None is the plain call.  batch: the most views per launch; 0 or 1 is the
+        sequential call, >= 2 runs the views that share a window size as chunks of that many (at most LP_MAX_BATCH) on
+        `mgr_lpips_roi_batch_op` -- the same bits, a kept workspace of the largest chunk.  A full-frame batch is rects = the
+        frame: batch without rects is refused."""
         if self.blob is None:
             raise ManusHipError("LPIPS: no weights (build with LPIPS.from_state_dicts or LPIPS.load)")
         if rects is not None:
             return self._values_grad_roi(pred, target, mask, normalize, need_grad, grad_scale, out_grad, accumulate, rects, grad_scales,
-                                         target_taps)
+                                         target_taps, _batch(batch, "LPIPS"))
+        if _batch(batch, "LPIPS"):
+            raise ManusHipError("LPIPS: batch belongs to the windowed call (rects=); a full-frame batch is rects = the frame")
         if grad_scales is not None or target_taps is not None:
             raise ManusHipError("LPIPS: grad_scales and target_taps belong to the windowed call (rects=)")
         pred, target = f32c(pred), f32c(target)
@@ -267,7 +309,8 @@ class LPIPS:
                 raise ManusHipError("LPIPS: mask must be (N,H,W)")
         return pred, target, mask, V, H, W
 
-    def _values_grad_roi(self, pred, target, mask, normalize, need_grad, grad_scale, out_grad, accumulate, rects, grad_scales, taps):
+    def _values_grad_roi(self, pred, target, mask, normalize, need_grad, grad_scale, out_grad, accumulate, rects, grad_scales, taps,
+                         batch=0):
         if target is None and taps is None:
             raise ManusHipError("LPIPS: a windowed call needs target or target_taps")
         pred, target, mask, V, H, W = self._frames(pred, target, mask)
@@ -288,21 +331,42 @@ class LPIPS:
                 raise ManusHipError("LPIPS: out_grad must be fp32 of pred's shape")
         rp = rects.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
         # (0 where a rectangle is refused: the call below says which and why)
-        ws = self._grow(lib().mgr_lpips_roi_workspace_bytes(NETS[self.net], V, rp, int(bool(need_grad))))
         vals = torch.empty(V, dtype=torch.float32, device=pred.device)
+        if batch >= 2:
+            ws = self._grow(lib().mgr_lpips_roi_batch_workspace_bytes(NETS[self.net], V, rp, int(bool(need_grad)), batch))
+            check(lib().mgr_lpips_roi_batch_op(NETS[self.net], V, H, W, rp, ptr(pred), ptr(target), ptr(mask), ptr(self.blob),
+                                               self.blob.numel(), int(bool(normalize)), (ctypes.c_float * V)(*scales), ptr(vals), ptr(g),
+                                               int(bool(accumulate)), tap_ptrs, ptr(ws), ws.numel(), stream(), self._op, batch),
+                  "mgr_lpips_roi_batch_op")
+            return vals, g
+        ws = self._grow(lib().mgr_lpips_roi_workspace_bytes(NETS[self.net], V, rp, int(bool(need_grad))))
         check(lib().mgr_lpips_roi_op(NETS[self.net], V, H, W, rp, ptr(pred), ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
                                      int(bool(normalize)), (ctypes.c_float * V)(*scales), ptr(vals), ptr(g), int(bool(accumulate)),
                                      tap_ptrs, ptr(ws), ws.numel(), stream(), self._op), "mgr_lpips_roi_op")
         return vals, g
 
-    def target_taps(self, target, rects, mask=None, normalize=False):
+    def target_taps(self, target, rects, mask=None, normalize=False, batch=0):
         """The target tower's taps of every view's window (`mgr_lpips_roi_taps_op`), for `values_grad(target_taps=)`: a
-        `TargetTaps` holding mgr_lpips_taps_bytes per non-empty view.  target (V,3,H,W), mask (V,H,W) or None, rects (V,4)."""
+        `TargetTaps` holding mgr_lpips_taps_bytes per non-empty view.  target (V,3,H,W), mask (V,H,W) or None, rects (V,4).
+        batch >= 2: the views that share a window size are built as chunks of that many (`mgr_lpips_roi_taps_batch_op`); the
+        buffers are the same, bit for bit."""
         if self.blob is None:
             raise ManusHipError("LPIPS: no weights (build with LPIPS.from_state_dicts or LPIPS.load)")
         target, _, mask, V, H, W = self._frames(target, None, mask)
         rects = _rects(rects, V)
         net, bufs = NETS[self.net], []
+        batch = _batch(batch, "LPIPS.target_taps")
+        if batch >= 2:
+            # (0 bytes where a rectangle is refused: the call says which and why)
+            bufs = [None if rects[v, 2] == 0 or rects[v, 3] == 0 else
+                    torch.empty(max(int(lib().mgr_lpips_taps_bytes(net, int(rects[v, 3]), int(rects[v, 2]))), 1), dtype=torch.uint8,
+                                device=target.device) for v in range(V)]
+            rp = rects.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            ws = self._grow(lib().mgr_lpips_roi_batch_workspace_bytes(net, V, rp, 0, batch))
+            check(lib().mgr_lpips_roi_taps_batch_op(net, V, H, W, rp, ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
+                                                    int(bool(normalize)), (ctypes.c_void_p * V)(*[None if b is None else ptr(b) for b in bufs]),
+                                                    batch, ptr(ws), ws.numel(), stream(), self._op), "mgr_lpips_roi_taps_batch_op")
+            return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None)
         for v in range(V):
             x0, y0, w, h = (int(t) for t in rects[v])
             if w == 0 or h == 0:
