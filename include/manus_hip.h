@@ -927,6 +927,55 @@ int mgr_lpips_roi_batch(int net, int V, int H, int W, const int* rects, const fl
                         int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream,
                         int max_batch);
 
+/* The storage mode (the *_st entries): each is its base entry with trailing storage arguments.  MGR_LPIPS_STORE_F32 is the
+ * base entry, bit for bit (the base entries are calls of these).  MGR_LPIPS_STORE_BF16, valid with MGR_LPIPS_BF16 operands only:
+ *
+ *   layout     every tensor of the chain -- pred's 13 (AlexNet 5) convolution outputs, the target's taps and non-tap outputs,
+ *              every pool output, every gradient buffer -- is bf16 as [ceil(C/8)][h][w][8]: 16 bytes per (pixel, block of 8
+ *              channels), channel c at block c / 8, lane c % 8; pad lanes are written as zero.  Batch-major as before: view b
+ *              of a buffer sits at b times the bytes of one view.  The image-side pair stays (3,h,w) fp32 planar: the scaled
+ *              image and dL/d(scaled image), so windows and the frame-side bits are those of fp32 storage's scaling kernels.
+ *   conv       the operand mode's chunking, MFMA sequence, fp32 accumulation, fp32 bias and ReLU, then ONE round to nearest
+ *              even at the store.  A stored value is the next MFMA's operand as it is (no second rounding); the gate of a
+ *              data gradient is `stored value > 0`.
+ *   pool       the maximum of the stored values (exact); the winner is the FIRST maximum in row-major window order among the
+ *              STORED values, forward and backward -- ties that the rounding creates go to the first position.
+ *   head       reads the taps exactly (bf16 -> fp32), arithmetic as in fp32 storage (fp32, fp64 partials); its gradient is
+ *              rounded once at the store, with a deeper gradient present fp32(stored g) + t is rounded once.  The fold is
+ *              unchanged.
+ *   as before  no atomics (two runs give equal bits); V views equal V calls of one view; a batched call equals the
+ *              sequential one; a window equals the call on contiguous crops; d(x, x) and its gradient are exactly 0; a pixel
+ *              with all-zero tap features contributes no gradient.
+ *
+ * Sizes: mgr_lpips_workspace_bytes_st / mgr_lpips_layout_st / mgr_lpips_taps_bytes_st /
+ * mgr_lpips_roi_batch_workspace_bytes_st -- an act or tap region is mgr_align(2 G pad8(C) h w) bytes, the partials are
+ * unchanged.  The weight blob is the bf16 operand mode's, unchanged.  mgr_lpips_roi_batch_st with max_batch = 1 is the sequential
+ * windowed call; mgr_lpips_roi_taps_batch_st with max_batch = 1 builds the taps view by view.  mgr_lpips_conv_st (tests,
+ * tools/measure_lpips.py): x_storage is the storage of x and gate, y_storage that of y; any Cin and Cout, blocked tensors
+ * padded to 8 channels.
+ *
+ * Refused on the host before any launch (no buffer touched): a storage other than 0 / 1 (-1; the size queries return 0),
+ * MGR_LPIPS_STORE_BF16 with MGR_LPIPS_F32 operands (-1), and everything the base entries refuse.  A taps buffer built under the
+ * other storage cannot be told apart here: the Python layer (TargetTaps.matches) refuses it. */
+enum { MGR_LPIPS_STORE_F32 = 0, MGR_LPIPS_STORE_BF16 = 1 };
+size_t mgr_lpips_workspace_bytes_st(int net, int H, int W, int need_grad, int storage);
+int mgr_lpips_layout_st(int net, int H, int W, int need_grad, size_t* offsets, int n, int storage);
+size_t mgr_lpips_taps_bytes_st(int net, int h, int w, int storage);
+size_t mgr_lpips_roi_batch_workspace_bytes_st(int net, int V, const int* rects, int need_grad, int max_batch, int storage);
+int mgr_lpips_st(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob,
+                 size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate, void* workspace,
+                 size_t workspace_bytes, void* stream, int operands, int storage);
+int mgr_lpips_roi_batch_st(int net, int V, int H, int W, const int* rects, const float* pred, const float* target, const float* mask,
+                           const void* blob, size_t blob_bytes, int normalize, const float* grad_scales, float* values, float* dL_dpred,
+                           int accumulate, const float* const* target_taps, void* workspace, size_t workspace_bytes, void* stream,
+                           int operands, int max_batch, int storage);
+int mgr_lpips_roi_taps_batch_st(int net, int V, int H, int W, const int* rects, const float* target, const float* mask, const void* blob,
+                                size_t blob_bytes, int normalize, float* const* taps_out, int max_batch, void* workspace,
+                                size_t workspace_bytes, void* stream, int operands, int storage);
+int mgr_lpips_conv_st(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                      const float* w, const float* bias, int relu, int transposed, float* y, void* scratch, size_t scratch_bytes,
+                      void* stream, int operands, int x_storage, int y_storage);
+
 /* ------------------------------------------------------------------------
  * Device frame store: the stored uint8 RGBA crops of a capture decoded into the float targets and masks of a step
  * (manus_amd/frames.py; SequenceDataset.fetch_images, brics_dynamic.py:343-373, restated bit for bit).

@@ -33,7 +33,8 @@ MGR_TIERS_BOX_LARGE, MGR_TIERS_BOX_MID, MGR_TIERS_WIDE_RECT = 1, 2, 4
 MGR_TIERS_NEAR_SMALL_SHIFT, MGR_TIERS_NEAR_LARGE_SHIFT, MGR_TIERS_NEAR_MASK = 8, 16, 0xFF
 MGR_TIERS_BEYOND_SMALL_SHIFT, MGR_TIERS_BEYOND_SMALL_MASK = 24, 0x7F
 MGR_LPIPS_F32, MGR_LPIPS_BF16 = 0, 1      # the operand mode of the mgr_lpips*_op entries
-LP_MAX_BATCH = 16                         # the most views of one launch of the mgr_lpips_roi*_batch* entries (manus_hip.h)
+MGR_LPIPS_STORE_F32, MGR_LPIPS_STORE_BF16 = 0, 1      # the storage mode of the mgr_lpips*_st entries
+LP_MAX_BATCH = 16                        # the most views of one launch of the mgr_lpips_roi*_batch* entries (manus_hip.h)
 
 c_int, c_i64, c_f32, c_vp, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -176,6 +177,18 @@ SIGNATURES = {
                                        ctypes.POINTER(c_f32), c_vp, c_vp, c_int, ctypes.POINTER(c_vp), c_vp, c_sz, c_vp, c_int, c_int]),
     "mgr_lpips_roi_batch": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_sz, c_int,
                                     ctypes.POINTER(c_f32), c_vp, c_vp, c_int, ctypes.POINTER(c_vp), c_vp, c_sz, c_vp, c_int]),
+    "mgr_lpips_workspace_bytes_st": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    "mgr_lpips_layout_st": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_sz), c_int, c_int]),
+    "mgr_lpips_taps_bytes_st": (c_sz, [c_int, c_int, c_int, c_int]),
+    "mgr_lpips_roi_batch_workspace_bytes_st": (c_sz, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int]),
+    "mgr_lpips_st": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_int, c_f32, c_vp, c_vp, c_int, c_vp, c_sz, c_vp,
+                             c_int, c_int]),
+    "mgr_lpips_roi_batch_st": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_vp, c_sz, c_int,
+                                       ctypes.POINTER(c_f32), c_vp, c_vp, c_int, ctypes.POINTER(c_vp), c_vp, c_sz, c_vp, c_int, c_int,
+                                       c_int]),
+    "mgr_lpips_roi_taps_batch_st": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_vp, c_vp, c_vp, c_sz, c_int,
+                                            ctypes.POINTER(c_vp), c_int, c_vp, c_sz, c_vp, c_int, c_int]),
+    "mgr_lpips_conv_st": (c_int, [c_int] * 8 + [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_sz, c_vp, c_int, c_int, c_int]),
     "mgr_frames_decode": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_i64, ctypes.POINTER(MgrFrameView), c_vp, c_vp, c_i64, c_vp]),
     "mgr_eval_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_eval_views": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

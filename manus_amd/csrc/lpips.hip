@@ -38,6 +38,20 @@
 // and scales, the fold one workgroup per view.  No sum changes: a batched call is the sequential call bit for bit, and every
 // other call of this file is the batch of one view.
 //
+// Storage (the *_st entries with storage = MGR_LPIPS_STORE_BF16, bf16 operands only): every tensor of the chain -- pred's
+// convolution outputs, the target's taps and non-tap outputs, the pool outputs, every gradient buffer -- is bf16 in the
+// channel-blocked layout [ceil(C / 8)][h][w][8]: 16 bytes per (pixel, block of 8 channels), channel c at block c / 8, lane
+// c % 8, pad lanes written as zero so that readers load unconditionally; view b of a batch-major buffer sits at b times the
+// bytes of one view.  The image-side pair stays (3,h,w) fp32 planar -- the scaled image and layer 0's data gradient -- so the
+// scaling kernels and the window semantics are untouched.  A convolution keeps its chunking, MFMA sequence, fp32 accumulation,
+// fp32 bias and ReLU and rounds ONCE (to nearest even) at the store; a stored value is the next MFMA's operand as it is (the
+// operand mode would have rounded the fp32 value to the same bits at the load), and the gate is `stored value > 0`.  A pool is
+// the maximum of the stored values (exact), the winner the FIRST maximum in row-major window order among the STORED values,
+// forward and backward: ties that the rounding creates go to the first position.  A head reads the taps exactly (bf16 ->
+// fp32), computes as in fp32 storage, and rounds its gradient once at the store; with add = 1 it forms fp32(stored g) + t and
+// rounds once.  The fold and the fp64 partials are unchanged.  No atomics; everything said of views, batches, windows and
+// d(x, x) = 0 above and below holds in this mode too.
+//
 // Spatial means travel as fp64 partials over a fixed tree (as k_map_loss does); no float atomics anywhere: bit-reproducible.
 //
 // One deviation from autograd: where a pixel's tap features are all zero, autograd through sqrt yields 0 * inf = NaN; here
@@ -48,6 +62,8 @@
 
 typedef float lp_f16v __attribute__((ext_vector_type(16)));
 typedef __bf16 lp_bf8 __attribute__((ext_vector_type(8)));
+typedef __bf16 lp_bf4 __attribute__((ext_vector_type(4)));
+typedef unsigned short lp_us8 __attribute__((ext_vector_type(8)));      // the bits of one (pixel, channel block) of bf16 storage
 
 #define LP_T 256           // threads of every kernel of this file
 #define LP_TW 32           // output columns per workgroup of k_lp_conv (the MFMA's columns)
@@ -99,6 +115,11 @@ static bool lp_net(int net, LpNet* n) {
 static inline size_t lp_pad64(size_t c) { return (c + 63) & ~(size_t)63; }
 static inline size_t lp_pad8(size_t c) { return (c + 7) & ~(size_t)7; }
 static inline bool lp_operands_ok(int operands) { return operands == MGR_LPIPS_F32 || operands == MGR_LPIPS_BF16; }
+static inline bool lp_storage_ok(int storage) { return storage == MGR_LPIPS_STORE_F32 || storage == MGR_LPIPS_STORE_BF16; }
+// bytes of a (C, h, w) tensor of the chain: fp32 planar, or bf16 [pad8(C) / 8][h][w][8]
+static inline size_t lp_tbytes(int storage, size_t C, size_t h, size_t w) {
+    return storage == MGR_LPIPS_STORE_BF16 ? lp_pad8(C) * h * w * 2 : C * h * w * 4;
+}
 // bytes of one packed weight set: fp32 [K][pad64(Cout)], bf16 [taps][pad8(Cin) / 8][pad64(Cout)][8]
 static inline size_t lp_wbytes(int operands, size_t cin, size_t kk, size_t cout) {
     return operands == MGR_LPIPS_BF16 ? kk * lp_pad8(cin) * lp_pad64(cout) * 2 : cin * kk * lp_pad64(cout) * 4;
@@ -150,36 +171,40 @@ static bool lp_shapes(const LpNet& n, int H, int W, LpShape* S) {
 
 // workspace: [pred's convolution outputs, in layer order][target's five taps][scratch A][scratch B][fp64 partials]
 // A chunk of G equal-size views (the batched entries) has every region G times as long, batch-major: view b of a buffer of e
-// elements sits at b e, view b's partials at b part_off[LP_NTAP].  G = 1 is the one-view layout.
+// bytes sits at b e, view b's partials at b part_off[LP_NTAP].  G = 1 is the one-view layout.  Sizes are lp_tbytes of the
+// storage; the scaled image and layer 0's data gradient, which the scratch holds too, are fp32 in both.
 struct LpLayout {
     size_t act[13], tap[LP_NTAP], bufa, bufb, part, total;
     size_t part_off[LP_NTAP + 1];      // in doubles: the slots of tap k are [part_off[k], part_off[k + 1])
 };
 
-static bool lp_layout(const LpNet& n, int H, int W, int need_grad, LpLayout* L, size_t G = 1) {
+static bool lp_layout(const LpNet& n, int H, int W, int need_grad, LpLayout* L, size_t G = 1, int st = MGR_LPIPS_STORE_F32) {
     LpShape S;
     if (H < 1 || W < 1 || (long long)H * W > (1ll << 24) || !lp_shapes(n, H, W, &S)) return false;
-    size_t o = 0, scratch = (size_t)3 * H * W;
+    // scratch B takes the scaled image (fp32 in both storages), so it is never smaller than one; in bf16 storage without a
+    // gradient scratch A holds blocked tensors only and is sized by them alone
+    const size_t img = (size_t)3 * H * W * 4;
+    size_t o = 0, scratch = st == MGR_LPIPS_STORE_BF16 && !need_grad ? 0 : img;
     int ci = 0;
     for (int i = 0; i < n.n_ops; ++i) {
         const LpOp& op = n.ops[i];
-        const size_t e = (size_t)op.cout * S.h[i] * S.w[i];
+        const size_t e = lp_tbytes(st, op.cout, S.h[i], S.w[i]);
         // scratch holds: the scaled image, every pool output, the target's convolution outputs that are no tap, and (with a
         // gradient) the gradient w.r.t. any of them
         if (!op.conv || op.tap < 0 || need_grad) scratch = scratch > e ? scratch : e;
-        if (op.conv) { L->act[ci++] = o;  o += mgr_align(G * e * 4); }
+        if (op.conv) { L->act[ci++] = o;  o += mgr_align(G * e); }
     }
     for (int i = 0; i < n.n_ops; ++i) {
         const LpOp& op = n.ops[i];
         if (op.conv && op.tap >= 0) {
-            L->tap[op.tap] = o;  o += mgr_align(G * op.cout * S.h[i] * S.w[i] * 4);
+            L->tap[op.tap] = o;  o += mgr_align(G * lp_tbytes(st, op.cout, S.h[i], S.w[i]));
             L->part_off[op.tap + 1] = ((size_t)S.h[i] * S.w[i] + LP_T - 1) / LP_T;
         }
     }
     L->part_off[0] = 0;
     for (int k = 0; k < LP_NTAP; ++k) L->part_off[k + 1] += L->part_off[k];
-    L->bufa = o;  o += mgr_align(G * scratch * 4);
-    L->bufb = o;  o += mgr_align(G * scratch * 4);
+    L->bufa = o;  o += mgr_align(G * scratch);
+    L->bufb = o;  o += mgr_align(G * (scratch > img ? scratch : img));
     L->part = o;  o += mgr_align(G * L->part_off[LP_NTAP] * 8);
     L->total = o;
     return true;
@@ -387,16 +412,29 @@ __global__ __launch_bounds__(LP_T) void k_lp_pack16(int Cout, int Cin, int KK, i
     for (size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x; e < (size_t)CoP; e += stride) bp[e] = e < (size_t)Cout ? bias[e] : 0.f;
 }
 
+// x / gate and y are fp32 planar or bf16 blocked, by the kernel's template arguments
 struct LpConv16Args {
     int Cin, Cout, CoP, NB, H, W, Ho, Wo, KH, KW, stride, pad, CK, KYN, relu, NZ;       // NB = pad8(Cin) / 8; NZ as in LpConvArgs
-    const float *x, *gate, *bias;
+    const void *x, *gate;
+    const float* bias;
     const lp_bf8* wp;
-    float* y;
+    void* y;
 };
+
+// one (pixel, channel block) of bf16 storage, zeroed where the gate's stored value is not positive
+__device__ __forceinline__ lp_us8 lp_gate8(lp_us8 v, lp_us8 g) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (!(__uint_as_float((unsigned)g[j] << 16) > 0.f)) v[j] = 0;
+    return v;
+}
 
 // A chunk is CK input channels (a multiple of 8) times KYN kernel rows (all of them for 3x3).  Its k runs over q = (tap, block
 // of 8 channels); one MFMA takes q = 2 m (lanes 0-31) and q = 2 m + 1 (lanes 32-63), an odd tail is zero.
-template <bool K3>
+// XB: x and gate are bf16 blocked -- a staged (pixel, channel block) is one 16-byte global load, the gate block a second, the
+// select is done in registers and nothing is converted.  YB: y is bf16 blocked -- the ONE rounding of the storage mode; a
+// lane's four consecutive rows of an accumulator are half a (pixel, block), the two halves of a wave interleave to full pixels.
+template <bool K3, bool XB, bool YB>
 __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lp_smem16[];
     const int KH = K3 ? 3 : a.KH, KW = K3 ? 3 : a.KW, st = K3 ? 1 : a.stride, pad = K3 ? 1 : a.pad, KYN = K3 ? 3 : a.KYN;
@@ -407,9 +445,15 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
     const int ix0 = ox0 * st - pad, iy0 = oy0 * st - pad;
     const bool two = a.Cout - co0 > 32;
     const size_t xoff = (size_t)zb * a.Cin * a.H * a.W;
-    const float* ax = a.x + xoff;
-    const float* agate = a.gate ? a.gate + xoff : nullptr;
-    float* ay = a.y + (size_t)zb * a.Cout * a.Ho * a.Wo;
+    const float* ax = (const float*)a.x + xoff;
+    const float* agate = a.gate ? (const float*)a.gate + xoff : nullptr;
+    float* ay = (float*)a.y + (size_t)zb * a.Cout * a.Ho * a.Wo;
+    // the blocked views of the same buffers: [NB][H][W] and [pad8(Cout) / 8][Ho][Wo] of 16 bytes
+    const size_t xboff = (size_t)zb * a.NB * a.H * a.W;
+    const lp_us8* bx = (const lp_us8*)a.x + xboff;
+    const lp_us8* bgate = a.gate ? (const lp_us8*)a.gate + xboff : nullptr;
+    const int NBo = (a.Cout + 7) >> 3;
+    lp_bf4* by = (lp_bf4*)a.y + (size_t)zb * NBo * a.Ho * a.Wo * 2;
     const int XS = a.CK * 2 + LP16_XPAD;                      // bytes per staged pixel
     lp_bf8* sW = (lp_bf8*)lp_smem16;                          // [q][64 output channels] of 8 bf16
     unsigned char* sX = lp_smem16 + (size_t)KYN * KW * (a.CK >> 3) * LP_TC * 16;       // [py][px] of XS bytes: CK bf16, padding
@@ -444,17 +488,26 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
                     const int ix = ix0 + px, iy = iy0 + py;
                     const bool in = ix >= 0 && ix < a.W && iy >= 0 && iy < a.H;
                     const size_t gp = (size_t)min(max(iy, 0), a.H - 1) * a.W + min(max(ix, 0), a.W - 1);
-                    float f[8], gt[8];
+                    if (XB) {
+                        // (the tail iteration's cb runs past the chunk: its address is clamped, its value dropped)
+                        const size_t g = (size_t)min((ci0 >> 3) + cb, a.NB - 1) * a.H * a.W + gp;
+                        lp_us8 v = bx[g];
+                        if (bgate) v = lp_gate8(v, bgate[g]);
+                        if (!in) v = (lp_us8)(0);
+                        if (e < 4 * NP) *(lp_us8*)(sX + p * (LP16_CK * 2 + LP16_XPAD) + cb * 16) = v;
+                    } else {
+                        float f[8], gt[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const size_t g = (size_t)min(ci0 + cb * 8 + j, a.Cin - 1) * a.H * a.W + gp;
-                        f[j] = ax[g];
-                        gt[j] = agate ? agate[g] : 1.f;
+                        for (int j = 0; j < 8; ++j) {
+                            const size_t g = (size_t)min(ci0 + cb * 8 + j, a.Cin - 1) * a.H * a.W + gp;
+                            f[j] = ax[g];
+                            gt[j] = agate ? agate[g] : 1.f;
+                        }
+                        lp_bf8 v;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) v[j] = (__bf16)(in && ci0 + cb * 8 + j < a.Cin && gt[j] > 0.f ? f[j] : 0.f);
+                        if (e < 4 * NP) *(lp_bf8*)(sX + p * (LP16_CK * 2 + LP16_XPAD) + cb * 16) = v;
                     }
-                    lp_bf8 v;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = (__bf16)(in && ci0 + cb * 8 + j < a.Cin && gt[j] > 0.f ? f[j] : 0.f);
-                    if (e < 4 * NP) *(lp_bf8*)(sX + p * (LP16_CK * 2 + LP16_XPAD) + cb * 16) = v;
                 }
             } else {
                 for (int e = tid; e < Q * LP_TC; e += LP_T) {
@@ -467,6 +520,17 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
                     const int cb = e / np, p = e - cb * np, py = p / PW, px = p - py * PW;
                     const int ix = ix0 + px, iy = iy0 + ky0 + py;
                     const bool in = ix >= 0 && ix < a.W && iy >= 0 && iy < a.H;
+                    if (XB) {
+                        // (ci0 / 8 + cb < NB: the chunk's blocks exist, their pad lanes are stored zeros)
+                        lp_us8 v = (lp_us8)(0);
+                        if (in) {
+                            const size_t g = ((size_t)((ci0 >> 3) + cb) * a.H + iy) * a.W + ix;
+                            v = bx[g];
+                            if (bgate) v = lp_gate8(v, bgate[g]);
+                        }
+                        *(lp_us8*)(sX + p * XS + cb * 16) = v;
+                        continue;
+                    }
                     lp_bf8 v;
     #pragma unroll
                     for (int j = 0; j < 8; ++j) {
@@ -525,6 +589,31 @@ __global__ __launch_bounds__(LP_T) void k_lp_conv16(const LpConv16Args a) {
     }
 
     const int ox = ox0 + col, oy = oy0 + wave;
+    if (YB) {
+        if (ox < a.Wo && oy < a.Ho) {
+            // rows (r & 3) + 8 q + 4 half, r = 4 q .. 4 q + 3: lanes 4 half .. 4 half + 3 of block co0 / 8 + q (+ 4 for acc1);
+            // a block that exists is written whole, its channels past Cout as zero
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                lp_bf4 v0, v1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c0 = co0 + 8 * q + 4 * half + j;
+                    float f0 = acc0[4 * q + j], f1 = acc1[4 * q + j];
+                    if (a.relu) {
+                        f0 = f0 < 0.f ? 0.f : f0;
+                        f1 = f1 < 0.f ? 0.f : f1;
+                    }
+                    v0[j] = (__bf16)(c0 < a.Cout ? f0 : 0.f);
+                    v1[j] = (__bf16)(c0 + 32 < a.Cout ? f1 : 0.f);
+                }
+                const int b0 = (co0 >> 3) + q, b1 = b0 + 4;
+                if (b0 < NBo) by[(((size_t)b0 * a.Ho + oy) * a.Wo + ox) * 2 + half] = v0;
+                if (two && b1 < NBo) by[(((size_t)b1 * a.Ho + oy) * a.Wo + ox) * 2 + half] = v1;
+            }
+        }
+        return;
+    }
     if (ox < a.Wo && oy < a.Ho) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -558,9 +647,27 @@ static void lp_conv16_chunk(int Cin, int KH, int KW, int stride, int* ck, int* k
     *ck = 8;  *kyn = 1;  *lds = lp_conv16_lds(8, 1, KW, stride);
 }
 
-// as lp_conv, on bf16 operands; wp: k_lp_pack16's layout
+template <bool XB, bool YB>
+static int lp_conv16_launch(hipStream_t stream, bool k3, dim3 grid, size_t lds, const LpConv16Args& a) {
+    if (k3) {
+        hipLaunchKernelGGL((k_lp_conv16<true, XB, YB>), grid, dim3(LP_T), lds, stream, a);
+    } else {
+        if (lds > 64 * 1024) {
+            static bool raised = false;       // (one per instantiation, as the attribute is)
+            if (!raised) {
+                MGR_HIP(hipFuncSetAttribute((const void*)k_lp_conv16<false, XB, YB>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                raised = true;
+            }
+        }
+        hipLaunchKernelGGL((k_lp_conv16<false, XB, YB>), grid, dim3(LP_T), lds, stream, a);
+    }
+    return MGR_OK;
+}
+
+// as lp_conv, on bf16 operands; wp: k_lp_pack16's layout.  xs / ys: the storage of x (and gate) and of y
 static int lp_conv16(hipStream_t stream, const char* name, int G, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad,
-                     const float* x, const float* gate, const void* wp, const float* bias, int relu, float* y) {
+                     const void* x, const void* gate, const void* wp, const float* bias, int relu, void* y,
+                     int xs = MGR_LPIPS_STORE_F32, int ys = MGR_LPIPS_STORE_F32) {
     LpConv16Args a;
     a.Cin = Cin; a.Cout = Cout; a.CoP = (int)lp_pad64(Cout); a.NB = (int)(lp_pad8(Cin) >> 3); a.H = H; a.W = W;
     a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1;
@@ -573,28 +680,23 @@ static int lp_conv16(hipStream_t stream, const char* name, int G, int Cin, int C
     const dim3 grid((a.Wo + LP_TW - 1) / LP_TW, (a.Ho + LP_TH - 1) / LP_TH, (unsigned)(G * a.NZ));
     if (grid.y > 65535u || grid.z > 65535u) return mgr_fail(MGR_EINVAL, "k_lp_conv16: image too large");
     MGR_PROF(name, stream);
-    if (KH == 3 && KW == 3 && stride == 1 && pad == 1) {
-        hipLaunchKernelGGL(k_lp_conv16<true>, grid, dim3(LP_T), lds, stream, a);
-    } else {
-        if (lds > 64 * 1024) {
-            static bool raised = false;
-            if (!raised) {
-                MGR_HIP(hipFuncSetAttribute((const void*)k_lp_conv16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                raised = true;
-            }
-        }
-        hipLaunchKernelGGL(k_lp_conv16<false>, grid, dim3(LP_T), lds, stream, a);
-    }
+    const bool k3 = KH == 3 && KW == 3 && stride == 1 && pad == 1, xb = xs == MGR_LPIPS_STORE_BF16, yb = ys == MGR_LPIPS_STORE_BF16;
+    const int rc = xb ? (yb ? lp_conv16_launch<true, true>(stream, k3, grid, lds, a) : lp_conv16_launch<true, false>(stream, k3, grid, lds, a))
+                      : (yb ? lp_conv16_launch<false, true>(stream, k3, grid, lds, a) : lp_conv16_launch<false, false>(stream, k3, grid, lds, a));
+    if (rc != MGR_OK) return rc;
     MGR_LAUNCH_CHECK(name, stream, 0);
     return MGR_OK;
 }
 
-// one convolution, of G views that sit batch-major in x / gate / y, in the call's operand mode
+// one convolution, of G views that sit batch-major in x / gate / y, in the call's operand mode; bf16 storage (xs, ys) goes
+// with bf16 operands only (the entries refuse the rest)
 static int lp_conv_op(int operands, hipStream_t stream, const char* name, const char* name16, int G, int Cin, int Cout, int H, int W,
-                      int KH, int KW, int stride, int pad, const float* x, const float* gate, const void* wp, const float* bias, int relu,
-                      float* y) {
-    if (operands == MGR_LPIPS_BF16) return lp_conv16(stream, name16, G, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, wp, bias, relu, y);
-    return lp_conv(stream, name, G, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, (const float*)wp, bias, relu, y);
+                      int KH, int KW, int stride, int pad, const void* x, const void* gate, const void* wp, const float* bias, int relu,
+                      void* y, int xs = MGR_LPIPS_STORE_F32, int ys = MGR_LPIPS_STORE_F32) {
+    if (operands == MGR_LPIPS_BF16)
+        return lp_conv16(stream, name16, G, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, wp, bias, relu, y, xs, ys);
+    return lp_conv(stream, name, G, Cin, Cout, H, W, KH, KW, stride, pad, (const float*)x, (const float*)gate, (const float*)wp, bias,
+                   relu, (float*)y);
 }
 
 // ---------------------------------------------------------------------------
@@ -734,6 +836,55 @@ __global__ __launch_bounds__(LP_T) void k_lp_pool2_bwd(int C, int H, int W, int 
     gx[e] = g;
 }
 
+// bf16 storage: one thread per (channel block, output pixel), 16-byte accesses; NBC = (views) x (blocks of 8 channels).  The
+// maximum of the stored values is exact, the first maximum in row-major window order wins (its bits are copied).
+__device__ __forceinline__ float lp_bf(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
+
+__global__ __launch_bounds__(LP_T) void k_lp_pool_b(int NBC, int H, int W, int Ho, int Wo, int k, const lp_us8* __restrict__ x,
+                                                    lp_us8* __restrict__ y) {
+    const size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x;
+    if (e >= (size_t)NBC * Ho * Wo) return;
+    const int ox = (int)(e % Wo), oy = (int)((e / Wo) % Ho);
+    const size_t c = e / ((size_t)Wo * Ho);
+    const lp_us8* src = x + (c * H + 2 * oy) * W + 2 * ox;
+    lp_us8 m = src[0];
+    for (int dy = 0; dy < k; ++dy)
+        for (int dx = 0; dx < k; ++dx) {
+            const lp_us8 v = src[dy * W + dx];
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (lp_bf(v[j]) > lp_bf(m[j])) m[j] = v[j];
+        }
+    y[e] = m;
+}
+
+// 2 x 2 stride 2 backward, bf16 storage: one thread per (channel block, INPUT pixel); the winner is recomputed from the stored
+// input, per lane.  Pad lanes hold zeros in x and gy, so they come out zero.
+__global__ __launch_bounds__(LP_T) void k_lp_pool2_bwd_b(int NBC, int H, int W, int Ho, int Wo, const lp_us8* __restrict__ x,
+                                                         const lp_us8* __restrict__ gy, lp_us8* __restrict__ gx) {
+    const size_t e = (size_t)blockIdx.x * LP_T + threadIdx.x;
+    if (e >= (size_t)NBC * H * W) return;
+    const int ix = (int)(e % W), iy = (int)((e / W) % H);
+    const size_t c = e / ((size_t)W * H);
+    const int ox = ix >> 1, oy = iy >> 1;
+    lp_us8 g = (lp_us8)(0);
+    if (ox < Wo && oy < Ho) {
+        const lp_us8* src = x + (c * H + 2 * oy) * W + 2 * ox;
+        const lp_us8 s0 = src[0], s1 = src[1], s2 = src[W], s3 = src[W + 1], go = gy[(c * Ho + oy) * Wo + ox];
+        const int me = (iy & 1) << 1 | (ix & 1);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float m = lp_bf(s0[j]);
+            int win = 0;
+            if (lp_bf(s1[j]) > m) { m = lp_bf(s1[j]); win = 1; }
+            if (lp_bf(s2[j]) > m) { m = lp_bf(s2[j]); win = 2; }
+            if (lp_bf(s3[j]) > m) { m = lp_bf(s3[j]); win = 3; }
+            if (win == me) g[j] = go[j];
+        }
+    }
+    gx[e] = g;
+}
+
 // ---------------------------------------------------------------------------
 // head
 // ---------------------------------------------------------------------------
@@ -793,6 +944,72 @@ __global__ __launch_bounds__(LP_T) void k_lp_head(int C, int HW, const float* __
                 const float d = a / n0 - b / n1;
                 const float t = r0 > 0.f ? gs * (2.f * lin[c] * d / n0 - k2 * a) : 0.f;
                 g[e] = add ? g[e] + t : t;
+            }
+        }
+    }
+    const double tot = lp_block_sum(val, s_red, tid);
+    if (tid == 0) part[blockIdx.x] = tot;
+}
+
+// k_lp_head on bf16 storage: f0, f1 and g are [ceil(C / 8)][HW][8] bf16 (t.f1 holds the per-view addresses of such buffers).
+// The taps are read exactly, the arithmetic and its channel order are k_lp_head's; the gradient is rounded once at the store --
+// with add = 1, fp32(stored g) + t rounded once -- and the pad lanes of g are written as zero.
+__global__ __launch_bounds__(LP_T) void k_lp_head_b(int C, int HW, const lp_us8* __restrict__ f0, const LpHeadArgs t,
+                                                    const float* __restrict__ lin, lp_us8* __restrict__ g, int add,
+                                                    double* __restrict__ part, int part_stride) {
+    __shared__ double s_red[LP_T];
+    const int tid = threadIdx.x, p = blockIdx.x * LP_T + tid, vb = blockIdx.y, NB = (C + 7) >> 3;
+    const lp_us8* __restrict__ f1 = (const lp_us8*)t.f1[vb];
+    const float gs = t.gs[vb];
+    f0 += (size_t)vb * NB * HW;
+    if (g) g += (size_t)vb * NB * HW;
+    part += (size_t)vb * part_stride;
+    double val = 0.0;
+    if (p < HW) {
+        float s0 = 0.f, s1 = 0.f;
+        for (int cb = 0; cb < NB; ++cb) {
+            const lp_us8 va = f0[(size_t)cb * HW + p], vbb = f1[(size_t)cb * HW + p];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {       // (a pad lane adds +0)
+                const float a = lp_bf(va[j]), b = lp_bf(vbb[j]);
+                s0 = fmaf(a, a, s0);
+                s1 = fmaf(b, b, s1);
+            }
+        }
+        const float r0 = sqrtf(s0), n0 = r0 + 1e-10f, n1 = sqrtf(s1) + 1e-10f;
+        float v = 0.f, dot = 0.f;
+        for (int cb = 0; cb < NB; ++cb) {
+            const lp_us8 va = f0[(size_t)cb * HW + p], vbb = f1[(size_t)cb * HW + p];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (cb * 8 + j >= C) break;
+                const float a = lp_bf(va[j]), b = lp_bf(vbb[j]);
+                const float d = a / n0 - b / n1, l = lin[cb * 8 + j];
+                v = fmaf(l, d * d, v);
+                dot = fmaf(2.f * l * d, a, dot);
+            }
+        }
+        val = (double)v;
+        if (g) {
+            const float k2 = r0 > 0.f ? dot / (n0 * n0 * r0) : 0.f;
+            for (int cb = 0; cb < NB; ++cb) {
+                const size_t e = (size_t)cb * HW + p;
+                const lp_us8 va = f0[e], vbb = f1[e];
+                lp_us8 old = (lp_us8)(0);
+                if (add) old = g[e];
+                lp_bf8 out;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float w = 0.f;
+                    if (cb * 8 + j < C) {
+                        const float a = lp_bf(va[j]), b = lp_bf(vbb[j]);
+                        const float d = a / n0 - b / n1;
+                        const float tt = r0 > 0.f ? gs * (2.f * lin[cb * 8 + j] * d / n0 - k2 * a) : 0.f;
+                        w = add ? lp_bf(old[j]) + tt : tt;
+                    }
+                    out[j] = (__bf16)w;
+                }
+                *(lp_bf8*)(g + e) = out;
             }
         }
     }
@@ -882,18 +1099,24 @@ extern "C" int mgr_lpips_net_pack(int net, const float* const* conv_w, const flo
     return mgr_lpips_net_pack_op(net, conv_w, conv_b, lin_w, blob, blob_bytes, stream, MGR_LPIPS_F32);
 }
 
-extern "C" size_t mgr_lpips_workspace_bytes(int net, int H, int W, int need_grad) {
+extern "C" size_t mgr_lpips_workspace_bytes_st(int net, int H, int W, int need_grad, int storage) {
     LpNet n;
     LpLayout L;
-    if (!lp_net(net, &n) || !lp_layout(n, H, W, need_grad, &L)) return 0;
+    if (!lp_net(net, &n) || !lp_storage_ok(storage) || !lp_layout(n, H, W, need_grad, &L, 1, storage)) return 0;
     return L.total;
 }
 
-extern "C" int mgr_lpips_layout(int net, int H, int W, int need_grad, size_t* offsets, int n_off) {
+extern "C" size_t mgr_lpips_workspace_bytes(int net, int H, int W, int need_grad) {
+    return mgr_lpips_workspace_bytes_st(net, H, W, need_grad, MGR_LPIPS_STORE_F32);
+}
+
+extern "C" int mgr_lpips_layout_st(int net, int H, int W, int need_grad, size_t* offsets, int n_off, int storage) {
     LpNet n;
     LpLayout L;
     if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: net must be 0 (vgg) or 1 (alex)");
-    if (!lp_layout(n, H, W, need_grad, &L)) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: image too small for the deepest tap (or too large)");
+    if (!lp_storage_ok(storage)) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: storage must be 0 (fp32) or 1 (bf16)");
+    if (!lp_layout(n, H, W, need_grad, &L, 1, storage))
+        return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: image too small for the deepest tap (or too large)");
     const int need = n.n_conv + LP_NTAP + 4;
     if (!offsets || n_off < need) return mgr_fail(MGR_EINVAL, "mgr_lpips_layout: offsets holds fewer than n_conv + 9 entries");
     int j = 0;
@@ -906,11 +1129,24 @@ extern "C" int mgr_lpips_layout(int net, int H, int W, int need_grad, size_t* of
     return need;
 }
 
-extern "C" int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+extern "C" int mgr_lpips_layout(int net, int H, int W, int need_grad, size_t* offsets, int n_off) {
+    return mgr_lpips_layout_st(net, H, W, need_grad, offsets, n_off, MGR_LPIPS_STORE_F32);
+}
+
+// the refusal shared by the *_st entries: null where (operands, storage) is a mode of this file
+static const char* lp_storage_refusal(int operands, int storage) {
+    if (!lp_storage_ok(storage)) return "storage must be 0 (fp32) or 1 (bf16)";
+    if (storage == MGR_LPIPS_STORE_BF16 && operands == MGR_LPIPS_F32) return "bf16 storage needs bf16 operands (fp32 operands are refused)";
+    return nullptr;
+}
+
+extern "C" int mgr_lpips_conv_st(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
                                  const float* w, const float* bias, int relu, int transposed, float* y, void* scratch,
-                                 size_t scratch_bytes, void* stream_, int operands) {
+                                 size_t scratch_bytes, void* stream_, int operands, int x_storage, int y_storage) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: operands must be 0 (fp32) or 1 (bf16)");
+    for (int s : {x_storage, y_storage})
+        if (const char* why = lp_storage_refusal(operands, s)) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: %s", why);
     if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || KH != KW || stride < 1 || pad < 0 || H + 2 * pad < KH || W + 2 * pad < KW)
         return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: bad sizes");
     if (!x || !w || !y || !scratch) return mgr_fail(MGR_EINVAL, "mgr_lpips_conv: null pointer");
@@ -935,9 +1171,16 @@ extern "C" int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW
     }
     if (transposed)
         return lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", 1, Cout, Cin, H, W, KH, KW, 1, pad, x, gate, base + o_t,
-                          nullptr, relu, y);
+                          nullptr, relu, y, x_storage, y_storage);
     return lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", 1, Cin, Cout, H, W, KH, KW, stride, pad, x, gate, base + o_f,
-                      bias ? (const float*)(base + o_b) : nullptr, relu, y);
+                      bias ? (const float*)(base + o_b) : nullptr, relu, y, x_storage, y_storage);
+}
+
+extern "C" int mgr_lpips_conv_op(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
+                                 const float* w, const float* bias, int relu, int transposed, float* y, void* scratch,
+                                 size_t scratch_bytes, void* stream, int operands) {
+    return mgr_lpips_conv_st(Cin, Cout, H, W, KH, KW, stride, pad, x, gate, w, bias, relu, transposed, y, scratch, scratch_bytes, stream,
+                             operands, MGR_LPIPS_STORE_F32, MGR_LPIPS_STORE_F32);
 }
 
 extern "C" int mgr_lpips_conv(int Cin, int Cout, int H, int W, int KH, int KW, int stride, int pad, const float* x, const float* gate,
@@ -960,34 +1203,44 @@ extern "C" size_t mgr_lpips_conv_scratch_bytes(int Cin, int Cout, int KH, int KW
 // forward of G images: scaled images -> sb, then the ops; a convolution writes to its slot of `store` (by convolution index)
 // where that is not null, else to the scratch buffer its input is not in.  Every buffer is batch-major.  win = null: G = 1 and
 // img / mask are one contiguous (3,H,W) / (H,W) image; else they are the frames and (H, W) is the size of win's G rectangles.
+// st: the storage of every tensor but the scaled image, which is fp32 (the first convolution reads it so).
 static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, const LpShape& S, int H, int W,
-                      int G, const float* img, const float* mask, int normalize, float* const* store, float* sa, float* sb,
-                      const LpWin* win = nullptr) {
+                      int G, const float* img, const float* mask, int normalize, void* const* store, void* sa, void* sb,
+                      const LpWin* win = nullptr, int st = MGR_LPIPS_STORE_F32) {
     const int HW = H * W;
     if (win) {
-        hipLaunchKernelGGL(k_lp_scale_win, dim3((W + LP_T - 1) / LP_T, H, G), dim3(LP_T), 0, stream, W, H, *win, img, mask, normalize, sb);
+        hipLaunchKernelGGL(k_lp_scale_win, dim3((W + LP_T - 1) / LP_T, H, G), dim3(LP_T), 0, stream, W, H, *win, img, mask, normalize,
+                           (float*)sb);
         MGR_LAUNCH_CHECK("k_lp_scale_win", stream, 0);
     } else {
-        hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, sb);
+        hipLaunchKernelGGL(k_lp_scale, dim3((HW + LP_T - 1) / LP_T), dim3(LP_T), 0, stream, HW, img, mask, normalize, (float*)sb);
         MGR_LAUNCH_CHECK("k_lp_scale", stream, 0);
     }
-    const float* cur = sb;
+    const void* cur = sb;
     int h = H, w = W, ci = 0;
     for (int i = 0; i < n.n_ops; ++i) {
         const LpOp& op = n.ops[i];
-        float* out;
+        void* out;
         if (op.conv) {
             out = store[ci] ? store[ci] : (cur == sa ? sb : sa);
             const int rc = lp_conv_op(operands, stream, "k_lp_conv", "k_lp_conv16", G, op.cin, op.cout, h, w, op.k, op.k, op.s, op.p, cur,
-                                      nullptr, blob + B.w[ci], (const float*)(blob + B.b[ci]), 1, out);
+                                      nullptr, blob + B.w[ci], (const float*)(blob + B.b[ci]), 1, out, i ? st : MGR_LPIPS_STORE_F32, st);
             if (rc != MGR_OK) return rc;
             ++ci;
+        } else if (st == MGR_LPIPS_STORE_BF16) {
+            // a per-block kernel: the G views are G pad8(cout) / 8 blocks
+            out = cur == sa ? sb : sa;
+            const int nbc = G * (int)(lp_pad8(op.cout) >> 3);
+            const size_t ne = (size_t)nbc * S.h[i] * S.w[i];
+            hipLaunchKernelGGL(k_lp_pool_b, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, nbc, h, w, S.h[i], S.w[i],
+                               op.k, (const lp_us8*)cur, (lp_us8*)out);
+            MGR_LAUNCH_CHECK("k_lp_pool_b", stream, 0);
         } else {
             // a per-channel kernel: the G views are G cout channels
             out = cur == sa ? sb : sa;
             const size_t ne = (size_t)G * op.cout * S.h[i] * S.w[i];
             hipLaunchKernelGGL(k_lp_pool, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, G * op.cout, h, w, S.h[i],
-                               S.w[i], op.k, cur, out);
+                               S.w[i], op.k, (const float*)cur, (float*)out);
             MGR_LAUNCH_CHECK("k_lp_pool", stream, 0);
         }
         cur = out;
@@ -1004,13 +1257,14 @@ static int lp_forward(int operands, hipStream_t stream, const LpNet& n, const Lp
 // rectangles.  taps[b]: view b's five target taps as mgr_lpips_roi_taps_op left them (in the one-view layout), or null.
 static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, int H, int W, int G,
                     const LpWin* win, const float* pred, const float* target, const float* mk, const float* const* taps, int normalize,
-                    const float* grad_scale, float* values, float* dL, int accumulate, char* ws) {
+                    const float* grad_scale, float* values, float* dL, int accumulate, char* ws, int st = MGR_LPIPS_STORE_F32) {
     const int need_grad = dL != nullptr;
+    const bool blocked = st == MGR_LPIPS_STORE_BF16;
     LpLayout L, L1;
     LpShape S;
-    if (!lp_layout(n, H, W, need_grad, &L, (size_t)G) || !lp_layout(n, H, W, need_grad, &L1) || !lp_shapes(n, H, W, &S))
+    if (!lp_layout(n, H, W, need_grad, &L, (size_t)G, st) || !lp_layout(n, H, W, need_grad, &L1, 1, st) || !lp_shapes(n, H, W, &S))
         return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small");
-    float *sa = (float*)(ws + L.bufa), *sb = (float*)(ws + L.bufb);
+    void *sa = ws + L.bufa, *sb = ws + L.bufb;
     double* part = (double*)(ws + L.part);
     const int part_stride = (int)L.part_off[LP_NTAP];
     // the views whose target tower runs: slot j of the workspace's tap regions is view tw.view[j]
@@ -1027,7 +1281,7 @@ static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBl
         if (win) { tw.view[GT] = win->view[b];  tw.x0[GT] = win->x0[b];  tw.y0[GT] = win->y0[b]; }
         ++GT;
     }
-    float *act[13], *tgt[13];
+    void *act[13], *tgt[13];
     LpHeadArgs ha[LP_NTAP];
     int tap_conv[LP_NTAP], tap_op[LP_NTAP];
     {
@@ -1035,17 +1289,17 @@ static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBl
         for (int i = 0; i < n.n_ops; ++i) {
             const LpOp& op = n.ops[i];
             if (!op.conv) continue;
-            act[ci] = (float*)(ws + L.act[ci]);
+            act[ci] = ws + L.act[ci];
             tgt[ci] = nullptr;
             if (op.tap >= 0) {
-                tgt[ci] = (float*)(ws + L.tap[op.tap]);
-                const size_t e = (size_t)op.cout * S.h[i] * S.w[i];
+                tgt[ci] = ws + L.tap[op.tap];
+                const size_t e = lp_tbytes(st, op.cout, S.h[i], S.w[i]);       // bytes of one view
                 for (int b = 0; b < LP_MAX_BATCH; ++b) {
                     ha[op.tap].f1[b] = nullptr;
                     ha[op.tap].gs[b] = 0.f;
                     if (b >= G) continue;
                     ha[op.tap].f1[b] = slot[b] < 0 ? (const float*)((const char*)taps[b] + (L1.tap[op.tap] - L1.tap[0]))
-                                                   : tgt[ci] + (size_t)slot[b] * e;
+                                                   : (const float*)((const char*)tgt[ci] + (size_t)slot[b] * e);
                 }
                 tap_conv[op.tap] = ci;
                 tap_op[op.tap] = i;
@@ -1063,23 +1317,28 @@ static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBl
 
     int rc;
     if (GT) {
-        rc = lp_forward(operands, stream, n, B, blob, S, H, W, GT, target, mk, normalize, tgt, sa, sb, win ? &tw : nullptr);
+        rc = lp_forward(operands, stream, n, B, blob, S, H, W, GT, target, mk, normalize, tgt, sa, sb, win ? &tw : nullptr, st);
         if (rc != MGR_OK) return rc;
     }
-    rc = lp_forward(operands, stream, n, B, blob, S, H, W, G, pred, mk, normalize, act, sa, sb, win);
+    rc = lp_forward(operands, stream, n, B, blob, S, H, W, G, pred, mk, normalize, act, sa, sb, win, st);
     if (rc != MGR_OK) return rc;
     if (!need_grad) {
         MGR_PROF("k_lp_head", stream);
         for (int k = 0; k < LP_NTAP; ++k) {
             const int i = tap_op[k], hw = S.h[i] * S.w[i];
-            hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
-                               (const float*)act[tap_conv[k]], ha[k], (const float*)(blob + B.lin[k]), (float*)nullptr, 0,
-                               part + L.part_off[k], part_stride);
+            if (blocked)
+                hipLaunchKernelGGL(k_lp_head_b, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
+                                   (const lp_us8*)act[tap_conv[k]], ha[k], (const float*)(blob + B.lin[k]), (lp_us8*)nullptr, 0,
+                                   part + L.part_off[k], part_stride);
+            else
+                hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, n.ops[i].cout, hw,
+                                   (const float*)act[tap_conv[k]], ha[k], (const float*)(blob + B.lin[k]), (float*)nullptr, 0,
+                                   part + L.part_off[k], part_stride);
             MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
         }
     } else {
         // from the deepest tap down: g holds dL/d(post-ReLU output) of the current op
-        float *g = sa, *o = sb;
+        void *g = sa, *o = sb;
         bool have = false;       // g holds a gradient from deeper layers
         int h_in, w_in;
         for (int i = n.n_ops - 1; i >= 0; --i) {
@@ -1092,27 +1351,39 @@ static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBl
                 if (op.tap >= 0) {
                     const int hw = S.h[i] * S.w[i], k = op.tap;
                     MGR_PROF("k_lp_head", stream);
-                    hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, op.cout, hw,
-                                       (const float*)act[ci], ha[k], (const float*)(blob + B.lin[k]), g, have ? 1 : 0,
-                                       part + L.part_off[k], part_stride);
+                    if (blocked)
+                        hipLaunchKernelGGL(k_lp_head_b, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, op.cout, hw,
+                                           (const lp_us8*)act[ci], ha[k], (const float*)(blob + B.lin[k]), (lp_us8*)g, have ? 1 : 0,
+                                           part + L.part_off[k], part_stride);
+                    else
+                        hipLaunchKernelGGL(k_lp_head, dim3((hw + LP_T - 1) / LP_T, G), dim3(LP_T), 0, stream, op.cout, hw,
+                                           (const float*)act[ci], ha[k], (const float*)(blob + B.lin[k]), (float*)g, have ? 1 : 0,
+                                           part + L.part_off[k], part_stride);
                     MGR_LAUNCH_CHECK("k_lp_head", stream, 0);
                     have = true;
                 }
-                // dL/d(input) = conv(g * [y > 0], W')
+                // dL/d(input) = conv(g * [y > 0], W'); layer 0's is dL/d(scaled image), fp32 in both storages
                 rc = lp_conv_op(operands, stream, "k_lp_conv_bwd", "k_lp_conv16_bwd", G, op.cout, op.cin, S.h[i], S.w[i], op.k, op.k, 1,
-                                op.p, g, act[ci], blob + B.wt[ci], nullptr, 0, o);
+                                op.p, g, act[ci], blob + B.wt[ci], nullptr, 0, o, st, i ? st : MGR_LPIPS_STORE_F32);
                 if (rc != MGR_OK) return rc;
             } else {
                 // the pool's input is the previous convolution's stored output
                 int ci = -1;
                 for (int j = 0; j < i; ++j) ci += n.ops[j].conv;
-                const size_t ne = (size_t)G * op.cin * h_in * w_in;
                 MGR_PROF("k_lp_pool2_bwd", stream);
-                hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, G * op.cin, h_in, w_in,
-                                   S.h[i], S.w[i], (const float*)act[ci], (const float*)g, o);
+                if (blocked) {
+                    const int nbc = G * (int)(lp_pad8(op.cin) >> 3);
+                    const size_t ne = (size_t)nbc * h_in * w_in;
+                    hipLaunchKernelGGL(k_lp_pool2_bwd_b, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, nbc, h_in, w_in,
+                                       S.h[i], S.w[i], (const lp_us8*)act[ci], (const lp_us8*)g, (lp_us8*)o);
+                } else {
+                    const size_t ne = (size_t)G * op.cin * h_in * w_in;
+                    hipLaunchKernelGGL(k_lp_pool2_bwd, dim3((unsigned)((ne + LP_T - 1) / LP_T)), dim3(LP_T), 0, stream, G * op.cin, h_in,
+                                       w_in, S.h[i], S.w[i], (const float*)act[ci], (const float*)g, (float*)o);
+                }
                 MGR_LAUNCH_CHECK("k_lp_pool2_bwd", stream, 0);
             }
-            float* t = g;  g = o;  o = t;
+            void* t = g;  g = o;  o = t;
         }
         if (win) {
             const dim3 grid = accumulate ? dim3((W + LP_T - 1) / LP_T, H, G) : dim3((win->FW + LP_T - 1) / LP_T, win->FH, G);
@@ -1130,19 +1401,20 @@ static int lp_views(int operands, hipStream_t stream, const LpNet& n, const LpBl
     return MGR_OK;
 }
 
-extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob_,
+extern "C" int mgr_lpips_st(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob_,
                             size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
-                            void* workspace, size_t workspace_bytes, void* stream_, int operands) {
+                            void* workspace, size_t workspace_bytes, void* stream_, int operands, int storage) {
     hipStream_t stream = (hipStream_t)stream_;
     LpNet n;
     if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips: net must be 0 (vgg) or 1 (alex)");
     if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips: operands must be 0 (fp32) or 1 (bf16)");
+    if (const char* why = lp_storage_refusal(operands, storage)) return mgr_fail(MGR_EINVAL, "mgr_lpips: %s", why);
     if (V <= 0 || H <= 0 || W <= 0) return mgr_fail(MGR_EINVAL, "mgr_lpips: bad sizes");
     if (!pred || !target || !blob_ || !values || !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips: null pointer");
     if (dL_dpred && !n.has_bwd) return mgr_fail(MGR_EINVAL, "mgr_lpips: the AlexNet network is forward only (dL_dpred must be null)");
     const int need_grad = dL_dpred != nullptr;
     LpLayout L;
-    if (!lp_layout(n, H, W, need_grad, &L))
+    if (!lp_layout(n, H, W, need_grad, &L, 1, storage))
         return mgr_fail(MGR_EINVAL, "mgr_lpips: image too small for the deepest tap to have one pixel (or above 2^24 pixels)");
     const LpBlob B = lp_blob(n, operands);
     if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "mgr_lpips: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
@@ -1151,10 +1423,17 @@ extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, con
     for (int v = 0; v < V; ++v) {
         const int rc = lp_views(operands, stream, n, B, (const char*)blob_, H, W, 1, nullptr, pred + v * img, target + v * img,
                                 mask ? mask + v * px : nullptr, nullptr, normalize, &grad_scale, values + v,
-                                dL_dpred ? dL_dpred + v * img : nullptr, accumulate, (char*)workspace);
+                                dL_dpred ? dL_dpred + v * img : nullptr, accumulate, (char*)workspace, storage);
         if (rc != MGR_OK) return rc;
     }
     return MGR_OK;
+}
+
+extern "C" int mgr_lpips_op(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob,
+                            size_t blob_bytes, int normalize, float grad_scale, float* values, float* dL_dpred, int accumulate,
+                            void* workspace, size_t workspace_bytes, void* stream, int operands) {
+    return mgr_lpips_st(net, V, H, W, pred, target, mask, blob, blob_bytes, normalize, grad_scale, values, dL_dpred, accumulate, workspace,
+                        workspace_bytes, stream, operands, MGR_LPIPS_STORE_F32);
 }
 
 extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const float* target, const float* mask, const void* blob,
@@ -1168,12 +1447,12 @@ extern "C" int mgr_lpips(int net, int V, int H, int W, const float* pred, const 
 // the windowed call
 // ---------------------------------------------------------------------------
 // 0: empty, 1: fine, < 0: refused (-1 negative size, -2 outside the frame, -3 too small for the deepest tap or too large)
-static int lp_rect_check(const LpNet& n, int H, int W, const int* r, int need_grad, LpLayout* L) {
+static int lp_rect_check(const LpNet& n, int H, int W, const int* r, int need_grad, LpLayout* L, int st = MGR_LPIPS_STORE_F32) {
     const long long x0 = r[0], y0 = r[1], w = r[2], h = r[3];
     if (w < 0 || h < 0) return -1;
     if (w == 0 || h == 0) return 0;
     if (x0 < 0 || y0 < 0 || x0 + w > W || y0 + h > H) return -2;
-    return lp_layout(n, (int)h, (int)w, need_grad, L) ? 1 : -3;
+    return lp_layout(n, (int)h, (int)w, need_grad, L, 1, st) ? 1 : -3;
 }
 
 static int lp_rect_fail(const char* who, int rc) {
@@ -1213,17 +1492,17 @@ static void lp_chunks(int V, const int* rects, int cap, std::vector<LpChunk>* ou
 static inline int lp_batch_cap(int max_batch) { return max_batch < LP_MAX_BATCH ? max_batch : LP_MAX_BATCH; }
 
 // the largest chunk's workspace; 0 where a rectangle is refused
-static size_t lp_chunks_bytes(const LpNet& n, const std::vector<LpChunk>& chunks, int need_grad) {
+static size_t lp_chunks_bytes(const LpNet& n, const std::vector<LpChunk>& chunks, int need_grad, int st = MGR_LPIPS_STORE_F32) {
     size_t need = 0;
     for (const LpChunk& c : chunks) {
         LpLayout L;
-        if (!lp_layout(n, c.h, c.w, need_grad, &L, (size_t)c.n)) return 0;
+        if (!lp_layout(n, c.h, c.w, need_grad, &L, (size_t)c.n, st)) return 0;
         need = need > L.total ? need : L.total;
     }
     return need;
 }
 
-static size_t lp_roi_bytes(const LpNet& n, int V, const int* rects, int need_grad, int cap) {
+static size_t lp_roi_bytes(const LpNet& n, int V, const int* rects, int need_grad, int cap, int st = MGR_LPIPS_STORE_F32) {
     for (int v = 0; v < V; ++v) {
         const int* r = rects + 4 * v;
         if (r[2] == 0 || r[3] == 0) continue;
@@ -1231,7 +1510,7 @@ static size_t lp_roi_bytes(const LpNet& n, int V, const int* rects, int need_gra
     }
     std::vector<LpChunk> chunks;
     lp_chunks(V, rects, cap, &chunks);
-    return lp_chunks_bytes(n, chunks, need_grad);
+    return lp_chunks_bytes(n, chunks, need_grad, st);
 }
 
 extern "C" size_t mgr_lpips_roi_workspace_bytes(int net, int V, const int* rects, int need_grad) {
@@ -1240,18 +1519,24 @@ extern "C" size_t mgr_lpips_roi_workspace_bytes(int net, int V, const int* rects
     return lp_roi_bytes(n, V, rects, need_grad, 1);
 }
 
-extern "C" size_t mgr_lpips_roi_batch_workspace_bytes(int net, int V, const int* rects, int need_grad, int max_batch) {
+extern "C" size_t mgr_lpips_roi_batch_workspace_bytes_st(int net, int V, const int* rects, int need_grad, int max_batch, int storage) {
     LpNet n;
-    if (!lp_net(net, &n) || V <= 0 || !rects || max_batch < 1) return 0;
-    return lp_roi_bytes(n, V, rects, need_grad, lp_batch_cap(max_batch));
+    if (!lp_net(net, &n) || !lp_storage_ok(storage) || V <= 0 || !rects || max_batch < 1) return 0;
+    return lp_roi_bytes(n, V, rects, need_grad, lp_batch_cap(max_batch), storage);
 }
 
-extern "C" size_t mgr_lpips_taps_bytes(int net, int h, int w) {
+extern "C" size_t mgr_lpips_roi_batch_workspace_bytes(int net, int V, const int* rects, int need_grad, int max_batch) {
+    return mgr_lpips_roi_batch_workspace_bytes_st(net, V, rects, need_grad, max_batch, MGR_LPIPS_STORE_F32);
+}
+
+extern "C" size_t mgr_lpips_taps_bytes_st(int net, int h, int w, int storage) {
     LpNet n;
     LpLayout L;
-    if (!lp_net(net, &n) || !lp_layout(n, h, w, 0, &L)) return 0;
+    if (!lp_net(net, &n) || !lp_storage_ok(storage) || !lp_layout(n, h, w, 0, &L, 1, storage)) return 0;
     return L.bufa - L.tap[0];
 }
+
+extern "C" size_t mgr_lpips_taps_bytes(int net, int h, int w) { return mgr_lpips_taps_bytes_st(net, h, w, MGR_LPIPS_STORE_F32); }
 
 // view b's n floats at src + b n -> dst[b] + off (the taps of a chunk leave the batch-major workspace for the views' buffers)
 struct LpTapOut {
@@ -1266,11 +1551,12 @@ __global__ __launch_bounds__(LP_T) void k_lp_taps_out(size_t n, const float* __r
 // the target tower of one chunk into its views' tap buffers; one view writes them directly (the one-view entry), more go through
 // the workspace's batch-major tap regions
 static int lp_taps_chunk(int operands, hipStream_t stream, const LpNet& n, const LpBlob& B, const char* blob, int H, int W, const int* rects,
-                         const LpChunk& c, const float* target, const float* mask, int normalize, float* const* taps_out, char* ws) {
+                         const LpChunk& c, const float* target, const float* mask, int normalize, float* const* taps_out, char* ws,
+                         int st = MGR_LPIPS_STORE_F32) {
     LpLayout L, L1;
     LpShape S;
-    lp_layout(n, c.h, c.w, 0, &L, (size_t)c.n);
-    lp_layout(n, c.h, c.w, 0, &L1);
+    lp_layout(n, c.h, c.w, 0, &L, (size_t)c.n, st);
+    lp_layout(n, c.h, c.w, 0, &L1, 1, st);
     lp_shapes(n, c.h, c.w, &S);
     LpWin win = {};
     win.FH = H;
@@ -1280,25 +1566,25 @@ static int lp_taps_chunk(int operands, hipStream_t stream, const LpNet& n, const
         win.x0[b] = rects[4 * c.view[b]];
         win.y0[b] = rects[4 * c.view[b] + 1];
     }
-    float* tgt[13];
+    void* tgt[13];
     int ci = 0;
     for (int i = 0; i < n.n_ops; ++i) {
         const LpOp& op = n.ops[i];
         if (!op.conv) continue;
         tgt[ci] = nullptr;
         if (op.tap >= 0)
-            tgt[ci] = c.n == 1 ? (float*)((char*)taps_out[c.view[0]] + (L1.tap[op.tap] - L1.tap[0])) : (float*)(ws + L.tap[op.tap]);
+            tgt[ci] = c.n == 1 ? (void*)((char*)taps_out[c.view[0]] + (L1.tap[op.tap] - L1.tap[0])) : (void*)(ws + L.tap[op.tap]);
         ++ci;
     }
-    const int rc = lp_forward(operands, stream, n, B, blob, S, c.h, c.w, c.n, target, mask, normalize, tgt, (float*)(ws + L.bufa),
-                              (float*)(ws + L.bufb), &win);
+    const int rc = lp_forward(operands, stream, n, B, blob, S, c.h, c.w, c.n, target, mask, normalize, tgt, ws + L.bufa, ws + L.bufb, &win,
+                              st);
     if (rc != MGR_OK || c.n == 1) return rc;
     LpTapOut to = {};
     for (int b = 0; b < c.n; ++b) to.dst[b] = taps_out[c.view[b]];
     for (int i = 0; i < n.n_ops; ++i) {
         const LpOp& op = n.ops[i];
         if (!op.conv || op.tap < 0) continue;
-        const size_t e = (size_t)op.cout * S.h[i] * S.w[i];
+        const size_t e = lp_tbytes(st, op.cout, S.h[i], S.w[i]) / 4;       // a view's tap in 4-byte words: the copy is by bytes
         hipLaunchKernelGGL(k_lp_taps_out, dim3((unsigned)((e + LP_T - 1) / LP_T), c.n), dim3(LP_T), 0, stream, e,
                            (const float*)(ws + L.tap[op.tap]), to, (L1.tap[op.tap] - L1.tap[0]) / 4);
         MGR_LAUNCH_CHECK("k_lp_taps_out", stream, 0);
@@ -1326,19 +1612,20 @@ extern "C" int mgr_lpips_roi_taps_op(int net, int H, int W, const int* rect, con
     return lp_taps_chunk(operands, stream, n, B, (const char*)blob_, H, W, rect, c, target_v, mask_v, normalize, &taps_out, (char*)workspace);
 }
 
-extern "C" int mgr_lpips_roi_taps_batch_op(int net, int V, int H, int W, const int* rects, const float* target, const float* mask,
+extern "C" int mgr_lpips_roi_taps_batch_st(int net, int V, int H, int W, const int* rects, const float* target, const float* mask,
                                            const void* blob_, size_t blob_bytes, int normalize, float* const* taps_out, int max_batch,
-                                           void* workspace, size_t workspace_bytes, void* stream_, int operands) {
+                                           void* workspace, size_t workspace_bytes, void* stream_, int operands, int storage) {
     hipStream_t stream = (hipStream_t)stream_;
     LpNet n;
     if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: net must be 0 (vgg) or 1 (alex)");
     if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: operands must be 0 (fp32) or 1 (bf16)");
+    if (const char* why = lp_storage_refusal(operands, storage)) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: %s", why);
     if (V <= 0 || H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: bad sizes");
     if (max_batch < 1) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: max_batch must be at least 1");
     if (!rects || !target || !blob_ || !taps_out) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: null pointer");
     for (int v = 0; v < V; ++v) {
         LpLayout L;
-        const int ok = lp_rect_check(n, H, W, rects + 4 * v, 0, &L);
+        const int ok = lp_rect_check(n, H, W, rects + 4 * v, 0, &L, storage);
         if (ok < 0) return lp_rect_fail("mgr_lpips_roi_taps_batch", ok);
         if (ok && !taps_out[v]) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: null pointer (a non-empty view has no tap buffer)");
     }
@@ -1347,27 +1634,35 @@ extern "C" int mgr_lpips_roi_taps_batch_op(int net, int V, int H, int W, const i
         return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode");
     std::vector<LpChunk> chunks;
     lp_chunks(V, rects, lp_batch_cap(max_batch), &chunks);
-    const size_t need = lp_chunks_bytes(n, chunks, 0);
+    const size_t need = lp_chunks_bytes(n, chunks, 0, storage);
     if (need && !workspace) return mgr_fail(MGR_EINVAL, "mgr_lpips_roi_taps_batch: null pointer");
     if (workspace_bytes < need)
         return mgr_fail(MGR_ENOMEM, "mgr_lpips_roi_taps_batch: workspace smaller than mgr_lpips_roi_batch_workspace_bytes(.., 0, max_batch)");
     for (const LpChunk& c : chunks) {
         // the one-view entry takes the view's own frame: chunk views index the call's frames here
         const int rc = lp_taps_chunk(operands, stream, n, B, (const char*)blob_, H, W, rects, c, target, mask, normalize, taps_out,
-                                     (char*)workspace);
+                                     (char*)workspace, storage);
         if (rc != MGR_OK) return rc;
     }
     return MGR_OK;
+}
+
+extern "C" int mgr_lpips_roi_taps_batch_op(int net, int V, int H, int W, const int* rects, const float* target, const float* mask,
+                                           const void* blob, size_t blob_bytes, int normalize, float* const* taps_out, int max_batch,
+                                           void* workspace, size_t workspace_bytes, void* stream, int operands) {
+    return mgr_lpips_roi_taps_batch_st(net, V, H, W, rects, target, mask, blob, blob_bytes, normalize, taps_out, max_batch, workspace,
+                                       workspace_bytes, stream, operands, MGR_LPIPS_STORE_F32);
 }
 
 // the windowed call, sequential (cap = 1) or batched
 static int lp_roi_run(const char* who, int net, int V, int H, int W, const int* rects, const float* pred, const float* target,
                       const float* mask, const void* blob_, size_t blob_bytes, int normalize, const float* grad_scales, float* values,
                       float* dL_dpred, int accumulate, const float* const* target_taps, int max_batch, void* workspace,
-                      size_t workspace_bytes, hipStream_t stream, int operands) {
+                      size_t workspace_bytes, hipStream_t stream, int operands, int storage = MGR_LPIPS_STORE_F32) {
     LpNet n;
     if (!lp_net(net, &n)) return mgr_fail(MGR_EINVAL, "%s: net must be 0 (vgg) or 1 (alex)", who);
     if (!lp_operands_ok(operands)) return mgr_fail(MGR_EINVAL, "%s: operands must be 0 (fp32) or 1 (bf16)", who);
+    if (const char* why = lp_storage_refusal(operands, storage)) return mgr_fail(MGR_EINVAL, "%s: %s", who, why);
     if (V <= 0 || H <= 0 || W <= 0 || H > 65535) return mgr_fail(MGR_EINVAL, "%s: bad sizes", who);
     if (max_batch < 1) return mgr_fail(MGR_EINVAL, "%s: max_batch must be at least 1", who);
     if (!rects || !pred || !blob_ || !values || (dL_dpred && !grad_scales)) return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
@@ -1376,7 +1671,7 @@ static int lp_roi_run(const char* who, int net, int V, int H, int W, const int* 
     // every view is judged before the first launch
     for (int v = 0; v < V; ++v) {
         LpLayout L;
-        const int ok = lp_rect_check(n, H, W, rects + 4 * v, need_grad, &L);
+        const int ok = lp_rect_check(n, H, W, rects + 4 * v, need_grad, &L, storage);
         if (ok < 0) return lp_rect_fail(who, ok);
         if (ok == 0) continue;
         if (!target && !(target_taps && target_taps[v]))
@@ -1386,7 +1681,7 @@ static int lp_roi_run(const char* who, int net, int V, int H, int W, const int* 
     if (blob_bytes != B.total) return mgr_fail(MGR_EINVAL, "%s: blob_bytes is not mgr_lpips_net_bytes(net) of this operand mode", who);
     std::vector<LpChunk> chunks;
     lp_chunks(V, rects, lp_batch_cap(max_batch), &chunks);
-    const size_t need = lp_chunks_bytes(n, chunks, need_grad);
+    const size_t need = lp_chunks_bytes(n, chunks, need_grad, storage);
     if (need && !workspace) return mgr_fail(MGR_EINVAL, "%s: null pointer", who);
     if (workspace_bytes < need) return mgr_fail(MGR_ENOMEM, "%s: workspace smaller than %s_workspace_bytes", who, who);
     const size_t img = (size_t)3 * H * W;
@@ -1424,7 +1719,7 @@ static int lp_roi_run(const char* who, int net, int V, int H, int W, const int* 
             gs[b] = need_grad ? grad_scales[c.view[b]] : 0.f;
         }
         const int rc = lp_views(operands, stream, n, B, (const char*)blob_, c.h, c.w, c.n, &win, pred, target, mask, taps, normalize, gs,
-                                values, dL_dpred, accumulate, (char*)workspace);
+                                values, dL_dpred, accumulate, (char*)workspace, storage);
         if (rc != MGR_OK) return rc;
     }
     return MGR_OK;
@@ -1451,6 +1746,14 @@ extern "C" int mgr_lpips_roi_batch_op(int net, int V, int H, int W, const int* r
                                       size_t workspace_bytes, void* stream, int operands, int max_batch) {
     return lp_roi_run("mgr_lpips_roi_batch", net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values,
                       dL_dpred, accumulate, target_taps, max_batch, workspace, workspace_bytes, (hipStream_t)stream, operands);
+}
+
+extern "C" int mgr_lpips_roi_batch_st(int net, int V, int H, int W, const int* rects, const float* pred, const float* target,
+                                      const float* mask, const void* blob, size_t blob_bytes, int normalize, const float* grad_scales,
+                                      float* values, float* dL_dpred, int accumulate, const float* const* target_taps, void* workspace,
+                                      size_t workspace_bytes, void* stream, int operands, int max_batch, int storage) {
+    return lp_roi_run("mgr_lpips_roi_batch", net, V, H, W, rects, pred, target, mask, blob, blob_bytes, normalize, grad_scales, values,
+                      dL_dpred, accumulate, target_taps, max_batch, workspace, workspace_bytes, (hipStream_t)stream, operands, storage);
 }
 
 extern "C" int mgr_lpips_roi_batch(int net, int V, int H, int W, const int* rects, const float* pred, const float* target,

@@ -11,6 +11,12 @@ no CPU fallback.
 rounded to bf16 (round to nearest even), the products summed in fp32; everything else stays fp32 (include/manus_hip.h).  The
 default, "fp32", is the k-ordered fp32 chain.
 
+`storage="bf16"` (with `operands="bf16"` only; the `mgr_lpips*_st` entries) also STORES every tensor of the chain -- activations,
+taps, pool outputs, gradients -- as bf16, channel-blocked [ceil(C/8)][h][w][8] with zero pad lanes: half the workspace and the
+cached taps, one rounding at each store, pool ties to the first position (include/manus_hip.h has the rules).  The scaled image
+and the gradient that leaves the chain stay fp32.  `pack_blocked` / `unpack_blocked` convert between (C,h,w) fp32 and those
+bytes.  The default, "fp32", is the code without the mode, bit for bit.
+
 Windows (`values_grad(rects=)`, `target_taps`, `fit_rects`): the distance of view v on the rectangle rects[v] = (x0, y0, w, h)
 of its frame is the LPIPS of the two crops -- the plain call on contiguous copies of that rectangle, bit for bit, with the
 crop's own zero padding and spatial means -- not the full-frame value restricted to a region.  Only the window is convolved
@@ -28,10 +34,12 @@ import functools
 import numpy as np
 import torch
 
-from ._lib import LP_MAX_BATCH, MGR_LPIPS_BF16, MGR_LPIPS_F32, ManusHipError, check, f32c, lib, ptr, stream
+from ._lib import (LP_MAX_BATCH, MGR_LPIPS_BF16, MGR_LPIPS_F32, MGR_LPIPS_STORE_BF16, MGR_LPIPS_STORE_F32, ManusHipError, check, f32c, lib,
+                   ptr, stream)
 
 NETS = {"vgg": 0, "alex": 1}
 OPERANDS = {"fp32": MGR_LPIPS_F32, "bf16": MGR_LPIPS_BF16}
+STORAGES = {"fp32": MGR_LPIPS_STORE_F32, "bf16": MGR_LPIPS_STORE_BF16}
 # torchvision `features` indices of the convolutions, (Cout, Cin, K) of each, and the tap channels
 CONV_INDEX = {"vgg": (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28), "alex": (0, 3, 6, 8, 10)}
 CONV_SHAPE = {"vgg": ((64, 3, 3), (64, 64, 3), (128, 64, 3), (128, 128, 3), (256, 128, 3), (256, 256, 3), (256, 256, 3), (512, 256, 3),
@@ -48,16 +56,48 @@ def _operands(operands, who):
     return OPERANDS[operands]
 
 
+def _storage(storage, operands, who):
+    """The storage keyword as the C ABI's value; bf16 storage goes with bf16 operands only."""
+    if not isinstance(storage, str) or storage not in STORAGES:
+        raise ManusHipError("%s: storage must be 'fp32' or 'bf16' (got %r)" % (who, storage))
+    if storage == "bf16" and operands != "bf16":
+        raise ManusHipError("%s: storage='bf16' needs operands='bf16' (got operands=%r)" % (who, operands))
+    return STORAGES[storage]
+
+
+def pack_blocked(t):
+    """fp32 (C,h,w) -> the bytes of bf16 storage: uint8 of 2 * pad8(C) * h * w, laid out [ceil(C/8)][h][w][8], values rounded to
+    nearest even, pad lanes zero.  Any device."""
+    t = t.detach().to(torch.float32)
+    C, h, w = t.shape
+    nb = (C + 7) // 8
+    full = torch.zeros((nb * 8, h, w), dtype=torch.bfloat16, device=t.device)
+    full[:C] = t.to(torch.bfloat16)
+    return full.reshape(nb, 8, h, w).permute(0, 2, 3, 1).contiguous().view(torch.uint8).reshape(-1)
+
+
+def unpack_blocked(buf, C, h, w, pads=False):
+    """The bytes of bf16 storage -> fp32 (C,h,w), exactly; pads=True returns all pad8(C) channels (the pad lanes last)."""
+    nb = (C + 7) // 8
+    n = nb * 8 * h * w * 2
+    full = buf.reshape(-1)[:n].view(torch.bfloat16).reshape(nb, h, w, 8).permute(0, 3, 1, 2).reshape(nb * 8, h, w).to(torch.float32)
+    return full if pads else full[:C].contiguous()
+
+
 def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def layout(net, H, W, need_grad=True):
-    """Byte offsets of `mgr_lpips_layout`: {"act": pred's convolution outputs, "tap": the target's taps, "scratch": (a, b),
-    "part", "total"}."""
+def layout(net, H, W, need_grad=True, storage="fp32"):
+    """Byte offsets of `mgr_lpips_layout` (`mgr_lpips_layout_st` for storage="bf16"): {"act": pred's convolution outputs, "tap":
+    the target's taps, "scratch": (a, b), "part", "total"}."""
     n_conv = len(CONV_INDEX[net])
     buf = (ctypes.c_size_t * (n_conv + 9))()
-    rc = lib().mgr_lpips_layout(NETS[net], int(H), int(W), int(bool(need_grad)), buf, len(buf))
+    st = _storage(storage, "bf16", "layout")
+    if st == MGR_LPIPS_STORE_F32:
+        rc = lib().mgr_lpips_layout(NETS[net], int(H), int(W), int(bool(need_grad)), buf, len(buf))
+    else:
+        rc = lib().mgr_lpips_layout_st(NETS[net], int(H), int(W), int(bool(need_grad)), buf, len(buf), st)
     if rc < 0:
         check(rc, "mgr_lpips_layout")
     v = list(buf)
@@ -151,19 +191,21 @@ def _batch(batch, who):
 
 class TargetTaps:
     """The target tower's five taps of each view's window (`LPIPS.target_taps`): one device buffer per view (None for an empty
-    view), and what they were built with -- a call with other rects, frame size, network, operand mode or normalize / mask
-    flags refuses them."""
+    view), and what they were built with -- a call with other rects, frame size, network, operand mode, storage or normalize /
+    mask flags refuses them."""
 
-    def __init__(self, bufs, rects, frame, net, operands, normalize, masked):
+    def __init__(self, bufs, rects, frame, net, operands, normalize, masked, storage="fp32"):
         self.bufs, self.rects, self.frame = bufs, rects, frame
         self.net, self.operands, self.normalize, self.masked = net, operands, bool(normalize), bool(masked)
+        self.storage = storage
 
     @property
     def nbytes(self):
         return sum(int(b.numel()) for b in self.bufs if b is not None)
 
-    def matches(self, rects, frame, net, operands, normalize, masked):
-        return (self.frame == frame and self.net == net and self.operands == operands and self.normalize == bool(normalize)
+    def matches(self, rects, frame, net, operands, normalize, masked, storage="fp32"):
+        return (self.frame == frame and self.net == net and self.operands == operands and self.storage == storage
+                and self.normalize == bool(normalize)
                 and self.masked == bool(masked) and self.rects.shape == rects.shape and bool((self.rects == rects).all()))
 
 
@@ -186,20 +228,22 @@ class _Lpips(torch.autograd.Function):
 class LPIPS:
     """`lpips.LPIPS(net=...)` in eval mode with frozen weights.  Build with `from_state_dicts` or `load`."""
 
-    def __init__(self, net="vgg", operands="fp32"):
+    def __init__(self, net="vgg", operands="fp32", storage="fp32"):
         if net not in NETS:
             raise ManusHipError("LPIPS: net must be 'vgg' or 'alex' (got %r)" % (net,))
         self._op = _operands(operands, "LPIPS")
+        self._st = _storage(storage, operands, "LPIPS")
         self.net = net
         self.operands = operands
+        self.storage = storage
         self.blob = None
         self._ws = None
 
     # ---- weights
     @classmethod
-    def from_state_dicts(cls, backbone_sd, lin_sd, net="vgg", device="cuda", operands="fp32"):
+    def from_state_dicts(cls, backbone_sd, lin_sd, net="vgg", device="cuda", operands="fp32", storage="fp32"):
         """backbone_sd: torchvision's `vgg16` / `alexnet` state dict; lin_sd: the lpips package's linear layers."""
-        self = cls(net, operands)
+        self = cls(net, operands, storage)
         ws, bs, lins = [], [], []
         for i, (co, ci, k) in zip(CONV_INDEX[net], CONV_SHAPE[net]):
             for kind, shape, out in (("weight", (co, ci, k, k), ws), ("bias", (co,), bs)):
@@ -231,20 +275,35 @@ class LPIPS:
         return self
 
     @classmethod
-    def load(cls, backbone_path, lin_path, net="vgg", device="cuda", operands="fp32"):
+    def load(cls, backbone_path, lin_path, net="vgg", device="cuda", operands="fp32", storage="fp32"):
         """torch.load of the two user-supplied files (see the module docstring)."""
         return cls.from_state_dicts(torch.load(backbone_path, map_location="cpu"), torch.load(lin_path, map_location="cpu"), net, device,
-                                    operands)
+                                    operands, storage)
 
     # ---- the call
     def workspace(self, H, W, need_grad):
-        """The kept workspace of one view (mgr_lpips_workspace_bytes); grown, never shrunk."""
-        n = int(lib().mgr_lpips_workspace_bytes(NETS[self.net], int(H), int(W), int(bool(need_grad))))
+        """The kept workspace of one view (mgr_lpips_workspace_bytes, or its _st form for bf16 storage); grown, never shrunk."""
+        n = int(self._ws_bytes(H, W, need_grad))
         if n == 0:
             raise ManusHipError("LPIPS(%s): a %dx%d image is too small for the deepest tap to have one pixel" % (self.net, W, H))
         if self._ws is None or self._ws.numel() < n or self._ws.device != self.blob.device:
             self._ws = torch.empty(n, dtype=torch.uint8, device=self.blob.device)
         return self._ws
+
+    @property
+    def _blocked(self):
+        return self._st == MGR_LPIPS_STORE_BF16
+
+    # the size queries of the model's storage
+    def _ws_bytes(self, H, W, need_grad):
+        if self._blocked:
+            return lib().mgr_lpips_workspace_bytes_st(NETS[self.net], int(H), int(W), int(bool(need_grad)), self._st)
+        return lib().mgr_lpips_workspace_bytes(NETS[self.net], int(H), int(W), int(bool(need_grad)))
+
+    def _taps_bytes(self, h, w):
+        if self._blocked:
+            return lib().mgr_lpips_taps_bytes_st(NETS[self.net], int(h), int(w), self._st)
+        return lib().mgr_lpips_taps_bytes(NETS[self.net], int(h), int(w))
 
     def _grow(self, n):
         if self._ws is None or self._ws.numel() < n or self._ws.device != self.blob.device:
@@ -288,6 +347,11 @@ class LPIPS:
                 raise ManusHipError("LPIPS: out_grad must be fp32 of pred's shape")
         ws = self.workspace(H, W, need_grad)
         vals = torch.empty(V, dtype=torch.float32, device=pred.device)
+        if self._blocked:
+            check(lib().mgr_lpips_st(NETS[self.net], V, H, W, ptr(pred), ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
+                                     int(bool(normalize)), float(grad_scale), ptr(vals), ptr(g), int(bool(accumulate)), ptr(ws), ws.numel(),
+                                     stream(), self._op, self._st), "mgr_lpips_st")
+            return vals, g
         check(lib().mgr_lpips_op(NETS[self.net], V, H, W, ptr(pred), ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
                                  int(bool(normalize)), float(grad_scale), ptr(vals), ptr(g), int(bool(accumulate)), ptr(ws), ws.numel(),
                                  stream(), self._op), "mgr_lpips_op")
@@ -317,9 +381,10 @@ class LPIPS:
         rects = _rects(rects, V)
         tap_ptrs = None
         if taps is not None:
-            if not isinstance(taps, TargetTaps) or not taps.matches(rects, (H, W), self.net, self.operands, normalize, mask is not None):
-                raise ManusHipError("LPIPS: target_taps were built with other rects, frame size, network, operand mode or normalize / "
-                                    "mask flags than this call's")
+            if not isinstance(taps, TargetTaps) or not taps.matches(rects, (H, W), self.net, self.operands, normalize, mask is not None,
+                                                                    self.storage):
+                raise ManusHipError("LPIPS: target_taps were built with other rects, frame size, network, operand mode, storage or "
+                                    "normalize / mask flags than this call's")
             tap_ptrs = (ctypes.c_void_p * V)(*[None if b is None else ptr(b) for b in taps.bufs])
         scales = [float(grad_scale)] * V if grad_scales is None else [float(x) for x in grad_scales]
         if len(scales) != V:
@@ -332,6 +397,15 @@ class LPIPS:
         rp = rects.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
         # (0 where a rectangle is refused: the call below says which and why)
         vals = torch.empty(V, dtype=torch.float32, device=pred.device)
+        if self._blocked:
+            # (max_batch = 1 is the sequential windowed call)
+            mb = max(batch, 1)
+            ws = self._grow(lib().mgr_lpips_roi_batch_workspace_bytes_st(NETS[self.net], V, rp, int(bool(need_grad)), mb, self._st))
+            check(lib().mgr_lpips_roi_batch_st(NETS[self.net], V, H, W, rp, ptr(pred), ptr(target), ptr(mask), ptr(self.blob),
+                                               self.blob.numel(), int(bool(normalize)), (ctypes.c_float * V)(*scales), ptr(vals), ptr(g),
+                                               int(bool(accumulate)), tap_ptrs, ptr(ws), ws.numel(), stream(), self._op, mb, self._st),
+                  "mgr_lpips_roi_batch_st")
+            return vals, g
         if batch >= 2:
             ws = self._grow(lib().mgr_lpips_roi_batch_workspace_bytes(NETS[self.net], V, rp, int(bool(need_grad)), batch))
             check(lib().mgr_lpips_roi_batch_op(NETS[self.net], V, H, W, rp, ptr(pred), ptr(target), ptr(mask), ptr(self.blob),
@@ -356,17 +430,26 @@ class LPIPS:
         rects = _rects(rects, V)
         net, bufs = NETS[self.net], []
         batch = _batch(batch, "LPIPS.target_taps")
-        if batch >= 2:
+        if batch >= 2 or self._blocked:
             # (0 bytes where a rectangle is refused: the call says which and why)
             bufs = [None if rects[v, 2] == 0 or rects[v, 3] == 0 else
-                    torch.empty(max(int(lib().mgr_lpips_taps_bytes(net, int(rects[v, 3]), int(rects[v, 2]))), 1), dtype=torch.uint8,
-                                device=target.device) for v in range(V)]
+                    torch.empty(max(int(self._taps_bytes(rects[v, 3], rects[v, 2])), 1), dtype=torch.uint8, device=target.device)
+                    for v in range(V)]
             rp = rects.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            if self._blocked:
+                # (max_batch = 1 builds the taps view by view)
+                mb = max(batch, 1)
+                ws = self._grow(lib().mgr_lpips_roi_batch_workspace_bytes_st(net, V, rp, 0, mb, self._st))
+                check(lib().mgr_lpips_roi_taps_batch_st(net, V, H, W, rp, ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
+                                                        int(bool(normalize)),
+                                                        (ctypes.c_void_p * V)(*[None if b is None else ptr(b) for b in bufs]), mb, ptr(ws),
+                                                        ws.numel(), stream(), self._op, self._st), "mgr_lpips_roi_taps_batch_st")
+                return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None, self.storage)
             ws = self._grow(lib().mgr_lpips_roi_batch_workspace_bytes(net, V, rp, 0, batch))
             check(lib().mgr_lpips_roi_taps_batch_op(net, V, H, W, rp, ptr(target), ptr(mask), ptr(self.blob), self.blob.numel(),
                                                     int(bool(normalize)), (ctypes.c_void_p * V)(*[None if b is None else ptr(b) for b in bufs]),
                                                     batch, ptr(ws), ws.numel(), stream(), self._op), "mgr_lpips_roi_taps_batch_op")
-            return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None)
+            return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None, self.storage)
         for v in range(V):
             x0, y0, w, h = (int(t) for t in rects[v])
             if w == 0 or h == 0:
@@ -380,7 +463,7 @@ class LPIPS:
                                               int(bool(normalize)), ptr(buf), ptr(ws), ws.numel(), stream(), self._op),
                   "mgr_lpips_roi_taps_op")
             bufs.append(buf)
-        return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None)
+        return TargetTaps(bufs, rects.copy(), (H, W), self.net, self.operands, normalize, mask is not None, self.storage)
 
     def __call__(self, in0, in1, normalize=False):
         """d(in0, in1) of shape (N,1,1,1) for (N,3,H,W) images, differentiable in in0 (VGG only)."""
@@ -389,19 +472,38 @@ class LPIPS:
         return _Lpips.apply(in0, in1, self, bool(normalize))
 
 
-def conv2d(x, w, bias=None, stride=1, pad=0, relu=True, gate=None, transposed=False, operands="fp32"):
-    """One convolution of the backbones on its own (`mgr_lpips_conv_op`; tests and tools).  x (Cin,H,W), w (Cout,Cin,K,K)."""
+def conv2d(x, w, bias=None, stride=1, pad=0, relu=True, gate=None, transposed=False, operands="fp32", x_storage="fp32", y_storage="fp32",
+           raw=False):
+    """One convolution of the backbones on its own (`mgr_lpips_conv_op`, or `mgr_lpips_conv_st` where a storage is "bf16"; tests
+    and tools).  x (Cin,H,W), w (Cout,Cin,K,K).  x_storage="bf16": x and gate reach the kernel as `pack_blocked` of the fp32
+    tensors given (so rounded to bf16).  y_storage="bf16": the kernel writes blocked bf16; the result is `unpack_blocked` of it,
+    or with raw=True the bytes themselves."""
     op = _operands(operands, "conv2d")
+    xs, ys = _storage(x_storage, operands, "conv2d"), _storage(y_storage, operands, "conv2d")
     x, w = f32c(x), f32c(w)
     co, ci, kh, kw = w.shape
     cx, H, W = x.shape
     if cx != (co if transposed else ci):
         raise ManusHipError("conv2d: x has %d channels" % cx)
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
-    y = torch.empty((ci if transposed else co, Ho, Wo), dtype=torch.float32, device=x.device)
+    cy = ci if transposed else co
+    if ys == MGR_LPIPS_STORE_BF16:
+        y = torch.empty(((cy + 7) // 8) * 8 * Ho * Wo * 2, dtype=torch.uint8, device=x.device)
+    else:
+        y = torch.empty((cy, Ho, Wo), dtype=torch.float32, device=x.device)
     n = int(lib().mgr_lpips_conv_scratch_bytes_op(ci, co, kh, kw, op))
     scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
-    check(lib().mgr_lpips_conv_op(ci, co, H, W, kh, kw, int(stride), int(pad), ptr(x), ptr(None if gate is None else f32c(gate)), ptr(w),
-                                  ptr(None if bias is None else f32c(bias)), int(bool(relu)), int(bool(transposed)), ptr(y), ptr(scratch),
-                                  n, stream(), op), "mgr_lpips_conv_op")
+    gate = None if gate is None else f32c(gate)
+    if xs == MGR_LPIPS_STORE_BF16:
+        x, gate = pack_blocked(x), None if gate is None else pack_blocked(gate)
+    if xs == MGR_LPIPS_STORE_F32 and ys == MGR_LPIPS_STORE_F32:
+        check(lib().mgr_lpips_conv_op(ci, co, H, W, kh, kw, int(stride), int(pad), ptr(x), ptr(gate), ptr(w),
+                                      ptr(None if bias is None else f32c(bias)), int(bool(relu)), int(bool(transposed)), ptr(y), ptr(scratch),
+                                      n, stream(), op), "mgr_lpips_conv_op")
+        return y
+    check(lib().mgr_lpips_conv_st(ci, co, H, W, kh, kw, int(stride), int(pad), ptr(x), ptr(gate), ptr(w),
+                                  ptr(None if bias is None else f32c(bias)), int(bool(relu)), int(bool(transposed)), ptr(y), ptr(scratch), n,
+                                  stream(), op, xs, ys), "mgr_lpips_conv_st")
+    if ys == MGR_LPIPS_STORE_BF16 and not raw:
+        return unpack_blocked(y, cy, Ho, Wo)
     return y

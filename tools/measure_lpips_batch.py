@@ -2,7 +2,7 @@
 """Time a step's equal-size LPIPS windows as one batched call (mgr_lpips_roi_batch_op, mgr_lpips_roi_taps_batch_op;
 `LPIPS.values_grad(rects=, batch=)`, `LPIPS.target_taps(batch=)`, `HipViewCompute(lpips_batch=)`) beside the sequential call.
 
-    python tools/measure_lpips_batch.py [--out FILE.json] [--quick] [--no-step] [--views 8] [--batch 8]
+    python tools/measure_lpips_batch.py [--out FILE.json] [--quick] [--no-step] [--views 8] [--batch 8] [--storage bf16] [--modes bf16,bf16_store]
 
 One process, HIP events, every shape warmed, median of 5 samples with min - max (each sample a batch of repeats); the
 sequential and the batched call ALTERNATE sample by sample, so that both see the same box.  Stand-in weights as
@@ -13,6 +13,9 @@ tools/measure_lpips.py.  Per operand mode (fp32, then bf16), VGG, V = 8 views of
   * the outputs of the two calls compared bit for bit at the sizes timed ("equal");
   * the bench step (bench.py's scene: 300k hand Gaussians, 8 views of 1920x1080, loss l1+ssim) on such rects, without and with
     `lpips_cache_targets`, `lpips_batch` 0 against 8.
+With --storage bf16 a third mode, "bf16_store" (bf16 operands, bf16 channel-blocked storage: the mgr_lpips*_st entries), gets
+every row, its workspace and taps bytes from the _st queries, and a "storage" table times the batched calls of "bf16" and
+"bf16_store" against each other, the two alternating sample by sample.  --modes restricts the run to some of the modes.
 No speed-up is fixed in advance.  One condition is checked and reported under "conditions" (exit status 1 when it fails): at
 256^2 and 512^2 every batched row is faster than the sequential row of the same run.  The 768^2 and full-frame rows carry no
 condition.  Needs a GPU; there is no fallback."""
@@ -61,12 +64,19 @@ def main():
     ap.add_argument("--no-step", action="store_true", help="skip the bench step")
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--storage", default="fp32", choices=("fp32", "bf16"), help="bf16: a third mode, bf16 operands with bf16 storage")
+    ap.add_argument("--modes", default=None, help="comma-separated subset of fp32,bf16,bf16_store to run")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "measure_lpips_batch.py needs a GPU"
     import ctypes
     from manus_amd._lib import lib
+    from manus_amd.lpips import STORAGES
     dev = "cuda:0"
-    modes = ("fp32", "bf16")
+    OPS = {"fp32": ("fp32", "fp32"), "bf16": ("bf16", "fp32"), "bf16_store": ("bf16", "bf16")}      # mode -> (operands, storage)
+    modes = ("fp32", "bf16") + (("bf16_store",) if a.storage == "bf16" else ())
+    if a.modes:
+        assert all(m in modes for m in a.modes.split(",")), "--modes: a subset of %s" % (modes,)
+        modes = tuple(m for m in modes if m in a.modes.split(","))
     V, B = a.views, a.batch
     W, H = (1920, 1080) if not a.quick else (96, 64)
     sides = (256, 512, 768) if not a.quick else (16, 32, 48)
@@ -74,7 +84,7 @@ def main():
     windows = [("%dx%d" % (s, s), spread(V, s, s, W, H)) for s in sides] + [("frame", [(0, 0, W, H)] * V)]
     res = {"device": torch.cuda.get_device_name(0), "frame": [W, H], "views": V, "batch": B,
            "modes": {m: {"call": {}, "taps": {}, "bytes": {}, "equal": {}, "step": {}} for m in modes}, "conditions": {}}
-    nets = {m: stand_in("vgg", dev, m)[0] for m in modes}
+    nets = {m: stand_in("vgg", dev, *OPS[m])[0] for m in modes}
     L = lib()
     g = torch.Generator().manual_seed(5)
     pred, target = torch.rand((V, 3, H, W), generator=g).to(dev), torch.rand((V, 3, H, W), generator=g).to(dev)
@@ -86,10 +96,13 @@ def main():
         for name, rects in windows:
             area = rects[0][2] * rects[0][3]
             reps = max(1, min(8, (W * H) // (8 * area))) * (1 if m == "fp32" else 2)
+            vgg._ws = None          # (the kept workspace of the last window is dropped before the next one's is made)
             ra = np.ascontiguousarray(np.asarray(rects, np.int32))
             rp = ra.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-            r["bytes"][name] = dict(sequential=int(L.mgr_lpips_roi_workspace_bytes(0, V, rp, 1)),
-                                    batched=int(L.mgr_lpips_roi_batch_workspace_bytes(0, V, rp, 1, B)))
+            st = STORAGES[OPS[m][1]]
+            r["bytes"][name] = dict(sequential=int(L.mgr_lpips_roi_batch_workspace_bytes_st(0, V, rp, 1, 1, st)),
+                                    batched=int(L.mgr_lpips_roi_batch_workspace_bytes_st(0, V, rp, 1, B, st)),
+                                    taps=V * int(L.mgr_lpips_taps_bytes_st(0, rects[0][3], rects[0][2], st)))
             # the same bits at the sizes timed
             v0, g0 = vgg.values_grad(pred, target, need_grad=True, rects=rects)
             v0, g0 = v0.clone(), g0.clone()
@@ -120,6 +133,24 @@ def main():
         print("equal %s" % m, json.dumps(r["equal"]), flush=True)
         print("bytes %s" % m, json.dumps(r["bytes"]), flush=True)
         print("conditions %s" % m, json.dumps(cond), flush=True)
+
+    if "bf16" in modes and "bf16_store" in modes:
+        # the two storages of bf16 operands against each other, batched, alternating
+        res["storage"] = {}
+        for name, rects in windows:
+            area = rects[0][2] * rects[0][3]
+            reps = 2 * max(1, min(8, (W * H) // (8 * area)))
+            taps = {m: nets[m].target_taps(target, rects, batch=B) for m in ("bf16", "bf16_store")}
+            for suffix, cached in (("", False), (" cached taps", True)):
+                fns = {m: (lambda m=m: nets[m].values_grad(pred, None if cached else target, need_grad=True, out_grad=grad, rects=rects,
+                                                           target_taps=taps[m] if cached else None, batch=B)) for m in ("bf16", "bf16_store")}
+                t = res["storage"][name + suffix] = timed_pair(fns, reps)
+                t["ratio"] = t["bf16"]["median_ms"] / t["bf16_store"]["median_ms"]
+                print("storage %s%s" % (name, suffix), json.dumps(t), flush=True)
+            del taps
+            for m in ("bf16", "bf16_store"):
+                nets[m]._ws = None
+            torch.cuda.empty_cache()
 
     if not a.no_step:
         from manus_amd import rasterizer as rz
