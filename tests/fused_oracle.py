@@ -21,6 +21,7 @@ import math
 import numpy as np
 import torch
 
+from regimes import oracle_rows_zero, regime_facts, view_depth
 from util import max_rel_err, psnr
 
 from tools.parity import (DEV, FLIP_EPS, align_threshold_decisions, device_alpha_decisions, fused_records,  # noqa: F401
@@ -52,14 +53,18 @@ def _ulps(a, b):
 
 
 def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5, sigma_range=(2e-3, 8e-3), account_flips=True,
-                        device=DEV, n_cameras=None, g_scale=1.0, own_projection=False):
+                        device=DEV, n_cameras=None, g_scale=1.0, own_projection=False, mutate=None):
     """One fused forward + backward of `views` views against the oracle on identical blend inputs.  Returns a dict of
     measured deviations; asserts nothing except exact integer state (visibility counts, radii).
 
     own_projection=True also runs the ORACLE'S OWN per-Gaussian preprocess (RasterOracle(blend=False) on the torch chain's
     posed means / covariances: an fp32 chain independent of the kernels') and reports, per view, how its integer state
     compares with the kernels': the Gaussians whose radius or tile rectangle differs (listed, with both values), the pair
-    counts of both sides, and the depth keys' distance in units of the last place."""
+    counts of both sides, and the depth keys' distance in units of the last place.
+
+    mutate(params) changes the scene's CPU leaves in place before anything reads them (tests/regimes.py): the upload and
+    the torch restatement both see the mutated leaves.  res["regime"] holds, per view, regimes.regime_facts of the
+    oracle's blend (and whether the oracle's own gradient rows of the Gaussians below 1/255 are exactly zero)."""
     from manus_amd import rasterizer as rz
     from manus_amd.engine import HipViewCompute
     from manus_amd.synthetic import camera_table, make_scene
@@ -67,6 +72,8 @@ def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5,
     from oracle import torch_ref as tr
     sc = make_scene(n_gaussians=n, kind=kind, seed=seed, grid_res=grid_res, n_cameras=n_cameras or views, width=W, height=H,
                     cam_radius=cam_radius, sigma_range=sigma_range, device="cpu")
+    if mutate is not None:
+        mutate(sc["params"])
     scd = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in sc.items() if k != "params"}
     scd["params"] = {k: v.to(device) for k, v in sc["params"].items()}
     ct = camera_table(sc["cameras"], device)
@@ -146,6 +153,10 @@ def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5,
                                     torch.tensor(np.asarray(c["world_view_transform"], np.float32)),
                                     torch.tensor(np.asarray(c["full_proj_transform"], np.float32)))
         visible = radii[v] > 0
+        facts = regime_facts(bos[v], r[:, 5], c, view_depth(o["posed_xyz"].detach().numpy(), c))
+        below = visible & (r[:, 5] < np.float32(1.0) / np.float32(255.0))
+        facts["oracle_faint_rows_zero"] = oracle_rows_zero(b, below)
+        res.setdefault("regime", []).append(facts)
         if own_projection:
             from oracle import RasterOracle
             ro = RasterOracle(W, H, math.tan(c["fovx"] / 2), math.tan(c["fovy"] / 2),

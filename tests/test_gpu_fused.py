@@ -19,10 +19,9 @@ def _scene(kind, n=4000, views=3):
     return sc, camera_table(sc["cameras"], DEV)
 
 
-@pytest.mark.parametrize("kind", ["hand", "object"])
-def test_fused_equals_modular(kind):
+def check_fused_equals_modular(sc, ct):
+    """Three views at 96 x 64 of a device scene through both routes (shared with tests/test_gpu_raster_regimes.py)."""
     from manus_amd.engine import HipViewCompute
-    sc, ct = _scene(kind)
     tg = torch.rand((3, 3, 64, 96), device=DEV)
     mod = HipViewCompute(sc, tg, ct, fused=False)
     fus = HipViewCompute(sc, tg, ct, fused=True)
@@ -45,18 +44,28 @@ def test_fused_equals_modular(kind):
     assert max_rel_err(of["grad2d"].cpu().numpy(), om["grad2d"].cpu().numpy()) < 5e-3
 
 
-def test_fused_run_to_run_determinism():
+@pytest.mark.parametrize("kind", ["hand", "object"])
+def test_fused_equals_modular(kind):
+    check_fused_equals_modular(*_scene(kind))
+
+
+def check_fused_run_to_run_determinism(sc, ct, views):
+    """Two fused steps of one compute object: bitwise equal gradients (shared with tests/test_gpu_raster_regimes.py)."""
     from manus_amd.engine import HipViewCompute
-    sc, ct = _scene("hand", n=6000, views=2)
-    tg = torch.rand((2, 3, 64, 96), device=DEV)
+    ids = list(range(views))
+    tg = torch.rand((views, 3, 64, 96), device=DEV)
     hc = HipViewCompute(sc, tg, ct, fused=True)
-    a = hc([0, 1], 0.5)
+    a = hc(ids, 1.0 / views)
     a = {k: ({n: g.clone() for n, g in v.items()} if isinstance(v, dict) else v.clone()) for k, v in a.items()}
-    b = hc([0, 1], 0.5)
+    b = hc(ids, 1.0 / views)
     for k in a["grads"]:
         assert torch.equal(a["grads"][k], b["grads"][k]), k
     assert torch.equal(a["grad2d"], b["grad2d"])
     assert abs(float(a["loss"]) - float(b["loss"])) < 1e-6  # the loss scalar is summed with float atomics
+
+
+def test_fused_run_to_run_determinism():
+    check_fused_run_to_run_determinism(*_scene("hand", n=6000, views=2), 2)
 
 
 @pytest.mark.parametrize("views", [1, 5, 8, 11, 16])
