@@ -560,6 +560,38 @@ int mgr_skin_grid_adam(const int32_t* voxel, const float* grad, const uint32_t* 
                        float* grid, int grid_stride, int B, float* exp_avg, float* exp_avg_sq,
                        double lr, double beta1, double beta2, double eps, int step, int clamp, float clamp_min,
                        void* stream);
+/* Refinement step of the grid on such a list: prior gradient, the row Adam above, clamp, projection of the row back onto sum 1
+ * and the prior's value, in ONE pass over the listed rows (k_sg_refine: 32 lanes per row, 8 rows per workgroup).  The reference
+ * (HandGaussianModel.optimizing_skin_weights) would use a dense Adam on the whole grid and keeps grid_weights_init beside
+ * grid_weights for such a prior; it has no kernel of its own.  For every listed row r < min(*count, capacity), v = voxel[r],
+ * channels b < B:
+ *   1. x = grid[v][b]; prior_weight != 0: d = x - grid0[v][b], g = grad[r][b] + w2 * d with w2 = (float)(2 * prior_weight);
+ *      prior_weight == 0: g = grad[r][b], no prior arithmetic at all, grid0 and prior_value may be NULL
+ *   2. Adam with the expressions and roundings of mgr_skin_grid_adam (one device function serves both): with prior_weight == 0
+ *      and project == 0 the grid and both moments come out bit for bit as mgr_skin_grid_adam leaves them
+ *   3. clamp != 0: x' = max(x', clamp_min) (fmaxf: a NaN x' becomes clamp_min, as in mgr_skin_grid_adam; the moments keep the NaN)
+ *   4. project != 0: S = sum_b x'_b in fp32 in a fixed order (a butterfly over the row's 32 lanes); S > min_sum -- false for a
+ *      NaN -- : x'_b = x'_b / S, a true division; otherwise the row stays as clamped.  The division never creates a NaN.
+ *   5. *prior_value = prior_weight * sum_rows sum_b (double)d * (double)d: the prior ON THE GRID BEFORE THE STEP (the grid its
+ *      gradient was taken on), over the LISTED rows only, added in fp64 in a tree fixed by the count alone -- no atomics, the same
+ *      bits from run to run and for every capacity >= the count.  Written as 0 when prior_weight == 0 and the pointer is given.
+ * The forward divides every sample by its raw sum, so a row's scale is a gauge: without the projection Adam drifts along it.
+ * Pad channels (b >= B) of grid and moments are not touched, rows behind the count are not read, unlisted voxels stay bitwise
+ * as they are.  The list is mgr_skin_grid_bwd's, strictly ascending; a voxel listed twice is UNDEFINED (two half-waves would
+ * step the same row).  voxel entries are trusted to lie inside the grid, as in mgr_skin_grid_adam.
+ * workspace_bytes >= mgr_skin_grid_refine_workspace_bytes(capacity): one double per 8 rows of capacity.
+ * MGR_EINVAL (nothing launched, nothing written, prior_value included): B outside 1 .. MGR_MAX_BONES, grid_stride neither B nor
+ * 24 (or 24 below B), capacity < 0, step < 1, prior_weight negative or not finite, prior_weight != 0 with grid0 or prior_value
+ * NULL, min_sum < 0 (or NaN), a null voxel / grad / count / grid / moment pointer with capacity > 0; MGR_ENOMEM: a short
+ * workspace.  capacity == 0: MGR_OK, prior_value (if given) written 0. */
+size_t mgr_skin_grid_refine_workspace_bytes(int capacity);
+int mgr_skin_grid_refine(const int32_t* voxel, const float* grad, const uint32_t* count, int capacity,
+                         float* grid, const float* grid0, int grid_stride, int B,
+                         float* exp_avg, float* exp_avg_sq,
+                         double lr, double beta1, double beta2, double eps, int step,
+                         int clamp, float clamp_min,
+                         double prior_weight, int project, float min_sum,
+                         double* prior_value, void* workspace, size_t workspace_bytes, void* stream);
 /* mask[i] = 1 where row i of dL_dw (n,B) holds an entry != 0 (a NaN counts), else 0; every mask[0 .. n) is written.  With
  * mgr_exchange_index behind it: the ascending list of the non-zero rows of a skin-weight gradient, the `index` of mgr_skin_grid_bwd
  * where more than one backward added into dL_dw.  MGR_EINVAL (nothing launched): n < 0, B outside 1 .. MGR_MAX_BONES, a null

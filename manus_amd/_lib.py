@@ -98,6 +98,10 @@ SIGNATURES = {
                                   c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_vp]),
     "mgr_skin_grid_adam": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, c_int, c_int, c_f32, c_vp]),
+    "mgr_skin_grid_refine_workspace_bytes": (c_sz, [c_int]),
+    "mgr_skin_grid_refine": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, c_int, c_int, c_f32, ctypes.c_double, c_int, c_f32, c_vp, c_vp,
+                                     c_sz, c_vp]),
     "mgr_skin_rows_mask": (c_int, [c_int, c_int, c_vp, c_vp, c_vp]),
     "mgr_views_backward_run_lists": (c_int, [c_int]),
     "mgr_views_active_list": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),

@@ -20,6 +20,13 @@
 //   k_sg_reduce               one wave per listed voxel, a lane per channel: the ranked segment added in order
 // No float atomics anywhere: the sums are fixed by the Gaussian indices alone, so any permutation of the same list gives the
 // same bits.
+//
+// The refinement step on such a list (mgr_skin_grid_refine):
+//   k_sg_refine<PRIOR>        32 lanes per listed row, 8 rows per workgroup: prior gradient towards a kept grid, the row Adam,
+//                             clamp, the row divided by its sum, the row's share of the prior's value -- one pass
+//   k_sg_refine_fold          the workgroups' fp64 partials of the prior's value added in a fixed tree
+// The reference (HandGaussianModel.optimizing_skin_weights, src/models/hand_gaussian.py) would run a dense torch Adam over the
+// whole grid_weights tensor and keeps grid_weights_init beside it; it has no kernel for any of this.
 #include "skin_tri.h"
 
 #define SG_RS 32        // floats per kept r row (MGR_MAX_BONES)
@@ -335,6 +342,23 @@ __global__ __launch_bounds__(256) void k_sg_reduce(const uint32_t* __restrict__ 
 // ---------------------------------------------------------------------------
 // row Adam (torch.optim.SparseAdam): one thread per (listed row, channel)
 // ---------------------------------------------------------------------------
+// One element's Adam step, shared by k_sg_adam and k_sg_refine: the moments are stored, the stepped (unclamped) value returned.
+__device__ __forceinline__ float sg_adam_update(float x, float g, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, size_t o,
+                                                float step_size, float omb1, float omb2, float eps) {
+    const float m0 = exp_avg[o], v0 = exp_avg_sq[o];
+    const float m = m0 + (g - m0) * omb1;      // omb = 1 - beta, rounded once from double (1.0f - 0.999f is off by 5e-5 of itself: the hyper-parameters are doubles, as in mgr_adam_step)
+    const float v = v0 + (g * g - v0) * omb2;
+    exp_avg[o] = m;
+    exp_avg_sq[o] = v;
+    return x - step_size * (m / (sqrtf(v) + eps));
+}
+
+// the step size with the bias corrections of the global step, in double as torch takes them
+static inline float sg_adam_step_size(double lr, double beta1, double beta2, int step) {
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    return (float)(lr * sqrt(bc2) / bc1);
+}
+
 __global__ __launch_bounds__(256) void k_sg_adam(const int32_t* __restrict__ voxel, const float* __restrict__ grad,
                                                  const uint32_t* __restrict__ count, int capacity, float* __restrict__ grid,
                                                  int grid_stride, int B, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
@@ -346,14 +370,95 @@ __global__ __launch_bounds__(256) void k_sg_adam(const int32_t* __restrict__ vox
     if (row >= rows) return;
     const size_t o = (size_t)voxel[row] * grid_stride + b;
     const float g = grad[row * grid_stride + b];
-    const float m0 = exp_avg[o], v0 = exp_avg_sq[o];
-    const float m = m0 + (g - m0) * omb1;      // omb = 1 - beta, rounded once from double (1.0f - 0.999f is off by 5e-5 of itself: the hyper-parameters are doubles, as in mgr_adam_step)
-    const float v = v0 + (g * g - v0) * omb2;
-    exp_avg[o] = m;
-    exp_avg_sq[o] = v;
-    float x = grid[o] - step_size * (m / (sqrtf(v) + eps));
+    float x = sg_adam_update(grid[o], g, exp_avg, exp_avg_sq, o, step_size, omb1, omb2, eps);
     if (clamp) x = fmaxf(x, clamp_min);
     grid[o] = x;
+}
+
+// ---------------------------------------------------------------------------
+// refinement step: prior gradient + row Adam + clamp + projection of the row onto sum 1 + the prior's value, one pass
+// ---------------------------------------------------------------------------
+// 32 lanes per listed row (lane = channel), 8 rows per workgroup: a row of the padded layout is one 96-byte access per array.
+// The row sum and the row's fp64 prior partial meet by __shfl_xor 16 .. 1, which stays inside the half-wave; every lane of the
+// half-wave ends with the same bits (a + b == b + a).  A workgroup walks the blocks of eight rows blk = blockIdx.x, blockIdx.x +
+// gridDim.x, ... below the count (the capacity is min(8 * entries, D*H*W) rows, the count a fraction of it: one workgroup per
+// block of the capacity would launch mostly workgroups that leave at once); a block's eight row partials are added in a fixed
+// order and stored plainly at partial[blk], and k_sg_refine_fold adds the partials of the blocks below the count in a tree fixed
+// by the count alone -- neither depends on the grid size.  No atomics.  PRIOR false: the instantiation has no prior arithmetic
+// at all, the Adam sees the loaded gradient as in k_sg_adam.
+#define SGR_ROWS 8          // rows per workgroup and pass of k_sg_refine
+#define SGR_MAX_BLOCKS 4096 // workgroups of k_sg_refine at most (k_sg_rank, k_sg_reduce)
+
+template <bool PRIOR>
+__global__ __launch_bounds__(256) void k_sg_refine(const int32_t* __restrict__ voxel, const float* __restrict__ grad,
+                                                   const uint32_t* __restrict__ count, int capacity, float* __restrict__ grid,
+                                                   const float* __restrict__ grid0, int grid_stride, int B,
+                                                   float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, float step_size,
+                                                   float omb1, float omb2, float eps, int clamp, float clamp_min, float w2,
+                                                   int project, float min_sum, double* __restrict__ partial) {
+    __shared__ double s_part[SGR_ROWS];
+    const int sub = threadIdx.x >> 5, b = threadIdx.x & 31;
+    const uint32_t rows = min(*count, (uint32_t)capacity);
+    for (size_t blk = blockIdx.x; blk * SGR_ROWS < rows; blk += gridDim.x) {     // (uniform over the workgroup: the barriers below are met by all of it)
+        const size_t row = blk * SGR_ROWS + sub;
+        const bool live = row < rows && b < B;       // (lanes of the pad channels and of rows behind the count read and write nothing)
+        size_t o = 0;
+        float x = 0.f;
+        double dd = 0.0;
+        if (live) {
+            o = (size_t)voxel[row] * grid_stride + b;
+            float g = grad[row * grid_stride + b];
+            const float x0 = grid[o];
+            if (PRIOR) {
+                const float d = x0 - grid0[o];
+                g = g + w2 * d;
+                dd = (double)d * (double)d;
+            }
+            x = sg_adam_update(x0, g, exp_avg, exp_avg_sq, o, step_size, omb1, omb2, eps);
+            if (clamp) x = fmaxf(x, clamp_min);
+        }
+        if (project) {
+            float S = x;
+#pragma unroll
+            for (int d = 16; d >= 1; d >>= 1) S += __shfl_xor(S, d, 64);
+            if (S > min_sum) x = x / S;      // false for a NaN sum: the row stays as clamped, and no division ever creates a NaN
+        }
+        if (live) grid[o] = x;
+        if (PRIOR) {
+#pragma unroll
+            for (int d = 16; d >= 1; d >>= 1) dd += __shfl_xor(dd, d, 64);
+            if (b == 0) s_part[sub] = dd;
+            __syncthreads();
+            if (threadIdx.x == 0)
+                partial[blk] = ((s_part[0] + s_part[1]) + (s_part[2] + s_part[3])) + ((s_part[4] + s_part[5]) + (s_part[6] + s_part[7]));
+            __syncthreads();                 // (s_part is written again by the next pass)
+        }
+    }
+}
+
+// one workgroup over the partials of the row blocks below the count: thread t adds partial[t], partial[t + 256], ... in ascending
+// order (eight loads in flight, the adds in that order), the 256 sums meet in a fixed tree
+__global__ __launch_bounds__(256) void k_sg_refine_fold(const double* __restrict__ partial, const uint32_t* __restrict__ count,
+                                                        int capacity, double prior_weight, double* __restrict__ prior_value) {
+    __shared__ double s_sum[256];
+    const uint32_t rows = min(*count, (uint32_t)capacity), nblk = rows / SGR_ROWS + (rows % SGR_ROWS != 0u ? 1u : 0u);
+    double acc = 0.0;
+    uint32_t k = threadIdx.x;
+    for (; k + 7u * 256u < nblk; k += 8u * 256u) {
+        double p[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p[j] = partial[k + (uint32_t)j * 256u];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += p[j];
+    }
+    for (; k < nblk; k += 256u) acc += partial[k];
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *prior_value = prior_weight * s_sum[0];
 }
 
 // ---------------------------------------------------------------------------
@@ -429,13 +534,56 @@ extern "C" int mgr_skin_grid_adam(const int32_t* voxel, const float* grad, const
     if (capacity == 0) return MGR_OK;
     if (!voxel || !grad || !count || !grid || !exp_avg || !exp_avg_sq) return mgr_fail(MGR_EINVAL, "mgr_skin_grid_adam: null pointer");
     hipStream_t stream = (hipStream_t)stream_;
-    // the bias corrections of the global step, in double as torch takes them
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const float step_size = (float)(lr * sqrt(bc2) / bc1);
+    const float step_size = sg_adam_step_size(lr, beta1, beta2, step);
     const size_t threads = (size_t)capacity * B;
     { MGR_PROF("k_sg_adam", stream); hipLaunchKernelGGL(k_sg_adam, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, voxel, grad, count, capacity,
                          grid, grid_stride, B, exp_avg, exp_avg_sq, step_size, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, clamp, clamp_min); }
     MGR_LAUNCH_CHECK("k_sg_adam", stream, 0);
+    return MGR_OK;
+}
+
+static inline size_t sg_refine_blocks(int capacity) { return ((size_t)(capacity > 0 ? capacity : 0) + SGR_ROWS - 1) / SGR_ROWS; }
+
+extern "C" size_t mgr_skin_grid_refine_workspace_bytes(int capacity) {
+    const size_t nblk = sg_refine_blocks(capacity);
+    return nblk ? mgr_align(nblk * sizeof(double)) : 0;       // one fp64 partial per workgroup
+}
+
+extern "C" int mgr_skin_grid_refine(const int32_t* voxel, const float* grad, const uint32_t* count, int capacity, float* grid,
+                                    const float* grid0, int grid_stride, int B, float* exp_avg, float* exp_avg_sq, double lr,
+                                    double beta1, double beta2, double eps, int step, int clamp, float clamp_min, double prior_weight,
+                                    int project, float min_sum, double* prior_value, void* workspace, size_t workspace_bytes,
+                                    void* stream_) {
+    if (B <= 0 || B > MGR_MAX_BONES || (grid_stride != B && grid_stride != SKIN_BP) || grid_stride < B)
+        return mgr_fail(MGR_EINVAL, "mgr_skin_grid_refine: B must be 1 .. MGR_MAX_BONES and grid_stride B or 24");
+    if (capacity < 0 || step < 1) return mgr_fail(MGR_EINVAL, "mgr_skin_grid_refine: capacity < 0 or step < 1");
+    if (!(prior_weight >= 0.0) || !std::isfinite(prior_weight)) return mgr_fail(MGR_EINVAL, "mgr_skin_grid_refine: prior_weight must be finite and >= 0");
+    const bool prior = prior_weight != 0.0;
+    if (prior && (!grid0 || !prior_value)) return mgr_fail(MGR_EINVAL, "mgr_skin_grid_refine: a prior needs grid0 and prior_value");
+    if (!(min_sum >= 0.f)) return mgr_fail(MGR_EINVAL, "mgr_skin_grid_refine: min_sum < 0");
+    if (capacity > 0 && (!voxel || !grad || !count || !grid || !exp_avg || !exp_avg_sq)) return mgr_fail(MGR_EINVAL, "mgr_skin_grid_refine: null pointer");
+    const size_t need = mgr_skin_grid_refine_workspace_bytes(capacity);
+    if (workspace_bytes < need || (need && !workspace)) return mgr_fail(MGR_ENOMEM, "mgr_skin_grid_refine: workspace too small");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (capacity == 0 || !prior) {
+        if (prior_value) MGR_HIP(hipMemsetAsync(prior_value, 0, sizeof(double), stream));
+        if (capacity == 0) return MGR_OK;
+    }
+    const float step_size = sg_adam_step_size(lr, beta1, beta2, step);
+    const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2), w2 = (float)(2.0 * prior_weight);
+    const size_t cblk = sg_refine_blocks(capacity);
+    const unsigned nblk = (unsigned)(cblk < SGR_MAX_BLOCKS ? cblk : SGR_MAX_BLOCKS);
+    double* partial = (double*)workspace;
+    if (prior) {
+        { MGR_PROF("k_sg_refine", stream); hipLaunchKernelGGL(k_sg_refine<true>, dim3(nblk), dim3(256), 0, stream, voxel, grad, count, capacity, grid, grid0,
+                             grid_stride, B, exp_avg, exp_avg_sq, step_size, omb1, omb2, (float)eps, clamp, clamp_min, w2, project, min_sum, partial); }
+        { MGR_PROF("k_sg_refine_fold", stream); hipLaunchKernelGGL(k_sg_refine_fold, dim3(1), dim3(256), 0, stream, partial, count, capacity, prior_weight, prior_value); }
+    } else {
+        MGR_PROF("k_sg_refine", stream);
+        hipLaunchKernelGGL(k_sg_refine<false>, dim3(nblk), dim3(256), 0, stream, voxel, grad, count, capacity, grid, grid0, grid_stride, B,
+                           exp_avg, exp_avg_sq, step_size, omb1, omb2, (float)eps, clamp, clamp_min, w2, project, min_sum, partial);
+    }
+    MGR_LAUNCH_CHECK("k_sg_refine", stream, 0);
     return MGR_OK;
 }
 

@@ -1467,12 +1467,19 @@ class Trainer:
     `frames`, `load_step` has just written the items' UNCORRECTED transforms, so the Gaussians train on those; on a fixed view
     set the table keeps the transforms of the last `apply`.  The pruning tests (`compute.prune_views`) keep testing against the
     DATASET's keypoints, not the corrected ones; their masks and cameras are those of the drawn items
-    (`load_step(scene_masks=True)`), with or without a mask table on the compute object."""
+    (`load_step(scene_masks=True)`), with or without a mask table on the compute object.
+
+    Skin-weight grid refinement (one rank; None: the step above, bit for bit).  skin_grid: an `optim.SkinGridRefiner` on
+    `compute.grid`, the compute object built with skin_grid_grad=True -- at the global steps g >= skin_grid_from_iter with
+    (g - skin_grid_from_iter) % skin_grid_every == 0 the grid takes its step (prior, row Adam, clamp, projection) on
+    `out["d_skin_grid"]` behind the Gaussians' optimizer step and the pose corrections', on both branches of `train_step`, on the
+    final run of an overflow re-run and on steps whose leaves densify / prune replaced; `out["loss_skin_prior"]` is then the
+    refiner's `last_prior` (a device scalar, not read here).  Off schedule the gradient is still formed and ignored."""
 
     def __init__(self, compute, n_views, extent, opts=None, spatial_lr_scale=1.0, rank=0, world_size=1, group=None,
                  bg_white=True, kind=None, compact_allreduce=False, sharded_adam=False, view_weights=None, depth_cut=False,
                  sort_rows=False, persistent_grads=True, start_lpips_iter=1000, frames=None, pose=None, pose_from_iter=0,
-                 pose_every=1, pose_frames=None):
+                 pose_every=1, pose_frames=None, skin_grid=None, skin_grid_from_iter=0, skin_grid_every=1):
         if frames is not None:
             if world_size > 1:
                 raise ValueError("Trainer(frames=...) needs world_size == 1: the frame pool is one rank's")
@@ -1487,7 +1494,17 @@ class Trainer:
                 raise ValueError("pose_every must be at least 1")
             if frames is None and (pose_frames is None or len(pose_frames) != n_views):
                 raise ValueError("Trainer(pose=...) without frames needs pose_frames: one frame row per view of the fixed set")
+        if skin_grid is not None:
+            if not getattr(compute, "skin_grid_grad", False):
+                raise ValueError("Trainer(skin_grid=...) needs a compute object with skin_grid_grad=True (its step returns d_skin_grid)")
+            if skin_grid.sg is not getattr(compute, "grid", None):
+                raise ValueError("Trainer(skin_grid=...): the refiner steps another grid than compute.grid, the one the step differentiates")
+            if world_size > 1:
+                raise ValueError("Trainer(skin_grid=...) needs world_size == 1: d_skin_grid is not reduced across ranks")
+            if int(skin_grid_every) < 1:
+                raise ValueError("skin_grid_every must be at least 1")
         self.frames, self.pose, self.pose_from_iter, self.pose_every = frames, pose, int(pose_from_iter), int(pose_every)
+        self.skin_grid, self.skin_grid_from_iter, self.skin_grid_every = skin_grid, int(skin_grid_from_iter), int(skin_grid_every)
         self.pose_frames = None if pose_frames is None else [int(f) for f in pose_frames]
         self.last_items = None          # with frames: the dataset items of the last step
         # sharded_adam (world_size > 1): reduce-scatter of the gradients -> every rank takes the Adam step on the 1/world
@@ -1679,6 +1696,16 @@ class Trainer:
         self.pose.apply(c, ids, rows)
         return ids, rows
 
+    def _skin_grid_step(self, gs, out):
+        """Behind the Gaussians' optimizer step (and the pose corrections'): the skin-weight grid's own step on the step's
+        `out["d_skin_grid"]` -- the gradient of the parameters the step rendered, also where densify / prune has just replaced the
+        leaves (the grid tensor is never replaced) -- at the scheduled global steps; off schedule the gradient is formed and ignored."""
+        r = self.skin_grid
+        if r is None or gs < self.skin_grid_from_iter or (gs - self.skin_grid_from_iter) % self.skin_grid_every != 0:
+            return
+        r.step(out["d_skin_grid"])
+        out["loss_skin_prior"] = r.last_prior
+
     def train_step(self, views=None):
         """One optimisation step; returns the step's output dict (loss, statistics) plus "changed".
         views: optional list of per-view dicts for the pruning tests (default: `compute.prune_views`).
@@ -1704,6 +1731,7 @@ class Trainer:
                 self.compute.mark_params_changed()
             if posed_step is not None:
                 self.pose.step(out["d_transforms"], *posed_step)
+            self._skin_grid_step(gs, out)
             self.global_step += 1
             out["changed"] = False
             return out
@@ -1759,6 +1787,7 @@ class Trainer:
             self.compute.mark_params_changed()
         if posed_step is not None:
             self.pose.step(out["d_transforms"], *posed_step)
+        self._skin_grid_step(gs, out)
         self.global_step += 1
         if resized:
             self.compute.set_params(self.opt.parameters(), None)

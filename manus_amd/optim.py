@@ -440,3 +440,92 @@ class SkinGridAdam:
                                        sg.B, ptr(self.exp_avg), ptr(self.exp_avg_sq), self.lr, self.betas[0], self.betas[1], self.eps,
                                        self.steps, int(clamp), float(self.clamp_min) if clamp else 0.0, stream()), "mgr_skin_grid_adam")
         sg.bump()
+
+
+class SkinGridRefiner:
+    """Training stage of a `ops.SkinGrid` on the sparse gradient of `ops.skin_grid_grad`, ONE call per step
+    (`mgr_skin_grid_refine`): the gradient of the prior  prior_weight * ||row - prior row||^2  towards the grid kept at
+    construction (the reference keeps `grid_weights_init` beside `grid_weights` for this), the row Adam of `SkinGridAdam` on the
+    listed voxels, max(x, clamp_min) (None: no clamp), and -- project=True -- the stepped rows divided by their sum where it
+    exceeds min_sum: the forward divides every sample by its raw sum, so a row's scale is a gauge that Adam would drift along.
+    With prior_weight = 0 and project=False the grid and the moments are bit for bit `SkinGridAdam`'s.
+
+    `last_prior`: a (1,) float64 tensor on the device, the prior's value over the listed rows on the grid BEFORE the last step
+    (zero at weight 0); it is overwritten by the next step and reading it is the caller's synchronisation, not this object's.
+    The prior and its value cover the listed rows only: a voxel no Gaussian touches is neither pulled nor counted.
+    The reference (HandGaussianModel.optimizing_skin_weights) would use a dense Adam on the whole grid."""
+
+    HYPER = ("lr", "betas", "eps", "clamp_min", "prior_weight", "project", "min_sum")
+
+    def __init__(self, sg, lr, betas=(0.9, 0.999), eps=1e-8, clamp_min=0.0, prior_weight=0.0, project=True, min_sum=1e-12):
+        from .ops import SkinGrid
+        if not isinstance(sg, SkinGrid):
+            raise ManusHipError("SkinGridRefiner takes a SkinGrid")
+        self.sg, self.lr, self.betas, self.eps = sg, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.clamp_min = None if clamp_min is None else float(clamp_min)
+        self.prior_weight, self.project, self.min_sum = float(prior_weight), bool(project), float(min_sum)
+        if not (self.prior_weight >= 0.0 and math.isfinite(self.prior_weight)):
+            raise ValueError("SkinGridRefiner: prior_weight must be finite and >= 0")
+        if not self.min_sum >= 0.0:
+            raise ValueError("SkinGridRefiner: min_sum must be >= 0")
+        self.steps = 0
+        self.exp_avg = self.exp_avg_sq = self._ws = None
+        self.prior = sg.data.clone()
+        self.last_prior = torch.zeros(1, dtype=torch.float64, device=sg.data.device)
+
+    def set_prior(self, grid_weights):
+        """Replace the prior target by `grid_weights` (D,H,W,B), e.g. a checkpoint's `grid_weights_init`."""
+        sg = self.sg
+        g = torch.as_tensor(grid_weights, dtype=torch.float32)
+        if tuple(g.shape) != (sg.D, sg.H, sg.W, sg.B):
+            raise ValueError("SkinGridRefiner.set_prior: the grid is %s, the prior %s" % ((sg.D, sg.H, sg.W, sg.B), tuple(g.shape)))
+        self.prior.zero_()
+        self.prior[..., : sg.B] = g.to(self.prior.device)
+
+    def step(self, grad):
+        sg = self.sg
+        if tuple(grad.shape) != (sg.D, sg.H, sg.W, sg.B) or grad.grad.shape[1] != sg.stride:
+            raise ManusHipError("SkinGridRefiner: the gradient is not of this grid")
+        cap = grad.voxel.numel()
+        if self.exp_avg is None:
+            self.exp_avg, self.exp_avg_sq = torch.zeros_like(sg.data), torch.zeros_like(sg.data)
+        nbytes = int(lib().mgr_skin_grid_refine_workspace_bytes(cap))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=sg.data.device)
+        self.steps += 1
+        clamp = self.clamp_min is not None
+        check(lib().mgr_skin_grid_refine(ptr(grad.voxel), ptr(grad.grad), ptr(grad.count), cap, ptr(sg.data), ptr(self.prior), sg.stride,
+                                         sg.B, ptr(self.exp_avg), ptr(self.exp_avg_sq), self.lr, self.betas[0], self.betas[1], self.eps,
+                                         self.steps, int(clamp), self.clamp_min if clamp else 0.0, self.prior_weight, int(self.project),
+                                         self.min_sum, ptr(self.last_prior), ptr(self._ws), self._ws.numel(), stream()),
+              "mgr_skin_grid_refine")
+        sg.bump()
+
+    # -- resume ---------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """Moments (None before the first step), step count, prior target and hyper-parameters, on the CPU: plain tensors and
+        numbers, which `checkpoint.save_checkpoint(extra_state=...)` stores and the safe loader reads back.  The grid itself is
+        the checkpoint's `grid_weights`, not part of this state."""
+        c = lambda t: None if t is None else t.detach().cpu().clone()
+        sg = self.sg
+        return dict(shape=(sg.D, sg.H, sg.W, sg.B), stride=sg.stride, steps=self.steps, exp_avg=c(self.exp_avg),
+                    exp_avg_sq=c(self.exp_avg_sq), prior=c(self.prior), hyper={k: getattr(self, k) for k in self.HYPER})
+
+    def load_state_dict(self, state):
+        sg = self.sg
+        if tuple(state["shape"]) != (sg.D, sg.H, sg.W, sg.B) or int(state["stride"]) != sg.stride:
+            raise ValueError("SkinGridRefiner.load_state_dict: the state is of a grid %s with stride %d, this grid is %s with stride %d"
+                             % (tuple(state["shape"]), int(state["stride"]), (sg.D, sg.H, sg.W, sg.B), sg.stride))
+        for k in ("exp_avg", "exp_avg_sq", "prior"):
+            t = state[k]
+            if t is not None and tuple(t.shape) != tuple(sg.data.shape):
+                raise ValueError("SkinGridRefiner.load_state_dict: %s is %s, the grid's storage %s" % (k, tuple(t.shape), tuple(sg.data.shape)))
+        dev = sg.data.device
+        take = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float32).clone().contiguous()
+        self.exp_avg, self.exp_avg_sq = take(state["exp_avg"]), take(state["exp_avg_sq"])
+        self.prior.copy_(state["prior"])
+        self.steps = int(state["steps"])
+        h = state["hyper"]
+        self.lr, self.betas, self.eps = float(h["lr"]), (float(h["betas"][0]), float(h["betas"][1])), float(h["eps"])
+        self.clamp_min = None if h["clamp_min"] is None else float(h["clamp_min"])
+        self.prior_weight, self.project, self.min_sum = float(h["prior_weight"]), bool(h["project"]), float(h["min_sum"])
