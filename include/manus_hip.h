@@ -809,6 +809,39 @@ int mgr_image_loss_tiles_finish(int V, int H, int W, const float* pred, const fl
                                 float grad_scale, float loss_offset, float* dL_dpred, float* sums, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Spatial image loss: L1 + the STANDARD 2-D SSIM, forward + backward in one pass (csrc/ssim2d.hip).  Opt-in; mgr_image_loss
+ * above stays the reference's statistic.  Here the 11x11 Gaussian window (sigma 1.5; G = g g^T with the fp32 g of
+ * mgr_image_loss) slides over H x W of every colour channel separately, zero padding 5 -- what the reference's ssim() computes
+ * when it is handed CHW images, as upstream 3DGS does.  pred, target (V,3,H,W) fp32; mask (V,H,W) fp32, possibly fractional, or
+ * NULL: x = pred * mask, y = target * mask at load, the same map for the three channels.  Per channel
+ *   E_s = G * s for s in {x, y, xx, yy, xy} (zero outside the image),
+ *   S = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),  C1 = 1e-4, C2 = 9e-4.
+ *   sums[0] = sum|x - y|, sums[1] = sum S (both over V*3*H*W values), sums[2] = grad_scale * (w_l1 * sums[0] - w_ssim * sums[1])
+ *             + loss_offset: the meaning they have in mgr_image_loss;
+ *   view_sums (V,2) or NULL: the two sums of every view;
+ *   dL_dpred (V,3,H,W) = grad_scale * mask * (w_l1 * sign(x - y) - w_ssim * d(sum S)/dx); NULL = forward only (the same sums,
+ *             bit for bit).
+ * Blocks: the image is cut into blocks of mgr_image_loss2d_block() = (block_w << 16) | block_h pixels.  A block is SETTLED when
+ * x - y == 0 in fp32 (tested on the difference: NaN and Inf never count as equal) over the block dilated by 10 px and clipped to
+ * the image -- exact: a pixel's gradient reaches 5 px to the derivative maps and those 5 px to the statistics.  A settled block
+ * contributes exactly its value count to sum S and 0 to sum L1, gets zeros as its gradient, and does not run the heavy kernel.
+ * flags & MGR_IL2D_DENSE: every block runs it.
+ * The sums are accumulated as 64-bit fixed point (2^-32) per view: independent of the order the blocks ran in (two calls give
+ * equal bits) and of the other views of the call.  A view whose inputs hold a NaN, or whose block sums leave the fixed-point
+ * range (|sum over a block| beyond 2^31 / blocks of a view), reports NaN for its two sums, and so does `sums`; the other views'
+ * view_sums keep their bits.
+ * Refusals (MGR_EINVAL / MGR_ENOMEM, nothing touched): sizes <= 0, NULL pred / target / sums / workspace, H or V > 65535,
+ * 3 H W >= 2^31, an unknown flag, workspace_bytes below mgr_image_loss2d_workspace_bytes(V,H,W) (sum slots, one bit per pixel,
+ * the list of blocks; 0 for sizes <= 0).
+ * ------------------------------------------------------------------------ */
+#define MGR_IL2D_DENSE 1
+size_t mgr_image_loss2d_workspace_bytes(int V, int H, int W);
+int mgr_image_loss2d_block(void);
+int mgr_image_loss2d(int V, int H, int W, const float* pred, const float* target, const float* mask, float w_l1, float w_ssim,
+                     float grad_scale, float loss_offset, float* dL_dpred, float* sums, float* view_sums, int flags,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Silhouette and depth terms on the maps of mgr_raster_blend_features, value and gradient in one pass.  No reference
  * counterpart.
  *   L_mask  = mean over V H W of |alpha - mask|               mask (V,H,W) fp32 in [0,1]

@@ -34,6 +34,7 @@ MGR_TIERS_NEAR_SMALL_SHIFT, MGR_TIERS_NEAR_LARGE_SHIFT, MGR_TIERS_NEAR_MASK = 8,
 MGR_TIERS_BEYOND_SMALL_SHIFT, MGR_TIERS_BEYOND_SMALL_MASK = 24, 0x7F
 MGR_LPIPS_F32, MGR_LPIPS_BF16 = 0, 1      # the operand mode of the mgr_lpips*_op entries
 MGR_LPIPS_STORE_F32, MGR_LPIPS_STORE_BF16 = 0, 1      # the storage mode of the mgr_lpips*_st entries
+MGR_IL2D_DENSE = 1                       # mgr_image_loss2d flags: every block runs the heavy kernel (no settled blocks)
 LP_MAX_BATCH = 16                        # the most views of one launch of the mgr_lpips_roi*_batch* entries (manus_hip.h)
 
 c_int, c_i64, c_f32, c_vp, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
@@ -151,6 +152,9 @@ SIGNATURES = {
     "mgr_image_loss_tiles_list": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_image_loss_tiles_finish": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_sz,
                                             c_vp]),
+    "mgr_image_loss2d_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_image_loss2d_block": (c_int, []),
+    "mgr_image_loss2d": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_vp]),
     "mgr_map_loss_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_map_loss": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_lpips_net_bytes": (c_sz, [c_int]),

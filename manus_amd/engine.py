@@ -214,7 +214,7 @@ class ViewShardedStep:
             res = dict(grads=out["grads"], grad2d=out["grad2d"], vis=out["vis"], radii=radii, loss=out["loss"],
                        overflow=out.get("overflow"))
             # (one rank, nothing to reduce: what the compute object returned beside the reduced quantities travels as it is)
-            for name in ("loss_lpips", "d_transforms", "d_skin_grid", "loss_mask", "loss_depth"):
+            for name in ("loss_lpips", "loss_ssim", "d_transforms", "d_skin_grid", "loss_mask", "loss_depth"):
                 if name in out:
                     res[name] = out[name]
             return res
@@ -552,6 +552,14 @@ class HipViewCompute:
       overlap_loss  without target maps: the span list is built on a second stream while the forward blend runs (forward split
                     at the blend, MGR_FWD_NO_BLEND / MGR_FWD_BLEND_ONLY).  MANUS_OVERLAP_LOSS=0.
 
+    SSIM statistic (`ssim`; a plain attribute, "rows" or "spatial", anything else raises ValueError at the step): "rows"
+    (default) is the reference's ssim() on its HWC images, the window over the (W,3) plane of every image row -- the step without
+    the keyword, bit for bit.  "spatial" with loss="l1+ssim": the image term of both routes is w_rgb * mean|d| + w_ssim * (1 - mean S) of
+    the standard 2-D SSIM (`ops.image_loss2d_grad`, csrc/ssim2d.hip) on the same scales; the fused step then takes the plain
+    route (no span list, dL/dimage written in full) and LPIPS, the map terms, pose_grad and skin_grid_grad work behind it
+    unchanged.  The output dict gains "loss_ssim": the unweighted sum over the views of 1 - mean S_v on the step's scale (one
+    rank only, like "loss_lpips").  With loss="l1" the attribute has no effect.
+
     Map supervision (`mask_targets`, `w_mask`, `depth_targets`, `w_depth`; plain attributes, settable after construction): with
     `mask_targets` (V_all,H,W) and a non-zero weight the step adds, per view,
         w_mask * mean|alpha - mask| + w_depth * mean(mask * |depth - depth_target|)
@@ -598,11 +606,14 @@ class HipViewCompute:
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
                  persistent_grads=True, pose_grad=False, skin_grid_grad=False, mask_targets=None, w_mask=0.0, depth_targets=None,
                  w_depth=0.0, lpips=None, w_lpips=0.0, lpips_rects=None, lpips_norm="frame", lpips_cache_targets=False,
-                 lpips_batch=0):
+                 lpips_batch=0, ssim="rows"):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
             raise ValueError("loss must be 'l1' or 'l1+ssim'")
+        self.ssim = ssim                # "rows" | "spatial" (class docstring); a plain attribute, asked again at every step
+        self._loss_ssim = None          # "spatial": the step's unweighted SSIM term
+        self._ssim_mode()
         env = os.environ.get
         self.ops, self.rz, self.fz, self.fused = ops, rasterizer, fused_mod, fused
         # -- scene and per-view constants
@@ -913,6 +924,12 @@ class HipViewCompute:
                                     p["_features_rest"], w, sel["T"], sel["cams"], s["bg"], s["width"], s["height"],
                                     stats=stats, grad2d_scale=grad2d_scale, grad_arena=self.grad_arena)
 
+    def _ssim_mode(self):
+        """`self.ssim`, or ValueError for anything but "rows" / "spatial"."""
+        if self.ssim not in ("rows", "spatial"):
+            raise ValueError("ssim must be 'rows' or 'spatial' (got %r)" % (self.ssim,))
+        return self.ssim
+
     def _loss_scales(self, img, scale):
         """(k, const) of the image-loss kernels for scale * sum over the views of the per-view loss of `img` (V,3,H,W):
         the factor on the per-pixel terms, and the "1 -" of 1 - ssim, once per view."""
@@ -972,6 +989,11 @@ class HipViewCompute:
         if self.loss == "l1":
             loss_sum, g = self.ops.l1_loss_grad(img, tgt, scale=k)
             return loss_sum[0] * k, g
+        if self._ssim_mode() == "spatial":
+            # the standard 2-D SSIM (mgr_image_loss2d): the same scales, no span list, the gradient written in full
+            sums, _, g = self.ops.image_loss2d_grad(img, tgt, self.w_rgb, self.w_ssim, k, const)
+            self._loss_ssim = scale * (img.shape[0] - sums[1] / img[0].numel())
+            return sums[2], g
         bg, ts = tiles if (tiles is not None and self.sparse_loss) else (None, None)
         sums, g = self.ops.image_loss_grad(img, tgt, self.w_rgb, self.w_ssim, k, const, bg=bg, tile_start_ptr=ts)
         return sums[2], g
@@ -1045,7 +1067,8 @@ class HipViewCompute:
                 ptr(p["_opacity"].reshape(-1)), ptr(p["_features_dc"]), ptr(f_rest), ptr(w), ptr(sel["T"]))
         fwd = (head, out, radii, kept)
         # route of the image loss (class docstring): "mapped" / "overlap" span lists, or None = plain / g_img given
-        listed = g_img is None and self.loss == "l1+ssim" and self.sparse_loss
+        self._loss_ssim = None
+        listed = g_img is None and self.loss == "l1+ssim" and self.sparse_loss and self._ssim_mode() == "rows"
         route = None if not listed else "mapped" if self.target_map else "overlap" if self.overlap_loss else None
         loss_list = self._mapped_loss_list(view_ids, sel, V, H, W) if route == "mapped" else None
         ctx = self.rz.context(dev)
@@ -1082,6 +1105,8 @@ class HipViewCompute:
         if lp is not None:
             res["loss"] = res["loss"] + self.w_lpips * lp
             res["loss_lpips"] = lp
+        if self._loss_ssim is not None:
+            res["loss_ssim"] = self._loss_ssim
         if d_T is not None:
             res["d_transforms"] = d_T
         if d_grid is not None:
@@ -1318,6 +1343,8 @@ class HipViewCompute:
         if self.fused:
             return self._step_direct(view_ids, scale)
         self.last_active = None
+        self._loss_ssim = None
+        self._ssim_mode()
         for v in self.params.values():
             v.grad = None
         sel = self._select(view_ids)
@@ -1351,6 +1378,8 @@ class HipViewCompute:
         if lp is not None:
             res["loss"] = res["loss"] + self.w_lpips * lp
             res["loss_lpips"] = lp
+        if self._loss_ssim is not None:
+            res["loss_ssim"] = self._loss_ssim
         if T is not None:
             res["d_transforms"] = T.grad
         if self.skin_grid_grad:
@@ -1596,7 +1625,7 @@ class Trainer:
             self.stepper.all_gather_params(self.opt.mflat)
             self.stepper.all_gather_params(self.opt.vflat)
 
-    def validate(self, view_ids, masks=None, validator=None, group=8, lpips=None):
+    def validate(self, view_ids, masks=None, validator=None, group=8, lpips=None, ssim="rows"):
         """The validation pass over the views `view_ids` of the compute object (validation_step / on_validation_epoch_end,
         src/modules/base.py:112-188): rendered under no_grad with `forward_views` in groups of `group` views (the group
         size of `HipViewCompute.pairs_per_view`), compared with `compute.targets` by `ops.eval_views` / `ops.eval_triptych`
@@ -1605,9 +1634,11 @@ class Trainer:
         (ones).  validator: a `validation.Validator` that receives every view (metrics, its share of the group's render
         time, triptych); the caller brackets the pass with its start() / end(global_step).  lpips: a `manus_amd.lpips.LPIPS`
         (the reference's is AlexNet, loss_utils.py:19): its per-view value on the masked images, render * mask against
-        target * mask, goes to the validator's CSV column and to the result's "lpips" list.
+        target * mask, goes to the validator's CSV column and to the result's "lpips" list.  ssim: "rows" (default; the
+        reference's statistic on HWC images, from `ops.eval_views`) or "spatial" (the standard 2-D SSIM of the masked images,
+        `validation.spatial_ssim`): which one fills the result's "ssim" list and the CSV column; anything else raises ValueError.
 
-        Returns dict(psnr, ssim: per-view lists; psnr_mean, ssim_mean; render_time: seconds from the start of each
+        Returns dict(psnr, ssim: per-view lists; psnr_mean, ssim_mean; ssim_kind; render_time: seconds from the start of each
         group's render to the end of its last kernel, summed (two events on the stream: the group's host work included,
         no extra synchronisation);
         images: (len(view_ids),3H,W,3) uint8 on the device).
@@ -1616,7 +1647,8 @@ class Trainer:
         learnt capacities, fences and sync policy of the training context are not touched), the compute object's cache of
         per-view constants is put back, nothing is written into the kept gradient / image / loss buffers, and
         `global_step` does not move -- a train_step after a validate computes what it would have without it."""
-        from .validation import psnr_from_sums
+        from .validation import check_ssim_kind, psnr_from_sums, spatial_ssim
+        check_ssim_kind(ssim)
         c = self.compute
         ids = list(view_ids)
         dev = getattr(c, "device", None)
@@ -1647,7 +1679,7 @@ class Trainer:
                         sq, ss, gmax = ops.eval_views(img, tgt, m)
                         trip = ops.eval_triptych(img, tgt, gmax)
                         n = float(img[0].numel())
-                        rows = [psnr_from_sums(sq, n), ss / n]
+                        rows = [psnr_from_sums(sq, n), spatial_ssim(img, tgt, m) if ssim == "spatial" else ss / n]
                         if lpips is not None:
                             rows.append(lpips.values_grad(img, tgt, m, need_grad=False)[0])
                         both = torch.stack(rows).cpu()      # the group's one synchronisation
@@ -1674,7 +1706,7 @@ class Trainer:
             c._cache, c._const_stamp = saved_cache, saved_stamp
         import numpy as np
         res = dict(psnr=psnrs, ssim=ssims, psnr_mean=float(np.mean(psnrs)) if psnrs else float("nan"),
-                   ssim_mean=float(np.mean(ssims)) if ssims else float("nan"), render_time=render_time,
+                   ssim_mean=float(np.mean(ssims)) if ssims else float("nan"), ssim_kind=ssim, render_time=render_time,
                    images=torch.cat(images) if images else None)
         if lpips is not None:
             res["lpips"] = lps

@@ -11,6 +11,9 @@ src/utils/gaussian_utils.py:418; `gt` may carry a leading batch dimension of 1) 
 differentiable w.r.t. the first argument.  `ssim` reproduces the reference's behaviour on HWC
 input exactly: `channel = img1.size(-3)` is the image height, so the window runs over the (W,3)
 plane of each row.  GPU tensors only; there is no CPU fallback.
+
+Beside them, opt-in, the standard SSIM (`mgr_image_loss2d`): `ssim_chw(img1, img2)` on CHW images and
+`rgb_ssim_loss(..., ssim="spatial")` on the reference's HWC images run the window over H x W of every colour channel.
 """
 import weakref
 
@@ -114,9 +117,42 @@ def ssim(img1, img2, window_size=11, size_average=True):
     return -_ImageLoss.apply(img1, img2, 0.0, 1.0)
 
 
-def rgb_ssim_loss(pred_image, gt_image, w_rgb=0.8, w_ssim=0.2):
+class _ImageLoss2D(torch.autograd.Function):
+    """w_l1 * mean|d| - w_ssim * mean S of the spatial kernel (`ops.image_loss2d_grad`) on (V,3,H,W) images."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, w_l1, w_ssim):
+        sums, _, g = ops.image_loss2d_grad(pred, gt, w_l1, w_ssim, 1.0 / pred.numel(), need_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(g)
+        return sums[2].clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        (g,) = ctx.saved_tensors
+        return g * go, None, None, None
+
+
+def ssim_chw(img1, img2):
+    """The standard SSIM of (3,H,W) or (V,3,H,W) images -- 11x11 Gaussian window, sigma 1.5, over H x W of every channel,
+    zero padding 5, the mean over all values: what loss_utils.ssim (loss_utils.py:57-97) computes on CHW images, as upstream
+    3DGS calls it.  Differentiable w.r.t. img1.  GPU tensors only."""
+    if img1.dim() not in (3, 4) or img1.shape[-3] != 3 or img1.shape != img2.shape:
+        raise ManusHipError("ssim_chw: images are (3,H,W) or (V,3,H,W), both of one shape")
+    a, b = (img1[None], img2[None]) if img1.dim() == 3 else (img1, img2)
+    return -_ImageLoss2D.apply(a, b.detach(), 0.0, 1.0)
+
+
+def rgb_ssim_loss(pred_image, gt_image, w_rgb=0.8, w_ssim=0.2, ssim="rows"):
     """w_rgb * l1_loss + w_ssim * (1 - ssim) in one kernel: the first two terms of
-    config/HAND_GAUSSIAN.yaml:22-23 as combined by loss_func (base.py:356-364)."""
+    config/HAND_GAUSSIAN.yaml:22-23 as combined by loss_func (base.py:356-364).  ssim="rows" (default) is the reference's
+    statistic on its HWC images; "spatial" the standard SSIM of `ssim_chw` on the same images."""
+    if ssim not in ("rows", "spatial"):
+        raise ValueError("ssim must be 'rows' or 'spatial' (got %r)" % (ssim,))
+    if ssim == "spatial":
+        pred = pred_image[0] if pred_image.dim() == 4 else pred_image
+        if pred.dim() != 3 or pred.shape[-1] != 3:
+            raise ManusHipError("losses: images are (H,W,3) like the reference's render / gt")
+        return _ImageLoss2D.apply(pred.permute(2, 0, 1)[None], _gt_chw(gt_image)[None], w_rgb, w_ssim) + w_ssim
     return _ImageLoss.apply(pred_image, gt_image, w_rgb, w_ssim) + w_ssim
 
 

@@ -10,6 +10,7 @@ Each op mirrors one block of MANUS Python code (reference tree brown-ivl/manus):
     project_points project_points                        src/utils/transforms.py:304-311
     distCUDA2      simple_knn._C.distCUDA2               src/models/gaussian.py:110
     eval_views, eval_triptych   validation_step's metrics / image   src/modules/base.py:112-154
+    image_loss2d_grad           L1 + ssim() as it computes on CHW images   src/utils/loss_utils.py:22-97
 
 All of them require GPU tensors; there is no CPU or PyTorch fallback.
 """
@@ -17,7 +18,7 @@ import ctypes
 
 import torch
 
-from ._lib import MGR_MAX_BONES, ManusHipError, check, f32c, lib, ptr, stream
+from ._lib import MGR_IL2D_DENSE, MGR_MAX_BONES, ManusHipError, check, f32c, lib, ptr, stream
 
 
 class SkinGrid:
@@ -381,6 +382,50 @@ def image_loss_grad(pred, target, w_l1=0.8, w_ssim=0.2, grad_scale=1.0, loss_off
     check(lib().mgr_image_loss(V, H, W, ptr(pred), ptr(target), float(w_l1), float(w_ssim), float(grad_scale),
                                float(loss_offset), ptr(g), ptr(sums), ptr(ws), nbytes, stream()), "mgr_image_loss")
     return sums, g
+
+
+def image_loss2d_block():
+    """(block_w, block_h) of `mgr_image_loss2d`: the pixel blocks it settles or lists."""
+    word = int(lib().mgr_image_loss2d_block())
+    return word >> 16, word & 0xFFFF
+
+
+def image_loss2d_grad(pred, target, w_l1=0.8, w_ssim=0.2, grad_scale=1.0, loss_offset=0.0, mask=None, need_grad=True, dense=False):
+    """Fused L1 + SPATIAL SSIM image loss (`mgr_image_loss2d`), forward and backward, on (V,3,H,W) images: the standard
+    SSIM -- an 11x11 Gaussian window (sigma 1.5) over H x W of every colour channel separately, zero padding 5 -- where
+    `image_loss_grad` is the reference's statistic on HWC images.  mask (V,H,W), possibly fractional: both images are
+    multiplied by it at load.
+
+    Returns (sums, view_sums, grad or None): sums[0] = sum|x - y|, sums[1] = sum of the SSIM map, sums[2] = grad_scale *
+    (w_l1 * sums[0] - w_ssim * sums[1]) + loss_offset (device tensor of 3 floats); view_sums (V,2): the two sums of every view;
+    grad = d sums[2] / d pred (need_grad=False: None, the same sums).  Blocks of `image_loss2d_block()` pixels whose 10 px
+    surroundings hold no difference are settled without the heavy kernel (sum S += their values, gradient 0); dense=True runs
+    every block.  Deterministic: two calls give the same bits.  GPU tensors only."""
+    for t in (pred, target, mask):
+        if t is not None and not t.is_cuda:
+            raise ManusHipError("image_loss2d_grad needs GPU tensors (got %s); there is no CPU fallback" % t.device)
+    pred, target = f32c(pred), f32c(target)
+    if pred.dim() == 3:
+        pred, target = pred[None], target[None]
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape[1] != 3:
+        raise ManusHipError("image_loss2d_grad: pred and target must both be (V,3,H,W)")
+    V, _, H, W = pred.shape
+    if mask is not None:
+        mask = f32c(mask)
+        if mask.dim() == 2:
+            mask = mask[None]
+        if tuple(mask.shape) != (V, H, W):
+            raise ManusHipError("image_loss2d_grad: mask must be (V,H,W)")
+    dev = pred.device
+    g = torch.empty_like(pred) if need_grad else None
+    sums = torch.empty(3, dtype=torch.float32, device=dev)
+    view_sums = torch.empty((V, 2), dtype=torch.float32, device=dev)
+    nbytes = int(lib().mgr_image_loss2d_workspace_bytes(V, H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib().mgr_image_loss2d(V, H, W, ptr(pred), ptr(target), ptr(mask), float(w_l1), float(w_ssim), float(grad_scale),
+                                 float(loss_offset), ptr(g), ptr(sums), ptr(view_sums), MGR_IL2D_DENSE if dense else 0, ptr(ws), nbytes,
+                                 stream()), "mgr_image_loss2d")
+    return sums, view_sums, g
 
 
 def isotropic_reg_grad(log_scale, condition_number=0.4, weight=1.0, grad_out=None):

@@ -55,10 +55,31 @@ def psnr_from_sums(sq_sum, n_elements):
     return -10 * torch.log10(sq_sum / float(n_elements))
 
 
-def validation_step(render_hwc, batch):
+SSIM_KINDS = ("rows", "spatial")
+
+
+def check_ssim_kind(ssim):
+    """"rows": the reference's ssim() on its HWC images (the window over the (W,3) plane of every image row; csrc/eval.hip);
+    "spatial": the standard 2-D SSIM (csrc/ssim2d.hip), comparable with the SSIM of a paper.  Anything else: ValueError."""
+    if ssim not in SSIM_KINDS:
+        raise ValueError("ssim must be 'rows' or 'spatial' (got %r)" % (ssim,))
+    return ssim
+
+
+def spatial_ssim(pred, tgt, mask):
+    """(V,) mean spatial SSIM of the masked images render * mask, target * mask (base.py:144-147): `view_sums` of a
+    forward-only `ops.image_loss2d_grad`."""
+    _, view_sums, _ = ops.image_loss2d_grad(pred, tgt, 0.0, 1.0, mask=mask, need_grad=False)
+    return view_sums[:, 1] / float(pred[0].numel())
+
+
+def validation_step(render_hwc, batch, ssim="rows"):
     """One held-out view, shaped like the reference's: render (H,W,3); batch["rgb"] (H,W,3) and batch["mask"] (H,W,1)
     (or (H,W)), each optionally with a leading batch dimension of 1; a missing / None mask means ones.  GPU tensors.
-    Returns {"psnr", "ssim": 0-dim device tensors, "image": (3H,W,3) uint8 device tensor}."""
+    ssim: "rows" (the reference's statistic) or "spatial" (`check_ssim_kind`) -- which SSIM fills the "ssim" value; PSNR and
+    the triptych are the same either way.
+    Returns {"psnr", "ssim": 0-dim device tensors, "image": (3H,W,3) uint8 device tensor, "ssim_kind": ssim}."""
+    check_ssim_kind(ssim)
     gt, mask = batch["rgb"], batch.get("mask")
     if not (torch.is_tensor(render_hwc) and render_hwc.is_cuda and torch.is_tensor(gt) and gt.is_cuda):
         raise ManusHipError("validation_step needs GPU tensors; there is no CPU fallback")
@@ -82,7 +103,8 @@ def validation_step(render_hwc, batch):
     sq, ss, gmax = ops.eval_views(pred, tgt, mask)
     image = ops.eval_triptych(pred, tgt, gmax)[0]
     n = 3 * H * W
-    return {"psnr": psnr_from_sums(sq, n)[0], "ssim": (ss / float(n))[0], "image": image}
+    ss = spatial_ssim(pred, tgt, mask) if ssim == "spatial" else ss / float(n)
+    return {"psnr": psnr_from_sums(sq, n)[0], "ssim": ss[0], "image": image, "ssim_kind": ssim}
 
 
 def _scalar(x):
