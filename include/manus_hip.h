@@ -703,7 +703,25 @@ int mgr_bone_transforms(int B, int background, const float* posed, const float* 
  * mgr_pose_adam: the row Adam of mgr_skin_grid_adam (torch.optim.SparseAdam: parameters and moments of the listed rows only,
  *   bias correction of the global `step` >= 1) on the rows frames_listed[u] (distinct, inside the tables: the caller's to
  *   ensure; negative entries are skipped) of rotvec / trans and their moments m_r, v_r, m_t, v_t (F,B,3), from d_rotvec /
- *   d_trans (U,B,3).  Separate learning rates, no clamp. */
+ *   d_trans (U,B,3).  Separate learning rates, no clamp.
+ * mgr_pose_backward_prior: mgr_pose_backward (one kernel body instantiated twice: the same sums in the same order; the two
+ *   instantiations may differ in the last bit of the chain gradient, as the compiler fuses other products) with priors.  For
+ *   x = rotvec or trans, each with its own pair of weights (finite, >= 0),
+ *       E = w_mag sum_f |x_f|^2 + w_smooth sum_edges |x_f - x_next(f)|^2
+ *   where neighbours (F,2) int32 gives (prev, next) of every frame row, -1 = none (an index outside [-1,F) is read as -1; the
+ *   caller keeps the table symmetric: next(prev(f)) = f).  Row u of d_rotvec / d_trans gains the true dE/dx_f of f =
+ *   frames_listed[u], 2 w_mag x_f + 2 w_smooth ((x_f - x_prev) + (x_f - x_next)), formed in fp32 in that order -- the
+ *   differences, their sum prev first, the two products, then the addition to the chain gradient -- uncontracted.  Neighbours
+ *   that are not listed are read, never written: the tables are read-only here, and mgr_pose_adam behind this entry is what
+ *   moves the listed rows, so every prior gradient of a step is taken at the tables before the step.  *prior_value (double,
+ *   device) = the part of E that touches the listed rows, each term once: their magnitude terms, every edge (f, next(f)) of
+ *   a listed f, and every edge (prev(f), f) of a listed f whose prev is NOT listed (found by walking frames_listed, which may
+ *   be in any order).  The differences are the gradient's fp32 ones, squared and added in fp64: one share per (u, bone)
+ *   thread in the workspace (mgr_pose_prior_workspace_bytes(U, B) bytes), folded by one workgroup in a fixed order -- no
+ *   float atomics, equal bits run to run.  With all four weights zero this is mgr_pose_backward's own launch (equal bits),
+ *   neighbours / workspace may be NULL, and *prior_value, if given, is set to 0.  Refused before any launch, nothing written:
+ *   all of mgr_pose_backward's conditions; a negative or non-finite weight; NULL neighbours with a smoothness weight
+ *   non-zero; NULL prior_value or workspace with any weight non-zero; a short workspace (MGR_ENOMEM). */
 int mgr_pose_apply(int V, int B, int F, const int32_t* view_rows, const int32_t* frame_of_view, const float* posed,
                    const float* rest, const float* rotvec, const float* trans, float* transforms, float* gathered, void* stream);
 int mgr_pose_backward(int V, int B, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
@@ -712,8 +730,14 @@ int mgr_pose_backward(int V, int B, int F, int U, const int32_t* frames_listed, 
 int mgr_pose_adam(int U, int B, const int32_t* frames_listed, const float* d_rotvec, const float* d_trans, float* rotvec,
                   float* trans, float* m_r, float* v_r, float* m_t, float* v_t, double lr_rot, double lr_trans, double beta1,
                   double beta2, double eps, int step, void* stream);
+size_t mgr_pose_prior_workspace_bytes(int U, int B);
+int mgr_pose_backward_prior(int V, int B, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                            const int32_t* frame_of_view, const float* posed, const float* rest, const float* rotvec,
+                            const float* trans, const float* d_transforms, float* d_rotvec, float* d_trans,
+                            const int32_t* neighbours, double w_mag_rot, double w_smooth_rot, double w_mag_trans,
+                            double w_smooth_trans, double* prior_value, void* workspace, size_t workspace_bytes, void* stream);
 
-/* uv = (K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
+/* uv =(K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
 int mgr_project_points(int N, const float* xyz, const float* K9, const float* E12, float* uv,
                        void* stream);
 

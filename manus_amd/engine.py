@@ -1494,8 +1494,13 @@ class Trainer:
     the same items and transforms.  Without `frames`, pose_frames gives the frame row of each of the fixed views.  On a step
     at which the corrections are NOT applied (before pose_from_iter, between pose_every steps) the two modes differ: with
     `frames`, `load_step` has just written the items' UNCORRECTED transforms, so the Gaussians train on those; on a fixed view
-    set the table keeps the transforms of the last `apply`.  The pruning tests (`compute.prune_views`) keep testing against the
-    DATASET's keypoints, not the corrected ones; their masks and cameras are those of the drawn items
+    set the table keeps the transforms of the last `apply`.  pose_hold=True closes that gap: on every step g >= pose_from_iter
+    that is OFF the pose_every schedule the corrected transforms of the step's frames are written before the step
+    (`PoseRefiner.hold`) and no correction step follows, so the Gaussians never see a frame at two poses; a re-run after an
+    overflow uses the same transforms, and before pose_from_iter nothing is applied in either mode.  The default False is the
+    Trainer described above, bit for bit.  When the refiner has priors, `out["loss_pose_prior"]` is its `last_prior` on the
+    steps at which the corrections took their step (a device scalar, not read here and not added to `out["loss"]`).
+    The pruning tests (`compute.prune_views`) keep testing against the DATASET's keypoints, not the corrected ones; their masks and cameras are those of the drawn items
     (`load_step(scene_masks=True)`), with or without a mask table on the compute object.
 
     Skin-weight grid refinement (one rank; None: the step above, bit for bit).  skin_grid: an `optim.SkinGridRefiner` on
@@ -1508,7 +1513,7 @@ class Trainer:
     def __init__(self, compute, n_views, extent, opts=None, spatial_lr_scale=1.0, rank=0, world_size=1, group=None,
                  bg_white=True, kind=None, compact_allreduce=False, sharded_adam=False, view_weights=None, depth_cut=False,
                  sort_rows=False, persistent_grads=True, start_lpips_iter=1000, frames=None, pose=None, pose_from_iter=0,
-                 pose_every=1, pose_frames=None, skin_grid=None, skin_grid_from_iter=0, skin_grid_every=1):
+                 pose_every=1, pose_frames=None, skin_grid=None, skin_grid_from_iter=0, skin_grid_every=1, pose_hold=False):
         if frames is not None:
             if world_size > 1:
                 raise ValueError("Trainer(frames=...) needs world_size == 1: the frame pool is one rank's")
@@ -1535,6 +1540,7 @@ class Trainer:
         self.frames, self.pose, self.pose_from_iter, self.pose_every = frames, pose, int(pose_from_iter), int(pose_every)
         self.skin_grid, self.skin_grid_from_iter, self.skin_grid_every = skin_grid, int(skin_grid_from_iter), int(skin_grid_every)
         self.pose_frames = None if pose_frames is None else [int(f) for f in pose_frames]
+        self.pose_hold = bool(pose_hold)
         self.last_items = None          # with frames: the dataset items of the last step
         # sharded_adam (world_size > 1): reduce-scatter of the gradients -> every rank takes the Adam step on the 1/world
         # of the parameter elements it owns -> all-gather of the parameters.  The same bytes on the wire as the
@@ -1715,18 +1721,35 @@ class Trainer:
     def _point_views(self, gs):
         """Before the step at global step gs: the drawn items into the compute object's rows, then the pose corrections into
         its transforms.  -> (view ids, frame rows) when the corrections were applied (they take their step behind this one's
-        backward), else None."""
+        backward), else None -- also where `pose_hold` wrote the corrected transforms of an off-schedule step, which no
+        correction step follows."""
         c, ids = self.compute, list(self.stepper.local_views)
         if self.frames is not None:
             self.last_items = self.frames.items(gs)
             # (scene_masks: without a mask table the pruning masks of the scene still follow the drawn items)
             self.frames.store.load_step(c, self.last_items, masks=c.mask_targets is not None, lpips_rects=c.lpips_rects is not None,
                                         scene_masks=True)
-        if self.pose is None or gs < self.pose_from_iter or (gs - self.pose_from_iter) % self.pose_every != 0:
+        if self.pose is None or gs < self.pose_from_iter:
+            return None
+        due = (gs - self.pose_from_iter) % self.pose_every == 0
+        if not due and not self.pose_hold:
             return None
         rows = self.pose.frames_of(self.frames.store, self.last_items) if self.frames is not None else self.pose_frames
+        if not due:
+            self.pose.hold(c, ids, rows)
+            return None
         self.pose.apply(c, ids, rows)
         return ids, rows
+
+    def _pose_step(self, out, posed_step):
+        """Behind the Gaussians' optimizer step: the corrections' own step when `_point_views` applied them, and the value of
+        the refiner's prior (if it has one) on the rows that moved."""
+        if posed_step is None:
+            return
+        before = self.pose.steps
+        self.pose.step(out["d_transforms"], *posed_step)
+        if self.pose.steps != before and getattr(self.pose, "last_prior", None) is not None:
+            out["loss_pose_prior"] = self.pose.last_prior
 
     def _skin_grid_step(self, gs, out):
         """Behind the Gaussians' optimizer step (and the pose corrections'): the skin-weight grid's own step on the step's
@@ -1761,8 +1784,7 @@ class Trainer:
                 self.opt.step(out["grads"])
             if hasattr(self.compute, "mark_params_changed"):
                 self.compute.mark_params_changed()
-            if posed_step is not None:
-                self.pose.step(out["d_transforms"], *posed_step)
+            self._pose_step(out, posed_step)
             self._skin_grid_step(gs, out)
             self.global_step += 1
             out["changed"] = False
@@ -1817,8 +1839,7 @@ class Trainer:
             self.opt.step(out["grads"])   # skips the groups replaced above (all of them after a densify / prune)
         if hasattr(self.compute, "mark_params_changed"):
             self.compute.mark_params_changed()
-        if posed_step is not None:
-            self.pose.step(out["d_transforms"], *posed_step)
+        self._pose_step(out, posed_step)
         self._skin_grid_step(gs, out)
         self.global_step += 1
         if resized:

@@ -4,7 +4,8 @@ to them.
 
 Two forms of the same chain.  `PoseCorrection` / `pose_backward` are plain host torch on B small matrices under autograd: the
 form the tests check against, and what validation and contact renders call.  `PoseRefiner` is the chain on the device (csrc/pose.hip: apply,
-backward, row Adam; three launches per step, no autograd graph, no read-back), which `engine.Trainer(pose=...)` schedules.
+backward, row Adam; three launches per step -- four with priors on the corrections, whose value is folded by a launch of its own --,
+no autograd graph, no read-back), which `engine.Trainer(pose=...)` schedules.
 
 No reference counterpart: the reference's config/model/pose_optimizer.yaml names `src.models.pose_optimizer`, which was
 never released."""
@@ -59,6 +60,36 @@ def pose_backward(d_transforms, posed, rest, background=True):
     return dT.to(posed.dtype) @ inv_t
 
 
+def neighbour_table(frame_keys, max_gap=None):
+    """(F,2) int32 on the host: (prev, next) of every row of `frame_keys` along its take, -1 = none -- the edges of the
+    smoothness prior of `PoseRefiner`.  The rows are the distinct (action, frame_id) pairs in first-seen order, as `PoseRefiner`
+    numbers them.  Within an action the rows are ordered by int(frame_id) (equal numbers: first seen first) and rows adjacent in
+    that order are neighbours, unless `max_gap` is given and their ids differ by more than it.  An action with an id that does
+    not convert keeps its first-seen order, and `max_gap`, which has no numbers to compare there, does not cut it.  Rows of
+    different actions are never neighbours."""
+    keys = list(dict.fromkeys((k[0], k[1]) for k in frame_keys))
+    if max_gap is not None and not float(max_gap) >= 0.0:
+        raise ValueError("neighbour_table: max_gap must be None or >= 0 (got %r)" % (max_gap,))
+    table = torch.full((len(keys), 2), -1, dtype=torch.int32)
+    takes = {}
+    for row, (action, _) in enumerate(keys):
+        takes.setdefault(action, []).append(row)
+    for rows in takes.values():
+        try:
+            ids = [int(keys[r][1]) for r in rows]
+        except (TypeError, ValueError):
+            ids = None
+        if ids is not None:
+            order = sorted(range(len(rows)), key=lambda j: ids[j])          # (stable: first seen first among equal ids)
+            rows, ids = [rows[j] for j in order], [ids[j] for j in order]
+        for j in range(len(rows) - 1):
+            if ids is not None and max_gap is not None and ids[j + 1] - ids[j] > max_gap:
+                continue
+            table[rows[j], 1] = rows[j + 1]
+            table[rows[j + 1], 0] = rows[j]
+    return table
+
+
 class PoseRefiner:
     """The correction tables of `PoseCorrection` -- rotvec and trans (F,B,3), zero at the start -- kept, applied, differentiated
     and stepped on the device (mgr_pose_apply / mgr_pose_backward / mgr_pose_adam).
@@ -69,12 +100,23 @@ class PoseRefiner:
     move, the bias correction uses the global count `steps`), with a rate each for rotations and translations and no clamp;
     the moments are allocated at the first step.
 
+    Priors (all weights 0: none, today's two entries exactly).  For x = rotvec and x = trans, each with its own weights,
+        E = w_mag sum_f |x_f|^2 + w_smooth sum_edges |x_f - x_next(f)|^2
+    over the edges of `neighbour_table(frame_keys, max_gap)`: a pull towards zero and towards the neighbouring frames of the
+    take.  With any weight non-zero `step` calls mgr_pose_backward_prior in place of mgr_pose_backward: the listed rows'
+    gradient gains the true dE/dx_f, taken at the tables before the step (a listed neighbour's update is not seen; a neighbour
+    that is not listed is read and stays), and `last_prior` is the part of E that touches the listed rows, each term once --
+    a device double scalar, not read back.  The weights are configuration, not state: `state_dict()` does not carry them.
+
         frames = refiner.frames_of(store, items)             # one row per view, -1: no correction
         refiner.apply(compute, view_ids, frames)             # corrected transforms into the compute object's tables
         out = compute(view_ids, scale)                       # HipViewCompute(pose_grad=True)
-        refiner.step(out["d_transforms"], view_ids, frames)"""
+        refiner.step(out["d_transforms"], view_ids, frames)
 
-    def __init__(self, frame_keys, n_bones, rest, lr_rot, lr_trans, betas=(0.9, 0.999), eps=1e-8, device=None):
+    `hold` is `apply` for a step that no `step` follows."""
+
+    def __init__(self, frame_keys, n_bones, rest, lr_rot, lr_trans, betas=(0.9, 0.999), eps=1e-8, device=None, w_mag_rot=0.0,
+                 w_smooth_rot=0.0, w_mag_trans=0.0, w_smooth_trans=0.0, max_gap=None):
         self.frame_keys = list(dict.fromkeys((k[0], k[1]) for k in frame_keys))
         self.row = {k: j for j, k in enumerate(self.frame_keys)}
         F, B = len(self.frame_keys), int(n_bones)
@@ -95,6 +137,15 @@ class PoseRefiner:
         self.m_r = self.v_r = self.m_t = self.v_t = None
         self.steps = 0
         self.last_grad = None           # (frames listed, d_rotvec (U,B,3), d_trans (U,B,3)) of the last step
+        self.weights = tuple(float(w) for w in (w_mag_rot, w_smooth_rot, w_mag_trans, w_smooth_trans))
+        for name, w in zip(("w_mag_rot", "w_smooth_rot", "w_mag_trans", "w_smooth_trans"), self.weights):
+            if not (w >= 0.0 and w != float("inf")):
+                raise ValueError("PoseRefiner: %s must be finite and >= 0 (got %r)" % (name, w))
+        self.has_prior = any(w != 0.0 for w in self.weights)
+        self.max_gap = max_gap
+        self.neighbours = neighbour_table(self.frame_keys, max_gap).to(self.device)      # (F,2) int32: prev, next; -1 none
+        self.last_prior = None          # with a prior: its value on the rows of the last step (device double scalar)
+        self._prior_ws = None           # the per-thread shares of mgr_pose_backward_prior (kept across steps)
         self._posed = None              # the posed table of the compute object last applied to
         self._lists = {}                # (view ids, frames) -> their device lists
 
@@ -158,9 +209,15 @@ class PoseRefiner:
         self._posed = posed
         compute.transforms_changed(written=view_ids if gathered is not None else None)
 
+    def hold(self, compute, view_ids, frames):
+        """`apply` on a step at which the corrections do not move: the step's frames are rendered at their corrected
+        transforms and no `step` follows."""
+        self.apply(compute, view_ids, frames)
+
     def step(self, d_transforms, view_ids, frames):
         """One Adam step of the frames the views show, from the step's `out["d_transforms"]` (len(view_ids),B+1,4,4) at the
-        transforms the last `apply` wrote.  Views with frame -1 contribute nothing; with no frame at all nothing happens."""
+        transforms the last `apply` wrote.  Views with frame -1 contribute nothing; with no frame at all nothing happens.
+        With a prior its gradient is added at the tables before the step and `last_prior` is its value on the listed rows."""
         if self._posed is None:
             raise ValueError("PoseRefiner.step before apply")
         B, V = self.n_bones, len(view_ids)
@@ -175,8 +232,19 @@ class PoseRefiner:
         g_r = torch.empty((U, B, 3), dtype=torch.float32, device=self.device)
         g_t = torch.empty((U, B, 3), dtype=torch.float32, device=self.device)
         L = lib()
-        check(L.mgr_pose_backward(V, B, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self._posed), ptr(self.rest),
-                                  ptr(self.rotvec), ptr(self.trans), ptr(d_transforms), ptr(g_r), ptr(g_t), stream()), "mgr_pose_backward")
+        if self.has_prior:
+            nbytes = int(L.mgr_pose_prior_workspace_bytes(U, B))
+            if self._prior_ws is None or self._prior_ws.numel() < nbytes:
+                self._prior_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            value = torch.empty((), dtype=torch.float64, device=self.device)
+            check(L.mgr_pose_backward_prior(V, B, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self._posed), ptr(self.rest),
+                                            ptr(self.rotvec), ptr(self.trans), ptr(d_transforms), ptr(g_r), ptr(g_t), ptr(self.neighbours),
+                                            *self.weights, ptr(value), ptr(self._prior_ws), self._prior_ws.numel(), stream()),
+                  "mgr_pose_backward_prior")
+            self.last_prior = value
+        else:
+            check(L.mgr_pose_backward(V, B, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self._posed), ptr(self.rest),
+                                      ptr(self.rotvec), ptr(self.trans), ptr(d_transforms), ptr(g_r), ptr(g_t), stream()), "mgr_pose_backward")
         self.steps += 1
         check(L.mgr_pose_adam(U, B, ptr(listed_t), ptr(g_r), ptr(g_t), ptr(self.rotvec), ptr(self.trans), ptr(self.m_r), ptr(self.v_r),
                               ptr(self.m_t), ptr(self.v_t), self.lr_rot, self.lr_trans, self.betas[0], self.betas[1], self.eps, self.steps,

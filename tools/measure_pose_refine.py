@@ -7,8 +7,10 @@
                  backward per view, torch.optim.Adam
     device chain the same step driven by pose.PoseRefiner (mgr_pose_apply, the step, mgr_pose_backward, mgr_pose_adam)
     entries      the three entries alone
+    --prior      also: the device chain with the priors on (PoseRefiner(w_mag_*, w_smooth_*): mgr_pose_backward_prior in place of
+                 mgr_pose_backward, the eight frames one take) beside the chain without, and the new entry alone
 
-    python tools/measure_pose_refine.py [--out FILE.json] [--quick]
+    python tools/measure_pose_refine.py [--out FILE.json] [--quick] [--prior]
 
 One process, HIP events around a batch of steps (a step that waits for the host shows as a longer step), every shape warmed,
 median of 5 samples with min and max; host and device chain alternate so that a drift of the clocks shows.  Needs a GPU; there
@@ -43,6 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="small sizes (a rehearsal of the script, not a measurement)")
+    ap.add_argument("--prior", action="store_true", help="also time the chain and the backward entry with the priors on")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "measure_pose_refine.py needs a GPU"
     from manus_amd import rasterizer
@@ -90,9 +93,21 @@ def main():
         out = on(ids, 1.0 / V)
         ref.step(out["d_transforms"], ids, ids)
 
-    for name, fn in (("plain_pose_grad_off", lambda: off(ids, 1.0 / V)), ("plain_pose_grad_on", lambda: on(ids, 1.0 / V)),
-                     ("host_chain", host_step), ("device_chain", device_step), ("host_chain_again", host_step),
-                     ("device_chain_again", device_step), ("plain_pose_grad_off_again", lambda: off(ids, 1.0 / V))):
+    weights = dict(w_mag_rot=1e-3, w_smooth_rot=1e-2, w_mag_trans=1e-3, w_smooth_trans=1e-2)
+    ref_p = PoseRefiner([("capture", v) for v in ids], nb, rest, 1e-4, 1e-4, device=dev, **weights)
+
+    def device_step_prior():
+        ref_p.apply(on, ids, ids)
+        out = on(ids, 1.0 / V)
+        ref_p.step(out["d_transforms"], ids, ids)
+
+    runs = [("plain_pose_grad_off", lambda: off(ids, 1.0 / V)), ("plain_pose_grad_on", lambda: on(ids, 1.0 / V)),
+            ("host_chain", host_step), ("device_chain", device_step), ("host_chain_again", host_step),
+            ("device_chain_again", device_step), ("plain_pose_grad_off_again", lambda: off(ids, 1.0 / V))]
+    if a.prior:      # off and on alternate, so that a drift of the clocks shows
+        runs += [("device_chain_prior", device_step_prior), ("device_chain_off", device_step),
+                 ("device_chain_prior_again", device_step_prior), ("device_chain_off_again", device_step)]
+    for name, fn in runs:
         res[name] = timed(fn, reps)
         print("%-26s %s" % (name, json.dumps(res[name])), flush=True)
 
@@ -114,6 +129,15 @@ def main():
                                                        ptr(ref.v_r), ptr(ref.m_t), ptr(ref.v_t), 1e-4, 1e-4, 0.9, 0.999, 1e-8, ref.steps + 1, stream()),
                                        "mgr_pose_adam"),
     }
+    if a.prior:
+        value = torch.zeros((), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(int(L.mgr_pose_prior_workspace_bytes(U, nb)), 8), dtype=torch.uint8, device=dev)
+        w = [weights[k] for k in ("w_mag_rot", "w_smooth_rot", "w_mag_trans", "w_smooth_trans")]
+        entries["mgr_pose_backward_prior"] = lambda: check(
+            L.mgr_pose_backward_prior(V, nb, F, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(posed), ptr(ref.rest), ptr(ref.rotvec), ptr(ref.trans),
+                                      ptr(d_T), ptr(g_r), ptr(g_t), ptr(ref_p.neighbours), *w, ptr(value), ptr(ws), ws.numel(), stream()),
+            "mgr_pose_backward_prior")
+        entries["mgr_pose_backward_again"] = entries["mgr_pose_backward"]
     for name, fn in entries.items():
         res[name] = timed(fn, 200)
         print("%-26s %s" % (name, json.dumps(res[name])), flush=True)
