@@ -129,25 +129,52 @@ def test_persistent_gradient_buffers_equal_fresh_ones(kind, views):
     empty tiles are written once (mgr_views_forward, debug bit 1024).  Over steps between which the
     model moves (Gaussians come into view and leave it) every step's gradients, statistics and loss are bit for bit those
     of a compute object that gets fresh, fully zeroed buffers; the same after the rows were disturbed by another
-    compute object's backward on the same workspace, and with the run lists switched off in between."""
+    compute object's backward on the same workspace, and with the run lists switched off in between.
+
+    Two passes: the object with fresh buffers takes its seven steps first, the one with kept buffers afterwards on the same
+    seeded motion.  (Step by step in turn, both objects get the same pooled workspace: the fresh object's backward leaves the
+    workspace's row state its own, and the kept object's next backward, finding another owner, fills in full -- the selective
+    fill is never reached.)  Positive control: the last Gaussian is made inert (opacity sigmoid(-40): under the blend's 1/255
+    threshold in every view, and left out of the flips), so no step gives its row a gradient; after every kept step a sentinel
+    is planted in that row of the `_xyz` gradient through `.data` (no version-counter change).  A sentinel that survives the
+    next step proves that step filled selectively; then the rows that had a gradient the step before and have none now -- there
+    must be some -- were zeroed by the row-selective branch alone.  It must be gone after the other object's backward."""
     from manus_amd._lib import lib
     from manus_amd.engine import HipViewCompute
+    from util import keep
     sc, ct = _scene(kind, n=5000, views=views)
+    inert = sc["params"]["_xyz"].shape[0] - 1
+    sc = dict(sc, params={k: v.clone() for k, v in sc["params"].items()})
+    sc["params"]["_opacity"][inert] = -40.0
     tg = torch.rand((views, 3, 64, 96), device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
     ids = list(range(views))
     a = HipViewCompute(sc, tg, ct, fused=True, depth_cut=False, persistent_grads=False)
     b = HipViewCompute(sc, tg, ct, fused=True, depth_cut=False, persistent_grads=True)
     c = HipViewCompute(sc, tg, ct, fused=True, depth_cut=False, persistent_grads=True)   # shares the pooled workspace with b
-    gen = torch.Generator(device=DEV).manual_seed(7)
-    n_rows = []
-    for it in range(7):
-        with torch.no_grad():   # move the model: positions jitter, a tenth of the Gaussians turn transparent / opaque
+
+    def move(gen, comps):   # move the model: positions jitter, a tenth of the Gaussians turn transparent / opaque
+        with torch.no_grad():
             noise = 0.004 * torch.randn(a.params["_xyz"].shape, device=DEV, generator=gen)
             flip = torch.rand(a.params["_opacity"].shape, device=DEV, generator=gen) < 0.1
-            for comp in (a, b, c):
+            flip[inert] = False
+            for comp in comps:
                 comp.params["_xyz"].add_(noise)
                 comp.params["_opacity"][flip] = -comp.params["_opacity"][flip]
                 comp.mark_params_changed()
+
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    want, n_rows = [], []
+    for it in range(7):
+        move(gen, (a,))
+        oa = keep(a(ids, 1.0 / views))
+        want.append((oa, a.last_image.clone()))
+        assert float(oa["grads"]["_xyz"][inert].abs().sum()) == 0.0      # the inert row never gets a gradient
+        n_rows.append(int((oa["grads"]["_xyz"].abs().sum(1) != 0).sum()))
+    assert len(set(n_rows)) > 1          # the set of rows with a gradient did change from step to step
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    sentinel, engaged, left = 777.0, [], []
+    for it in range(7):
+        move(gen, (b, c))
         if it == 3:
             c(ids, 1.0 / views)                                  # another object's backward on the same workspace
         if it == 5:
@@ -156,13 +183,25 @@ def test_persistent_gradient_buffers_equal_fresh_ones(kind, views):
                 b(ids, 1.0 / views)
             finally:
                 lib().mgr_views_backward_run_lists(prev)
-        oa, ob = a(ids, 1.0 / views), b(ids, 1.0 / views)
+        (oa, img_a), ob = want[it], b(ids, 1.0 / views)
+        row = ob["grads"]["_xyz"].data[inert]
+        engaged.append(it > 0 and bool((row == sentinel).all()))
+        if engaged[-1]:                                          # untouched by a selective fill: what it holds is the test's own
+            row.zero_()
         for k in oa["grads"]:
             assert torch.equal(oa["grads"][k], ob["grads"][k]), (it, k)
         assert torch.equal(oa["grad2d"], ob["grad2d"]) and torch.equal(oa["vis"], ob["vis"]) and torch.equal(oa["radii"], ob["radii"])
-        assert torch.equal(a.last_image, b.last_image), it     # (the image is kept too: tiles that stay empty are not written again)
-        n_rows.append(int((oa["grads"]["_xyz"].abs().sum(1) != 0).sum()))
-    assert len(set(n_rows)) > 1          # the set of rows with a gradient did change from step to step
+        assert torch.equal(img_a, b.last_image), it            # (the image is kept too: tiles that stay empty are not written again)
+        if it > 0:                                               # rows that had a gradient the step before and have none now
+            had = want[it - 1][0]["grads"]["_xyz"].abs().sum(1) != 0
+            left.append(int((had & (oa["grads"]["_xyz"].abs().sum(1) == 0)).sum()))
+        row.fill_(sentinel)
+        assert not b._kept.touched()
+    print("kept buffers %s %d: selective fill engaged %s, rows that left %s" % (kind, views, engaged, left))
+    if views >= 3:     # (one and two views go through the plain gather, which has no selective fill: it fills in full every step)
+        assert engaged[1] and engaged[2] and engaged[4] and engaged[6], engaged      # the selective fill is in use ...
+        assert sum(left[it - 1] for it in (1, 2, 4, 6)) > 0, left                    # ... and rows did leave on those steps
+    assert not engaged[3], engaged                                                   # ... but not behind another object's backward
 
 
 @pytest.mark.parametrize("kind,views", [("hand", 8), ("composite", 3)])
