@@ -737,6 +737,52 @@ int mgr_pose_backward_prior(int V, int B, int F, int U, const int32_t* frames_li
                             const int32_t* neighbours, double w_mag_rot, double w_smooth_rot, double w_mag_trans,
                             double w_smooth_trans, double* prior_value, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Kinematic pose chain on the device (csrc/fk.hip; manus_amd/pose.py: KinematicPoseRefiner): joint angles through forward
+ * kinematics instead of a free correction per bone.  The reference's config/model/pose_optimizer.yaml names this
+ * parametrisation (num_pose_parameters: 23, optimize_global_R / optimize_global_T) and src/utils/transforms.py carries its
+ * host machinery (euler_angles_to_armature_space, apply_constraints_to_poses, apply_limits_to_poses); the optimizer itself was
+ * never released.  J bones, parents[i] (int32) in {-1} u [0, i) -- several roots are allowed; an entry outside that set is
+ * READ AS -1 by the kernels, so no list can make them index outside their tables (the Python class refuses such a list).
+ * theta (F, J+2, 3) per frame row: row 0 the global Euler angles g, rows 1..J the bones' Euler angles e_i, row J+1 the global
+ * translation t.  E(e) = Rz(e2) Ry(e1) Rx(e0) (transforms.euler_angles_to_matrix(e, "XYZ", intrinsic=True)), H(R) its
+ * homogeneous 4x4.  Constants, built once by the caller in fp64 and stored in fp32: local (J,4,4) = inv(rest_parent(i)) rest_i,
+ * rest_i for a root; base (F,4,4), a fixed left transform per frame from armature to world.
+ *     A_f = base_f [[E(g), t], [0,0,0,1]]
+ *     M_i = (A_f for a root, M_parent(i) otherwise) local_i H(E(e_i))
+ *     T[v,i] = M_i inv(rest_i)                                             f = the frame view v shows
+ * The inverse and the last product are those of mgr_bone_transforms (bone_math.h).  fp32, row-major 4x4, one workgroup of one
+ * wave per view / per listed frame; the tree is walked sequentially in index order (four threads, one matrix row each), every
+ * sum in a fixed order, no atomics, no workspace: two runs give equal bits.  All pointers are DEVICE pointers; posed
+ * (V_all,J,4,4), transforms (V_all,J+1,4,4), view_rows, frame_of_view and frames_listed as for the pose chain above.
+ * Every entry refuses with MGR_EINVAL, before any launch and with nothing written: J outside 1 .. MGR_MAX_BONES, V, U or F
+ * below 1, a NULL pointer other than gathered / posed_out, and (mgr_fk_adam) step < 1 or a non-finite rate.
+ *
+ * mgr_fk_apply: T of the positions k < V into transforms[view_rows[k], 0..J-1], the identity into row J, and the same J+1 rows
+ *   into gathered[k] (V,J+1,4,4) when it is given -- the background row and the gathered copy exactly as mgr_pose_apply
+ *   writes them.  posed_out (V,J,4,4), when given, receives the M_i by position.  A position whose frame lies outside [0,F)
+ *   (-1: a validation view) gets the bits of mgr_bone_transforms on its row of posed (and that row in posed_out); rows of
+ *   views not listed are not touched.
+ * mgr_fk_backward: d_transforms (V,J+1,4,4) by position.  Per listed frame f: G_i = the sum, in ascending position, over the
+ *   positions showing f of dT[k,i] inv(rest_i)^T; bones in descending index pass G_i (local_i H(E(e_i)))^T up to their parent
+ *   (a root: into dA); dL/dE(e_i) is the 3x3 block of (M_parent local_i)^T G_i (A_f in place of M_parent for a root), dL/de_i
+ *   its contraction with the three analytic partials of Rz Ry Rx (no division: finite at e_1 = pi/2); dL/dg and dL/dt come
+ *   from base_f^T dA in the same way.  Row u of d_theta (U,J+2,3) is that gradient of frames_listed[u], every element taken
+ *   times mask (J+2,3) of 0 / 1 -- an element with mask 0 is exactly 0, whatever the sums hold.  A listed frame that no position
+ *   shows (or outside [0,F)) gets zeros; rows behind U are not touched.
+ * mgr_fk_adam: mgr_pose_adam's row Adam (the same device function) on the rows frames_listed[u] of theta and its moments m, v
+ *   (F,J+2,3) from d_theta (U,J+2,3): rows 0..J at lr_rot, row J+1 at lr_trans; the stepped value is then clamped to
+ *   [lo, hi] (J+2,3), +-inf: no limit.  Elements with mask 0 and frames not listed (negative entries are skipped) keep their
+ *   bits, moments included. */
+int mgr_fk_apply(int V, int J, int F, const int32_t* view_rows, const int32_t* frame_of_view, const float* posed, const float* rest,
+                 const float* local, const int32_t* parents, const float* base, const float* theta, float* transforms,
+                 float* gathered, float* posed_out, void* stream);
+int mgr_fk_backward(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                    const int32_t* frame_of_view, const float* rest, const float* local, const int32_t* parents, const float* base,
+                    const float* theta, const float* mask, const float* d_transforms, float* d_theta, void* stream);
+int mgr_fk_adam(int U, int J, const int32_t* frames_listed, const float* d_theta, float* theta, float* m, float* v,
+                const float* mask, const float* lo, const float* hi, double lr_rot, double lr_trans, double beta1, double beta2,
+                double eps, int step, void* stream);
+
 /* uv =(K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
 int mgr_project_points(int N, const float* xyz, const float* K9, const float* E12, float* uv,
                        void* stream);

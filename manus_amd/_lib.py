@@ -127,6 +127,9 @@ SIGNATURES = {
     "mgr_pose_adam": (c_int, [c_int, c_int] + [c_vp] * 9 + [ctypes.c_double] * 5 + [c_int, c_vp]),
     "mgr_pose_prior_workspace_bytes": (c_sz, [c_int, c_int]),
     "mgr_pose_backward_prior": (c_int, [c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_vp] + [ctypes.c_double] * 4 + [c_vp, c_vp, c_sz, c_vp]),
+    "mgr_fk_apply": (c_int, [c_int, c_int, c_int] + [c_vp] * 11 + [c_vp]),
+    "mgr_fk_backward": (c_int, [c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_vp]),
+    "mgr_fk_adam": (c_int, [c_int, c_int] + [c_vp] * 8 + [ctypes.c_double] * 5 + [c_int, c_vp]),
     "mgr_project_points": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_dilate_mask": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "mgr_points_outside_mask": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),

@@ -1,0 +1,368 @@
+// Kinematic pose chain on the device (manus_amd/pose.py: KinematicPoseRefiner): joint angles through forward kinematics to
+// the bone transforms of a step's views, the chain rule from dL/d(bone transforms) back to the angles, and their row Adam
+// with joint limits.
+//
+//   theta (F, J+2, 3): row 0 the global Euler angles g, rows 1..J the bones' Euler angles e_i, row J+1 the global translation t
+//   E(e) = Rz(e2) Ry(e1) Rx(e0)  (transforms.euler_angles_to_matrix(e, "XYZ", intrinsic=True)),  H(R) its homogeneous 4x4
+//   A_f  = base_f [[E(g), t], [0,0,0,1]]
+//   M_i  = (A_f for a root, M_parent(i) otherwise) local_i H(E(e_i)),     T[v,i] = M_i inv(rest_i)
+//
+// fp32, ONE workgroup of one wave per view (apply) or per listed frame (backward): these launches are bound by latency.  The
+// tree is walked sequentially, parents before children, by FOUR threads: row r of M_parent L_i needs only row r of M_parent
+// (and row r of G_i L_i^T only row r of G_i), so thread r owns row r of every matrix of the walk and reads back nothing but
+// what it wrote itself -- no barrier inside the walk, no atomics, one fixed order of sums.  Everything that is per bone and
+// independent (L_i = local_i H(E(e_i)), the view sums, inv(rest), the last product, the angle partials) runs one thread per
+// bone around the walk, behind workgroup barriers that every thread reaches.  The inverse and the last product are those of
+// k_bone_transforms (bone_math.h), fed from LDS behind a barrier and stored straight to global memory as k_pose_apply does:
+// a view without a frame gets the bits of mgr_bone_transforms on its posed row.
+//
+// parents[i] outside {-1} u [0, i) is read as -1 (a root): the kernels never index outside their tables whatever the list
+// holds; pose.KinematicPoseRefiner refuses such a list on the host.
+#include <cmath>
+
+#include "bone_math.h"
+#include "mgr_common.h"
+#include "pose_adam.h"
+
+#define FK_BLOCK 64           // one wave: J + 1 <= MGR_MAX_BONES + 1 threads are live
+#define FK_ADAM_BLOCK 256
+
+// sines and cosines of the three angles, and R (3x3 row-major) = Rz(e[2]) Ry(e[1]) Rx(e[0]) from them
+struct FkTrig {
+    float sx, cx, sy, cy, sz, cz;
+};
+
+__device__ __forceinline__ FkTrig fk_trig(const float* __restrict__ e) {
+    return FkTrig{sinf(e[0]), cosf(e[0]), sinf(e[1]), cosf(e[1]), sinf(e[2]), cosf(e[2])};
+}
+
+__device__ __forceinline__ void fk_rotation(const FkTrig& t, float (&R)[3][3]) {
+    R[0][0] = t.cz * t.cy;
+    R[0][1] = t.cz * t.sy * t.sx - t.sz * t.cx;
+    R[0][2] = t.cz * t.sy * t.cx + t.sz * t.sx;
+    R[1][0] = t.sz * t.cy;
+    R[1][1] = t.sz * t.sy * t.sx + t.cz * t.cx;
+    R[1][2] = t.sz * t.sy * t.cx - t.cz * t.sx;
+    R[2][0] = -t.sy;
+    R[2][1] = t.cy * t.sx;
+    R[2][2] = t.cy * t.cx;
+}
+
+__device__ __forceinline__ void fk_euler(const float* __restrict__ e, float (&R)[3][3]) {
+    fk_rotation(fk_trig(e), R);
+}
+
+// g[k] = <Q, dR/de_k> for R = Rz Ry Rx at e, Q = dL/dR: the three analytic partials.  dR/de0 = R Kx (columns: 0, R[:,2], -R[:,1]),
+// dR/de2 = Kz R (rows: -R[1], R[0], 0), dR/de1 written out.  Finite at e1 = pi/2 (no division anywhere)
+__device__ __forceinline__ void fk_euler_vjp(const float* __restrict__ e, const float (&Q)[3][3], float (&g)[3]) {
+    const FkTrig t = fk_trig(e);
+    float R[3][3];
+    fk_rotation(t, R);
+    g[0] = (Q[0][1] * R[0][2] + Q[1][1] * R[1][2] + Q[2][1] * R[2][2]) - (Q[0][2] * R[0][1] + Q[1][2] * R[1][1] + Q[2][2] * R[2][1]);
+    g[1] = Q[0][0] * (-t.cz * t.sy) + Q[0][1] * (t.cz * t.cy * t.sx) + Q[0][2] * (t.cz * t.cy * t.cx)
+         + Q[1][0] * (-t.sz * t.sy) + Q[1][1] * (t.sz * t.cy * t.sx) + Q[1][2] * (t.sz * t.cy * t.cx)
+         + Q[2][0] * (-t.cy) + Q[2][1] * (-t.sy * t.sx) + Q[2][2] * (-t.sy * t.cx);
+    g[2] = (Q[1][0] * R[0][0] + Q[1][1] * R[0][1] + Q[1][2] * R[0][2]) - (Q[0][0] * R[1][0] + Q[0][1] * R[1][1] + Q[0][2] * R[1][2]);
+}
+
+// o (4x4 row-major) = l @ [[R, t], [0,0,0,1]]
+__device__ __forceinline__ void fk_mul_rt(const float* __restrict__ l, const float (&R)[3][3], float tx, float ty, float tz,
+                                          float* __restrict__ o) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[r * 4 + c] = l[r * 4 + 0] * R[0][c] + l[r * 4 + 1] * R[1][c] + l[r * 4 + 2] * R[2][c];
+        o[r * 4 + 3] = l[r * 4 + 0] * tx + l[r * 4 + 1] * ty + l[r * 4 + 2] * tz + l[r * 4 + 3];
+    }
+}
+
+__device__ __forceinline__ int fk_parent(const int32_t* __restrict__ parents, int i) {
+    const int p = parents[i];
+    return (p >= 0 && p < i) ? p : -1;
+}
+
+// Row r of M_i = M_parent(i) L_i for i = 0 .. J-1 in ascending order (the parent's index is below the child's), A for a root.
+// Called by the threads r < 4; s_L and s_A are complete behind a barrier, s_M is written here and read back by row only
+__device__ __forceinline__ void fk_walk_row(int J, int r, const int32_t* __restrict__ parents, const float* __restrict__ s_A,
+                                            const float* __restrict__ s_L, float* __restrict__ s_M) {
+    for (int i = 0; i < J; ++i) {
+        const int p = fk_parent(parents, i);
+        const float* src = (p < 0 ? s_A : s_M + p * 16) + r * 4;
+        const float a0 = src[0], a1 = src[1], a2 = src[2], a3 = src[3];
+        const float* L = s_L + i * 16;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s_M[i * 16 + r * 4 + c] = a0 * L[c] + a1 * L[4 + c] + a2 * L[8 + c] + a3 * L[12 + c];
+    }
+}
+
+// workgroup k: position k of the step.  thread i < J: bone i; thread J: the global transform, then the background row
+__global__ __launch_bounds__(FK_BLOCK) void k_fk_apply(int V, int J, int F, const int32_t* __restrict__ view_rows,
+                                                       const int32_t* __restrict__ frame_of_view, const float* __restrict__ posed,
+                                                       const float* __restrict__ rest, const float* __restrict__ local,
+                                                       const int32_t* __restrict__ parents, const float* __restrict__ base,
+                                                       const float* __restrict__ theta, float* __restrict__ transforms,
+                                                       float* __restrict__ gathered, float* __restrict__ posed_out) {
+    __shared__ float s_L[MGR_MAX_BONES * 16];
+    __shared__ float s_M[MGR_MAX_BONES * 16];
+    __shared__ float s_A[16];
+    const int k = blockIdx.x, b = threadIdx.x;
+    const int v = view_rows[k];
+    if (v < 0) return;                                        // (the whole workgroup: nothing to write)
+    const int f = frame_of_view[k];
+    const bool fk = f >= 0 && f < F;                          // uniform over the workgroup
+    if (fk) {
+        const float* th = theta + (size_t)f * (J + 2) * 3;
+        float R[3][3];
+        if (b < J) {
+            fk_euler(th + (1 + b) * 3, R);
+            fk_mul_rt(local + (size_t)b * 16, R, 0.f, 0.f, 0.f, s_L + b * 16);
+        } else if (b == J) {
+            const float* t = th + (J + 1) * 3;
+            fk_euler(th, R);
+            fk_mul_rt(base + (size_t)f * 16, R, t[0], t[1], t[2], s_A);
+        }
+        __syncthreads();
+        if (b < 4) fk_walk_row(J, b, parents, s_A, s_L, s_M);
+    } else if (b < J) {
+        const float* p = posed + ((size_t)v * J + b) * 16;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s_M[b * 16 + q] = p[q];
+    }
+    __syncthreads();
+    if (b > J) return;
+    // the last product in the shape of k_bone_transforms / k_pose_apply: the two branches and NOTHING else between the matrix in
+    // memory and the stores to the table.  The compiler forms these sums by what surrounds them (bone_math.h); with more code
+    // in a branch it fuses other products and the last bits of a view without a frame leave those of mgr_bone_transforms
+    float* o = transforms + ((size_t)v * (J + 1) + b) * 16;
+    const float* m = s_M + b * 16;
+    if (b >= J) {
+        bone_identity(o);
+    } else {
+        float a[4][8];
+        bone_invert(rest + (size_t)b * 16, a);
+        bone_mul_inverse(m, a, o);
+    }
+    if (gathered) {
+        const float4* t4 = (const float4*)o;
+        float4* g4 = (float4*)(gathered + ((size_t)k * (J + 1) + b) * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g4[q] = t4[q];
+    }
+    if (posed_out && b < J) {
+        const float4* m4 = (const float4*)m;
+        float4* p4 = (float4*)(posed_out + ((size_t)k * J + b) * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) p4[q] = m4[q];
+    }
+}
+
+// workgroup u: listed frame u.  thread i < J: bone i; thread J: the global transform
+__global__ __launch_bounds__(FK_BLOCK) void k_fk_backward(int V, int J, int F, int U, const int32_t* __restrict__ frames_listed,
+                                                          const int32_t* __restrict__ view_rows,
+                                                          const int32_t* __restrict__ frame_of_view, const float* __restrict__ rest,
+                                                          const float* __restrict__ local, const int32_t* __restrict__ parents,
+                                                          const float* __restrict__ base, const float* __restrict__ theta,
+                                                          const float* __restrict__ mask, const float* __restrict__ d_transforms,
+                                                          float* __restrict__ d_theta) {
+    __shared__ float s_L[MGR_MAX_BONES * 16];
+    __shared__ float s_M[MGR_MAX_BONES * 16];
+    __shared__ float s_G[MGR_MAX_BONES * 16];
+    __shared__ float s_A[16];
+    __shared__ float s_dA[16];
+    const int u = blockIdx.x, b = threadIdx.x;
+    const int f = frames_listed[u];
+    float* out = d_theta + (size_t)u * (J + 2) * 3;
+    int shown = 0;                                            // every thread counts the same views: uniform
+    if (f >= 0 && f < F)
+        for (int k = 0; k < V; ++k) shown += (frame_of_view[k] == f && view_rows[k] >= 0) ? 1 : 0;
+    if (shown == 0) {                                         // a frame outside the table or without a view: zeros
+        for (int q = b; q < (J + 2) * 3; q += FK_BLOCK) out[q] = 0.f;
+        return;
+    }
+    const float* th = theta + (size_t)f * (J + 2) * 3;
+    if (b < J) {
+        float a[4][8];
+        bone_invert(rest + (size_t)b * 16, a);
+        float G[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) G[i][j] = 0.f;
+        for (int k = 0; k < V; ++k) {
+            if (frame_of_view[k] != f || view_rows[k] < 0) continue;
+            const float* dT = d_transforms + ((size_t)k * (J + 1) + b) * 16;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc += dT[i * 4 + q] * a[j][4 + q];      // dT inv(rest)^T
+                    G[i][j] += acc;
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s_G[b * 16 + i * 4 + j] = G[i][j];
+        float R[3][3];
+        fk_euler(th + (1 + b) * 3, R);
+        fk_mul_rt(local + (size_t)b * 16, R, 0.f, 0.f, 0.f, s_L + b * 16);
+    } else if (b == J) {
+        const float* t = th + (J + 1) * 3;
+        float R[3][3];
+        fk_euler(th, R);
+        fk_mul_rt(base + (size_t)f * 16, R, t[0], t[1], t[2], s_A);
+    }
+    __syncthreads();
+    if (b < 4) {
+        fk_walk_row(J, b, parents, s_A, s_L, s_M);
+        // row b of the gradients, children before parents: G_parent += G_i L_i^T, dA += G_root L_root^T
+        float dA[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int i = J - 1; i >= 0; --i) {
+            const float* g = s_G + i * 16 + b * 4;
+            const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
+            const float* L = s_L + i * 16;
+            const int p = fk_parent(parents, i);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float up = g0 * L[c * 4] + g1 * L[c * 4 + 1] + g2 * L[c * 4 + 2] + g3 * L[c * 4 + 3];
+                if (p < 0)
+                    dA[c] += up;
+                else
+                    s_G[p * 16 + b * 4 + c] += up;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s_dA[b * 4 + c] = dA[c];
+    }
+    __syncthreads();
+    if (b < J) {
+        // Q = the 3x3 block of (M_parent local_i)^T G_i, with A in place of M_parent for a root
+        const int p = fk_parent(parents, b);
+        const float* Mp = p < 0 ? s_A : s_M + p * 16;
+        const float* l = local + (size_t)b * 16;
+        float P[4][3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                P[r][c] = Mp[r * 4] * l[c] + Mp[r * 4 + 1] * l[4 + c] + Mp[r * 4 + 2] * l[8 + c] + Mp[r * 4 + 3] * l[12 + c];
+        const float* G = s_G + b * 16;
+        float Q[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Q[i][j] = P[0][i] * G[j] + P[1][i] * G[4 + j] + P[2][i] * G[8 + j] + P[3][i] * G[12 + j];
+        float g[3];
+        fk_euler_vjp(th + (1 + b) * 3, Q, g);
+        const float* mk = mask + (1 + b) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(1 + b) * 3 + c] = mk[c] != 0.f ? g[c] * mk[c] : 0.f;
+    } else if (b == J) {
+        // dC = base^T dA for A = base C, C = [[E(g), t], [0,0,0,1]]
+        const float* bs = base + (size_t)f * 16;
+        float dC[3][4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dC[i][j] = bs[i] * s_dA[j] + bs[4 + i] * s_dA[4 + j] + bs[8 + i] * s_dA[8 + j] + bs[12 + i] * s_dA[12 + j];
+        float Q[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Q[i][j] = dC[i][j];
+        float g[3];
+        fk_euler_vjp(th, Q, g);
+        const float* mt = mask + (J + 1) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            out[c] = mask[c] != 0.f ? g[c] * mask[c] : 0.f;
+            out[(J + 1) * 3 + c] = mt[c] != 0.f ? dC[c][3] * mt[c] : 0.f;
+        }
+    }
+}
+
+// thread (u, e): element e of the (J+2, 3) row of listed frame u.  pose_adam_one (k_pose_adam's update), rows 0..J at the
+// rotations' rate and row J+1 at the translation's, then the clamp to [lo, hi]; an element with mask 0 is not touched
+__global__ __launch_bounds__(FK_ADAM_BLOCK) void k_fk_adam(int U, int J, const int32_t* __restrict__ frames_listed,
+                                                           const float* __restrict__ d_theta, float* __restrict__ theta,
+                                                           float* __restrict__ m_, float* __restrict__ v_,
+                                                           const float* __restrict__ mask, const float* __restrict__ lo,
+                                                           const float* __restrict__ hi, float step_rot, float step_trans, float omb1,
+                                                           float omb2, float eps) {
+    const int gid = blockIdx.x * FK_ADAM_BLOCK + threadIdx.x;
+    const int row = (J + 2) * 3;
+    if (gid >= U * row) return;
+    const int u = gid / row, e = gid - u * row;
+    const int f = frames_listed[u];
+    if (f < 0 || mask[e] == 0.f) return;
+    const size_t o = (size_t)f * row + e;
+    float x = theta[o];
+    pose_adam_one(d_theta[gid], &x, m_ + o, v_ + o, e >= (J + 1) * 3 ? step_trans : step_rot, omb1, omb2, eps);
+    theta[o] = fminf(fmaxf(x, lo[e]), hi[e]);
+}
+
+// ---------------------------------------------------------------------------
+// host entries: every refusal is decided on the arguments, before any launch
+// ---------------------------------------------------------------------------
+extern "C" int mgr_fk_apply(int V, int J, int F, const int32_t* view_rows, const int32_t* frame_of_view, const float* posed,
+                            const float* rest, const float* local, const int32_t* parents, const float* base, const float* theta,
+                            float* transforms, float* gathered, float* posed_out, void* stream_) {
+    if (V < 1 || J < 1 || J > MGR_MAX_BONES || F < 1)
+        return mgr_fail(MGR_EINVAL, "mgr_fk_apply: V and F must be at least 1, J 1 .. MGR_MAX_BONES");
+    if (!view_rows || !frame_of_view || !posed || !rest || !local || !parents || !base || !theta || !transforms)
+        return mgr_fail(MGR_EINVAL, "mgr_fk_apply: null pointer");
+    if ((long long)V * (J + 1) > (1ll << 24)) return mgr_fail(MGR_EINVAL, "mgr_fk_apply: V * (J + 1) above 2^24");
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        MGR_PROF("k_fk_apply", stream);
+        hipLaunchKernelGGL(k_fk_apply, dim3(V), dim3(FK_BLOCK), 0, stream, V, J, F, view_rows, frame_of_view, posed, rest, local, parents,
+                           base, theta, transforms, gathered, posed_out);
+    }
+    MGR_LAUNCH_CHECK("k_fk_apply", stream, 0);
+    return MGR_OK;
+}
+
+extern "C" int mgr_fk_backward(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                               const int32_t* frame_of_view, const float* rest, const float* local, const int32_t* parents,
+                               const float* base, const float* theta, const float* mask, const float* d_transforms, float* d_theta,
+                               void* stream_) {
+    if (V < 1 || J < 1 || J > MGR_MAX_BONES || F < 1 || U < 1)
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward: V, F and U must be at least 1, J 1 .. MGR_MAX_BONES");
+    if (!frames_listed || !view_rows || !frame_of_view || !rest || !local || !parents || !base || !theta || !mask || !d_transforms || !d_theta)
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward: null pointer");
+    if ((long long)V * (J + 1) > (1ll << 24) || (long long)U * (J + 2) > (1ll << 24))
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward: V * (J + 1) or U * (J + 2) above 2^24");
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        MGR_PROF("k_fk_backward", stream);
+        hipLaunchKernelGGL(k_fk_backward, dim3(U), dim3(FK_BLOCK), 0, stream, V, J, F, U, frames_listed, view_rows, frame_of_view, rest,
+                           local, parents, base, theta, mask, d_transforms, d_theta);
+    }
+    MGR_LAUNCH_CHECK("k_fk_backward", stream, 0);
+    return MGR_OK;
+}
+
+extern "C" int mgr_fk_adam(int U, int J, const int32_t* frames_listed, const float* d_theta, float* theta, float* m, float* v,
+                           const float* mask, const float* lo, const float* hi, double lr_rot, double lr_trans, double beta1,
+                           double beta2, double eps, int step, void* stream_) {
+    if (U < 1 || J < 1 || J > MGR_MAX_BONES) return mgr_fail(MGR_EINVAL, "mgr_fk_adam: U must be at least 1, J 1 .. MGR_MAX_BONES");
+    if (step < 1) return mgr_fail(MGR_EINVAL, "mgr_fk_adam: step < 1");
+    if (!frames_listed || !d_theta || !theta || !m || !v || !mask || !lo || !hi) return mgr_fail(MGR_EINVAL, "mgr_fk_adam: null pointer");
+    if (!std::isfinite(lr_rot) || !std::isfinite(lr_trans)) return mgr_fail(MGR_EINVAL, "mgr_fk_adam: the rates must be finite");
+    if ((long long)U * (J + 2) * 3 > (1ll << 24)) return mgr_fail(MGR_EINVAL, "mgr_fk_adam: U * (J + 2) above 2^24 / 3");
+    hipStream_t stream = (hipStream_t)stream_;
+    // the bias corrections of the global step, in double as torch takes them (mgr_pose_adam)
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double k = sqrt(bc2) / bc1;
+    const int n = U * (J + 2) * 3;
+    {
+        MGR_PROF("k_fk_adam", stream);
+        hipLaunchKernelGGL(k_fk_adam, dim3((n + FK_ADAM_BLOCK - 1) / FK_ADAM_BLOCK), dim3(FK_ADAM_BLOCK), 0, stream, U, J, frames_listed,
+                           d_theta, theta, m, v, mask, lo, hi, (float)(lr_rot * k), (float)(lr_trans * k), (float)(1.0 - beta1),
+                           (float)(1.0 - beta2), (float)eps);
+    }
+    MGR_LAUNCH_CHECK("k_fk_adam", stream, 0);
+    return MGR_OK;
+}

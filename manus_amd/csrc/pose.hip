@@ -15,6 +15,7 @@
 
 #include "bone_math.h"
 #include "mgr_common.h"
+#include "pose_adam.h"
 
 #define POSE_BLOCK 256
 #define POSE_SMALL 1e-6f      // |r|^2 below which exp and its derivative take their series (pose._exp_so3)
@@ -272,17 +273,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void k_pose_prior_fold(const double* __
 }
 
 // thread (u, b, c): element c of the correction of bone b of listed frame u, rotation vector and translation; the arithmetic
-// of k_sg_adam (torch.optim.SparseAdam), no clamp
-__device__ __forceinline__ void pose_adam_one(float g, float* __restrict__ x, float* __restrict__ m_, float* __restrict__ v_,
-                                              float step_size, float omb1, float omb2, float eps) {
-    const float m0 = *m_, v0 = *v_;
-    const float m = m0 + (g - m0) * omb1;
-    const float v = v0 + (g * g - v0) * omb2;
-    *m_ = m;
-    *v_ = v;
-    *x = *x - step_size * (m / (sqrtf(v) + eps));
-}
-
+// of k_sg_adam (torch.optim.SparseAdam), no clamp (pose_adam_one, pose_adam.h: shared with fk.hip)
 __global__ __launch_bounds__(POSE_BLOCK) void k_pose_adam(int U, int B, const int32_t* __restrict__ frames_listed,
                                                           const float* __restrict__ d_rotvec, const float* __restrict__ d_trans,
                                                           float* __restrict__ rotvec, float* __restrict__ trans,

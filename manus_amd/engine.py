@@ -1488,7 +1488,8 @@ class Trainer:
     Drawn frames and pose refinement (one rank; both None: exactly the step above on the fixed views 0 .. n_views - 1).
     frames: a `FrameSchedule` of n_views views per step -- before the step, the rows 0 .. n_views - 1 of the compute object's
     tables are pointed at `frames.items(global_step)` (`FrameStore.load_step`; `last_items` keeps the list).  pose: a
-    `pose.PoseRefiner` -- at the global steps g >= pose_from_iter with (g - pose_from_iter) % pose_every == 0 the corrected
+    `pose.PoseRefiner` or a `pose.KinematicPoseRefiner` (joint angles through forward kinematics: bone lengths stay fixed) -- the
+    Trainer uses nothing but their common surface, `frames_of`, `apply`, `hold`, `step`, `steps` and `last_prior` -- at the global steps g >= pose_from_iter with (g - pose_from_iter) % pose_every == 0 the corrected
     transforms of the step's frames are written before the step (`PoseRefiner.apply`) and the corrections take their own Adam
     step on `out["d_transforms"]` behind the Gaussians' optimizer step (`PoseRefiner.step`); a re-run after an overflow uses
     the same items and transforms.  Without `frames`, pose_frames gives the frame row of each of the fixed views.  On a step

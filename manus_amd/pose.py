@@ -7,8 +7,14 @@ form the tests check against, and what validation and contact renders call.  `Po
 backward, row Adam; three launches per step -- four with priors on the corrections, whose value is folded by a launch of its own --,
 no autograd graph, no read-back), which `engine.Trainer(pose=...)` schedules.
 
-No reference counterpart: the reference's config/model/pose_optimizer.yaml names `src.models.pose_optimizer`, which was
-never released."""
+`KinematicPoseRefiner` has the same surface on another parametrisation: joint angles per frame through forward kinematics on
+the device (csrc/fk.hip), 23 constrained angles for the hand (`dof_mask`), optionally a global rotation and translation, joint
+limits (`joint_limits`).  Where the free-form correction can pull the skeleton apart at the joints, this one keeps bone lengths
+and joint centres by construction.
+
+The reference's config/model/pose_optimizer.yaml names `src.models.pose_optimizer`, which was never released: the free-form
+correction has no reference counterpart; the kinematic one follows that config's parametrisation and the host machinery of
+src/utils/transforms.py (euler_angles_to_armature_space, apply_constraints_to_poses, apply_limits_to_poses)."""
 import torch
 
 from ._lib import MGR_MAX_BONES, check, lib, ptr, stream
@@ -90,7 +96,56 @@ def neighbour_table(frame_keys, max_gap=None):
     return table
 
 
-class PoseRefiner:
+class _FrameRows:
+    """What `PoseRefiner` and `KinematicPoseRefiner` share on the host: the rows of their tables are the distinct
+    (action, frame_id) pairs of `frame_keys` in first-seen order, and the int32 lists of one step -- view rows, the frame of every
+    view, the frames listed -- are built once per (view ids, frames) and cached on the device.  A subclass sets `frame_keys`,
+    `row`, `n_frames`, `device` and an empty `_lists`."""
+
+    @staticmethod
+    def _keys(frame_keys):
+        return list(dict.fromkeys((k[0], k[1]) for k in frame_keys))
+
+    # -- host lists ------------------------------------------------------------------------------------------------------
+    def frames_of(self, store, items):
+        """The rows of the dataset items `items` of a `frames.FrameStore` built by `from_dataset`; -1 (no correction) for an
+        item whose frame is not among `frame_keys`."""
+        if getattr(store, "frame_keys", None) is None:
+            raise ValueError("frames_of needs the frame keys of a store built by FrameStore.from_dataset")
+        return [self.row.get(store.frame_keys[store.row[int(i)]], -1) for i in items]
+
+    def _device_lists(self, view_ids, frames):
+        """(view rows, frame of view, frames listed: int32 device tensors; the listed frames on the host) of one step.  The
+        host drew the views, so the unique frames are listed here, ascending: nothing is read back from the device."""
+        name = type(self).__name__
+        key = (tuple(int(v) for v in view_ids), tuple(int(f) for f in frames))
+        if len(key[0]) != len(key[1]) or not key[0]:
+            raise ValueError("%s: one frame row per view, at least one view (got %d views, %d frames)" % (name, len(key[0]), len(key[1])))
+        ent = self._lists.get(key)
+        if ent is None:
+            if any(f >= self.n_frames for f in key[1]):
+                raise ValueError("%s: a frame row beyond the %d frames" % (name, self.n_frames))
+            if min(key[0]) < 0:
+                raise ValueError("%s: negative view id" % name)
+            listed = sorted({f for f in key[1] if f >= 0})
+            # the three lists in one host buffer and one copy (pinned and asynchronous where the host allows it): a shuffled
+            # schedule brings a new key almost every step
+            V, U = len(key[0]), len(listed)
+            host = torch.tensor(list(key[0]) + list(key[1]) + listed, dtype=torch.int32)
+            if self.device.type == "cuda":
+                try:
+                    host = host.pin_memory()
+                except RuntimeError:
+                    pass
+            buf = host.to(self.device, non_blocking=True)
+            ent = (buf[:V], buf[V:2 * V], buf[2 * V:] if U else None, listed, host)      # (host: alive until the copy has run)
+            if len(self._lists) >= 256:
+                self._lists.clear()
+            self._lists[key] = ent
+        return ent
+
+
+class PoseRefiner(_FrameRows):
     """The correction tables of `PoseCorrection` -- rotvec and trans (F,B,3), zero at the start -- kept, applied, differentiated
     and stepped on the device (mgr_pose_apply / mgr_pose_backward / mgr_pose_adam).
 
@@ -148,43 +203,6 @@ class PoseRefiner:
         self._prior_ws = None           # the per-thread shares of mgr_pose_backward_prior (kept across steps)
         self._posed = None              # the posed table of the compute object last applied to
         self._lists = {}                # (view ids, frames) -> their device lists
-
-    # -- host lists ------------------------------------------------------------------------------------------------------
-    def frames_of(self, store, items):
-        """The rows of the dataset items `items` of a `frames.FrameStore` built by `from_dataset`; -1 (no correction) for an
-        item whose frame is not among `frame_keys`."""
-        if getattr(store, "frame_keys", None) is None:
-            raise ValueError("frames_of needs the frame keys of a store built by FrameStore.from_dataset")
-        return [self.row.get(store.frame_keys[store.row[int(i)]], -1) for i in items]
-
-    def _device_lists(self, view_ids, frames):
-        """(view rows, frame of view, frames listed: int32 device tensors; the listed frames on the host) of one step.  The
-        host drew the views, so the unique frames are listed here, ascending: nothing is read back from the device."""
-        key = (tuple(int(v) for v in view_ids), tuple(int(f) for f in frames))
-        if len(key[0]) != len(key[1]) or not key[0]:
-            raise ValueError("PoseRefiner: one frame row per view, at least one view (got %d views, %d frames)" % (len(key[0]), len(key[1])))
-        ent = self._lists.get(key)
-        if ent is None:
-            if any(f >= self.n_frames for f in key[1]):
-                raise ValueError("PoseRefiner: a frame row beyond the %d frames" % self.n_frames)
-            if min(key[0]) < 0:
-                raise ValueError("PoseRefiner: negative view id")
-            listed = sorted({f for f in key[1] if f >= 0})
-            # the three lists in one host buffer and one copy (pinned and asynchronous where the host allows it): a shuffled
-            # schedule brings a new key almost every step
-            V, U = len(key[0]), len(listed)
-            host = torch.tensor(list(key[0]) + list(key[1]) + listed, dtype=torch.int32)
-            if self.device.type == "cuda":
-                try:
-                    host = host.pin_memory()
-                except RuntimeError:
-                    pass
-            buf = host.to(self.device, non_blocking=True)
-            ent = (buf[:V], buf[V:2 * V], buf[2 * V:] if U else None, listed, host)      # (host: alive until the copy has run)
-            if len(self._lists) >= 256:
-                self._lists.clear()
-            self._lists[key] = ent
-        return ent
 
     # -- the three launches -----------------------------------------------------------------------------------------------
     def apply(self, compute, view_ids, frames):
@@ -277,3 +295,277 @@ class PoseRefiner:
         m.rotvec = torch.nn.Parameter(self.rotvec, requires_grad=False)
         m.trans = torch.nn.Parameter(self.trans, requires_grad=False)
         return m
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Kinematic refinement: joint angles through forward kinematics (csrc/fk.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+LIMITS_XZ = ("bone_5", "bone_9", "bone_13", "bone_17")
+LIMITS_X = ("bone_6", "bone_7", "bone_10", "bone_11", "bone_14", "bone_15", "bone_18", "bone_19")
+
+
+def dof_mask(bnames, optimize_global_R=False, optimize_global_T=False):
+    """(J+2,3) float32 of 0 / 1, the free entries of a `KinematicPoseRefiner`'s theta (row 0 the global angles, rows 1..J the
+    bones, row J+1 the global translation), after the reference's apply_constraints_to_poses (src/utils/transforms.py:371-419):
+    a bone in `dataset.DOF_XZ` frees its angles 0 and 2, a bone in `dataset.DOF_X` its angle 2 -- as the reference's code does,
+    despite the name --, every other bone none: 23 ones for the hand's names (`num_pose_parameters: 23`).  The two flags of
+    config/model/pose_optimizer.yaml free row 0 and row J+1."""
+    from .dataset import DOF_X, DOF_XZ
+    names = [str(n) for n in bnames]
+    mask = torch.zeros((len(names) + 2, 3), dtype=torch.float32)
+    for i, bn in enumerate(names):
+        if bn in DOF_XZ:
+            mask[1 + i, 0] = mask[1 + i, 2] = 1.0
+        elif bn in DOF_X:
+            mask[1 + i, 2] = 1.0
+    if optimize_global_R:
+        mask[0] = 1.0
+    if optimize_global_T:
+        mask[-1] = 1.0
+    return mask
+
+
+def joint_limits(bnames):
+    """(lo, hi), each (J+2,3) float32: the explicit ranges of the reference's apply_limits_to_poses (src/utils/transforms.py:325-368)
+    on the entries `dof_mask` frees -- bones 5 / 9 / 13 / 17: [-pi/6, pi/6] on angle 0 and [-pi/2, pi/9] on angle 2; its
+    `limits_x` bones (6, 7, 10, 11, 14, 15, 18, 19): [-pi/2, 0] on angle 2 -- and +-pi on every other angle; the global
+    translation (row J+1) has no limit (+-inf).  NOT reproduced: the reference's `else` branch clamps column i of the CONSTRAINED
+    vector for a bone of INDEX i, i.e. it indexes the 23 free angles by bone index and so clamps entries that belong to other
+    bones; here every bone without an explicit range simply keeps +-pi on its own angles."""
+    import math
+    names = [str(n) for n in bnames]
+    J = len(names)
+    lo = torch.full((J + 2, 3), -math.pi, dtype=torch.float32)
+    hi = torch.full((J + 2, 3), math.pi, dtype=torch.float32)
+    for i, bn in enumerate(names):
+        if bn in LIMITS_XZ:
+            lo[1 + i, 0], hi[1 + i, 0] = -math.pi / 6, math.pi / 6
+            lo[1 + i, 2], hi[1 + i, 2] = -math.pi / 2, math.pi / 9
+        elif bn in LIMITS_X:
+            lo[1 + i, 2], hi[1 + i, 2] = -math.pi / 2, 0.0
+    lo[-1], hi[-1] = -float("inf"), float("inf")
+    return lo, hi
+
+
+def theta_from_bones(bones_posed):
+    """theta0 (F,J+2,3) float32 from a list of `bones_posed` records (one per frame row; `SequenceDataset` items carry them):
+    row 0 = root_rotation, rows 1..J = eulers, row J+1 = root_translation."""
+    rows = []
+    for b in bones_posed:
+        get = (lambda k: b[k]) if isinstance(b, dict) else (lambda k: getattr(b, k))
+        e = torch.as_tensor(get("eulers"), dtype=torch.float32).reshape(-1, 3)
+        g = torch.as_tensor(get("root_rotation"), dtype=torch.float32).reshape(1, 3)
+        t = torch.as_tensor(get("root_translation"), dtype=torch.float32).reshape(1, 3)
+        rows.append(torch.cat([g, e, t], 0))
+    if not rows:
+        raise ValueError("theta_from_bones: no frames")
+    return torch.stack(rows)
+
+
+def check_parents(parents, n_bones):
+    """The kinematic tree as a list of ints, refused unless parents[i] is -1 (a root) or an index below i: the walk of
+    `transforms.get_pose_wrt_root` and of csrc/fk.hip takes a parent before its children."""
+    if isinstance(parents, dict):                        # `transforms.build_kintree`'s {str(i): parent}
+        parents = [parents[str(i)] for i in range(len(parents))]
+    parents = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+    if len(parents) != n_bones:
+        raise ValueError("parents: %d entries for %d bones" % (len(parents), n_bones))
+    for i, p in enumerate(parents):
+        if not (p == -1 or 0 <= p < i):
+            raise ValueError("parents[%d] = %d: a parent must be -1 or an index below its child's" % (i, p))
+    return parents
+
+
+class KinematicPoseRefiner(_FrameRows):
+    """Pose refinement in joint angles: theta (F,J+2,3) per frame row -- row 0 the global Euler angles, rows 1..J the bones'
+    Euler angles (XYZ intrinsic, `transforms.euler_angles_to_matrix`), row J+1 the global translation -- through forward
+    kinematics on the device (mgr_fk_apply / mgr_fk_backward / mgr_fk_adam, include/manus_hip.h), with `PoseRefiner`'s surface,
+    so `engine.Trainer(pose=...)` schedules it unchanged.  Bone lengths and joint centres are fixed by construction: only
+    the entries `mask` frees move, and they stay inside `limits`.
+
+    frame_keys as for `PoseRefiner`; rest (J,4,4); parents: J ints, -1 or an index below the child's (several roots allowed;
+    `transforms.build_kintree`'s dict is accepted); theta0 (F,J+2,3), e.g. `theta_from_bones`; mask (J+2,3) of 0 / 1 (None: all
+    free), e.g. `dof_mask(bnames)`; limits = (lo, hi), each (J+2,3) (None: none), e.g. `joint_limits(bnames)`; base (F,4,4): a
+    fixed left transform per frame from armature to world (None: identity; `fit_base` computes it from a dataset's matrices).
+    The constants local_i = inv(rest_parent(i)) rest_i are formed in fp64 on the host.  The optimizer is `PoseRefiner`'s row
+    Adam with a clamp to the limits behind it.  mask, limits, base and the rates are configuration, not state.
+
+        refiner.residual(compute, view_ids, frames)          # does FK at theta0 reproduce the dataset's posed matrices?
+        refiner.apply(compute, view_ids, frames)             # as PoseRefiner: transforms of the step's views
+        out = compute(view_ids, scale)
+        refiner.step(out["d_transforms"], view_ids, frames)"""
+
+    def __init__(self, frame_keys, rest, parents, theta0, lr_rot, lr_trans, mask=None, limits=None, base=None, betas=(0.9, 0.999),
+                 eps=1e-8, device=None):
+        self.frame_keys = self._keys(frame_keys)
+        self.row = {k: j for j, k in enumerate(self.frame_keys)}
+        rest = torch.as_tensor(rest)
+        F, J = len(self.frame_keys), int(rest.shape[0]) if rest.dim() == 3 else 0
+        if F < 1:
+            raise ValueError("KinematicPoseRefiner needs at least one frame")
+        if not 1 <= J <= MGR_MAX_BONES or tuple(rest.shape) != (J, 4, 4):
+            raise ValueError("KinematicPoseRefiner: rest must be (J,4,4) with J 1 .. %d (got %s)" % (MGR_MAX_BONES, tuple(rest.shape)))
+        self.parents_host = check_parents(parents, J)
+        self.device = torch.device(device if device is not None else rest.device)
+        self.n_frames, self.n_bones = F, J
+        self.lr_rot, self.lr_trans = float(lr_rot), float(lr_trans)
+        for name, lr in (("lr_rot", self.lr_rot), ("lr_trans", self.lr_trans)):
+            if lr != lr or lr in (float("inf"), -float("inf")):
+                raise ValueError("KinematicPoseRefiner: %s must be finite (got %r)" % (name, lr))
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+
+        def table(x, shape, what):
+            x = torch.as_tensor(x)
+            if tuple(x.shape) != shape:
+                raise ValueError("KinematicPoseRefiner: %s must be %s (got %s)" % (what, shape, tuple(x.shape)))
+            return x.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        self.rest = table(rest, (J, 4, 4), "rest")
+        self.theta = table(theta0, (F, J + 2, 3), "theta0")
+        self.mask = table(torch.ones((J + 2, 3)) if mask is None else mask, (J + 2, 3), "mask")
+        if bool(((self.mask != 0) & (self.mask != 1)).any()):
+            raise ValueError("KinematicPoseRefiner: mask must hold 0 / 1 only")
+        inf = torch.full((J + 2, 3), float("inf"))
+        lo, hi = (-inf, inf) if limits is None else limits
+        self.lo, self.hi = table(lo, (J + 2, 3), "limits[0]"), table(hi, (J + 2, 3), "limits[1]")
+        if not bool((self.lo <= self.hi).all()):
+            raise ValueError("KinematicPoseRefiner: limits need lo <= hi everywhere")
+        self.base = table(torch.eye(4).repeat(F, 1, 1) if base is None else base, (F, 4, 4), "base")
+        rest64 = rest.detach().cpu().double()
+        inv64 = torch.linalg.inv(rest64)
+        self.local64 = torch.stack([rest64[i] if p < 0 else inv64[p] @ rest64[i] for i, p in enumerate(self.parents_host)])
+        self.local = self.local64.to(device=self.device, dtype=torch.float32).contiguous()
+        self.parents = torch.tensor(self.parents_host, dtype=torch.int32, device=self.device)
+        self.m = self.v = None
+        self.steps = 0
+        self.last_grad = None           # (frames listed, d_theta (U,J+2,3)) of the last step
+        self.last_prior = None          # no prior on the angles (DESIGN.md section 9)
+        self._posed = None              # the posed table of the compute object last applied to
+        self._lists = {}
+
+    # -- host fp64 ----------------------------------------------------------------------------------------------------------
+    def fk_host(self, theta=None, base=None):
+        """M (F,J,4,4) in fp64 on the host from theta (default: the current table) and base (default: the refiner's): the
+        reference's walk, `transforms.euler_angles_to_armature_space`, with base in front.  For set-up and checks, not the step."""
+        from . import transforms as T
+        theta = (self.theta if theta is None else torch.as_tensor(theta)).detach().cpu().double()
+        base = (self.base if base is None else torch.as_tensor(base)).detach().cpu().double()
+        J = self.n_bones
+        tree = {str(i): p for i, p in enumerate(self.parents_host)}
+        M = T.euler_angles_to_armature_space(theta[:, :J + 1], tree, self.rest.detach().cpu().double(), theta[:, J + 1])
+        return base[:, None] @ M
+
+    def fit_base(self, posed_table):
+        """The per-frame transform that aligns FK at the current theta to a dataset's posed matrices `posed_table` (F,J,4,4),
+        from the first root r: base_f = posed_table[f,r] inv(M_r) with M at base = identity, in fp64 on the host.  Sets `base`
+        (fp32) and returns the fp64 table.  A dataset whose matrices live in world space while its angles are in armature
+        space differs from FK by exactly such a transform per frame."""
+        posed_table = torch.as_tensor(posed_table).detach().cpu().double()
+        F, J = self.n_frames, self.n_bones
+        if tuple(posed_table.shape) != (F, J, 4, 4):
+            raise ValueError("fit_base: posed_table must be (%d,%d,4,4) (got %s)" % (F, J, tuple(posed_table.shape)))
+        r = self.parents_host.index(-1)
+        M = self.fk_host(base=torch.eye(4, dtype=torch.float64).repeat(F, 1, 1))
+        base = posed_table[:, r] @ torch.linalg.inv(M[:, r])
+        self.base.copy_(base.to(torch.float32))
+        return base
+
+    # -- the three launches -------------------------------------------------------------------------------------------------
+    def _tables(self, compute):
+        s, J = compute.s, self.n_bones
+        posed, tfm = s.get("posed"), s.get("transforms")
+        if not torch.is_tensor(posed) or not torch.is_tensor(tfm):
+            raise ValueError("KinematicPoseRefiner: the scene holds no posed / transforms tables")
+        n_all = tfm.shape[0]
+        if tuple(posed.shape) != (n_all, J, 4, 4) or tuple(tfm.shape) != (n_all, J + 1, 4, 4) or posed.dtype != torch.float32 \
+                or tfm.dtype != torch.float32:
+            raise ValueError("KinematicPoseRefiner: posed %s / transforms %s are not the float32 tables (V,%d,4,4) / (V,%d,4,4)"
+                             % (tuple(posed.shape), tuple(tfm.shape), J, J + 1))
+        return posed, tfm, n_all
+
+    def _fk_apply(self, V, rows, fov, posed, tfm, gathered, posed_out):
+        check(lib().mgr_fk_apply(V, self.n_bones, self.n_frames, ptr(rows), ptr(fov), ptr(posed), ptr(self.rest), ptr(self.local),
+                                 ptr(self.parents), ptr(self.base), ptr(self.theta), ptr(tfm), ptr(gathered), ptr(posed_out), stream()),
+              "mgr_fk_apply")
+
+    def apply(self, compute, view_ids, frames):
+        """Bone transforms of the views `view_ids` (frame rows `frames`; -1: the dataset's own posed row, uncorrected) from
+        theta into `compute.s["transforms"]`, and into the gathered copy of that view set when the compute object holds one;
+        then `compute.transforms_changed()`.  Rows of other views stay as they are."""
+        posed, tfm, n_all = self._tables(compute)
+        rows, fov = self._device_lists(view_ids, frames)[:2]
+        if max(int(v) for v in view_ids) >= n_all:
+            raise ValueError("KinematicPoseRefiner.apply: a view id beyond the %d views of the tables" % n_all)
+        gathered = compute.gathered_transforms(view_ids)
+        self._fk_apply(len(view_ids), rows, fov, posed, tfm, gathered, None)
+        self._posed = posed
+        compute.transforms_changed(written=view_ids if gathered is not None else None)
+
+    def hold(self, compute, view_ids, frames):
+        """`apply` on a step at which the angles do not move."""
+        self.apply(compute, view_ids, frames)
+
+    def posed(self, view_ids, frames, compute=None):
+        """The posed matrices M_i (len(view_ids),J,4,4) of FK at the current theta, one row per view; a view with frame -1 gets
+        its row of the posed table of `compute` (default: of the compute object last applied to).  Nothing of the compute
+        object is written."""
+        V, J = len(view_ids), self.n_bones
+        src = self._tables(compute)[0] if compute is not None else self._posed
+        if src is None:
+            if any(int(f) < 0 for f in frames):
+                raise ValueError("KinematicPoseRefiner.posed: a view without a frame needs a compute object's posed table")
+            sel = torch.zeros((V, J, 4, 4), dtype=torch.float32, device=self.device)
+        else:
+            if max(int(v) for v in view_ids) >= src.shape[0]:
+                raise ValueError("KinematicPoseRefiner.posed: a view id beyond the %d views of the tables" % src.shape[0])
+            sel = src[[int(v) for v in view_ids]].contiguous()
+        rows, fov = self._device_lists(range(V), frames)[:2]
+        tfm = torch.empty((V, J + 1, 4, 4), dtype=torch.float32, device=self.device)
+        out = torch.empty((V, J, 4, 4), dtype=torch.float32, device=self.device)
+        self._fk_apply(V, rows, fov, sel, tfm, None, out)
+        return out
+
+    def residual(self, compute, view_ids, frames):
+        """max |M_i - compute.s["posed"]| over the views (a float; one read-back): how closely FK at the current theta -- at
+        theta0, before any step -- reproduces the dataset's posed matrices.  Large: the dataset needs a `base` (`fit_base`)."""
+        want = self._tables(compute)[0][[int(v) for v in view_ids]]
+        return float((self.posed(view_ids, frames, compute=compute) - want).abs().max())
+
+    def step(self, d_transforms, view_ids, frames):
+        """One Adam step, then the clamp to the limits, of the free angles of the frames the views show, from the step's
+        `out["d_transforms"]` (len(view_ids),J+1,4,4) at the transforms the last `apply` wrote.  Views with frame -1 contribute
+        nothing; with no frame at all nothing happens."""
+        if self._posed is None:
+            raise ValueError("KinematicPoseRefiner.step before apply")
+        J, V = self.n_bones, len(view_ids)
+        if tuple(d_transforms.shape) != (V, J + 1, 4, 4) or d_transforms.dtype != torch.float32:
+            raise ValueError("KinematicPoseRefiner.step: d_transforms %s is not float32 (%d,%d,4,4)" % (tuple(d_transforms.shape), V, J + 1))
+        rows, fov, listed_t, listed = self._device_lists(view_ids, frames)[:4]
+        if not listed:
+            return
+        U = len(listed)
+        if self.m is None:
+            self.m, self.v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+        g = torch.empty((U, J + 2, 3), dtype=torch.float32, device=self.device)
+        L = lib()
+        check(L.mgr_fk_backward(V, J, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self.rest), ptr(self.local), ptr(self.parents),
+                                ptr(self.base), ptr(self.theta), ptr(self.mask), ptr(d_transforms), ptr(g), stream()), "mgr_fk_backward")
+        self.steps += 1
+        check(L.mgr_fk_adam(U, J, ptr(listed_t), ptr(g), ptr(self.theta), ptr(self.m), ptr(self.v), ptr(self.mask), ptr(self.lo), ptr(self.hi),
+                            self.lr_rot, self.lr_trans, self.betas[0], self.betas[1], self.eps, self.steps, stream()), "mgr_fk_adam")
+        self.last_grad = (listed, g)
+
+    # -- state --------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        return dict(frame_keys=list(self.frame_keys), steps=self.steps, theta=self.theta.clone(),
+                    m=None if self.m is None else self.m.clone(), v=None if self.v is None else self.v.clone())
+
+    def load_state_dict(self, state):
+        if [tuple(k) for k in state["frame_keys"]] != self.frame_keys:
+            raise ValueError("KinematicPoseRefiner.load_state_dict: the state is of other frames")
+        if tuple(state["theta"].shape) != tuple(self.theta.shape):
+            raise ValueError("KinematicPoseRefiner.load_state_dict: theta %s, expected %s" % (tuple(state["theta"].shape), tuple(self.theta.shape)))
+        self.theta.copy_(state["theta"])
+        for k in ("m", "v"):
+            t = state.get(k)
+            setattr(self, k, None if t is None else t.detach().to(device=self.device, dtype=torch.float32).clone().contiguous())
+        self.steps = int(state["steps"])
