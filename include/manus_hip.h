@@ -783,6 +783,46 @@ int mgr_fk_adam(int U, int J, const int32_t* frames_listed, const float* d_theta
                 const float* mask, const float* lo, const float* hi, double lr_rot, double lr_trans, double beta1, double beta2,
                 double eps, int step, void* stream);
 
+/* mgr_fk_backward_terms: mgr_fk_backward with three opt-in terms on the angles of the listed frames (a kernel of its own beside
+ * k_fk_backward, which keeps its text and its bits; the two share their device functions and the order of every sum).  Rows 0..J
+ * of theta take the "rot" weights, row J+1 the "trans" weights; all five weights finite and >= 0.
+ *     E_dev    = sum_f sum_{r,c: mask != 0} w_dev(r)    (theta_f[r,c] - theta_ref_f[r,c])^2
+ *     E_smooth = sum_{edges (f, next f)} sum_{r,c: mask != 0} w_smooth(r) (theta_f[r,c] - theta_next[r,c])^2
+ *     E_kp     = w_kp sum_f sum_{k<K} c[f,k] |p_k(theta_f) - y[f,k]|^2,   p_k = (M_{bone[k]}(theta_f) [o_k; 1])[:3]
+ *   theta_ref (F,J+2,3); neighbours (F,2) int32 = (prev, next) of every frame row, -1 = none (outside [-1,F): read as -1; the caller
+ *   keeps it symmetric), differences plain, without an angle wrap; kp_bone (K) int32, kp_offset (K,3) in the bone's own frame,
+ *   kp_target (F,K,3), kp_weight (F,K), K 1 .. MGR_FK_MAX_KEYPOINTS.  A keypoint is SKIPPED -- exactly 0 in gradient and value,
+ *   whatever its target holds -- unless its weight is > 0 (zero, negative, NaN: skipped) and its bone lies in [0,J).
+ *   Gradient: row u of d_theta gains the true dE/dtheta_f of f = frames_listed[u], everything at the tables before the step
+ *   (mgr_fk_adam is the launch behind: Jacobi; unlisted neighbours are read, never written).  Per element the prior part is
+ *   2 w_dev (x - x_ref) + 2 w_smooth ((x - x_prev) + (x - x_next)) in fp32, uncontracted: the differences, their sum prev first,
+ *   the two products ((float)(2 w) each), their sum, the addition to the chain gradient, then the mask (mask 0: exactly 0).
+ *   The keypoint part goes through the tree: with r_k = p_k - y and g_k = ((float)(2 w_kp) c) r_k, rows 0..2 of G_bone[k] gain
+ *   g_k (x) [o_k; 1] behind the view sum, in ascending k, by the one thread that owns the bone -- no atomics --, and the upward
+ *   pass and the angle partials of mgr_fk_backward follow unchanged.  The terms do not depend on views: a listed frame inside
+ *   [0,F) that no position shows gets the terms' gradient on a zero chain part; a listed frame outside [0,F) gets zeros.
+ *   values (4 doubles, device) = E_dev, E_smooth, E_kp and their sum, each the part that touches the listed rows, each term
+ *   once: every edge (f, next f) of a listed f and every edge (prev f, f) of a listed f whose prev is NOT listed (found by
+ *   walking frames_listed, in any order).  The gradient's fp32 differences and residuals are squared and added in fp64; one
+ *   share per listed frame and term in the workspace (mgr_fk_terms_workspace_bytes(U, J, K) bytes), folded by one workgroup in
+ *   list order: no float atomics, equal bits run to run.
+ *   All five weights zero: mgr_fk_backward's own launch (equal bits); theta_ref, neighbours, the keypoint pointers and the
+ *   workspace may be NULL; values, if given, is set to zeros.  Any weight non-zero: d_transforms may be NULL -- the chain part
+ *   is zero, view_rows / frame_of_view are not read and V may be 0.
+ *   Refused before any launch, nothing written: all of mgr_fk_backward's conditions but those relaxed above; a negative or
+ *   non-finite weight; NULL theta_ref with a dev weight on; NULL neighbours with a smooth weight on; w_kp != 0 with K outside
+ *   1 .. MGR_FK_MAX_KEYPOINTS or a NULL keypoint pointer; NULL values or workspace with any weight on; a short workspace
+ *   (MGR_ENOMEM). */
+#define MGR_FK_MAX_KEYPOINTS 64
+size_t mgr_fk_terms_workspace_bytes(int U, int J, int K);
+int mgr_fk_backward_terms(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                          const int32_t* frame_of_view, const float* rest, const float* local, const int32_t* parents, const float* base,
+                          const float* theta, const float* mask, const float* d_transforms, float* d_theta,
+                          const float* theta_ref, const int32_t* neighbours,
+                          double w_dev_rot, double w_smooth_rot, double w_dev_trans, double w_smooth_trans,
+                          int K, const int32_t* kp_bone, const float* kp_offset, const float* kp_target, const float* kp_weight, double w_kp,
+                          double* values, void* workspace, size_t workspace_bytes, void* stream);
+
 /* uv =(K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
 int mgr_project_points(int N, const float* xyz, const float* K9, const float* E12, float* uv,
                        void* stream);

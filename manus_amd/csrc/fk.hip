@@ -16,6 +16,13 @@
 // k_bone_transforms (bone_math.h), fed from LDS behind a barrier and stored straight to global memory as k_pose_apply does:
 // a view without a frame gets the bits of mgr_bone_transforms on its posed row.
 //
+// k_fk_backward_terms is k_fk_backward with three opt-in terms on the angles of the listed frames -- a pull towards a kept table,
+// temporal smoothness along the take, 3-D keypoints carried by the posed matrices -- in a kernel of its own, so that
+// k_fk_backward keeps its text and its bits.  The keypoints enter the tree between the walk down and the walk up: one thread per
+// keypoint forms residual and value share, one thread per bone adds its keypoints' outer products to G_i in ascending order; the
+// priors are added per element behind the angle partials.  The one workspace is three fp64 value shares per listed frame,
+// folded in list order by k_fk_terms_fold: no atomics, equal bits run to run.
+//
 // parents[i] outside {-1} u [0, i) is read as -1 (a root): the kernels never index outside their tables whatever the list
 // holds; pose.KinematicPoseRefiner refuses such a list on the host.
 #include <cmath>
@@ -283,6 +290,291 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward(int V, int J, int F, i
     }
 }
 
+// The terms of mgr_fk_backward_terms and what they read and leave: w_* in double for the values, c_* = (float)(2 w_*) for the
+// gradient.  K = 0 switches the keypoint term off
+struct FkTerms {
+    const float* theta_ref;        // (F,J+2,3), read only
+    const int32_t* neighbours;     // (F,2) prev, next; outside [0,F): none
+    double* partial;               // (U,3) the listed frames' shares of E_dev, E_smooth, E_kp
+    double w_dev_r, w_smooth_r, w_dev_t, w_smooth_t, w_kp;
+    float c_dev_r, c_smooth_r, c_dev_t, c_smooth_t, c_kp;
+    int K;
+    const int32_t* kp_bone;        // (K)
+    const float* kp_offset;        // (K,3)
+    const float* kp_target;        // (F,K,3)
+    const float* kp_weight;        // (F,K)
+};
+
+// The angle priors on row `row` of frame f (three elements): adds 2 w_dev (x - x_ref) + 2 w_smooth ((x - x_prev) + (x - x_next)) to
+// g -- fp32, the differences first, their sum prev first, the two products, then the addition, none of it contracted
+// (pose_prior_one of pose.hip) -- and adds this row's squared differences over the elements with mask != 0 to dev / smooth in
+// fp64: the edge to next, and the edge to prev when `count_prev`.  prev / next: -1 = none
+__device__ __forceinline__ void fk_prior_row(const float* __restrict__ theta, const float* __restrict__ theta_ref, int rowlen, int f,
+                                             int prev, int next, int row, bool count_prev, float c_dev, float c_smooth,
+                                             const float* __restrict__ mask, float* g, double& dev, double& smooth) {
+    const size_t e = (size_t)row * 3;
+    const float* x = theta + (size_t)f * rowlen + e;
+    const float* xr = theta_ref ? theta_ref + (size_t)f * rowlen + e : x;
+    const float* xp = theta + (size_t)(prev >= 0 ? prev : f) * rowlen + e;
+    const float* xn = theta + (size_t)(next >= 0 ? next : f) * rowlen + e;
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float xc = x[c];
+            const float dr = xc - xr[c], dp = xc - xp[c], dn = xc - xn[c];      // (0 where the neighbour is missing: it stands in for itself)
+            const float s = prev >= 0 ? (next >= 0 ? dp + dn : dp) : (next >= 0 ? dn : 0.f);
+            const float pd = c_dev * dr, ps = c_smooth * s;
+            g[c] = g[c] + (pd + ps);
+            if (mask[e + c] != 0.f) {
+                dev += (double)dr * (double)dr;
+                smooth += (prev >= 0 && count_prev ? (double)dp * (double)dp : 0.0) + (next >= 0 ? (double)dn * (double)dn : 0.0);
+            }
+        }
+    }
+}
+
+// k_fk_backward with the angle priors and the keypoint term (mgr_fk_backward_terms).  A kernel of its own: k_fk_backward keeps its
+// text and with it its bits (moved into a shared body, the compiler fuses other products: pose.hip).  The same sums in the same
+// order around three more barriers: behind the walk thread k < K forms keypoint k, p_k = (M_bone[k] [o_k; 1])[:3], its residual
+// r_k = p_k - y and g_k = (c_kp c) r_k; then thread i < J adds g_k (x) [o_k; 1] of its own keypoints to rows 0..2 of G_i, behind
+// the view sum and in ascending k; then the upward pass and the partials as they were.  The terms do not depend on views: a
+// listed frame inside [0,F) that no position shows runs the whole body on a zero view sum (d_transforms == NULL: every frame).
+// A keypoint is skipped -- exactly 0 in gradient and value, whatever its target holds -- unless its weight is > 0 (a NaN
+// weight skips) and its bone lies in [0,J).  tm.partial[3 u ..] = this frame's shares of E_dev, E_smooth, E_kp in fp64
+__global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms(int V, int J, int F, int U, const int32_t* __restrict__ frames_listed,
+                                                                const int32_t* __restrict__ view_rows,
+                                                                const int32_t* __restrict__ frame_of_view,
+                                                                const float* __restrict__ rest, const float* __restrict__ local,
+                                                                const int32_t* __restrict__ parents, const float* __restrict__ base,
+                                                                const float* __restrict__ theta, const float* __restrict__ mask,
+                                                                const float* __restrict__ d_transforms, float* __restrict__ d_theta,
+                                                                FkTerms tm) {
+    __shared__ float s_L[MGR_MAX_BONES * 16];
+    __shared__ float s_M[MGR_MAX_BONES * 16];
+    __shared__ float s_G[MGR_MAX_BONES * 16];
+    __shared__ float s_A[16];
+    __shared__ float s_dA[16];
+    __shared__ float s_kg[MGR_FK_MAX_KEYPOINTS * 3];          // g_k
+    __shared__ float s_ko[MGR_FK_MAX_KEYPOINTS * 3];          // o_k
+    __shared__ int s_kb[MGR_FK_MAX_KEYPOINTS];                // bone[k], -1: skipped
+    __shared__ double s_kv[MGR_FK_MAX_KEYPOINTS];             // c |r_k|^2
+    __shared__ double s_dev[MGR_MAX_BONES + 1];
+    __shared__ double s_smooth[MGR_MAX_BONES + 1];
+    const int u = blockIdx.x, b = threadIdx.x;
+    const int f = frames_listed[u];
+    const int rowlen = (J + 2) * 3;
+    float* out = d_theta + (size_t)u * rowlen;
+    if (f < 0 || f >= F) {                                    // a frame outside the table: zeros, no share of any value
+        for (int q = b; q < rowlen; q += FK_BLOCK) out[q] = 0.f;
+        if (b < 3) tm.partial[(size_t)u * 3 + b] = 0.0;
+        return;
+    }
+    const bool chain = d_transforms != nullptr;               // uniform
+    const float* th = theta + (size_t)f * rowlen;
+    if (b < J) {
+        float G[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) G[i][j] = 0.f;
+        if (chain) {
+            float a[4][8];
+            bone_invert(rest + (size_t)b * 16, a);
+            for (int k = 0; k < V; ++k) {
+                if (frame_of_view[k] != f || view_rows[k] < 0) continue;
+                const float* dT = d_transforms + ((size_t)k * (J + 1) + b) * 16;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float acc = 0.f;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc += dT[i * 4 + q] * a[j][4 + q];      // dT inv(rest)^T
+                        G[i][j] += acc;
+                    }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s_G[b * 16 + i * 4 + j] = G[i][j];
+        float R[3][3];
+        fk_euler(th + (1 + b) * 3, R);
+        fk_mul_rt(local + (size_t)b * 16, R, 0.f, 0.f, 0.f, s_L + b * 16);
+    } else if (b == J) {
+        const float* t = th + (J + 1) * 3;
+        float R[3][3];
+        fk_euler(th, R);
+        fk_mul_rt(base + (size_t)f * 16, R, t[0], t[1], t[2], s_A);
+    }
+    __syncthreads();
+    if (b < 4) fk_walk_row(J, b, parents, s_A, s_L, s_M);
+    __syncthreads();
+    const int K = tm.K;                                       // 0 .. MGR_FK_MAX_KEYPOINTS = FK_BLOCK: one thread per keypoint
+    if (b < K) {
+        const int bone = tm.kp_bone[b];
+        const float c = tm.kp_weight[(size_t)f * K + b];
+        const bool on = c > 0.f && bone >= 0 && bone < J;     // (a NaN weight compares false)
+        float g[3] = {0.f, 0.f, 0.f};
+        double val = 0.0;
+        const float* o = tm.kp_offset + (size_t)b * 3;
+        const float o0 = o[0], o1 = o[1], o2 = o[2];
+        if (on) {
+            const float* M = s_M + bone * 16;
+            const float* y = tm.kp_target + ((size_t)f * K + b) * 3;
+            const float ck = tm.c_kp * c;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const float p = M[r * 4] * o0 + M[r * 4 + 1] * o1 + M[r * 4 + 2] * o2 + M[r * 4 + 3];
+                const float res = p - y[r];
+                g[r] = ck * res;
+                val += (double)res * (double)res;
+            }
+            val *= (double)c;
+        }
+        s_kb[b] = on ? bone : -1;
+        s_kv[b] = val;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            s_kg[b * 3 + r] = g[r];
+            s_ko[b * 3 + r] = o[r];
+        }
+    }
+    __syncthreads();
+    if (b < J) {
+        for (int k = 0; k < K; ++k) {
+            if (s_kb[k] != b) continue;
+            const float o0 = s_ko[k * 3], o1 = s_ko[k * 3 + 1], o2 = s_ko[k * 3 + 2];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const float g = s_kg[k * 3 + r];
+                s_G[b * 16 + r * 4 + 0] += g * o0;
+                s_G[b * 16 + r * 4 + 1] += g * o1;
+                s_G[b * 16 + r * 4 + 2] += g * o2;
+                s_G[b * 16 + r * 4 + 3] += g;
+            }
+        }
+    }
+    __syncthreads();
+    if (b < 4) {
+        // row b of the gradients, children before parents: G_parent += G_i L_i^T, dA += G_root L_root^T
+        float dA[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int i = J - 1; i >= 0; --i) {
+            const float* g = s_G + i * 16 + b * 4;
+            const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
+            const float* L = s_L + i * 16;
+            const int p = fk_parent(parents, i);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float up = g0 * L[c * 4] + g1 * L[c * 4 + 1] + g2 * L[c * 4 + 2] + g3 * L[c * 4 + 3];
+                if (p < 0)
+                    dA[c] += up;
+                else
+                    s_G[p * 16 + b * 4 + c] += up;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s_dA[b * 4 + c] = dA[c];
+    }
+    __syncthreads();
+    // the neighbours of the priors; whether prev is listed is a walk over frames_listed (U is a step's views at most)
+    int prev = -1, next = -1;
+    if (tm.neighbours) {
+        prev = tm.neighbours[2 * (size_t)f];
+        next = tm.neighbours[2 * (size_t)f + 1];
+        if (prev < 0 || prev >= F) prev = -1;
+        if (next < 0 || next >= F) next = -1;
+    }
+    bool prev_listed = false;
+    if (prev >= 0)
+        for (int q = 0; q < U; ++q) prev_listed = prev_listed || frames_listed[q] == prev;
+    const bool prior_r = tm.w_dev_r != 0.0 || tm.w_smooth_r != 0.0, prior_t = tm.w_dev_t != 0.0 || tm.w_smooth_t != 0.0;
+    if (b < J) {
+        // Q = the 3x3 block of (M_parent local_i)^T G_i, with A in place of M_parent for a root
+        const int p = fk_parent(parents, b);
+        const float* Mp = p < 0 ? s_A : s_M + p * 16;
+        const float* l = local + (size_t)b * 16;
+        float P[4][3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                P[r][c] = Mp[r * 4] * l[c] + Mp[r * 4 + 1] * l[4 + c] + Mp[r * 4 + 2] * l[8 + c] + Mp[r * 4 + 3] * l[12 + c];
+        const float* G = s_G + b * 16;
+        float Q[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Q[i][j] = P[0][i] * G[j] + P[1][i] * G[4 + j] + P[2][i] * G[8 + j] + P[3][i] * G[12 + j];
+        float g[3];
+        fk_euler_vjp(th + (1 + b) * 3, Q, g);
+        double dev = 0.0, smooth = 0.0;
+        if (prior_r) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, 1 + b, !prev_listed, tm.c_dev_r, tm.c_smooth_r, mask, g, dev, smooth);
+        s_dev[b] = tm.w_dev_r * dev;
+        s_smooth[b] = tm.w_smooth_r * smooth;
+        const float* mk = mask + (1 + b) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(1 + b) * 3 + c] = mk[c] != 0.f ? g[c] * mk[c] : 0.f;
+    } else if (b == J) {
+        // dC = base^T dA for A = base C, C = [[E(g), t], [0,0,0,1]]
+        const float* bs = base + (size_t)f * 16;
+        float dC[3][4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dC[i][j] = bs[i] * s_dA[j] + bs[4 + i] * s_dA[4 + j] + bs[8 + i] * s_dA[8 + j] + bs[12 + i] * s_dA[12 + j];
+        float Q[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Q[i][j] = dC[i][j];
+        float g[3];
+        fk_euler_vjp(th, Q, g);
+        float gt[3] = {dC[0][3], dC[1][3], dC[2][3]};
+        double dev_r = 0.0, smooth_r = 0.0, dev_t = 0.0, smooth_t = 0.0;
+        if (prior_r) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, 0, !prev_listed, tm.c_dev_r, tm.c_smooth_r, mask, g, dev_r, smooth_r);
+        if (prior_t) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, J + 1, !prev_listed, tm.c_dev_t, tm.c_smooth_t, mask, gt, dev_t, smooth_t);
+        s_dev[J] = tm.w_dev_r * dev_r + tm.w_dev_t * dev_t;
+        s_smooth[J] = tm.w_smooth_r * smooth_r + tm.w_smooth_t * smooth_t;
+        const float* mt = mask + (J + 1) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            out[c] = mask[c] != 0.f ? g[c] * mask[c] : 0.f;
+            out[(J + 1) * 3 + c] = mt[c] != 0.f ? gt[c] * mt[c] : 0.f;
+        }
+    }
+    __syncthreads();
+    // this frame's shares: one thread per term, every sum in ascending index
+    if (b == 0) {
+        double acc = 0.0;
+        for (int i = 0; i <= J; ++i) acc += s_dev[i];
+        tm.partial[(size_t)u * 3] = acc;
+    } else if (b == 1) {
+        double acc = 0.0;
+        for (int i = 0; i <= J; ++i) acc += s_smooth[i];
+        tm.partial[(size_t)u * 3 + 1] = acc;
+    } else if (b == 2) {
+        double acc = 0.0;
+        for (int k = 0; k < K; ++k) acc += s_kv[k];
+        tm.partial[(size_t)u * 3 + 2] = tm.w_kp * acc;
+    }
+}
+
+// one workgroup over the (U,3) shares: thread t < 3 adds term t of the listed frames in list order; values[3] = their sum
+__global__ __launch_bounds__(FK_BLOCK) void k_fk_terms_fold(const double* __restrict__ partial, int U, double* __restrict__ values) {
+    __shared__ double s_sum[3];
+    const int t = threadIdx.x;
+    if (t < 3) {
+        double acc = 0.0;
+        for (int u = 0; u < U; ++u) acc += partial[(size_t)u * 3 + t];
+        s_sum[t] = acc;
+        values[t] = acc;
+    }
+    __syncthreads();
+    if (t == 0) values[3] = (s_sum[0] + s_sum[1]) + s_sum[2];
+}
+
 // thread (u, e): element e of the (J+2, 3) row of listed frame u.  pose_adam_one (k_pose_adam's update), rows 0..J at the
 // rotations' rate and row J+1 at the translation's, then the clamp to [lo, hi]; an element with mask 0 is not touched
 __global__ __launch_bounds__(FK_ADAM_BLOCK) void k_fk_adam(int U, int J, const int32_t* __restrict__ frames_listed,
@@ -364,5 +656,68 @@ extern "C" int mgr_fk_adam(int U, int J, const int32_t* frames_listed, const flo
                            (float)(1.0 - beta2), (float)eps);
     }
     MGR_LAUNCH_CHECK("k_fk_adam", stream, 0);
+    return MGR_OK;
+}
+
+extern "C" size_t mgr_fk_terms_workspace_bytes(int U, int J, int K) {
+    (void)K;      // (the keypoints' shares meet inside the workgroup)
+    return (U < 1 || J < 1) ? 0 : (size_t)U * 3 * sizeof(double);
+}
+
+extern "C" int mgr_fk_backward_terms(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                                     const int32_t* frame_of_view, const float* rest, const float* local, const int32_t* parents,
+                                     const float* base, const float* theta, const float* mask, const float* d_transforms,
+                                     float* d_theta, const float* theta_ref, const int32_t* neighbours, double w_dev_rot,
+                                     double w_smooth_rot, double w_dev_trans, double w_smooth_trans, int K, const int32_t* kp_bone,
+                                     const float* kp_offset, const float* kp_target, const float* kp_weight, double w_kp,
+                                     double* values, void* workspace, size_t workspace_bytes, void* stream_) {
+    const double w[5] = {w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans, w_kp};
+    for (int i = 0; i < 5; ++i)
+        if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
+            return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: the weights must be finite and >= 0");
+    const bool dev = w_dev_rot != 0.0 || w_dev_trans != 0.0, smooth = w_smooth_rot != 0.0 || w_smooth_trans != 0.0, kp = w_kp != 0.0;
+    const bool terms = dev || smooth || kp;
+    const bool chain = !terms || d_transforms != nullptr;      // (with a term on, d_transforms may be NULL: no chain part, no views read)
+    if (J < 1 || J > MGR_MAX_BONES || F < 1 || U < 1 || (chain ? V < 1 : V < 0))
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: F and U must be at least 1, V too unless d_transforms is NULL with a term on, J 1 .. MGR_MAX_BONES");
+    if (!frames_listed || !rest || !local || !parents || !base || !theta || !mask || !d_theta || (chain && (!view_rows || !frame_of_view || !d_transforms)))
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: null pointer");
+    if ((long long)V * (J + 1) > (1ll << 24) || (long long)U * (J + 2) > (1ll << 24))
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: V * (J + 1) or U * (J + 2) above 2^24");
+    if (dev && !theta_ref) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: a deviation weight needs theta_ref");
+    if (smooth && !neighbours) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: a smoothness weight needs the neighbour table");
+    if (kp && (K < 1 || K > MGR_FK_MAX_KEYPOINTS))
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: the keypoint term needs K 1 .. MGR_FK_MAX_KEYPOINTS");
+    if (kp && (!kp_bone || !kp_offset || !kp_target || !kp_weight))
+        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: the keypoint term needs kp_bone, kp_offset, kp_target and kp_weight");
+    if (terms && (!values || !workspace)) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: a term needs values and a workspace");
+    if (terms && workspace_bytes < mgr_fk_terms_workspace_bytes(U, J, K))
+        return mgr_fail(MGR_ENOMEM, "mgr_fk_backward_terms: workspace too small");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!terms) {      // mgr_fk_backward's own launch; the values of no term are 0
+        if (values) MGR_HIP(hipMemsetAsync(values, 0, 4 * sizeof(double), stream));
+        {
+            MGR_PROF("k_fk_backward", stream);
+            hipLaunchKernelGGL(k_fk_backward, dim3(U), dim3(FK_BLOCK), 0, stream, V, J, F, U, frames_listed, view_rows, frame_of_view, rest,
+                               local, parents, base, theta, mask, d_transforms, d_theta);
+        }
+        MGR_LAUNCH_CHECK("k_fk_backward", stream, 0);
+        return MGR_OK;
+    }
+    double* partial = (double*)workspace;
+    const FkTerms tm = {dev ? theta_ref : nullptr, smooth ? neighbours : nullptr, partial, w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans,
+                        w_kp, (float)(2.0 * w_dev_rot), (float)(2.0 * w_smooth_rot), (float)(2.0 * w_dev_trans),
+                        (float)(2.0 * w_smooth_trans), (float)(2.0 * w_kp), kp ? K : 0, kp_bone, kp_offset, kp_target, kp_weight};
+    {
+        MGR_PROF("k_fk_backward_terms", stream);
+        hipLaunchKernelGGL(k_fk_backward_terms, dim3(U), dim3(FK_BLOCK), 0, stream, chain ? V : 0, J, F, U, frames_listed, view_rows,
+                           frame_of_view, rest, local, parents, base, theta, mask, d_transforms, d_theta, tm);
+    }
+    MGR_LAUNCH_CHECK("k_fk_backward_terms", stream, 0);
+    {
+        MGR_PROF("k_fk_terms_fold", stream);
+        hipLaunchKernelGGL(k_fk_terms_fold, dim3(1), dim3(FK_BLOCK), 0, stream, partial, U, values);
+    }
+    MGR_LAUNCH_CHECK("k_fk_terms_fold", stream, 0);
     return MGR_OK;
 }

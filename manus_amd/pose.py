@@ -17,7 +17,7 @@ correction has no reference counterpart; the kinematic one follows that config's
 src/utils/transforms.py (euler_angles_to_armature_space, apply_constraints_to_poses, apply_limits_to_poses)."""
 import torch
 
-from ._lib import MGR_MAX_BONES, check, lib, ptr, stream
+from ._lib import MGR_FK_MAX_KEYPOINTS, MGR_MAX_BONES, check, lib, ptr, stream
 
 
 def _exp_so3(r):
@@ -376,6 +376,40 @@ def check_parents(parents, n_bones):
     return parents
 
 
+def keypoint_offsets(rest, rest_heads, rest_tails):
+    """(bones (K,) int32, offsets (K,3) float32) of the dataset's keypoint convention -- K = J+1: the first bone's head, then every
+    bone's tail (`FrameStore.keypoints`) -- for `KinematicPoseRefiner.set_keypoints`: keypoints 0 and 1 ride on bone 0, keypoint
+    k > 1 on bone k-1, and the offset is the rest point in its bone's own frame, inv(rest_b) [point; 1], formed in fp64."""
+    rest = torch.as_tensor(rest).detach().cpu().double()
+    heads, tails = (torch.as_tensor(x).detach().cpu().double() for x in (rest_heads, rest_tails))
+    J = rest.shape[0] if rest.dim() == 3 else 0
+    if J < 1 or tuple(rest.shape) != (J, 4, 4) or tuple(heads.shape) != (J, 3) or tuple(tails.shape) != (J, 3):
+        raise ValueError("keypoint_offsets: rest (J,4,4), rest_heads (J,3), rest_tails (J,3) (got %s, %s, %s)"
+                         % (tuple(rest.shape), tuple(heads.shape), tuple(tails.shape)))
+    bones = [0] + list(range(J))
+    points = torch.cat([heads[:1], tails], 0)
+    hom = torch.cat([points, torch.ones((J + 1, 1), dtype=torch.float64)], 1)
+    off = (torch.linalg.inv(rest)[bones] @ hom[..., None])[:, :3, 0]
+    return torch.tensor(bones, dtype=torch.int32), off.to(torch.float32)
+
+
+def keypoints_of_store(store, frame_keys):
+    """(F,J+1,3) on the store's device: the 3-D keypoints of the frame rows of `frame_keys` (distinct (action, frame_id) pairs in
+    first-seen order, as the refiners number them) from `FrameStore.keypoints` -- of every frame its first stored item (the
+    keypoints do not depend on the camera).  Raises for a key the store lacks."""
+    if getattr(store, "frame_keys", None) is None or getattr(store, "keypoints", None) is None:
+        raise ValueError("keypoints_of_store needs the frame keys and keypoints of a store built by FrameStore.from_dataset")
+    first = {}
+    for j, k in enumerate(store.frame_keys):
+        first.setdefault((k[0], k[1]), j)
+    rows = []
+    for k in _FrameRows._keys(frame_keys):
+        if k not in first:
+            raise ValueError("keypoints_of_store: the store holds no item of frame %r" % (k,))
+        rows.append(first[k])
+    return store.keypoints[rows]
+
+
 class KinematicPoseRefiner(_FrameRows):
     """Pose refinement in joint angles: theta (F,J+2,3) per frame row -- row 0 the global Euler angles, rows 1..J the bones'
     Euler angles (XYZ intrinsic, `transforms.euler_angles_to_matrix`), row J+1 the global translation -- through forward
@@ -390,13 +424,24 @@ class KinematicPoseRefiner(_FrameRows):
     The constants local_i = inv(rest_parent(i)) rest_i are formed in fp64 on the host.  The optimizer is `PoseRefiner`'s row
     Adam with a clamp to the limits behind it.  mask, limits, base and the rates are configuration, not state.
 
+    Terms on the angles (all five weights 0: none, today's two entries exactly), per frame row over the free elements:
+        E_dev    = sum_f w_dev |theta_f - theta_ref_f|^2                 a pull towards a kept table: theta0 until `set_reference`
+        E_smooth = sum_edges w_smooth |theta_f - theta_next(f)|^2        over `neighbour_table(frame_keys, max_gap)`, no angle wrap
+        E_kp     = w_kp sum_f sum_k c[f,k] |p_k(theta_f) - y[f,k]|^2     p_k = M_bone[k] [o_k; 1]: 3-D keypoints (`set_keypoints`)
+    with a weight each for the rotations (rows 0..J) and the translation (row J+1).  With any weight non-zero `step` calls
+    mgr_fk_backward_terms in place of mgr_fk_backward: the listed rows' gradient gains the true dE/dtheta_f at the tables before
+    the step; `last_terms` is the (4,) device double (E_dev, E_smooth, E_kp, their sum) of the part that touches the listed
+    rows, each term once, and `last_prior` a view of its last element -- neither is read back.  `fit_keypoints` runs the terms
+    alone, without a rendered frame.  Weights, theta_ref and keypoints are configuration, not state: `state_dict()` does not
+    carry them.
+
         refiner.residual(compute, view_ids, frames)          # does FK at theta0 reproduce the dataset's posed matrices?
         refiner.apply(compute, view_ids, frames)             # as PoseRefiner: transforms of the step's views
         out = compute(view_ids, scale)
         refiner.step(out["d_transforms"], view_ids, frames)"""
 
     def __init__(self, frame_keys, rest, parents, theta0, lr_rot, lr_trans, mask=None, limits=None, base=None, betas=(0.9, 0.999),
-                 eps=1e-8, device=None):
+                 eps=1e-8, device=None, w_dev_rot=0.0, w_smooth_rot=0.0, w_dev_trans=0.0, w_smooth_trans=0.0, max_gap=None, w_kp=0.0):
         self.frame_keys = self._keys(frame_keys)
         self.row = {k: j for j, k in enumerate(self.frame_keys)}
         rest = torch.as_tensor(rest)
@@ -438,9 +483,57 @@ class KinematicPoseRefiner(_FrameRows):
         self.m = self.v = None
         self.steps = 0
         self.last_grad = None           # (frames listed, d_theta (U,J+2,3)) of the last step
-        self.last_prior = None          # no prior on the angles
+        self.weights = tuple(float(w) for w in (w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans))
+        self.w_kp = float(w_kp)
+        for name, w in zip(("w_dev_rot", "w_smooth_rot", "w_dev_trans", "w_smooth_trans", "w_kp"), self.weights + (self.w_kp,)):
+            if not (w >= 0.0 and w != float("inf")):
+                raise ValueError("KinematicPoseRefiner: %s must be finite and >= 0 (got %r)" % (name, w))
+        self.has_terms = any(w != 0.0 for w in self.weights) or self.w_kp != 0.0
+        self.max_gap = max_gap
+        self.neighbours = neighbour_table(self.frame_keys, max_gap).to(self.device)      # (F,2) int32: prev, next; -1 none
+        self.theta_ref = self.theta.clone()
+        self.kp = None                  # (bones (K,) int32, offsets (K,3), targets (F,K,3), weights (F,K)) of `set_keypoints`
+        self.last_prior = None          # with a term on: the terms' sum on the rows of the last step (device double scalar)
+        self.last_terms = None          # with a term on: (E_dev, E_smooth, E_kp, sum) of the last step (device double (4,))
+        self._terms_ws = None           # the per-frame shares of mgr_fk_backward_terms (kept across steps)
         self._posed = None              # the posed table of the compute object last applied to
         self._lists = {}
+
+    # -- configuration of the terms -------------------------------------------------------------------------------------
+    def set_keypoints(self, bones, offsets, targets, weights=None):
+        """The keypoints of E_kp: bones (K,) ints in [0,J), offsets (K,3) in the bones' own frames (`keypoint_offsets`), targets
+        (F,K,3) per frame row (`keypoints_of_store`), weights (F,K), (K,) or None (ones); K <= 64.  A keypoint of a frame whose
+        weight is not > 0 (zero, negative, NaN) is skipped, whatever its target holds."""
+        F, J = self.n_frames, self.n_bones
+        bones = torch.as_tensor(bones)
+        K = int(bones.shape[0]) if bones.dim() == 1 else 0
+        if not 1 <= K <= MGR_FK_MAX_KEYPOINTS:
+            raise ValueError("KinematicPoseRefiner.set_keypoints: bones must be (K,) with K 1 .. %d (got %s)" % (MGR_FK_MAX_KEYPOINTS, tuple(bones.shape)))
+        if bones.dtype.is_floating_point or bones.dtype == torch.bool:
+            raise ValueError("KinematicPoseRefiner.set_keypoints: bones must be integers")
+        host = [int(b) for b in bones.tolist()]
+        if any(not 0 <= b < J for b in host):
+            raise ValueError("KinematicPoseRefiner.set_keypoints: a bone outside [0,%d)" % J)
+
+        def table(x, shape, what):
+            x = torch.as_tensor(x)
+            if tuple(x.shape) != shape:
+                raise ValueError("KinematicPoseRefiner.set_keypoints: %s must be %s (got %s)" % (what, shape, tuple(x.shape)))
+            return x.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        off, tgt = table(offsets, (K, 3), "offsets"), table(targets, (F, K, 3), "targets")
+        if weights is None:
+            w = torch.ones((F, K), dtype=torch.float32, device=self.device)
+        else:
+            weights = torch.as_tensor(weights)
+            w = table(weights.expand(F, K) if tuple(weights.shape) == (K,) else weights, (F, K), "weights")
+        self.kp = (torch.tensor(host, dtype=torch.int32, device=self.device), off, tgt, w)
+
+    def set_reference(self, theta=None):
+        """Re-anchors E_dev: theta_ref = theta (F,J+2,3), by default the current table."""
+        src = self.theta if theta is None else torch.as_tensor(theta)
+        if tuple(src.shape) != tuple(self.theta.shape):
+            raise ValueError("KinematicPoseRefiner.set_reference: theta must be %s (got %s)" % (tuple(self.theta.shape), tuple(src.shape)))
+        self.theta_ref.copy_(src.detach().to(device=self.device, dtype=torch.float32))
 
     # -- host fp64 ----------------------------------------------------------------------------------------------------------
     def fk_host(self, theta=None, base=None):
@@ -547,12 +640,66 @@ class KinematicPoseRefiner(_FrameRows):
             self.m, self.v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
         g = torch.empty((U, J + 2, 3), dtype=torch.float32, device=self.device)
         L = lib()
-        check(L.mgr_fk_backward(V, J, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self.rest), ptr(self.local), ptr(self.parents),
-                                ptr(self.base), ptr(self.theta), ptr(self.mask), ptr(d_transforms), ptr(g), stream()), "mgr_fk_backward")
+        if self.has_terms:
+            self._backward_terms(V, U, listed_t, rows, fov, d_transforms, g)
+        else:
+            check(L.mgr_fk_backward(V, J, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self.rest), ptr(self.local), ptr(self.parents),
+                                    ptr(self.base), ptr(self.theta), ptr(self.mask), ptr(d_transforms), ptr(g), stream()), "mgr_fk_backward")
         self.steps += 1
         check(L.mgr_fk_adam(U, J, ptr(listed_t), ptr(g), ptr(self.theta), ptr(self.m), ptr(self.v), ptr(self.mask), ptr(self.lo), ptr(self.hi),
                             self.lr_rot, self.lr_trans, self.betas[0], self.betas[1], self.eps, self.steps, stream()), "mgr_fk_adam")
         self.last_grad = (listed, g)
+
+    def _backward_terms(self, V, U, listed_t, rows, fov, d_transforms, g):
+        """mgr_fk_backward_terms into g (U,J+2,3) with the configured weights (d_transforms None: the terms alone); sets
+        `last_terms` and `last_prior`."""
+        J, L = self.n_bones, lib()
+        if self.w_kp != 0.0 and self.kp is None:
+            raise ValueError("KinematicPoseRefiner: w_kp is non-zero and no keypoints are set (set_keypoints)")
+        kp = self.kp if self.w_kp != 0.0 else (None, None, None, None)
+        K = int(kp[0].shape[0]) if kp[0] is not None else 0
+        nbytes = int(L.mgr_fk_terms_workspace_bytes(U, J, K))
+        if self._terms_ws is None or self._terms_ws.numel() < nbytes:
+            self._terms_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        values = torch.empty(4, dtype=torch.float64, device=self.device)
+        check(L.mgr_fk_backward_terms(V, J, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self.rest), ptr(self.local),
+                                      ptr(self.parents), ptr(self.base), ptr(self.theta), ptr(self.mask), ptr(d_transforms), ptr(g),
+                                      ptr(self.theta_ref), ptr(self.neighbours), *self.weights, K, ptr(kp[0]), ptr(kp[1]), ptr(kp[2]),
+                                      ptr(kp[3]), self.w_kp, ptr(values), ptr(self._terms_ws), self._terms_ws.numel(), stream()),
+              "mgr_fk_backward_terms")
+        self.last_terms, self.last_prior = values, values[3]
+
+    def fit_keypoints(self, steps, frames=None, lr_rot=None, lr_trans=None):
+        """`steps` Adam steps of the terms alone -- mgr_fk_backward_terms without d_transforms, then mgr_fk_adam -- on the frame
+        rows `frames` (default: all), with the configured weights: the best constrained angles for the keypoints, found without
+        rendering a frame.  lr_rot / lr_trans default to the refiner's.  The moments and the step count of this loop are its own:
+        `m`, `v` and `steps` of training are untouched, only `theta` moves.  Nothing is read back; `last_terms` holds the values
+        of the last iteration (at the angles before its step)."""
+        if not self.has_terms:
+            raise ValueError("KinematicPoseRefiner.fit_keypoints: every weight is zero")
+        F, J = self.n_frames, self.n_bones
+        listed = sorted({int(f) for f in (range(F) if frames is None else frames)})
+        if not listed or listed[0] < 0 or listed[-1] >= F:
+            raise ValueError("KinematicPoseRefiner.fit_keypoints: frames must be rows in [0,%d), at least one" % F)
+        lr_rot, lr_trans = (self.lr_rot if lr_rot is None else float(lr_rot)), (self.lr_trans if lr_trans is None else float(lr_trans))
+        U, L = len(listed), lib()
+        listed_t = torch.tensor(listed, dtype=torch.int32, device=self.device)
+        m, v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+        g = torch.empty((U, J + 2, 3), dtype=torch.float32, device=self.device)
+        for it in range(1, int(steps) + 1):
+            self._backward_terms(0, U, listed_t, None, None, None, g)
+            check(L.mgr_fk_adam(U, J, ptr(listed_t), ptr(g), ptr(self.theta), ptr(m), ptr(v), ptr(self.mask), ptr(self.lo), ptr(self.hi),
+                                lr_rot, lr_trans, self.betas[0], self.betas[1], self.eps, it, stream()), "mgr_fk_adam")
+
+    def keypoints(self, view_ids, frames, compute=None):
+        """The posed keypoints p_k = (M_bone[k] [o_k; 1])[:3] (len(view_ids),K,3) of the views, from `posed()` and the offsets of
+        `set_keypoints`: a host torch product on device tensors, for callers that want corrected keypoints."""
+        if self.kp is None:
+            raise ValueError("KinematicPoseRefiner.keypoints: no keypoints are set (set_keypoints)")
+        bones, off = self.kp[0].long(), self.kp[1]
+        M = self.posed(view_ids, frames, compute=compute)[:, bones]                           # (V,K,4,4)
+        hom = torch.cat([off, torch.ones((off.shape[0], 1), dtype=off.dtype, device=off.device)], 1)
+        return (M @ hom[None, :, :, None])[:, :, :3, 0]
 
     # -- state --------------------------------------------------------------------------------------------------------------
     def state_dict(self):

@@ -10,6 +10,8 @@ view, 20 bones in five chains of four, the hand's 23 free angles plus the global
     entries      the three entries alone
 
     python tools/measure_fk_refine.py [--out FILE.json] [--quick]
+    python tools/measure_fk_refine.py --terms [--out FILE.json]      the backward entry with the terms on the angles (deviation,
+                 smoothness, keypoints) against the plain one, and `fit_keypoints` against a host torch loop; renders nothing
 
 One process, HIP events around a batch of steps (a step that waits for the host shows as a longer step), every shape warmed,
 median of 5 samples with min and max; host and device chain alternate so that a drift of the clocks shows.  Needs a GPU; there
@@ -25,12 +27,97 @@ import torch  # noqa: E402
 from measure_pose_refine import timed  # noqa: E402
 
 
+def terms_main(a):
+    """--terms: the backward entry with the terms on the angles (mgr_fk_backward_terms: deviation, smoothness, 21 keypoints) against
+    the plain mgr_fk_backward on the same tables -- 8 listed frames of the 20-bone hand, 8 views, a random dL/dT --, and
+    `KinematicPoseRefiner.fit_keypoints(100)` against the same 100 Adam steps as host torch on the device (autograd through
+    `transforms.euler_angles_to_armature_space`, torch.optim.Adam).  No scene is rendered."""
+    from manus_amd import transforms as T
+    from manus_amd._lib import check, lib, ptr, stream
+    from manus_amd.pose import KinematicPoseRefiner, dof_mask
+    dev = "cuda:0"
+    V = F = 8
+    J, parents = 20, [-1 if i % 4 == 0 else i - 1 for i in range(20)]
+    g = torch.Generator().manual_seed(5)
+    rest = torch.eye(4).repeat(J, 1, 1)
+    rest[:, :3, :3] = T.euler_angles_to_matrix(torch.randn((J, 3), generator=g), "XYZ")
+    rest[:, :3, 3] = 0.05 * torch.randn((J, 3), generator=g)
+    mask = dof_mask(["bone_%d" % i for i in range(J)], True, True)
+    bones = [0] + list(range(J))
+    K = len(bones)
+    off = 0.03 * torch.randn((K, 3), generator=g)
+    ref = KinematicPoseRefiner([("capture", f) for f in range(F)], rest, parents, 0.3 * mask * torch.randn((F, J + 2, 3), generator=g), 0.02,
+                               0.002, mask=mask, device=dev, w_dev_rot=0.5, w_smooth_rot=0.25, w_dev_trans=2.0, w_smooth_trans=1.0, w_kp=10.0)
+    target = 0.1 * torch.randn((F, K, 3), generator=g)
+    ref.set_keypoints(bones, off, target)
+    ids = list(range(V))
+    rows, fov, listed_t, listed = ref._device_lists(ids, ids)[:4]
+    U = len(listed)
+    d_T = torch.randn((V, J + 1, 4, 4), generator=g).to(dev)
+    d_theta = torch.zeros((U, J + 2, 3), device=dev)
+    values = torch.zeros(4, dtype=torch.float64, device=dev)
+    L = lib()
+    ws = torch.empty(int(L.mgr_fk_terms_workspace_bytes(U, J, K)), dtype=torch.uint8, device=dev)
+    kp = ref.kp
+
+    def terms(weights, w_kp, chain=True):
+        check(L.mgr_fk_backward_terms(V if chain else 0, J, F, U, ptr(listed_t), ptr(rows) if chain else None, ptr(fov) if chain else None,
+                                      ptr(ref.rest), ptr(ref.local), ptr(ref.parents), ptr(ref.base), ptr(ref.theta), ptr(ref.mask),
+                                      ptr(d_T) if chain else None, ptr(d_theta), ptr(ref.theta_ref), ptr(ref.neighbours), *weights, K, ptr(kp[0]),
+                                      ptr(kp[1]), ptr(kp[2]), ptr(kp[3]), w_kp, ptr(values), ptr(ws), ws.numel(), stream()), "mgr_fk_backward_terms")
+
+    def plain():
+        check(L.mgr_fk_backward(V, J, F, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(ref.rest), ptr(ref.local), ptr(ref.parents), ptr(ref.base),
+                                ptr(ref.theta), ptr(ref.mask), ptr(d_T), ptr(d_theta), stream()), "mgr_fk_backward")
+    res = {"device": torch.cuda.get_device_name(0), "shape": dict(V=V, F=F, U=U, J=J, K=K)}
+    entries = [("mgr_fk_backward", plain), ("terms_all_on", lambda: terms(ref.weights, ref.w_kp)), ("terms_zero_weights", lambda: terms((0.0,) * 4, 0.0)),
+               ("terms_priors_only", lambda: terms(ref.weights, 0.0)), ("terms_keypoints_only", lambda: terms((0.0,) * 4, ref.w_kp)),
+               ("terms_without_d_transforms", lambda: terms(ref.weights, ref.w_kp, chain=False)), ("mgr_fk_backward_again", plain)]
+    for name, fn in entries:
+        res[name] = timed(fn, 200)
+        print("%-28s %s" % (name, json.dumps(res[name])), flush=True)
+
+    steps = 100 if not a.quick else 10
+    start = ref.theta.clone()
+    kintree = {str(i): p for i, p in enumerate(parents)}
+    rest_d, mask_d, ref_d, tgt, off_h = ref.rest, ref.mask, ref.theta_ref, kp[2], torch.cat([kp[1], torch.ones((K, 1), device=dev)], 1)
+    wd = torch.tensor([0.5] * (J + 1) + [2.0], device=dev)[:, None] * mask_d
+    wsm = torch.tensor([0.25] * (J + 1) + [1.0], device=dev)[:, None] * mask_d
+
+    def host_fit():
+        theta = start.clone().requires_grad_(True)
+        opt = torch.optim.Adam([theta], lr=0.02)
+        for _ in range(steps):
+            opt.zero_grad()
+            M = T.euler_angles_to_armature_space(theta[:, :J + 1], kintree, rest_d, theta[:, J + 1])
+            p = (M[:, bones] @ off_h[None, :, :, None])[:, :, :3, 0]
+            e = 10.0 * ((p - tgt) ** 2).sum() + (wd * (theta - ref_d) ** 2).sum() + (wsm * (theta[:-1] - theta[1:]) ** 2).sum()
+            e.backward()
+            theta.grad.mul_(mask_d)
+            opt.step()
+
+    def device_fit():
+        ref.theta.copy_(start)
+        ref.fit_keypoints(steps)
+    for name, fn in (("fit_keypoints_device", device_fit), ("fit_keypoints_host_torch", host_fit), ("fit_keypoints_device_again", device_fit)):
+        res[name] = timed(fn, 2)
+        res[name]["steps"] = steps
+        print("%-28s %s" % (name, json.dumps(res[name])), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="small sizes (a rehearsal of the script, not a measurement)")
+    ap.add_argument("--terms", action="store_true", help="time mgr_fk_backward_terms against mgr_fk_backward, and fit_keypoints against host torch")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "measure_fk_refine.py needs a GPU"
+    if a.terms:
+        return terms_main(a)
     from manus_amd import rasterizer
     from manus_amd import transforms as T
     from manus_amd._lib import check, lib, ptr, stream
