@@ -823,6 +823,47 @@ int mgr_fk_backward_terms(int V, int J, int F, int U, const int32_t* frames_list
                           int K, const int32_t* kp_bone, const float* kp_offset, const float* kp_target, const float* kp_weight, double w_kp,
                           double* values, void* workspace, size_t workspace_bytes, void* stream);
 
+/* mgr_fk_backward_terms2d: mgr_fk_backward_terms with a fourth opt-in term, the multi-view 2-D reprojection of the same keypoints
+ * (a kernel of its own once more: k_fk_backward and k_fk_backward_terms keep their text and their bits).  All of
+ * mgr_fk_backward_terms' arguments, and behind w_kp: C cameras, kp2d_proj (C,3,4) the projections P_c (for pixels K_c E_c[:3,:4],
+ * mgr_project_points' convention; formed by the caller in fp64, stored in fp32), kp2d_target (F,C,K,2), kp2d_weight (F,C,K),
+ * w_kp2d, delta (the Huber radius; 0: the plain square), z_min and kp2d_dist (U,C,K), which may be NULL.
+ *     q = P_c [p_k(theta_f); 1],   u = q[:2] / q[2],   r = u - t[f,c,k],   d = |r|
+ *     rho(d) = d^2 where delta == 0 or d <= delta,   2 delta d - delta^2 otherwise
+ *     E_kp2d = w_kp2d sum_f sum_{c<C} sum_{k<K} s[f,c,k] rho(d[f,c,k])
+ *   with p_k, kp_bone and kp_offset those of E_kp.  Units are the caller's: P and the targets may be pre-scaled, w_kp2d and delta
+ *   are then in that unit.  A detection is SKIPPED -- exactly 0 in gradient and value, NaN in kp2d_dist, whatever its target
+ *   holds -- unless its weight is > 0 (zero, negative, NaN: skipped), its bone lies in [0,J) and q[2] > (float)z_min.
+ *   Gradient, fp32 and uncontracted: g_u = (((float)(2 w_kp2d) s) h) r with h = 1 inside delta (or delta == 0) and delta / d
+ *   outside; dE/dq = [g_u0 / q2, g_u1 / q2, -(g_u0 u0 + g_u1 u1) / q2]; dE/dp = P_c[:, :3]^T dE/dq.  Per keypoint the cameras'
+ *   dE/dp are added over a fixed tree of camera slices: lane group g of the wave's 64 / K groups adds the cameras g, g + 64 / K, ...
+ *   in ascending index, and the keypoint's thread adds the groups' sums in ascending g -- an order that depends on C and K alone;
+ *   cameras are read from global memory and nothing is sized by C.  That sum is added to the 3-D term's g_k (the 3-D part first, 0
+ *   when w_kp == 0); g_k (x) [o_k; 1] then
+ *   enters rows 0..2 of G_bone[k] exactly as for E_kp and the upward pass follows unchanged.  Row u of d_theta depends on the inputs
+ *   of frame frames_listed[u] alone: not on U, the order of the list or the other frames listed.  The term needs no view.
+ *   values (5 doubles, device) = E_dev, E_smooth, E_kp, the sum of all four terms, E_kp2d: values[3] = ((v0 + v1) + v2) + v4.  The
+ *   fp32 residuals and distances of the active detections are weighted and added in fp64, one share per listed frame and term in
+ *   the workspace (mgr_fk_terms2d_workspace_bytes(U, J, K, C) bytes), folded by one workgroup in list order.
+ *   kp2d_dist, when given, receives d of every detection of the listed frames (NaN where skipped, and for a listed frame outside
+ *   [0,F)), also for a listed frame no view shows.  kp_target / kp_weight may be NULL when w_kp == 0; d_transforms may be NULL.
+ *   w_kp2d == 0: mgr_fk_backward_terms' own path on the first 31 arguments (its refusals, its launches, equal bits); values[4] = 0
+ *   when values is given, kp2d_dist (when given, with C and K >= 1) all NaN, and every 2-D pointer may be NULL.
+ *   Refused before any launch, nothing written: a negative or non-finite w_kp2d or delta; z_min not finite or not > 0; and with
+ *   w_kp2d != 0: all of mgr_fk_backward_terms' conditions for a call with a term on; C < 1; K outside 1 .. MGR_FK_MAX_KEYPOINTS; a
+ *   NULL kp_bone, kp_offset, kp2d_proj, kp2d_target or kp2d_weight; w_kp != 0 with a NULL kp_target or kp_weight; NULL values or
+ *   workspace; a short workspace (MGR_ENOMEM). */
+size_t mgr_fk_terms2d_workspace_bytes(int U, int J, int K, int C);
+int mgr_fk_backward_terms2d(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
+                            const int32_t* frame_of_view, const float* rest, const float* local, const int32_t* parents, const float* base,
+                            const float* theta, const float* mask, const float* d_transforms, float* d_theta,
+                            const float* theta_ref, const int32_t* neighbours,
+                            double w_dev_rot, double w_smooth_rot, double w_dev_trans, double w_smooth_trans,
+                            int K, const int32_t* kp_bone, const float* kp_offset, const float* kp_target, const float* kp_weight, double w_kp,
+                            int C, const float* kp2d_proj, const float* kp2d_target, const float* kp2d_weight,
+                            double w_kp2d, double delta, double z_min, float* kp2d_dist,
+                            double* values, void* workspace, size_t workspace_bytes, void* stream);
+
 /* uv =(K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
 int mgr_project_points(int N, const float* xyz, const float* K9, const float* E12, float* uv,
                        void* stream);

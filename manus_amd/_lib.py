@@ -134,6 +134,10 @@ SIGNATURES = {
     "mgr_fk_terms_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_fk_backward_terms": (c_int, [c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_vp, c_vp] + [ctypes.c_double] * 4
                               + [c_int] + [c_vp] * 4 + [ctypes.c_double] + [c_vp, c_vp, c_sz, c_vp]),
+    "mgr_fk_terms2d_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "mgr_fk_backward_terms2d": (c_int, [c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_vp, c_vp] + [ctypes.c_double] * 4
+                                + [c_int] + [c_vp] * 4 + [ctypes.c_double] + [c_int] + [c_vp] * 3 + [ctypes.c_double] * 3 + [c_vp]
+                                + [c_vp, c_vp, c_sz, c_vp]),
     "mgr_project_points": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_dilate_mask": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "mgr_points_outside_mask": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),

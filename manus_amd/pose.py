@@ -410,6 +410,27 @@ def keypoints_of_store(store, frame_keys):
     return store.keypoints[rows]
 
 
+def projection_matrices(K, extr):
+    """P (C,3,4) float32 = K_c E_c[:3,:4], formed in fp64 on the host: intrinsics K (C,3,3), extrinsics extr (C,3,4) or (C,4,4)
+    world to camera -- mgr_project_points' convention, q = K (E [x; 1]), pixel = q[:2] / q[2] -- for
+    `KinematicPoseRefiner.set_keypoints_2d`."""
+    K, E = (torch.as_tensor(x).detach().cpu().double() for x in (K, extr))
+    C = K.shape[0] if K.dim() == 3 else 0
+    if C < 1 or tuple(K.shape) != (C, 3, 3) or tuple(E.shape) not in ((C, 3, 4), (C, 4, 4)):
+        raise ValueError("projection_matrices: K (C,3,3) and extr (C,3,4) or (C,4,4) (got %s, %s)" % (tuple(K.shape), tuple(E.shape)))
+    return (K @ E[:, :3, :4]).to(torch.float32)
+
+
+def project_keypoints(proj, xyz):
+    """(...,C,K,2) float64 on the host: the points xyz (...,K,3) through the projections proj (C,3,4), u = q[:2] / q[2] with
+    q = P_c [x; 1], in fp64.  Nothing is clipped: a point behind a camera comes out mirrored."""
+    P, x = torch.as_tensor(proj).detach().cpu().double(), torch.as_tensor(xyz).detach().cpu().double()
+    if P.dim() != 3 or tuple(P.shape[1:]) != (3, 4) or x.dim() < 2 or x.shape[-1] != 3:
+        raise ValueError("project_keypoints: proj (C,3,4) and xyz (...,K,3) (got %s, %s)" % (tuple(P.shape), tuple(x.shape)))
+    q = torch.einsum("cij,...kj->...cki", P[:, :, :3], x) + P[:, None, :, 3]
+    return q[..., :2] / q[..., 2:]
+
+
 class KinematicPoseRefiner(_FrameRows):
     """Pose refinement in joint angles: theta (F,J+2,3) per frame row -- row 0 the global Euler angles, rows 1..J the bones'
     Euler angles (XYZ intrinsic, `transforms.euler_angles_to_matrix`), row J+1 the global translation -- through forward
@@ -435,13 +456,21 @@ class KinematicPoseRefiner(_FrameRows):
     alone, without a rendered frame.  Weights, theta_ref and keypoints are configuration, not state: `state_dict()` does not
     carry them.
 
+    A fourth term, also opt-in (w_kp2d = 0: none of it is run), fits the same keypoints to 2-D detections of C cameras:
+        E_kp2d   = w_kp2d sum_f sum_c sum_k s[f,c,k] rho(|P_c [p_k(theta_f); 1] dehomogenised - t[f,c,k]|)
+    with rho the square, or Huber's function of radius `kp2d_delta` > 0 (`set_keypoints_2d`; detections with a weight not > 0 or
+    nearer than `kp2d_zmin` in front of their camera are skipped).  With w_kp2d non-zero `step` and `fit_keypoints` call
+    mgr_fk_backward_terms2d; `last_terms` / `last_prior` then include the term and `last_kp2d` is its own value, all three views of
+    one (5,) device double.  `reprojection_error` returns the per-detection pixel distances.
+
         refiner.residual(compute, view_ids, frames)          # does FK at theta0 reproduce the dataset's posed matrices?
         refiner.apply(compute, view_ids, frames)             # as PoseRefiner: transforms of the step's views
         out = compute(view_ids, scale)
         refiner.step(out["d_transforms"], view_ids, frames)"""
 
     def __init__(self, frame_keys, rest, parents, theta0, lr_rot, lr_trans, mask=None, limits=None, base=None, betas=(0.9, 0.999),
-                 eps=1e-8, device=None, w_dev_rot=0.0, w_smooth_rot=0.0, w_dev_trans=0.0, w_smooth_trans=0.0, max_gap=None, w_kp=0.0):
+                 eps=1e-8, device=None, w_dev_rot=0.0, w_smooth_rot=0.0, w_dev_trans=0.0, w_smooth_trans=0.0, max_gap=None, w_kp=0.0,
+                 w_kp2d=0.0, kp2d_delta=0.0, kp2d_zmin=1e-2):
         self.frame_keys = self._keys(frame_keys)
         self.row = {k: j for j, k in enumerate(self.frame_keys)}
         rest = torch.as_tensor(rest)
@@ -488,13 +517,22 @@ class KinematicPoseRefiner(_FrameRows):
         for name, w in zip(("w_dev_rot", "w_smooth_rot", "w_dev_trans", "w_smooth_trans", "w_kp"), self.weights + (self.w_kp,)):
             if not (w >= 0.0 and w != float("inf")):
                 raise ValueError("KinematicPoseRefiner: %s must be finite and >= 0 (got %r)" % (name, w))
-        self.has_terms = any(w != 0.0 for w in self.weights) or self.w_kp != 0.0
+        self.w_kp2d, self.kp2d_delta, self.kp2d_zmin = float(w_kp2d), float(kp2d_delta), float(kp2d_zmin)
+        for name, w in (("w_kp2d", self.w_kp2d), ("kp2d_delta", self.kp2d_delta)):
+            if not (w >= 0.0 and w != float("inf")):
+                raise ValueError("KinematicPoseRefiner: %s must be finite and >= 0 (got %r)" % (name, w))
+        if not (self.kp2d_zmin > 0.0 and self.kp2d_zmin != float("inf")):
+            raise ValueError("KinematicPoseRefiner: kp2d_zmin must be finite and > 0 (got %r)" % self.kp2d_zmin)
+        self.has_terms = any(w != 0.0 for w in self.weights) or self.w_kp != 0.0 or self.w_kp2d != 0.0
         self.max_gap = max_gap
         self.neighbours = neighbour_table(self.frame_keys, max_gap).to(self.device)      # (F,2) int32: prev, next; -1 none
         self.theta_ref = self.theta.clone()
         self.kp = None                  # (bones (K,) int32, offsets (K,3), targets (F,K,3), weights (F,K)) of `set_keypoints`
         self.last_prior = None          # with a term on: the terms' sum on the rows of the last step (device double scalar)
         self.last_terms = None          # with a term on: (E_dev, E_smooth, E_kp, sum) of the last step (device double (4,))
+        self.kp2d = None                # (proj (C,3,4), targets (F,C,K,2), weights (F,C,K)) of `set_keypoints_2d`
+        self._kp_geom = None            # (bones (K,) int32, offsets (K,3)) the two setters share, and the bones on the host
+        self.last_kp2d = None           # with w_kp2d on: E_kp2d of the last step (device double scalar, a view beside last_terms)
         self._terms_ws = None           # the per-frame shares of mgr_fk_backward_terms (kept across steps)
         self._posed = None              # the posed table of the compute object last applied to
         self._lists = {}
@@ -526,7 +564,62 @@ class KinematicPoseRefiner(_FrameRows):
         else:
             weights = torch.as_tensor(weights)
             w = table(weights.expand(F, K) if tuple(weights.shape) == (K,) else weights, (F, K), "weights")
+        if self.kp2d is not None:
+            self._same_geometry("set_keypoints", host, off)
         self.kp = (torch.tensor(host, dtype=torch.int32, device=self.device), off, tgt, w)
+        self._kp_geom = (self.kp[0], off, host)
+
+    def _same_geometry(self, who, host, off):
+        """Both setters name one set of keypoints: the same K, bones and offsets."""
+        if self._kp_geom is not None and (host != self._kp_geom[2] or not torch.equal(off, self._kp_geom[1])):
+            raise ValueError("KinematicPoseRefiner.%s: bones / offsets differ from those already set: the 3-D and the 2-D term share "
+                             "one set of keypoints" % who)
+
+    def set_keypoints_2d(self, proj, targets, weights=None, bones=None, offsets=None):
+        """The detections of E_kp2d: proj (C,3,4), the cameras' projections (`projection_matrices`; pre-scale them and the targets
+        to fit in another unit than pixels), targets (F,C,K,2) per frame row and camera, weights (F,C,K), (C,K), (K,) or None
+        (ones): the detections' confidences.  A detection whose weight is not > 0 (zero, negative, NaN) is skipped, whatever its
+        target holds -- store a missing detection as weight 0 with any target, NaN included.  bones (K,) / offsets (K,3) as for
+        `set_keypoints`; needed only when `set_keypoints` has not set them, and when both are given they must be the same."""
+        F, J = self.n_frames, self.n_bones
+        if (bones is None) != (offsets is None):
+            raise ValueError("KinematicPoseRefiner.set_keypoints_2d: give bones and offsets together")
+        if bones is None and self._kp_geom is None:
+            raise ValueError("KinematicPoseRefiner.set_keypoints_2d: bones and offsets are needed (set_keypoints has not set them)")
+
+        def table(x, shape, what):
+            x = torch.as_tensor(x)
+            if tuple(x.shape) != shape:
+                raise ValueError("KinematicPoseRefiner.set_keypoints_2d: %s must be %s (got %s)" % (what, shape, tuple(x.shape)))
+            return x.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        if bones is not None:
+            bones = torch.as_tensor(bones)
+            K = int(bones.shape[0]) if bones.dim() == 1 else 0
+            if not 1 <= K <= MGR_FK_MAX_KEYPOINTS:
+                raise ValueError("KinematicPoseRefiner.set_keypoints_2d: bones must be (K,) with K 1 .. %d (got %s)"
+                                 % (MGR_FK_MAX_KEYPOINTS, tuple(bones.shape)))
+            if bones.dtype.is_floating_point or bones.dtype == torch.bool:
+                raise ValueError("KinematicPoseRefiner.set_keypoints_2d: bones must be integers")
+            host = [int(b) for b in bones.tolist()]
+            if any(not 0 <= b < J for b in host):
+                raise ValueError("KinematicPoseRefiner.set_keypoints_2d: a bone outside [0,%d)" % J)
+            off = table(offsets, (K, 3), "offsets")
+            self._same_geometry("set_keypoints_2d", host, off)
+            geom = (torch.tensor(host, dtype=torch.int32, device=self.device), off, host) if self._kp_geom is None else self._kp_geom
+        else:
+            geom = self._kp_geom
+        K = len(geom[2])
+        proj = torch.as_tensor(proj)
+        C = int(proj.shape[0]) if proj.dim() == 3 else 0
+        if C < 1:
+            raise ValueError("KinematicPoseRefiner.set_keypoints_2d: proj must be (C,3,4) with C >= 1 (got %s)" % (tuple(proj.shape),))
+        P, tgt = table(proj, (C, 3, 4), "proj"), table(targets, (F, C, K, 2), "targets")
+        if weights is None:
+            w = torch.ones((F, C, K), dtype=torch.float32, device=self.device)
+        else:
+            weights = torch.as_tensor(weights)
+            w = table(weights.expand(F, C, K) if tuple(weights.shape) in ((K,), (C, K)) else weights, (F, C, K), "weights")
+        self._kp_geom, self.kp2d = geom, (P, tgt, w)
 
     def set_reference(self, theta=None):
         """Re-anchors E_dev: theta_ref = theta (F,J+2,3), by default the current table."""
@@ -656,6 +749,10 @@ class KinematicPoseRefiner(_FrameRows):
         J, L = self.n_bones, lib()
         if self.w_kp != 0.0 and self.kp is None:
             raise ValueError("KinematicPoseRefiner: w_kp is non-zero and no keypoints are set (set_keypoints)")
+        if self.w_kp2d != 0.0:
+            values = self._terms2d(V, U, listed_t, rows, fov, d_transforms, g, self.weights, self.w_kp, self.w_kp2d, None)
+            self.last_terms, self.last_prior, self.last_kp2d = values[:4], values[3], values[4]
+            return
         kp = self.kp if self.w_kp != 0.0 else (None, None, None, None)
         K = int(kp[0].shape[0]) if kp[0] is not None else 0
         nbytes = int(L.mgr_fk_terms_workspace_bytes(U, J, K))
@@ -669,8 +766,48 @@ class KinematicPoseRefiner(_FrameRows):
               "mgr_fk_backward_terms")
         self.last_terms, self.last_prior = values, values[3]
 
+    def _terms2d(self, V, U, listed_t, rows, fov, d_transforms, g, weights, w_kp, w_kp2d, dist):
+        """One call of mgr_fk_backward_terms2d into g (U,J+2,3) and dist ((U,C,K) or None) -> values (5,) device double."""
+        J, L = self.n_bones, lib()
+        if self.kp2d is None:
+            raise ValueError("KinematicPoseRefiner: the 2-D keypoint term needs detections (set_keypoints_2d)")
+        bones, off = self._kp_geom[:2]
+        K, C = int(bones.shape[0]), int(self.kp2d[0].shape[0])
+        tgt3, w3 = (self.kp[2], self.kp[3]) if w_kp != 0.0 else (None, None)
+        nbytes = int(L.mgr_fk_terms2d_workspace_bytes(U, J, K, C))
+        if self._terms_ws is None or self._terms_ws.numel() < nbytes:
+            self._terms_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        values = torch.empty(5, dtype=torch.float64, device=self.device)
+        check(L.mgr_fk_backward_terms2d(V, J, self.n_frames, U, ptr(listed_t), ptr(rows), ptr(fov), ptr(self.rest), ptr(self.local),
+                                        ptr(self.parents), ptr(self.base), ptr(self.theta), ptr(self.mask), ptr(d_transforms), ptr(g),
+                                        ptr(self.theta_ref), ptr(self.neighbours), *weights, K, ptr(bones), ptr(off), ptr(tgt3), ptr(w3),
+                                        w_kp, C, ptr(self.kp2d[0]), ptr(self.kp2d[1]), ptr(self.kp2d[2]), w_kp2d, self.kp2d_delta,
+                                        self.kp2d_zmin, ptr(dist), ptr(values), ptr(self._terms_ws), self._terms_ws.numel(), stream()),
+              "mgr_fk_backward_terms2d")
+        return values
+
+    def reprojection_error(self, frames=None):
+        """(U,C,K) device float32: the distances |P_c [p_k; 1] dehomogenised - t[f,c,k]| of the detections of `set_keypoints_2d` at
+        the current angles, for the frame rows `frames` in the order given (default: all rows), NaN where a detection is skipped
+        (weight not > 0, or not `kp2d_zmin` in front of its camera).  One call of mgr_fk_backward_terms2d with the 2-D term
+        alone; its gradient goes to a scratch buffer: nothing is stepped, and `last_terms`, `last_prior`, `last_kp2d`, the moments
+        and `steps` stay as they are.  Nothing is read back."""
+        if self.kp2d is None:
+            raise ValueError("KinematicPoseRefiner.reprojection_error: no detections are set (set_keypoints_2d)")
+        F, J = self.n_frames, self.n_bones
+        listed = [int(f) for f in (range(F) if frames is None else frames)]
+        if not listed or min(listed) < 0 or max(listed) >= F:
+            raise ValueError("KinematicPoseRefiner.reprojection_error: frames must be rows in [0,%d), at least one" % F)
+        U, C, K = len(listed), int(self.kp2d[0].shape[0]), int(self._kp_geom[0].shape[0])
+        listed_t = torch.tensor(listed, dtype=torch.int32, device=self.device)
+        g = torch.empty((U, J + 2, 3), dtype=torch.float32, device=self.device)
+        dist = torch.empty((U, C, K), dtype=torch.float32, device=self.device)
+        self._terms2d(0, U, listed_t, None, None, None, g, (0.0, 0.0, 0.0, 0.0), 0.0, self.w_kp2d if self.w_kp2d != 0.0 else 1.0, dist)
+        return dist
+
     def fit_keypoints(self, steps, frames=None, lr_rot=None, lr_trans=None):
-        """`steps` Adam steps of the terms alone -- mgr_fk_backward_terms without d_transforms, then mgr_fk_adam -- on the frame
+        """`steps` Adam steps of the terms alone -- mgr_fk_backward_terms (mgr_fk_backward_terms2d with w_kp2d on; the 2-D term alone
+        is a fit to the cameras' detections) without d_transforms, then mgr_fk_adam -- on the frame
         rows `frames` (default: all), with the configured weights: the best constrained angles for the keypoints, found without
         rendering a frame.  lr_rot / lr_trans default to the refiner's.  The moments and the step count of this loop are its own:
         `m`, `v` and `steps` of training are untouched, only `theta` moves.  Nothing is read back; `last_terms` holds the values
