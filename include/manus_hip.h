@@ -864,6 +864,35 @@ int mgr_fk_backward_terms2d(int V, int J, int F, int U, const int32_t* frames_li
                             double w_kp2d, double delta, double z_min, float* kp2d_dist,
                             double* values, void* workspace, size_t workspace_bytes, void* stream);
 
+/* mgr_triangulate: robust multi-view triangulation of F * K independent (frame, keypoint) problems -- the input side of the two
+ * keypoint terms above.  proj (C,3,4), targets (F,C,K,2) and weights (F,C,K) in the layouts of mgr_fk_backward_terms2d's kp2d_*
+ * tables; C <= MGR_TRI_MAX_CAMERAS (a camera is a lane of the problem's wave, a set of cameras one ballot).  Deterministic, no
+ * sampling; the full definition stands above the entry in csrc/triangulate.hip.  In short, per problem:
+ *   active     s > (float)min_conf (NaN: not), both target coordinates finite, both plane norms finite and > 0
+ *   planes     a_u = t_x P2 - P0, a_v = t_y P2 - P1, each divided by the norm of its first three components -> (n, d), fp32
+ *   solve      N = sum w (n_u n_u^T + n_v n_v^T), b = -sum w (d_u n_u + d_v n_v); accepted iff det N > det_min (tr N / 3)^3;
+ *              X = adj(N) b / det N in closed form
+ *   inlier     active, q[2] > (float)z_min and |q[:2] / q[2] - t| < (float)tau with q = P_c [X; 1], fp32
+ *   seed       the pairs a < b of active cameras in lexicographic order, X_ab = solve({a,b}, 1) in fp32, accepted only with both
+ *              cameras' own depths above z_min; the FIRST pair with the most inliers; none accepted: invalid
+ *   refit      refit_rounds times: S = inliers(X); |S| < 2 or a rejected solve: invalid; X = solve(S, s), products and sums in fp64
+ *              over the cameras in ascending order, X rounded to fp32.  Then S = inliers(X), the final set
+ *   polish     gn_iters Gauss-Newton steps on sum_S s |u(X) - t|^2 over the fixed S: residuals and Jacobians fp32, H and g in fp64,
+ *              the same determinant test on H; a rejected H ends the polish and keeps X
+ * Outputs: xyz (F,K,3) = X after the polish; conf (F,K) = sum_S s / |S|; n_inliers (F,K) = |S|; inliers (F,C,K) bytes 0 / 1 = S, the
+ * set the fit used, classified BEFORE the polish; dist (F,C,K) = the pixel distance at the final X, AFTER the polish, for active
+ * cameras with q[2] > z_min there, NaN otherwise.  inliers and dist may be NULL.  A problem that is invalid by the rules above,
+ * or whose |S| < min_views, gives xyz = NaN, conf = 0, n_inliers = 0, inliers = 0, dist = NaN and nothing else.  No atomics, no
+ * workspace: equal bits run to run, and a problem's bits do not depend on the other problems of the call.
+ * Refused before any launch, nothing written: F, C or K < 1; C > MGR_TRI_MAX_CAMERAS; a NULL proj, targets, weights, xyz, conf or
+ * n_inliers; tau, z_min or det_min not finite or not > 0; min_conf negative or not finite; min_views < 2; refit_rounds < 1;
+ * gn_iters < 0; F * K above 2^30. */
+#define MGR_TRI_MAX_CAMERAS 64
+int mgr_triangulate(int F, int C, int K, const float* proj, const float* targets, const float* weights,
+                    double tau, double min_conf, int min_views, double z_min, double det_min,
+                    int refit_rounds, int gn_iters,
+                    float* xyz, float* conf, int32_t* n_inliers, uint8_t* inliers, float* dist, void* stream);
+
 /* uv =(K*E*[x;1])[:2]/z for N points; K (3,3), E (3,4) row-major. */
 int mgr_project_points(int N, const float* xyz, const float* K9, const float* E12, float* uv,
                        void* stream);

@@ -20,6 +20,7 @@ _LIB = None
 MGR_CAM_FLOATS = 40
 MGR_MAX_BONES = 32
 MGR_FK_MAX_KEYPOINTS = 64
+MGR_TRI_MAX_CAMERAS = 64      # cameras of one mgr_triangulate call (a camera is a lane of one wave)
 MGR_FRAMES_MAX_VIEWS = 16     # views per launch of mgr_frames_decode (the entry itself loops over larger calls)
 
 # The words of the rasterizer's ABI, value for value those of include/manus_hip.h (tests/test_abi_constants.py compares them).
@@ -138,6 +139,8 @@ SIGNATURES = {
     "mgr_fk_backward_terms2d": (c_int, [c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_vp, c_vp] + [ctypes.c_double] * 4
                                 + [c_int] + [c_vp] * 4 + [ctypes.c_double] + [c_int] + [c_vp] * 3 + [ctypes.c_double] * 3 + [c_vp]
                                 + [c_vp, c_vp, c_sz, c_vp]),
+    "mgr_triangulate": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double,
+                                ctypes.c_double, c_int, c_int] + [c_vp] * 5 + [c_vp]),
     "mgr_project_points": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mgr_dilate_mask": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "mgr_points_outside_mask": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),

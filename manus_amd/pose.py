@@ -10,11 +10,14 @@ no autograd graph, no read-back), which `engine.Trainer(pose=...)` schedules.
 `KinematicPoseRefiner` has the same surface on another parametrisation: joint angles per frame through forward kinematics on
 the device (csrc/fk.hip), 23 constrained angles for the hand (`dof_mask`), optionally a global rotation and translation, joint
 limits (`joint_limits`).  Where the free-form correction can pull the skeleton apart at the joints, this one keeps bone lengths
-and joint centres by construction.
+and joint centres by construction.  `triangulate_keypoints` (csrc/triangulate.hip) is the input side of its keypoint terms: 2-D
+detections of many cameras into 3-D keypoints with outlier rejection, on the device.
 
 The reference's config/model/pose_optimizer.yaml names `src.models.pose_optimizer`, which was never released: the free-form
 correction has no reference counterpart; the kinematic one follows that config's parametrisation and the host machinery of
 src/utils/transforms.py (euler_angles_to_armature_space, apply_constraints_to_poses, apply_limits_to_poses)."""
+import collections
+
 import torch
 
 from ._lib import MGR_FK_MAX_KEYPOINTS, MGR_MAX_BONES, check, lib, ptr, stream
@@ -431,6 +434,66 @@ def project_keypoints(proj, xyz):
     return q[..., :2] / q[..., 2:]
 
 
+Triangulation = collections.namedtuple("Triangulation", "xyz conf n_inliers inliers dist")
+Triangulation.__doc__ = """What `triangulate_keypoints` returns, all on the device: xyz (F,K,3) float32 (NaN for an invalid problem), conf (F,K)
+float32 (the mean weight of the inliers; 0 for an invalid problem), n_inliers (F,K) int32, inliers (F,C,K) bool -- the set the fit
+used, classified before the polish --, dist (F,C,K) float32 -- the pixel distance at the final point, after the polish, NaN for
+a camera that is not active or not in front."""
+
+
+def triangulate_keypoints(proj, targets, weights=None, tau=25.0, min_conf=0.1, min_views=3, z_min=1e-2, det_min=1e-6, refit_rounds=2,
+                          gn_iters=2, device=None):
+    """Robust multi-view triangulation on the device (mgr_triangulate, csrc/triangulate.hip; the algorithm stands above the entry
+    there): proj (C,3,4) (`projection_matrices`), targets (F,C,K,2), weights (F,C,K), (C,K), (K,) or None (ones) -- the layouts of
+    `KinematicPoseRefiner.set_keypoints_2d` -- -> `Triangulation`.  Per (frame, keypoint): the pair of cameras whose triangulated
+    point the most detections agree with to `tau` pixels seeds the set, `refit_rounds` weighted least-squares fits on the planes of
+    the agreeing detections and `gn_iters` Gauss-Newton steps on their reprojection error follow.  A detection takes part only
+    with a weight > `min_conf` and a finite target; a point needs `min_views` agreeing cameras, `z_min` in front of each.
+    Deterministic; at most 64 cameras.  tau / min_conf / min_views default to what the reference's preprocess/scripts/keypoints_3d.py
+    passes.  Tensors already on the device in float32 are used as they are; nothing is read back."""
+    from ._lib import MGR_TRI_MAX_CAMERAS
+    proj, targets = torch.as_tensor(proj), torch.as_tensor(targets)
+    C = int(proj.shape[0]) if proj.dim() == 3 else 0
+    if C < 1 or tuple(proj.shape) != (C, 3, 4):
+        raise ValueError("triangulate_keypoints: proj must be (C,3,4) with C >= 1 (got %s)" % (tuple(proj.shape),))
+    if C > MGR_TRI_MAX_CAMERAS:
+        raise ValueError("triangulate_keypoints: at most %d cameras (got %d)" % (MGR_TRI_MAX_CAMERAS, C))
+    if targets.dim() != 4 or targets.shape[1] != C or targets.shape[3] != 2 or targets.shape[0] < 1 or targets.shape[2] < 1:
+        raise ValueError("triangulate_keypoints: targets must be (F,%d,K,2) with F, K >= 1 (got %s)" % (C, tuple(targets.shape)))
+    F, K = int(targets.shape[0]), int(targets.shape[2])
+    for name, x in (("tau", tau), ("z_min", z_min), ("det_min", det_min)):
+        if not (float(x) > 0.0 and float(x) != float("inf")):
+            raise ValueError("triangulate_keypoints: %s must be finite and > 0 (got %r)" % (name, x))
+    if not (float(min_conf) >= 0.0 and float(min_conf) != float("inf")):
+        raise ValueError("triangulate_keypoints: min_conf must be finite and >= 0 (got %r)" % (min_conf,))
+    for name, x, lo in (("min_views", min_views, 2), ("refit_rounds", refit_rounds, 1), ("gn_iters", gn_iters, 0)):
+        if int(x) != x or int(x) < lo:
+            raise ValueError("triangulate_keypoints: %s must be an integer >= %d (got %r)" % (name, lo, x))
+    if device is None:
+        device = proj.device if proj.device.type == "cuda" else "cuda"
+    device = torch.device(device)
+    if weights is None:
+        w = torch.ones((F, C, K), dtype=torch.float32, device=device)
+    else:
+        weights = torch.as_tensor(weights)
+        if tuple(weights.shape) in ((K,), (C, K)):
+            weights = weights.expand(F, C, K)
+        if tuple(weights.shape) != (F, C, K):
+            raise ValueError("triangulate_keypoints: weights must be (F,C,K), (C,K) or (K,) = %s (got %s)" % ((F, C, K), tuple(weights.shape)))
+        w = weights.detach().to(device=device, dtype=torch.float32).contiguous()
+    P = proj.detach().to(device=device, dtype=torch.float32).contiguous()
+    t = targets.detach().to(device=device, dtype=torch.float32).contiguous()
+    xyz = torch.empty((F, K, 3), dtype=torch.float32, device=device)
+    conf = torch.empty((F, K), dtype=torch.float32, device=device)
+    n_inliers = torch.empty((F, K), dtype=torch.int32, device=device)
+    inliers = torch.empty((F, C, K), dtype=torch.uint8, device=device)
+    dist = torch.empty((F, C, K), dtype=torch.float32, device=device)
+    check(lib().mgr_triangulate(F, C, K, ptr(P), ptr(t), ptr(w), float(tau), float(min_conf), int(min_views), float(z_min), float(det_min),
+                                int(refit_rounds), int(gn_iters), ptr(xyz), ptr(conf), ptr(n_inliers), ptr(inliers), ptr(dist), stream()),
+          "mgr_triangulate")
+    return Triangulation(xyz, conf, n_inliers, inliers.view(torch.bool), dist)
+
+
 class KinematicPoseRefiner(_FrameRows):
     """Pose refinement in joint angles: theta (F,J+2,3) per frame row -- row 0 the global Euler angles, rows 1..J the bones'
     Euler angles (XYZ intrinsic, `transforms.euler_angles_to_matrix`), row J+1 the global translation -- through forward
@@ -620,6 +683,33 @@ class KinematicPoseRefiner(_FrameRows):
             weights = torch.as_tensor(weights)
             w = table(weights.expand(F, C, K) if tuple(weights.shape) in ((K,), (C, K)) else weights, (F, C, K), "weights")
         self._kp_geom, self.kp2d = geom, (P, tgt, w)
+
+    def triangulate(self, set_3d=True, mask_2d=True, **kw):
+        """`triangulate_keypoints` on the tables `set_keypoints_2d` stored (keywords: tau, min_conf, min_views, z_min, det_min,
+        refit_rounds, gn_iters) -> its `Triangulation`.  The detections so feed both keypoint terms:
+        set_3d: the triangulated points become E_kp's targets and their confidences its weights, on the shared bones and offsets
+        -- what `set_keypoints(bones, offsets, xyz, conf)` stores; an invalid keypoint has weight 0 and a NaN target, which the
+        term skips exactly;
+        mask_2d: the stored 2-D weights are multiplied by `inliers`, so E_kp2d no longer sees a detection the consensus rejected
+        (Huber's function only down-weights it).  Calling it again triangulates the masked weights.
+        Nothing is read back."""
+        if self.kp2d is None:
+            raise ValueError("KinematicPoseRefiner.triangulate: no detections are set (set_keypoints_2d)")
+        P, tgt, w = self.kp2d
+        res = triangulate_keypoints(P, tgt, w, device=self.device, **kw)
+        self._adopt(res, set_3d, mask_2d)
+        return res
+
+    def _adopt(self, res, set_3d, mask_2d):
+        """The bookkeeping of `triangulate`: tensors of the tables' shapes on the refiner's device in, `kp` / `kp2d` replaced."""
+        P, tgt, w = self.kp2d
+        F, C, K = tuple(w.shape)
+        if tuple(res.xyz.shape) != (F, K, 3) or tuple(res.conf.shape) != (F, K) or tuple(res.inliers.shape) != (F, C, K):
+            raise ValueError("KinematicPoseRefiner.triangulate: the result is not of the stored detections' shape %s" % ((F, C, K),))
+        if set_3d:
+            self.kp = (self._kp_geom[0], self._kp_geom[1], res.xyz, res.conf)
+        if mask_2d:
+            self.kp2d = (P, tgt, w * res.inliers.to(w.dtype))
 
     def set_reference(self, theta=None):
         """Re-anchors E_dev: theta_ref = theta (F,J+2,3), by default the current table."""
