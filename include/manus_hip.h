@@ -1264,7 +1264,10 @@ int mgr_frames_decode(int V, int H, int W, int k, const uint8_t* pool, int64_t p
  * 1-based step number of this update (bias correction).
  *
  * mgr_reset_opacity: reset_opacity, gaussian.py:148-165 (opacity <-
- * inverse_sigmoid(min(sigmoid(opacity), 0.01)), both moments zeroed).
+ * inverse_sigmoid(min(sigmoid(opacity), 0.01)), both moments zeroed).  The fp32 expression of
+ * the reference, edge rows included: a NaN logit stays NaN (torch.min propagates it), -inf stays
+ * -inf, +inf is clamped like any logit above log(0.01 / 0.99), and a logit below about -88.7
+ * becomes -inf (exp(-x) overflows in fp32, so sigmoid is 0 there in torch's fp32 too).
  *
  * mgr_densify_plan + mgr_densify_apply: densify_and_prune, gaussian.py:310-333
  * (clone :288-308, split with N=2 :254-286, prune :183-200, optimizer-state

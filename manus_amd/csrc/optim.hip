@@ -58,10 +58,13 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
                                          float inv_sqrt_bc2, float eps, float step_size) {
     // torch: exp_avg.lerp_(grad, 1-b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1-b2);
     //        denom = exp_avg_sq.sqrt() / sqrt(bc2) + eps; param.addcdiv_(exp_avg, denom, value=-step_size)
-    m = m + (g - m) * omb1;
-    v = v * b2 + omb2 * (g * g);
-    const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-    p = p - step_size * (m / denom);
+    // The fused multiply-adds are spelled out: left to the compiler's contraction, the float4 path fused v * b2 + omb2 * g^2
+    // and the scalar path (misaligned pointer, tail) did not, so an element's bits depended on which path reached it and a
+    // step on element ranges (GaussianOptimizer.step_range) was not the plain step.  These are the float4 path's roundings.
+    m = fmaf(g - m, omb1, m);
+    v = fmaf(v, b2, omb2 * (g * g));
+    const float denom = fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+    p = fmaf(-step_size, m / denom, p);
 }
 
 __global__ __launch_bounds__(256) void k_adam(AdamGroups G, long long total_quads, float omb1, float b2, float omb2,
@@ -183,7 +186,9 @@ __global__ __launch_bounds__(256) void k_reset_opacity(int N, float* __restrict_
                                                        float* __restrict__ v) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const float s = fminf(1.0f / (1.0f + expf(-op[i])), 0.01f);
+    // the reference's fp32 expression, overflow included: below about -88.7 expf(-x) is inf, the sigmoid 0 and the result -inf
+    float s = 1.0f / (1.0f + expf(-op[i]));
+    s = s > 0.01f ? 0.01f : s;   // torch.min(a, b) propagates NaN (fminf would return 0.01 for a NaN logit)
     op[i] = logf(s / (1.0f - s));
     m[i] = 0.f;
     v[i] = 0.f;
