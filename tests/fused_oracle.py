@@ -53,7 +53,7 @@ def _ulps(a, b):
 
 
 def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5, sigma_range=(2e-3, 8e-3), account_flips=True,
-                        device=DEV, n_cameras=None, g_scale=1.0, own_projection=False, mutate=None):
+                        device=DEV, n_cameras=None, g_scale=1.0, own_projection=False, mutate=None, cameras=None):
     """One fused forward + backward of `views` views against the oracle on identical blend inputs.  Returns a dict of
     measured deviations; asserts nothing except exact integer state (visibility counts, radii).
 
@@ -64,7 +64,11 @@ def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5,
 
     mutate(params) changes the scene's CPU leaves in place before anything reads them (tests/regimes.py): the upload and
     the torch restatement both see the mutated leaves.  res["regime"] holds, per view, regimes.regime_facts of the
-    oracle's blend (and whether the oracle's own gradient rows of the Gaussians below 1/255 are exactly zero)."""
+    oracle's blend (and whether the oracle's own gradient rows of the Gaussians below 1/255 are exactly zero).
+
+    cameras(scene) replaces or appends entries of the CPU scene's camera list in place, before anything reads it (tests/fused_shapes.py:
+    a camera turned away from the scene; one that appends also appends the pose rows of its view).  A view that sees nothing
+    adds nothing to the projection figures."""
     from manus_amd import rasterizer as rz
     from manus_amd.engine import HipViewCompute
     from manus_amd.synthetic import camera_table, make_scene
@@ -74,6 +78,8 @@ def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5,
                     cam_radius=cam_radius, sigma_range=sigma_range, device="cpu")
     if mutate is not None:
         mutate(sc["params"])
+    if cameras is not None:
+        cameras(sc)
     scd = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in sc.items() if k != "params"}
     scd["params"] = {k: v.to(device) for k, v in sc["params"].items()}
     ct = camera_table(sc["cameras"], device)
@@ -179,9 +185,10 @@ def run_fused_vs_oracle(kind, views, n, W, H, seed, grid_res=24, cam_radius=0.5,
                             xy_max=float(np.abs(geo["xy"][both] - r[both, 0:2]).max()) if both.any() else 0.0))
             ro.close()
         pix = ((ndc.detach().numpy() + 1.0) * np.array([W, H]) - 1.0) * 0.5
-        res["proj_pix"] = max(res["proj_pix"], float(np.abs(pix[visible] - r[visible, 0:2]).max()))
-        res["proj_conic"] = max(res["proj_conic"], max_rel_err(conic.detach().numpy()[visible], r[visible, 2:5]))
-        res["proj_col"] = max(res["proj_col"], float(np.abs(o["colors"].detach().numpy()[visible] - r[visible, 6:9]).max()))
+        if visible.any():
+            res["proj_pix"] = max(res["proj_pix"], float(np.abs(pix[visible] - r[visible, 0:2]).max()))
+            res["proj_conic"] = max(res["proj_conic"], max_rel_err(conic.detach().numpy()[visible], r[visible, 2:5]))
+            res["proj_col"] = max(res["proj_col"], float(np.abs(o["colors"].detach().numpy()[visible] - r[visible, 6:9]).max()))
         tv = torch.tensor(visible[:, None].astype(np.float32))
         chain = chain + ((ndc * torch.tensor(b["means2D"][:, :2])).mul(tv).sum()
                          + (conic * wts * torch.tensor(b["conic"])).mul(tv).sum()

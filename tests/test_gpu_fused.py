@@ -20,18 +20,21 @@ def _scene(kind, n=4000, views=3):
 
 
 def check_fused_equals_modular(sc, ct):
-    """Three views at 96 x 64 of a device scene through both routes (shared with tests/test_gpu_raster_regimes.py)."""
+    """Every view of a device scene (three at 96 x 64 for the callers here and in tests/test_gpu_raster_regimes.py; the sizes
+    are the scene's: tests/test_gpu_fused_shapes.py) through both routes."""
     from manus_amd.engine import HipViewCompute
-    tg = torch.rand((3, 3, 64, 96), device=DEV)
+    V, H, W = int(ct.shape[0]), int(sc["height"]), int(sc["width"])
+    ids = list(range(V))
+    tg = torch.rand((V, 3, H, W), device=DEV)
     mod = HipViewCompute(sc, tg, ct, fused=False)
     fus = HipViewCompute(sc, tg, ct, fused=True)
     with torch.no_grad():
-        im_m, rad_m, _ = mod.forward_views([0, 1, 2])
-        im_f, rad_f = fus.forward_views_fused([0, 1, 2])
+        im_m, rad_m, _ = mod.forward_views(ids)
+        im_f, rad_f = fus.forward_views_fused(ids)
     assert torch.equal(rad_m, rad_f)
     d = (im_m - im_f).abs()
     assert float(d.max()) < 5e-3 and float(d.mean()) < 2e-6
-    om, of = mod([0, 1, 2], 1.0 / 3), fus([0, 1, 2], 1.0 / 3)
+    om, of = mod(ids, 1.0 / V), fus(ids, 1.0 / V)
     assert abs(float(om["loss"]) - float(of["loss"])) < 1e-6
     for k in om["grads"]:
         a, b = of["grads"][k].cpu().numpy().astype(np.float64), om["grads"][k].cpu().numpy().astype(np.float64)
@@ -53,7 +56,7 @@ def check_fused_run_to_run_determinism(sc, ct, views):
     """Two fused steps of one compute object: bitwise equal gradients (shared with tests/test_gpu_raster_regimes.py)."""
     from manus_amd.engine import HipViewCompute
     ids = list(range(views))
-    tg = torch.rand((views, 3, 64, 96), device=DEV)
+    tg = torch.rand((views, 3, int(sc["height"]), int(sc["width"])), device=DEV)
     hc = HipViewCompute(sc, tg, ct, fused=True)
     a = hc(ids, 1.0 / views)
     a = {k: ({n: g.clone() for n, g in v.items()} if isinstance(v, dict) else v.clone()) for k, v in a.items()}
