@@ -1477,10 +1477,14 @@ int mgr_ceval_collage(int V, int H, int W, int M, const uint8_t* gt_rgba, const 
  *   distance (replaces torch.cdist(points, mano_verts).topk(k, largest=False), train_utils.py:70-72; ties keep the lower
  *   index), out (n,C) = mean of rows[idx] (m,C) added nearest first in fp32 (np.mean(init_weights[indices], axis=1),
  *   :73), out_idx (n,k) int32 the indices (nearest first; -1 beyond m).  Either output may be NULL.  1 <= k <= 32.
+ *   A neighbour is a reference whose fp32 squared distance is below 3e38; the mean is over the neighbours there are, and a
+ *   point without any (a non-finite coordinate, every squared distance overflowing, m = 0 -- refs and rows may then be
+ *   NULL) gets indices -1 and a NaN mean.
  * mgr_mesh_sdf: signed distance (n,) of the points to the triangle mesh verts (nv,3) / faces (nf,3) int32, positive
  *   inside (replaces pysdf.SDF(verts, faces)(points), train_utils.py:55-58; pysdf is an external package that is not in
  *   this image: parity unpinned).  |distance| is the exact point-triangle minimum; the sign comes from the generalised
- *   winding number (|sum of solid angles| / 4 pi > 1/2), also written to out_winding (n,) when not NULL.
+ *   winding number (|sum of solid angles| / 4 pi > 1/2), also written to out_winding (n,) when not NULL.  A mesh
+ *   without faces (nf = 0) gives -sqrt(3e38) and winding 0 for every point.
  * ------------------------------------------------------------------------ */
 int mgr_knn_mean_rows(int n, const float* points, int m, const float* refs, const float* rows, int C, int k, float* out,
                       int32_t* out_idx, void* stream);

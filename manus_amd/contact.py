@@ -18,7 +18,7 @@ from ._lib import ManusHipError, check, f32c, lib, ptr, stream
 
 def _nearest(pt1, pt2, want_idx):
     pt1, pt2 = f32c(pt1), f32c(pt2)
-    if not pt1.is_cuda:
+    if not pt1.is_cuda or not pt2.is_cuda:
         raise ManusHipError("manus_amd.contact needs GPU tensors; there is no CPU fallback")
     if pt1.dim() != 2 or pt1.shape[1] != 3 or pt2.dim() != 2 or pt2.shape[1] != 3:
         raise ManusHipError("contact: points are (N,3)")

@@ -20,7 +20,7 @@
 // ---------------------------------------------------------------------------------------------------------------------
 // k nearest rows.  The running list is kept sorted (nearest first) in registers / scratch; a candidate enters only when it
 // beats the current k-th distance (strictly: among equal distances the lower index stays, the order torch.topk yields
-// for exact ties is unspecified).
+// for exact ties is unspecified) and goes behind the entries as near as itself, so equal distances stay in index order.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int K>
 __global__ __launch_bounds__(MS_T) void k_knn_mean_rows(int n, const float* __restrict__ pts, int m,
@@ -51,11 +51,14 @@ __global__ __launch_bounds__(MS_T) void k_knn_mean_rows(int n, const float* __re
             if (d < bd[k - 1]) {
                 int id = j0 + t;
                 if (K > 0) {   // fully unrolled compare-exchange chain: everything stays in registers
+                    bool placed = false;   // once the candidate has its slot every later entry moves down one, equal ones too:
+                                           // comparing the displaced entry strictly would drop it and keep a later, equal one
 #pragma unroll
                     for (int j = 0; j < K; ++j) {
-                        if (d < bd[j]) {
+                        if (placed || d < bd[j]) {
                             const float td = bd[j]; const int ti = bi[j];
                             bd[j] = d; bi[j] = id; d = td; id = ti;
+                            placed = true;
                         }
                     }
                 } else {
@@ -67,18 +70,21 @@ __global__ __launch_bounds__(MS_T) void k_knn_mean_rows(int n, const float* __re
         }
     }
     if (i >= n) return;
-    // a query with a non-finite coordinate has no nearest row (no distance beats the sentinel): NaN / -1 like torch.cdist +
-    // topk + mean propagate it, not rows[0] k times; with fewer than k rows the mean is over the rows there are
+    // A neighbour is a reference whose fp32 squared distance beat the sentinel; the list is sorted, so the slots that still
+    // hold the sentinel are its tail.  The mean is over the neighbours there are (fewer than k rows, or some distances at
+    // or above 3e38); a query with none -- a non-finite coordinate, every squared distance overflowing, m = 0 -- gets
+    // NaN / -1, like torch.cdist + topk + mean propagate a NaN, not rows[0] k times or a finite 0.
     const int kk = min(k, m);
-    const bool finite = px - px == 0.f && py - py == 0.f && pz - pz == 0.f;
+    int nv = 0;
+    for (int j = 0; j < kk; ++j) nv += bd[j] < 3.0e38f ? 1 : 0;
     if (out_idx)
-        for (int j = 0; j < k; ++j) out_idx[(size_t)i * k + j] = (finite && j < kk) ? bi[j] : -1;
+        for (int j = 0; j < k; ++j) out_idx[(size_t)i * k + j] = j < nv ? bi[j] : -1;
     if (out) {
-        const float inv = 1.0f / (float)(kk > 0 ? kk : 1);
+        const float inv = 1.0f / (float)(nv > 0 ? nv : 1);
         for (int c = 0; c < C; ++c) {
             float s = 0.f;
-            for (int j = 0; j < kk; ++j) s += rows[(size_t)bi[j] * C + c];
-            out[(size_t)i * C + c] = finite ? s * inv : __builtin_nanf("");
+            for (int j = 0; j < nv; ++j) s += rows[(size_t)bi[j] * C + c];
+            out[(size_t)i * C + c] = nv > 0 ? s * inv : __builtin_nanf("");
         }
     }
 }
@@ -156,7 +162,9 @@ __global__ __launch_bounds__(MS_T) void k_mesh_sdf(int n, const float* __restric
     const int tid = threadIdx.x, i = blockIdx.x * MS_T + tid;
     float px = 0.f, py = 0.f, pz = 0.f;
     if (i < n) { px = pts[3 * (size_t)i]; py = pts[3 * (size_t)i + 1]; pz = pts[3 * (size_t)i + 2]; }
-    float best = 3.0e38f, omega = 0.f;
+    // the solid angles are summed with a compensation term (Kahan): a plain fp32 running sum near 4 pi loses up to half an
+    // ulp of 12.57 per face, 9e-7 of the winding number over 513 faces where the terms themselves are good to 2e-7
+    float best = 3.0e38f, omega = 0.f, omega_lost = 0.f;
     for (int f0 = 0; f0 < nf; f0 += MS_T) {
         const int cnt = min(MS_T, nf - f0);
         __syncthreads();
@@ -169,7 +177,10 @@ __global__ __launch_bounds__(MS_T) void k_mesh_sdf(int n, const float* __restric
         for (int t = 0; t < cnt; ++t) {
             const MsTri tr = s_tri[t];
             best = fminf(best, ms_tri_dist2(px, py, pz, tr));
-            omega += ms_solid_angle(px, py, pz, tr);
+            const float term = ms_solid_angle(px, py, pz, tr) - omega_lost;
+            const float sum = omega + term;
+            omega_lost = (sum - omega) - term;
+            omega = sum;
         }
     }
     if (i >= n) return;
@@ -183,7 +194,8 @@ extern "C" int mgr_knn_mean_rows(int n, const float* points, int m, const float*
                                  float* out, int32_t* out_idx, void* stream_) {
     if (n < 0 || m < 0 || k < 1 || k > MS_KMAX || (out && C < 1)) return mgr_fail(MGR_EINVAL, "mgr_knn_mean_rows: bad sizes (1 <= k <= 32)");
     if (n == 0) return MGR_OK;
-    if (!points || (m > 0 && !refs) || (out && !rows) || (!out && !out_idx)) return mgr_fail(MGR_EINVAL, "mgr_knn_mean_rows: null pointer");
+    // m = 0: nothing is read from refs or rows, which may then be null (an empty tensor's pointer)
+    if (!points || (m > 0 && (!refs || (out && !rows))) || (!out && !out_idx)) return mgr_fail(MGR_EINVAL, "mgr_knn_mean_rows: null pointer");
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((n + MS_T - 1) / MS_T), block(MS_T);
     MGR_PROF("k_knn_mean_rows", stream);

@@ -57,7 +57,9 @@ def knn_mean_rows(points, refs, rows, k, want_idx=False):
 
 
 def mesh_sdf(points, verts, faces, want_winding=False):
-    """Signed distance (positive inside) of the points (n, 3) to the mesh verts (nv, 3) / faces (nf, 3)."""
+    """Signed distance (positive inside) of the points (n, 3) to the mesh verts (nv, 3) / faces (nf, 3).  A mesh without
+    faces (nf = 0) has no surface and no inside: every point gets -sqrt(3e38) (the kernel's "no face yet" squared distance,
+    rooted; about -1.73e19) and winding 0."""
     points, verts = f32c(points), f32c(verts)
     if not points.is_cuda:
         raise ManusHipError("mesh_sdf needs GPU tensors; there is no CPU fallback")
