@@ -923,6 +923,64 @@ int mgr_knn3_mean_dist2(int N, const float* xyz, float* out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Exact k nearest neighbours of every point among the points themselves (knn_k.hip).
+ *
+ * xyz (N,3) device floats, 1 <= k <= MGR_KNN_MAX_K.  The squared distance is fp32, (dx*dx + dy*dy) + dz*dz with no
+ * contraction (mgr_contact_dist's rule).  The neighbours of i are the points j with the smallest keys (d2, j): the lower
+ * index wins a tie.  include_self = 1 keeps i itself (d2 = 0: what a kd-tree query at a stored point returns);
+ * include_self = 0 excludes i by index, not by distance.  A point with a non-finite coordinate is nobody's neighbour and
+ * has no neighbours; n_i = min(k, number of finite candidates).
+ *   out_idx (N,k) int32, out_d2 (N,k)   row i in ascending key order; slots beyond n_i hold -1 / +inf
+ *   out_sigma (N)    sqrtf((float)(S / n_i)), S the fp64 sum of the row's d2 taken in an order that is a function of the
+ *                    sorted row alone (every 64th entry from each of 64 starts, nearest first, then a fixed butterfly of the
+ *                    64 partial sums); NaN for n_i = 0
+ *   out_count (N)    int32 n_i
+ * Every output may be NULL.  N = 0 is valid (nothing is launched); N < k, N = k and N = k + 1 are ordinary cases.
+ * Results are the same bits run to run: nothing depends on the order the grid's cells were filled in.
+ * workspace_bytes >= mgr_knn_self_workspace_bytes(N, k) (a grid of at most max(N, 64) cells and 16 bytes per point).
+ * Refused before any launch, outputs untouched: MGR_EINVAL for N < 0, k out of range, a NULL xyz with N > 0; MGR_ENOMEM for a
+ * NULL or short workspace.
+ * The cell edge follows k: about max(MGR_KNN_CELL_MIN_POINTS, k / MGR_KNN_CELL_K_DIV) points per cell over the bounding box.
+ * ------------------------------------------------------------------------ */
+#define MGR_KNN_MAX_K 512
+#ifndef MGR_KNN_CELL_K_DIV            /* (-DMGR_KNN_CELL_K_DIV=... builds a library with another cell size: a measurement aid) */
+#define MGR_KNN_CELL_K_DIV 16.0f
+#endif
+#define MGR_KNN_CELL_MIN_POINTS 2.0f
+size_t mgr_knn_self_workspace_bytes(int N, int k);
+int mgr_knn_self(int N, const float* xyz, int k, int include_self, float* out_d2, int32_t* out_idx, float* out_sigma,
+                 int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Local Outlier Probability (LoOP; Kriegel, Kroeger, Schubert, Zimek, CIKM 2009) of every point, on the neighbourhoods of
+ * mgr_knn_self: the filter behind the reference's update_mask_based_on_outliers (src/utils/gaussian_utils.py:557-568 calls
+ * MeshLab's compute_selection_point_cloud_outliers through pymeshlab).  MeshLab's own constants (its erf approximation,
+ * whether it counts the query point) cannot be pinned without it; every such choice is an argument or a constant here.
+ *
+ * With S_i the neighbour set of i above (n_i members) and lambda = MGR_LOOP_LAMBDA = 1:
+ *   sigma_i = as out_sigma of mgr_knn_self
+ *   den_i   = (float)((fp64 sum over j in S_i of sigma_j, in the order of sigma's own sum) / n_i)
+ *   plof_i  = sigma_i / den_i - 1                      (0 where den_i == 0)
+ *   nplof   = lambda * sqrt(mean over the valid points of plof_i^2)     (fp64: one partial per workgroup, then a fixed-order
+ *             fold; no float atomics; 0 when no point is valid)
+ *   score_i = max(0, erff(plof_i / (nplof * sqrt(2)))) (0 for every valid point when nplof == 0)
+ *   mask_i  = score_i > prob                           (a NaN score gives 0)
+ * A point with n_i = 0 (non-finite, or alone with include_self = 0) has NaN sigma, plof and score and is left out of the mean.
+ *   out_score (N) required; out_mask (N) uint8, out_sigma (N), out_plof (N) or NULL
+ *   out_stats       3 device doubles [nplof, n_valid, n_flagged] or NULL
+ * Nothing is read back to the host.  Equal bits run to run.  The second pass reads the neighbour indices the first stored in
+ * the workspace: workspace_bytes >= mgr_outlier_scores_workspace_bytes(N, k) = the search's + 4 N k + 28 N bytes, rounded.
+ * Refused before any launch, outputs untouched: MGR_EINVAL for N < 0, k out of range, a NULL xyz or out_score with N > 0;
+ * MGR_ENOMEM for a NULL or short workspace.  N = 0: out_stats (if given) becomes [0, 0, 0].
+ * ------------------------------------------------------------------------ */
+#define MGR_LOOP_LAMBDA 1.0f
+#define MGR_LOOP_SQRT2 1.41421356237309505f
+size_t mgr_outlier_scores_workspace_bytes(int N, int k);
+int mgr_outlier_scores(int N, const float* xyz, int k, int include_self, float prob, float* out_score, uint8_t* out_mask,
+                       float* out_sigma, float* out_plof, double* out_stats, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------
  * Image loss used by the benchmark step: L = mean|a-b| over (V,3,H,W);
  * writes dL/da = sign(a-b) * scale and accumulates sum|a-b| into loss_sum[0].
  * (src/utils/loss_utils.py:22-27 with src/modules/base.py:329-331.)
@@ -1322,6 +1380,14 @@ int mgr_densify_plan(int N, const float* grad_accum, const float* denom, const f
 int mgr_prune_plan(int N, const uint8_t* prune_mask, void* workspace, size_t workspace_bytes, int64_t* counts_host,
                    void* stream);
 int mgr_gather_rows(int N, int64_t M, const void* workspace, const void* src, void* dst, int width, void* stream);
+/* The prune tests of densify_and_prune (gaussian.py:315-320) on rows as they are, in mgr_densify_plan's own fp32 expressions:
+ * out_mask[i] = sigmoid(opacity_logit[i]) < min_opacity, or max_j exp(log_scale[i,j]) > 0.1 * extent (only with
+ * max_screen_size > 0), or a NaN log scale.  On the rows a plan with the tests disabled (min_opacity = -inf,
+ * max_screen_size = 0) produced, this is the mask the plan with the tests enabled would have applied, row for row: the
+ * pruning half of densify_and_prune taken after clone and split, where an outlier mask can be ORed in.
+ * MGR_EINVAL: N < 0 or a NULL pointer with N > 0. */
+int mgr_prune_tests(int N, const float* log_scale, const float* opacity_logit, float min_opacity, float extent,
+                    float max_screen_size, uint8_t* out_mask, void* stream);
 int mgr_densify_apply(int N, int64_t M, int64_t n_selected, const void* workspace, const float* const* params,
                       const float* const* exp_avg, const float* const* exp_avg_sq, float* const* new_params,
                       float* const* new_exp_avg, float* const* new_exp_avg_sq, const float* skin, float* new_skin, int B,

@@ -37,6 +37,7 @@ MGR_TIERS_BEYOND_SMALL_SHIFT, MGR_TIERS_BEYOND_SMALL_MASK = 24, 0x7F
 MGR_LPIPS_F32, MGR_LPIPS_BF16 = 0, 1      # the operand mode of the mgr_lpips*_op entries
 MGR_LPIPS_STORE_F32, MGR_LPIPS_STORE_BF16 = 0, 1      # the storage mode of the mgr_lpips*_st entries
 MGR_IL2D_DENSE = 1                       # mgr_image_loss2d flags: every block runs the heavy kernel (no settled blocks)
+MGR_KNN_MAX_K = 512                      # the largest k of mgr_knn_self / mgr_outlier_scores (manus_hip.h)
 LP_MAX_BATCH = 16                        # the most views of one launch of the mgr_lpips_roi*_batch* entries (manus_hip.h)
 
 c_int, c_i64, c_f32, c_vp, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
@@ -147,6 +148,10 @@ SIGNATURES = {
     "mgr_keypoint_far_mask": (c_int, [c_int, c_vp, c_int, c_vp, c_f32, c_vp, c_vp]),
     "mgr_knn3_workspace_bytes": (c_sz, [c_int]),
     "mgr_knn3_mean_dist2": (c_int, [c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_knn_self_workspace_bytes": (c_sz, [c_int, c_int]),
+    "mgr_knn_self": (c_int, [c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_outlier_scores_workspace_bytes": (c_sz, [c_int, c_int]),
+    "mgr_outlier_scores": (c_int, [c_int, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mgr_exchange_mask": (c_int, [c_int, c_vp, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mgr_exchange_index_workspace_bytes": (c_sz, [c_int]),
     "mgr_exchange_index": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -233,6 +238,7 @@ SIGNATURES = {
                                       ctypes.c_double, c_vp]),
     "mgr_prune_plan": (c_int, [c_int, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "mgr_gather_rows": (c_int, [c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_vp]),
+    "mgr_prune_tests": (c_int, [c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "mgr_densify_apply": (c_int, [c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
                                    c_vp, c_vp]),
     "mgr_isotropic_reg_workspace_bytes": (c_sz, [c_int]),

@@ -417,6 +417,33 @@ extern "C" int mgr_prune_plan(int N, const uint8_t* prune_mask, void* workspace,
     return MGR_OK;
 }
 
+// The prune tests of k_dens_flags (prune_self) on rows as they are: on the rows of a plan run with the tests disabled they
+// give what the plan would have applied (a split child's stored scale is logf(s / 1.6f), so expf of it is k_dens_flags' c0).
+__global__ __launch_bounds__(256) void k_prune_tests(int N, const float* __restrict__ log_scale,
+                                                     const float* __restrict__ op_logit, float min_opacity,
+                                                     float big_extent, uint8_t* __restrict__ mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float l0 = log_scale[3 * (size_t)i], l1 = log_scale[3 * (size_t)i + 1], l2 = log_scale[3 * (size_t)i + 2];
+    const float s0 = expf(l0), s1 = expf(l1), s2 = expf(l2);
+    const float smax = fmaxf(fmaxf(s0, s1), s2);
+    const bool nan_row = (l0 != l0) || (l1 != l1) || (l2 != l2);
+    const bool low_op = 1.0f / (1.0f + expf(-op_logit[i])) < min_opacity;
+    mask[i] = (low_op || smax > big_extent || nan_row) ? 1 : 0;
+}
+
+extern "C" int mgr_prune_tests(int N, const float* log_scale, const float* opacity_logit, float min_opacity, float extent,
+                               float max_screen_size, uint8_t* out_mask, void* stream_) {
+    if (N < 0) return mgr_fail(MGR_EINVAL, "mgr_prune_tests: bad size");
+    if (N == 0) return MGR_OK;
+    if (!log_scale || !opacity_logit || !out_mask) return mgr_fail(MGR_EINVAL, "mgr_prune_tests: null pointer");
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(k_prune_tests, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, N, log_scale, opacity_logit,
+                       min_opacity, max_screen_size > 0.0f ? 0.1f * extent : __builtin_huge_valf(), out_mask);
+    MGR_LAUNCH_CHECK("k_prune_tests", stream, 0);
+    return MGR_OK;
+}
+
 // dst[o, :] = src[map[o] & 0x3FFFFFFF, :] for the M rows of the plan in `workspace` (rows of `width` 4-byte words)
 __global__ __launch_bounds__(256) void k_gather_rows(uint32_t M, int width, const uint32_t* __restrict__ map,
                                                      const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {

@@ -37,6 +37,10 @@ DEFAULT_OPTS = dict(  # config/model/gaussian/gaussian.yaml
 
 ALL_GROUPS = frozenset(n for n, _, _ in GROUPS)
 
+# densify_and_prune(remove_outliers=True): the arguments the reference passes to update_mask_based_on_outliers (gaussian.py:324)
+OUTLIER_PROB = 0.8
+OUTLIER_NEIGHBORS = 512
+
 
 def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
     """Log-linear learning-rate decay, gaussian_utils.py:212-245 (host arithmetic, float64)."""
@@ -253,11 +257,17 @@ class GaussianOptimizer:
         `noise`: optional standard normals (2*n_selected, 3) for the split offsets (default: torch.randn).
         noise_is_pool=True: `noise` is a larger pool (>= 2*n_selected rows, e.g. one broadcast to all ranks before
         the selection count is known); its first 2*n_selected rows are used.
-        remove_outliers (:323-326, scikit-learn LocalOutlierFactor-style filter on the host, off in every shipped
-        config: remove_outliers_step -1) is not built."""
+        remove_outliers (:323-326; the reference runs it at global_step == remove_outliers_step, off in every shipped
+        config): the Local Outlier Probability filter of `outliers.outlier_mask` (MeshLab's "select outliers", which the
+        reference calls through pymeshlab with propthreshold 0.8, knearest 512 = OUTLIER_PROB, OUTLIER_NEIGHBORS) is taken
+        over the centres as they are AFTER clone and split and BEFORE the final prune, and ORed with the opacity / size /
+        NaN-scale tests: a clone / split pass with those tests disabled, `prune_mask`, the outlier mask, then `prune_points`
+        on the combined mask, which gives the reference's row order.  (A row with a NaN scale leaves in the first pass, so
+        it is not among the points the filter sees.)  The returned dict then counts the rows that survive per segment and
+        gains `split_children` and `outliers`, the number flagged.  In a world of more than one rank every rank holds all
+        Gaussians and the mask is a deterministic function of them: no exchange is added."""
         if remove_outliers:
-            raise ManusHipError("densify_and_prune: remove_outliers is not supported (SURVEY 8f: host-side "
-                                "update_mask_based_on_outliers; remove_outliers_step is -1 in every shipped config)")
+            return self._densify_prune_outliers(max_grad, min_opacity, extent, max_screen_size, noise, noise_is_pool)
         N, dev = self.N, self.device
         nbytes = int(lib().mgr_densify_workspace_bytes(N))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -292,6 +302,32 @@ class GaussianOptimizer:
         self._reset_stats()
         self.replaced = ALL_GROUPS
         return dict(kept=int(counts[0]), cloned=int(counts[1]), split_selected=n_sel, split_kept=int(counts[3]), total=M)
+
+    def prune_mask(self, min_opacity, extent, max_screen_size=None):
+        """(N,) device bool: the prune tests of `densify_and_prune` (gaussian.py:315-320) on the rows as they are -- opacity
+        below min_opacity, world size above 0.1 * extent (only with max_screen_size set), a NaN scale -- in the plan
+        kernel's own fp32 expressions (`mgr_prune_tests`)."""
+        N = self.N
+        mask = torch.empty((N,), dtype=torch.uint8, device=self.device)
+        check(lib().mgr_prune_tests(N, ptr(self.p["_scaling"]), ptr(self.p["_opacity"]), float(min_opacity), float(extent),
+                                    float(max_screen_size or 0.0), ptr(mask), stream()), "mgr_prune_tests")
+        return mask.bool()
+
+    def _densify_prune_outliers(self, max_grad, min_opacity, extent, max_screen_size, noise, noise_is_pool):
+        """densify_and_prune(remove_outliers=True): see there."""
+        from .outliers import outlier_mask
+        first = self.densify_and_prune(max_grad, float("-inf"), extent, None, False, noise=noise, noise_is_pool=noise_is_pool)
+        a, b, c = first["kept"], first["cloned"], first["split_kept"]
+        if self.N == 0:
+            return dict(first, split_children=0, outliers=0)
+        outl = outlier_mask(self.p["_xyz"], prob=OUTLIER_PROB, neighbors=OUTLIER_NEIGHBORS)
+        gone = self.prune_mask(min_opacity, extent, max_screen_size) | outl
+        stay = ~gone
+        both = stay[a + b:a + b + c] & stay[a + b + c:a + b + 2 * c]
+        n = torch.stack([stay[:a].sum(), stay[a:a + b].sum(), both.sum(), stay[a + b:].sum(), outl.sum()]).tolist()   # one read
+        M = self.prune_points(gone)
+        return dict(kept=n[0], cloned=n[1], split_selected=first["split_selected"], split_kept=n[2], split_children=n[3],
+                    total=M, outliers=n[4])
 
     # -- prune_points, gaussian.py:185-203 -------------------------------------------------------
     def prune_points(self, mask, extra=None):
