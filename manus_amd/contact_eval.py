@@ -154,6 +154,8 @@ def skin_labels(frame, hand, fill=True, return_unfilled=False):
     fr = _u8(frame, dev, 3, "frame")
     if fr.shape[0] != V or fr.shape[1] != H or fr.shape[2] not in (W, 2 * W):
         raise ValueError("frame must be (V,H,W,3) or (V,H,2W,3) for hand (V,H,W): got %s, %s" % (tuple(fr.shape), tuple(hd.shape)))
+    if fr.data_ptr() % 4 != 0:      # a contiguous slice of a larger tensor (frames[k:]): the kernel stages rows with dword loads
+        fr = fr.clone()
     ws, n = _workspace(V, H, W, dev)
     labels = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
     check(lib().mgr_ceval_labels(V, H, W, fr.data_ptr(), int(fr.shape[2]), hd.data_ptr(), labels.data_ptr(), ws.data_ptr(), n,

@@ -23,8 +23,10 @@
 //                  bitmap of the labelled pixels per 16 x 16 tile (16 rows of 16 bits), the tile bounding box of the
 //                  view's labelled pixels and the compacted list of residual pixels (inside the hand, no label).
 // k_ceval_fill     one lane per residual pixel.  The nearest labelled pixel under  min (d^2, row * W + col)  -- the
-//                  reference's strict '<' scan of np.argwhere order on fp32 roots, which for coordinates below 2^11 is
-//                  this integer rule -- is searched over tiles in rings of growing Chebyshev distance, starting at the
+//                  reference's strict '<' scan of np.argwhere order on fp32 roots, which is this integer rule whenever
+//                  the winning d^2 is below 4197200: fp32 sqrt over the integers is strictly increasing up to there (the
+//                  first n with sqrt32(n) == sqrt32(n + 1), just above 2^22), so for a nearest labelled pixel closer than
+//                  2048 px -- is searched over tiles in rings of growing Chebyshev distance, starting at the
 //                  first ring that reaches the view's bounding box and ending when the nearest possible pixel of the
 //                  next ring is farther than the best d^2 (or the box is exhausted).  In a tile row the nearest set bit
 //                  to the pixel's column (left one on a tie: lower index) is the only candidate that can win, so a tile
