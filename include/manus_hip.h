@@ -1097,6 +1097,45 @@ int mgr_map_loss(int V, int H, int W, const float* alpha, const float* mask, con
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Per-camera exposure: a learnt affine colour transform between the render and the image terms of the loss (csrc/exposure.hip).
+ * No reference counterpart; the definition is the per-image 3x4 transform of upstream 3DGS' exposure option.
+ *
+ *   E (C,3,4) fp32, one row per camera, A = E[:,:,:3], b = E[:,:,3].  cam_of_view (V) int32 gives the row r of the view at
+ *   position k; r outside [0,C) means "no correction".  img / out / g_in / g_out are planar (V,3,H,W) fp32.
+ *     out[k,c,p]   = ((A[r,c,0] img[k,0,p] + A[r,c,1] img[k,1,p]) + A[r,c,2] img[k,2,p]) + b[r,c]       every pixel, background too
+ *     g_out[k,j,p] = (A[r,0,j] g_in[k,0,p] + A[r,1,j] g_in[k,1,p]) + A[r,2,j] g_in[k,2,p]
+ *     dE[k,c,j]    = sum_p g_in[k,c,p] img[k,j,p]  (j < 3),     dE[k,c,3] = sum_p g_in[k,c,p]            dE (V,3,4) by position
+ *   in fp32, in that order, uncontracted.  A view without correction: out[k] = img[k] and g_out[k] = g_in[k] bit for bit,
+ *   dE[k] = 0.  With the identity row out = img and g_out = g_in for finite inputs.
+ *
+ * mgr_exposure_apply: out may not alias img.  One grid row per view, mgr_exposure_block() pixels per workgroup; 16-byte
+ *   accesses when H W is a multiple of 4 and both buffers are 16-byte aligned, single floats otherwise; nothing beyond H W is
+ *   read or written.
+ * mgr_exposure_backward: one pass reads img and g_in and writes g_out; g_out == g_in (in place) is allowed and gives the bits of
+ *   the out-of-place call; g_out may not alias img.  The same pass forms the sums: products in fp32, added in fp64 -- per
+ *   thread in ascending pixel order, across the wave and the workgroup in a fixed tree, one record of 12 doubles per workgroup
+ *   in the workspace, folded per view by one workgroup in a fixed order.  No atomics: equal bits run to run.  A term that is
+ *   not finite makes all of dE[k] NaN; the other views keep the bits of a run without it.  workspace_bytes >=
+ *   mgr_exposure_workspace_bytes(V, H, W) (96 bytes per mgr_exposure_block() pixels of a view); contents need not be initialised.
+ * mgr_exposure_block: the pixels of one workgroup of the two image kernels (a constant of the build).
+ * mgr_exposure_adam: mgr_pose_adam's row Adam (the same device function; torch.optim.SparseAdam, bias correction of the
+ *   global `step` >= 1, no clamp) on the rows cams_listed[u] (U entries, distinct: the caller's to ensure) of E and its moments
+ *   m, v (C,3,4).  The gradient of row cams_listed[u] is the sum of dE[k] over the positions k < V with cam_of_view[k] ==
+ *   cams_listed[u], in ascending k by one thread per (u, element) -- several views of a step may share a camera; a listed
+ *   camera without a view steps on a zero gradient.  Rows that are not listed, and entries outside [0,C), keep their bits,
+ *   moments included.
+ * Refused before any launch, nothing written, mgr_last_error() naming the cause: a NULL pointer; V, H, W, C or U below 1; more
+ *   than 65535 views or H W beyond 2^31; aliasing as above; a short workspace (MGR_ENOMEM); step < 1 or a non-finite rate. */
+int mgr_exposure_block(void);
+size_t mgr_exposure_workspace_bytes(int V, int H, int W);
+int mgr_exposure_apply(int V, int H, int W, int C, const int32_t* cam_of_view, const float* E, const float* img, float* out,
+                       void* stream);
+int mgr_exposure_backward(int V, int H, int W, int C, const int32_t* cam_of_view, const float* E, const float* img,
+                          const float* g_in, float* g_out, float* dE, void* workspace, size_t workspace_bytes, void* stream);
+int mgr_exposure_adam(int C, int U, const int32_t* cams_listed, int V, const int32_t* cam_of_view, const float* dE, float* E,
+                      float* m, float* v, double lr, double beta1, double beta2, double eps, int step, void* stream);
+
+/* ------------------------------------------------------------------------
  * LPIPS: the reference's fourth loss term, lpips.LPIPS(net="vgg") from start_lpips_iter on (base.py:333-341), and the
  * LPIPS-AlexNet column of its validation CSV (loss_utils.py:111-117).  csrc/lpips.hip; convolutions on the fp32 matrix pipe, or
  * (the *_op entries with operands = MGR_LPIPS_BF16) on the bf16 matrix pipe.

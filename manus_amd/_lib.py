@@ -178,6 +178,11 @@ SIGNATURES = {
     "mgr_image_loss2d": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_vp]),
     "mgr_map_loss_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "mgr_map_loss": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mgr_exposure_block": (c_int, []),
+    "mgr_exposure_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "mgr_exposure_apply": (c_int, [c_int] * 4 + [c_vp] * 4 + [c_vp]),
+    "mgr_exposure_backward": (c_int, [c_int] * 4 + [c_vp] * 6 + [c_vp, c_sz, c_vp]),
+    "mgr_exposure_adam": (c_int, [c_int, c_int, c_vp, c_int] + [c_vp] * 5 + [ctypes.c_double] * 4 + [c_int, c_vp]),
     "mgr_lpips_net_bytes": (c_sz, [c_int]),
     "mgr_lpips_net_pack": (c_int, [c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_sz, c_vp]),
     "mgr_lpips_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),

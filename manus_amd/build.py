@@ -11,7 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["raster_fwd.hip", "raster_feat.hip", "raster_bwd.hip", "lbs_sh.hip", "skin_grid.hip", "knn.hip", "knn_k.hip", "image_loss.hip", "ssim2d.hip", "map_loss.hip", "lpips.hip", "frames.hip", "eval.hip", "contact_eval.hip", "optim.hip", "contact.hip", "mesh.hip", "exchange.hip", "pose.hip", "fk.hip", "triangulate.hip"]
+SOURCES = ["raster_fwd.hip", "raster_feat.hip", "raster_bwd.hip", "lbs_sh.hip", "skin_grid.hip", "knn.hip", "knn_k.hip", "image_loss.hip", "ssim2d.hip", "map_loss.hip", "exposure.hip", "lpips.hip", "frames.hip", "eval.hip", "contact_eval.hip", "optim.hip", "contact.hip", "mesh.hip", "exchange.hip", "pose.hip", "fk.hip", "triangulate.hip"]
 HEADERS = ["mgr_common.h", "instance_math.h", "skin_tri.h", "il_list.h", "bone_math.h", "pose_adam.h", os.path.join("..", "..", "include", "manus_hip.h")]
 # MGR_VARIANT=name builds an instrumented copy (libmanus_hip_<name>.so, objects under build_<name>/) next to the product
 # library; MANUS_HIP_VARIANT=name makes _lib load it (tools/instr only)

@@ -214,7 +214,7 @@ class ViewShardedStep:
             res = dict(grads=out["grads"], grad2d=out["grad2d"], vis=out["vis"], radii=radii, loss=out["loss"],
                        overflow=out.get("overflow"))
             # (one rank, nothing to reduce: what the compute object returned beside the reduced quantities travels as it is)
-            for name in ("loss_lpips", "loss_ssim", "d_transforms", "d_skin_grid", "loss_mask", "loss_depth"):
+            for name in ("loss_lpips", "loss_ssim", "d_transforms", "d_exposure", "d_skin_grid", "loss_mask", "loss_depth"):
                 if name in out:
                     res[name] = out[name]
             return res
@@ -597,7 +597,19 @@ class HipViewCompute:
     change of `targets` -- and on new rects.  None (default): exactly the step above.  `lpips_batch` (a plain attribute like the
     others): the most views per launch of the windowed term and of the cached taps build (`LPIPS.values_grad(batch=)`,
     `LPIPS.target_taps(batch=)`): views whose rectangles share a size run as one chain of launches, the same bits (so it is no
-    part of the window cache's key); `FrameStore.lpips_fit` gives a drawn step such rectangles.  0 (default) is the step above."""
+    part of the window cache's key); `FrameStore.lpips_fit` gives a drawn step such rectangles.  0 (default) is the step above.
+
+    Per-camera exposure (`exposure`, `exposure_ids`, `exposure_on`; plain attributes): `exposure` is a (C,3,4) fp32 device table
+    E, one affine colour transform per camera (csrc/exposure.hip), used as it is -- never copied, so whoever steps it
+    (`exposure.ExposureRefiner`) is seen by the next step; `exposure_ids` a HOST int sequence over all view rows giving each
+    view's table row (default: the view id itself, which needs C == V_all; a row outside [0,C) leaves the view uncorrected).
+    With a table and `exposure_on` true both routes apply E to the render (`mgr_exposure_apply`), take every image term -- L1,
+    either SSIM, LPIPS full-frame, windowed or batched -- on the corrected image out', DENSE (no span list: under empty tiles
+    out' is the corrected background, not the target), send dL/dout' through `mgr_exposure_backward` in place and hand the
+    rasterizer's backward the raw render and dL/drender.  Map terms are untouched.  The output dict gains "d_exposure" (V,3,4)
+    by position, on the scale of `grads`; `last_image` stays the raw render, `last_corrected` holds out' (None with the
+    correction off).  `_step_direct(g_img=...)` is a gradient with respect to the render and bypasses the correction.  No
+    reference counterpart.  None, or `exposure_on` False: exactly the step without these arguments."""
 
     # per-view target maps kept (130 KB per 1080p view)
     MAX_TARGET_MAPS = 4096
@@ -606,7 +618,7 @@ class HipViewCompute:
                  sh_storage="fp32", sparse_loss=True, overlap_loss=True, depth_cut=False, max_cut_hints=1024,
                  persistent_grads=True, pose_grad=False, skin_grid_grad=False, mask_targets=None, w_mask=0.0, depth_targets=None,
                  w_depth=0.0, lpips=None, w_lpips=0.0, lpips_rects=None, lpips_norm="frame", lpips_cache_targets=False,
-                 lpips_batch=0, ssim="rows"):
+                 lpips_batch=0, ssim="rows", exposure=None, exposure_ids=None):
         if sh_storage not in ("fp32", "fp16"):
             raise ValueError("sh_storage must be 'fp32' or 'fp16'")
         if loss not in ("l1", "l1+ssim"):
@@ -703,6 +715,56 @@ class HipViewCompute:
         self.mask_targets = mask_targets
         self.depth_targets = depth_targets
         self._map_terms()               # (the combinations a map term refuses)
+        # -- per-camera exposure (class docstring): the table, each view row's table row, the per-step switch
+        self.exposure, self.exposure_ids, self.exposure_on = exposure, exposure_ids, True
+        self.last_corrected = None
+        self._exp_rows = None           # (host rows of the last corrected step, their device vector)
+        self._exp_ws = None             # workspace of mgr_exposure_backward, kept across steps
+        self._exposure_table()
+
+    def _exposure_table(self):
+        """The exposure table of the step about to run (None: no correction); ValueError for a table or an id list the step
+        cannot use.  Asked at construction and again at every step: the three are plain attributes."""
+        E = self.exposure
+        if E is None:
+            return None
+        V_all = int(self.cams.shape[0])
+        if not torch.is_tensor(E) or E.dim() != 3 or tuple(E.shape[1:]) != (3, 4) or E.shape[0] < 1:
+            raise ValueError("exposure must be a (C,3,4) tensor (got %s)" % (tuple(E.shape) if torch.is_tensor(E) else type(E),))
+        if E.dtype != torch.float32 or not E.is_contiguous():
+            raise ValueError("exposure must be a contiguous float32 table (got %s)" % (E.dtype,))
+        if E.device != self.cams.device:
+            raise ValueError("exposure is on %s, the step's views are on %s" % (E.device, self.cams.device))
+        if self.exposure_ids is None:
+            if E.shape[0] != V_all:
+                raise ValueError("exposure has %d rows for %d views: pass exposure_ids (one table row per view row)" % (E.shape[0], V_all))
+        elif len(self.exposure_ids) != V_all:
+            raise ValueError("exposure_ids has %d entries for %d view rows" % (len(self.exposure_ids), V_all))
+        return E if self.exposure_on else None
+
+    def _exposure_rows(self, view_ids):
+        """Device int32 vector: the table row of every view of the step (kept while the host rows stay the same)."""
+        ids = self.exposure_ids
+        rows = tuple(int(v) if ids is None else int(ids[v]) for v in view_ids)
+        if self._exp_rows is None or self._exp_rows[0] != rows or self._exp_rows[1].device != self.device:
+            self._exp_rows = (rows, torch.tensor(rows, dtype=torch.int32, device=self.device))
+        return self._exp_rows[1]
+
+    def _exposure_loss(self, img, E, sel, view_ids, scale):
+        """The image terms of a corrected step: E applied to the raw render `img` (detached), `_image_loss` and `_lpips_term` on
+        the corrected image -- dense: under empty tiles it is not the target --, the exposure backward in place.
+        -> (loss, dL/dimg, LPIPS term or None, d_exposure (V,3,4) by position)."""
+        rows = self._exposure_rows(view_ids)
+        tgt = sel["targets"]
+        corr = self.ops.exposure_forward(img, E, rows)
+        loss, g = self._image_loss(corr, tgt, scale)
+        lp = self._lpips_term(corr, tgt, scale, g, sel, view_ids)
+        nbytes = int(lib().mgr_exposure_workspace_bytes(*[int(x) for x in (img.shape[0], img.shape[2], img.shape[3])]))
+        if self._exp_ws is None or self._exp_ws.numel() < nbytes or self._exp_ws.device != img.device:
+            self._exp_ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        g, d_E = self.ops.exposure_backward(img, E, rows, g, inplace=True, workspace=self._exp_ws)
+        self.last_corrected = corr
+        return loss, g, lp, d_E
 
     def _map_target(self, t, what):
         """A (V_all,H,W) float map on the step's device, or None; ValueError otherwise."""
@@ -1068,7 +1130,10 @@ class HipViewCompute:
         fwd = (head, out, radii, kept)
         # route of the image loss (class docstring): "mapped" / "overlap" span lists, or None = plain / g_img given
         self._loss_ssim = None
-        listed = g_img is None and self.loss == "l1+ssim" and self.sparse_loss and self._ssim_mode() == "rows"
+        self.last_corrected = None
+        # (a given g_img is a gradient with respect to the render: it bypasses the correction)
+        E = self._exposure_table() if g_img is None else None
+        listed = g_img is None and E is None and self.loss == "l1+ssim" and self.sparse_loss and self._ssim_mode() == "rows"
         route = None if not listed else "mapped" if self.target_map else "overlap" if self.overlap_loss else None
         loss_list = self._mapped_loss_list(view_ids, sel, V, H, W) if route == "mapped" else None
         ctx = self.rz.context(dev)
@@ -1079,8 +1144,12 @@ class HipViewCompute:
             if route != "overlap" and ctx.fenced(self.sync_check):
                 ctx.fence(ws)
             given = g_img is not None
-            loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
-            lp = None if given else self._lpips_term(out, sel["targets"], scale, g_img, sel, view_ids)
+            d_E = None
+            if E is not None:
+                loss, g_img, lp, d_E = self._exposure_loss(out, E, sel, view_ids, scale)
+            else:
+                loss, g_img = self._loss(ctx, ws, fwd, sel, scale, g_img, route, loss_list)
+                lp = None if given else self._lpips_term(out, sel["targets"], scale, g_img, sel, view_ids)
             grads, d_w, st_g, st_v, st_r, d_T = self._backward(ws, fwd, g_img, scale, full_rows=any(map_on))
             map_out = self._map_chain(ws, head, sel, view_ids, scale, map_on, grads, d_w, d_T) if any(map_on) else None
             active = self._skin_backward(ws, head, p["_xyz"], d_w, grads["_xyz"], full_rows=any(map_on))
@@ -1109,6 +1178,8 @@ class HipViewCompute:
             res["loss_ssim"] = self._loss_ssim
         if d_T is not None:
             res["d_transforms"] = d_T
+        if d_E is not None:
+            res["d_exposure"] = d_E
         if d_grid is not None:
             res["d_skin_grid"] = d_grid
         return res
@@ -1352,10 +1423,22 @@ class HipViewCompute:
         map_on = self._map_terms()
         tgt = sel["targets"]
         map_out = None
+        self.last_corrected = None
+        E, d_E = self._exposure_table(), None
+
+        def image_terms(img):
+            # (loss, dL/dimg, LPIPS term); corrected: the terms on E applied to the render, the gradient sent back through it
+            nonlocal d_E
+            if E is not None:
+                self.last_image = img.detach()
+                loss, g, lp, d_E = self._exposure_loss(self.last_image, E, sel, view_ids, scale)
+                return loss, g, lp
+            loss, g = self._image_loss(img, tgt, scale)
+            return loss, g, self._lpips_term(img, tgt, scale, g, sel, view_ids)
+
         if any(map_on):
             img, radii, means2D, extras = self.forward_views(view_ids, T=T, maps=(True, map_on[1]))
-            loss, g = self._image_loss(img, tgt, scale)
-            lp = self._lpips_term(img, tgt, scale, g, sel, view_ids)
+            loss, g, lp = image_terms(img)
             masks, depths = self._map_sel(sel, view_ids, map_on[1])
             k = scale * len(view_ids)
             ml, sums = losses.map_loss(extras["alpha"], masks, self.w_mask, extras["depth"] if map_on[1] else None, depths,
@@ -1365,8 +1448,7 @@ class HipViewCompute:
             loss = loss + map_out[0]
         else:
             img, radii, means2D = self.forward_views(view_ids, T=T)
-            loss, g = self._image_loss(img, tgt, scale)
-            lp = self._lpips_term(img, tgt, scale, g, sel, view_ids)
+            loss, g, lp = image_terms(img)
             img.backward(g)
         vis = radii > 0
         g2 = means2D.grad[..., :2].norm(dim=-1) * (1.0 / scale)
@@ -1382,6 +1464,8 @@ class HipViewCompute:
             res["loss_ssim"] = self._loss_ssim
         if T is not None:
             res["d_transforms"] = T.grad
+        if d_E is not None:
+            res["d_exposure"] = d_E
         if self.skin_grid_grad:
             w, self._skin_w = self._skin_w, None
             if w is None or w.grad is None:
@@ -1509,12 +1593,35 @@ class Trainer:
     (g - skin_grid_from_iter) % skin_grid_every == 0 the grid takes its step (prior, row Adam, clamp, projection) on
     `out["d_skin_grid"]` behind the Gaussians' optimizer step and the pose corrections', on both branches of `train_step`, on the
     final run of an overflow re-run and on steps whose leaves densify / prune replaced; `out["loss_skin_prior"]` is then the
-    refiner's `last_prior` (a device scalar, not read here).  Off schedule the gradient is still formed and ignored."""
+    refiner's `last_prior` (a device scalar, not read here).  Off schedule the gradient is still formed and ignored.
+
+    Per-camera exposure (one rank; None: the step above, bit for bit).  exposure: an `exposure.ExposureRefiner`, attached to the
+    compute object here unless it already is (`ExposureRefiner.attach`: one table row per view row; with `frames` every row
+    starts at -1).  `compute.exposure_on` is set to g >= exposure_from_iter before every step -- before that the step is the
+    step without the keyword --, with `frames` the table rows of the drawn items (`ExposureRefiner.rows_of`) are written into
+    `compute.exposure_ids` beside `load_step`, and at the global steps g >= exposure_from_iter with (g - exposure_from_iter) %
+    exposure_every == 0 the table takes its step on `out["d_exposure"]` behind the Gaussians' optimizer step, the pose
+    corrections' and the skin grid's, on both branches of `train_step`.  Off schedule the gradient is formed and ignored.  The
+    refiner's state travels through `checkpoint.save_checkpoint(extra_state=)`."""
 
     def __init__(self, compute, n_views, extent, opts=None, spatial_lr_scale=1.0, rank=0, world_size=1, group=None,
                  bg_white=True, kind=None, compact_allreduce=False, sharded_adam=False, view_weights=None, depth_cut=False,
                  sort_rows=False, persistent_grads=True, start_lpips_iter=1000, frames=None, pose=None, pose_from_iter=0,
-                 pose_every=1, pose_frames=None, skin_grid=None, skin_grid_from_iter=0, skin_grid_every=1, pose_hold=False):
+                 pose_every=1, pose_frames=None, skin_grid=None, skin_grid_from_iter=0, skin_grid_every=1, pose_hold=False,
+                 exposure=None, exposure_from_iter=0, exposure_every=1):
+        if exposure is not None:
+            if world_size > 1:
+                raise ValueError("Trainer(exposure=...) needs world_size == 1: d_exposure is not reduced across ranks")
+            if int(exposure_every) < 1:
+                raise ValueError("exposure_every must be at least 1")
+            if not hasattr(compute, "exposure_on"):
+                raise ValueError("Trainer(exposure=...) needs a compute object with an exposure table (HipViewCompute)")
+            if frames is not None and getattr(frames.store, "camera_keys", None) is None:
+                raise ValueError("Trainer(exposure=..., frames=...) needs the camera keys of a store built by FrameStore.from_dataset")
+            if getattr(compute, "exposure", None) is not exposure.E:
+                # with frames the rows of the drawn items are written before every step; until then no view is corrected
+                exposure.attach(compute, [-1] * int(compute.cams.shape[0]) if frames is not None else None)
+        self.exposure, self.exposure_from_iter, self.exposure_every = exposure, int(exposure_from_iter), int(exposure_every)
         if frames is not None:
             if world_size > 1:
                 raise ValueError("Trainer(frames=...) needs world_size == 1: the frame pool is one rank's")
@@ -1632,7 +1739,7 @@ class Trainer:
             self.stepper.all_gather_params(self.opt.mflat)
             self.stepper.all_gather_params(self.opt.vflat)
 
-    def validate(self, view_ids, masks=None, validator=None, group=8, lpips=None, ssim="rows"):
+    def validate(self, view_ids, masks=None, validator=None, group=8, lpips=None, ssim="rows", exposure=False):
         """The validation pass over the views `view_ids` of the compute object (validation_step / on_validation_epoch_end,
         src/modules/base.py:112-188): rendered under no_grad with `forward_views` in groups of `group` views (the group
         size of `HipViewCompute.pairs_per_view`), compared with `compute.targets` by `ops.eval_views` / `ops.eval_triptych`
@@ -1644,6 +1751,9 @@ class Trainer:
         target * mask, goes to the validator's CSV column and to the result's "lpips" list.  ssim: "rows" (default; the
         reference's statistic on HWC images, from `ops.eval_views`) or "spatial" (the standard 2-D SSIM of the masked images,
         `validation.spatial_ssim`): which one fills the result's "ssim" list and the CSV column; anything else raises ValueError.
+        exposure: True takes metrics, LPIPS and the triptych on the render corrected by the compute object's exposure table
+        (`compute.exposure`, rows `compute.exposure_ids`; a view whose row is -1 is taken as it is) -- what the training loss saw;
+        False (default) on the raw render, every output as without the keyword.
 
         Returns dict(psnr, ssim: per-view lists; psnr_mean, ssim_mean; ssim_kind; render_time: seconds from the start of each
         group's render to the end of its last kernel, summed (two events on the stream: the group's host work included,
@@ -1661,6 +1771,16 @@ class Trainer:
         dev = getattr(c, "device", None)
         if masks is not None and (masks.dim() != 3 or masks.shape[0] != len(ids)):
             raise ValueError("validate: masks must be (len(view_ids),H,W)")
+        exp_table = exp_ids = None
+        if exposure:
+            if getattr(c, "exposure", None) is None:
+                raise ValueError("validate(exposure=True): the compute object has no exposure table")
+            on, c.exposure_on = c.exposure_on, True       # (the table's own checks, whatever the training schedule says)
+            try:
+                exp_table = c._exposure_table()
+            finally:
+                c.exposure_on = on
+            exp_ids = c.exposure_ids if c.exposure_ids is not None else range(int(c.cams.shape[0]))
         idx = self._rz.context(dev).device.index
         train_ctx = self._rz._CONTEXTS[idx]
         if getattr(self, "_val_ctx", None) is None or self._val_ctx.device != train_ctx.device:
@@ -1682,6 +1802,8 @@ class Trainer:
                         e0.record()
                         img, _, _ = c.forward_views(part)       # no host read: the private context runs fenced
                         e1.record()
+                        if exp_table is not None:
+                            img = ops.exposure_forward(img, exp_table, [exp_ids[v] for v in part])
                         tgt = c._select(part)["targets"]
                         sq, ss, gmax = ops.eval_views(img, tgt, m)
                         trip = ops.eval_triptych(img, tgt, gmax)
@@ -1730,6 +1852,10 @@ class Trainer:
             # (scene_masks: without a mask table the pruning masks of the scene still follow the drawn items)
             self.frames.store.load_step(c, self.last_items, masks=c.mask_targets is not None, lpips_rects=c.lpips_rects is not None,
                                         scene_masks=True)
+            if self.exposure is not None:      # the table rows follow the drawn items (slots 0 .. n_views - 1, as load_step's)
+                table = list(c.exposure_ids)
+                table[:len(self.last_items)] = self.exposure.rows_of(self.frames.store, self.last_items)
+                c.exposure_ids = table
         if self.pose is None or gs < self.pose_from_iter:
             return None
         due = (gs - self.pose_from_iter) % self.pose_every == 0
@@ -1762,6 +1888,15 @@ class Trainer:
         r.step(out["d_skin_grid"])
         out["loss_skin_prior"] = r.last_prior
 
+    def _exposure_step(self, gs, out):
+        """Behind the Gaussians' optimizer step, the pose corrections' and the skin grid's: the exposure table's own step on the
+        step's `out["d_exposure"]` at the scheduled global steps; off schedule the gradient is formed and ignored."""
+        r = self.exposure
+        if r is None or gs < self.exposure_from_iter or (gs - self.exposure_from_iter) % self.exposure_every != 0:
+            return
+        ids = list(self.stepper.local_views)
+        r.step(out["d_exposure"], ids, [self.compute.exposure_ids[v] for v in ids])
+
     def train_step(self, views=None):
         """One optimisation step; returns the step's output dict (loss, statistics) plus "changed".
         views: optional list of per-view dicts for the pruning tests (default: `compute.prune_views`).
@@ -1773,6 +1908,8 @@ class Trainer:
         o, gs = self.opt.opts, self.global_step
         if getattr(self.compute, "lpips", None) is not None:
             self.compute.lpips_on = gs >= self.start_lpips_iter
+        if self.exposure is not None:
+            self.compute.exposure_on = gs >= self.exposure_from_iter
         posed_step = self._point_views(gs) if (self.frames is not None or self.pose is not None) else None
         out = self._run_step()
         if not self.density_enabled:     # composite: render + reduce + Adam only (see __init__)
@@ -1787,6 +1924,7 @@ class Trainer:
                 self.compute.mark_params_changed()
             self._pose_step(out, posed_step)
             self._skin_grid_step(gs, out)
+            self._exposure_step(gs, out)
             self.global_step += 1
             out["changed"] = False
             return out
@@ -1842,6 +1980,7 @@ class Trainer:
             self.compute.mark_params_changed()
         self._pose_step(out, posed_step)
         self._skin_grid_step(gs, out)
+        self._exposure_step(gs, out)
         self.global_step += 1
         if resized:
             self.compute.set_params(self.opt.parameters(), None)

@@ -62,6 +62,7 @@ class FrameStore:
     cam_rows (n,40), transforms (n,J+1,4,4), posed (n,J,4,4), keypoints (n,J+1,3)    on the device, only from `from_dataset`: the
               per-item camera rows and poses `load_step` copies into a compute object's tables
     frame_keys    per row the (action, frame_id) of the item, host, only from `from_dataset`
+    camera_keys   per row the camera name of the item, host, only from `from_dataset`
     """
 
     def __init__(self, pool, offsets, bboxes, height, width, k=1, items=None):
@@ -74,6 +75,7 @@ class FrameStore:
         self.cam_rows = self.transforms = self.posed = self.keypoints = None
         self.cameras = None          # per row the camera dict of the dataset (host)
         self.frame_keys = None       # per row the (action, frame_id) of the item (host; `from_dataset`): the rows of `pose.PoseRefiner`
+        self.camera_keys = None      # per row the camera name of the item (host; `from_dataset`): the rows of `exposure.ExposureRefiner`
         self._state = {}             # (targets.data_ptr(), slot) -> (weak reference to the table, rectangle, background, masks pointer)
         self._scene_masks = None     # (targets.data_ptr(), float table): masks decoded for a scene's pruning masks alone (`load_step(scene_masks=True)`)
         self._bg_host = None         # (id, version) of a compute object's background tensor and its three floats
@@ -147,6 +149,7 @@ class FrameStore:
             keyp.append(sk["keypoints"][0].float())
         st.cameras = cams
         st.frame_keys = [tuple(ds.index_list[i][:2]) for i in indices]
+        st.camera_keys = [ds.index_list[i][2] for i in indices]
         if indices:
             st.cam_rows = torch.stack(cam_rows).to(device)
             st.transforms, st.posed, st.keypoints = torch.stack(tfs).to(device), torch.stack(posed).to(device), torch.stack(keyp).to(device)

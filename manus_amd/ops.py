@@ -11,6 +11,7 @@ Each op mirrors one block of MANUS Python code (reference tree brown-ivl/manus):
     distCUDA2      simple_knn._C.distCUDA2               src/models/gaussian.py:110
     eval_views, eval_triptych   validation_step's metrics / image   src/modules/base.py:112-154
     image_loss2d_grad           L1 + ssim() as it computes on CHW images   src/utils/loss_utils.py:22-97
+    exposure_apply              per-camera affine colour correction of the render (no reference counterpart)
 
 All of them require GPU tensors; there is no CPU or PyTorch fallback.
 """
@@ -350,6 +351,86 @@ def map_loss_grad(alpha, mask, w_mask=1.0, depth=None, depth_target=None, w_dept
     check(lib().mgr_map_loss(V, H, W, ptr(alpha), ptr(mask), ptr(depth), ptr(depth_target), float(w_mask), float(w_depth),
                              float(grad_scale), ptr(g_a), ptr(g_d), ptr(sums), ptr(ws), nbytes, stream()), "mgr_map_loss")
     return sums, g_a, g_d
+
+
+def exposure_block():
+    """Pixels per workgroup of the exposure kernels (`mgr_exposure_block`)."""
+    return int(lib().mgr_exposure_block())
+
+
+def _exposure_args(img, E, cam_of_view, what):
+    """(V, H, W, C, cam_of_view as a device int32 vector) of an exposure call; ManusHipError for anything else."""
+    for t in (img, E):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ManusHipError("%s needs GPU tensors; there is no CPU fallback" % what)
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32:
+        raise ManusHipError("%s: the image must be (V,3,H,W) fp32 (got %s %s)" % (what, tuple(img.shape), img.dtype))
+    if E.dim() != 3 or tuple(E.shape[1:]) != (3, 4) or E.dtype != torch.float32 or E.device != img.device:
+        raise ManusHipError("%s: the table must be (C,3,4) fp32 on the image's device (got %s %s)" % (what, tuple(E.shape), E.dtype))
+    V = img.shape[0]
+    if not torch.is_tensor(cam_of_view):
+        cam_of_view = torch.tensor([int(c) for c in cam_of_view], dtype=torch.int32, device=img.device)
+    if cam_of_view.dtype != torch.int32 or tuple(cam_of_view.shape) != (V,) or cam_of_view.device != img.device:
+        raise ManusHipError("%s: cam_of_view must be %d int32 entries on the image's device" % (what, V))
+    return V, img.shape[2], img.shape[3], E.shape[0], cam_of_view.contiguous()
+
+
+def exposure_forward(img, E, cam_of_view):
+    """out'[k] = A[r] img[k] + b[r] per pixel, r = cam_of_view[k], A = E[:,:,:3], b = E[:,:,3] (`mgr_exposure_apply`); a row
+    outside [0,C) copies the view.  No autograd: `exposure_apply` is the differentiable form."""
+    V, H, W, C, cov = _exposure_args(img, E, cam_of_view, "exposure_apply")
+    img, E = img.contiguous(), E.contiguous()
+    out = torch.empty_like(img)
+    check(lib().mgr_exposure_apply(V, H, W, C, ptr(cov), ptr(E), ptr(img), ptr(out), stream()), "mgr_exposure_apply")
+    return out
+
+
+def exposure_backward(img, E, cam_of_view, g, inplace=False, workspace=None):
+    """The raw backward (`mgr_exposure_backward`): (dL/dimg, dE) from g = dL/dout' (V,3,H,W).  dE is (V,3,4) BY POSITION: the
+    rows of views that share a camera are summed by whoever consumes them (`mgr_exposure_adam`, `exposure_apply`'s backward).
+    inplace: dL/dimg overwrites g (same bits).  Deterministic: two calls give equal bits."""
+    V, H, W, C, cov = _exposure_args(img, E, cam_of_view, "exposure_backward")
+    if not torch.is_tensor(g) or g.shape != img.shape or g.dtype != torch.float32 or g.device != img.device:
+        raise ManusHipError("exposure_backward: the gradient must have the image's shape, dtype and device")
+    img, E = img.contiguous(), E.contiguous()
+    if inplace and not g.is_contiguous():
+        raise ManusHipError("exposure_backward: an in-place gradient must be contiguous")
+    g = g.contiguous()
+    g_out = g if inplace else torch.empty_like(g)
+    dE = torch.empty((V, 3, 4), dtype=torch.float32, device=img.device)
+    nbytes = int(lib().mgr_exposure_workspace_bytes(V, H, W))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    check(lib().mgr_exposure_backward(V, H, W, C, ptr(cov), ptr(E), ptr(img), ptr(g), ptr(g_out), ptr(dE), ptr(workspace),
+                                      workspace.numel(), stream()), "mgr_exposure_backward")
+    return g_out, dE
+
+
+class _ExposureApply(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, E, cov):
+        ctx.save_for_backward(img, E, cov)
+        return exposure_forward(img, E, cov)
+
+    @staticmethod
+    def backward(ctx, g):
+        img, E, cov = ctx.saved_tensors
+        g_img, dE = exposure_backward(img, E, cov, g.contiguous())
+        # the dense table gradient: the per-view rows added in ascending position (index_add_ over sorted positions is not
+        # ordered, a loop over the views is)
+        d_tab = torch.zeros_like(E)
+        rows = cov.tolist()
+        for k, r in enumerate(rows):
+            if 0 <= r < E.shape[0]:
+                d_tab[r] += dE[k]
+        return g_img, d_tab, None
+
+
+def exposure_apply(img, E, cam_of_view):
+    """Per-camera affine colour correction under autograd: out' as `exposure_forward`, gradients to `img` and to the table `E`
+    (dense (C,3,4), the per-view rows of `exposure_backward` summed per camera in ascending position)."""
+    V, H, W, C, cov = _exposure_args(img, E, cam_of_view, "exposure_apply")
+    return _ExposureApply.apply(img, E, cov)
 
 
 def image_loss_grad(pred, target, w_l1=0.8, w_ssim=0.2, grad_scale=1.0, loss_offset=0.0, bg=None, tile_start_ptr=None):
