@@ -783,8 +783,8 @@ int mgr_fk_adam(int U, int J, const int32_t* frames_listed, const float* d_theta
                 const float* mask, const float* lo, const float* hi, double lr_rot, double lr_trans, double beta1, double beta2,
                 double eps, int step, void* stream);
 
-/* mgr_fk_backward_terms: mgr_fk_backward with three opt-in terms on the angles of the listed frames (a kernel of its own beside
- * k_fk_backward, which keeps its text and its bits; the two share their device functions and the order of every sum).  Rows 0..J
+/* mgr_fk_backward_terms: mgr_fk_backward with three opt-in terms on the angles of the listed frames (another
+ * instantiation of mgr_fk_backward's kernel template: one body, the same order of every sum, and that entry's bits).  Rows 0..J
  * of theta take the "rot" weights, row J+1 the "trans" weights; all five weights finite and >= 0.
  *     E_dev    = sum_f sum_{r,c: mask != 0} w_dev(r)    (theta_f[r,c] - theta_ref_f[r,c])^2
  *     E_smooth = sum_{edges (f, next f)} sum_{r,c: mask != 0} w_smooth(r) (theta_f[r,c] - theta_next[r,c])^2
@@ -824,7 +824,7 @@ int mgr_fk_backward_terms(int V, int J, int F, int U, const int32_t* frames_list
                           double* values, void* workspace, size_t workspace_bytes, void* stream);
 
 /* mgr_fk_backward_terms2d: mgr_fk_backward_terms with a fourth opt-in term, the multi-view 2-D reprojection of the same keypoints
- * (a kernel of its own once more: k_fk_backward and k_fk_backward_terms keep their text and their bits).  All of
+ * (a third instantiation of the same kernel template: the other two entries keep their bits).  All of
  * mgr_fk_backward_terms' arguments, and behind w_kp: C cameras, kp2d_proj (C,3,4) the projections P_c (for pixels K_c E_c[:3,:4],
  * mgr_project_points' convention; formed by the caller in fp64, stored in fp32), kp2d_target (F,C,K,2), kp2d_weight (F,C,K),
  * w_kp2d, delta (the Huber radius; 0: the plain square), z_min and kp2d_dist (U,C,K), which may be NULL.

@@ -16,18 +16,24 @@
 // k_bone_transforms (bone_math.h), fed from LDS behind a barrier and stored straight to global memory as k_pose_apply does:
 // a view without a frame gets the bits of mgr_bone_transforms on its posed row.
 //
-// k_fk_backward_terms is k_fk_backward with three opt-in terms on the angles of the listed frames -- a pull towards a kept table,
-// temporal smoothness along the take, 3-D keypoints carried by the posed matrices -- in a kernel of its own, so that
-// k_fk_backward keeps its text and its bits.  The keypoints enter the tree between the walk down and the walk up: one thread per
-// keypoint forms residual and value share, one thread per bone adds its keypoints' outer products to G_i in ascending order; the
-// priors are added per element behind the angle partials.  The one workspace is three fp64 value shares per listed frame,
-// folded in list order by k_fk_terms_fold: no atomics, equal bits run to run.
+// k_fk_backward_t<TERMS> is the backward of the chain, alone (FK_TERMS_NONE) or with opt-in terms on the angles of the listed
+// frames.  FK_TERMS_3D: a pull towards a kept table, temporal smoothness along the take, 3-D keypoints carried by the posed matrices.  The keypoints enter the tree between
+// the walk down and the walk up: one thread per keypoint forms residual and value share, one thread per bone adds its keypoints'
+// outer products to G_i in ascending order; the priors are added per element behind the angle partials.  FK_TERMS_2D: those and
+// the reprojection of the same keypoints onto 2-D detections of C cameras (confidence weights, Huber).  The wave's 64 / K lane
+// groups share a keypoint's cameras (group g: cameras g, g + groups, ... in ascending order); the keypoint's thread adds the
+// groups' dE/dp in ascending group behind the 3-D part of g_k.  Cameras, targets and weights are read from global memory, so
+// nothing is sized by C.  The one workspace is three (four) fp64 value shares per listed frame, folded in list order by
+// k_fk_terms_fold_t<3> (<4>): no atomics, equal bits run to run.  MGR_PROF keeps the names the instantiations had as kernels of
+// their own: k_fk_backward, k_fk_backward_terms / k_fk_backward_terms2d, k_fk_terms_fold / k_fk_terms2d_fold.
 //
-// k_fk_backward_terms2d is k_fk_backward_terms with a fourth opt-in term, the reprojection of the same keypoints onto 2-D detections
-// of C cameras (confidence weights, Huber) -- a kernel of its own once more.  The wave's 64 / K lane groups share a keypoint's
-// cameras (group g: cameras g, g + groups, ... in ascending order); the keypoint's thread adds the groups' dE/dp in ascending group
-// behind the 3-D part of g_k.  Cameras, targets and weights are read from global memory, so nothing is sized by C.  Four value
-// shares per listed frame, folded by k_fk_terms2d_fold.
+// TERMS selects, by `if constexpr`, the LDS arrays, which frames leave at once and what they clear, the keypoint phase with
+// its barriers, the priors and the number of shares; every other phase stands once.  What holds the bits in place: the body
+// stays inside the __global__ function -- the backend contracts a*b + c*d by what surrounds it, and a phase moved into a shared
+// device function, or chosen by a run-time switch, has moved last bits before (LAB.md) -- and each instantiation compiles to
+// the instruction stream of the kernel it replaces (tools/kernel_isa_diff.py against the commit before; two expressions of
+// FK_TERMS_NONE are written as that kernel had them for this, marked where they stand).
+// tests/test_gpu_fk_backward_golden.py holds the three entries to recorded bits.
 //
 // parents[i] outside {-1} u [0, i) is read as -1 (a root): the kernels never index outside their tables whatever the list
 // holds; pose.KinematicPoseRefiner refuses such a list on the host.
@@ -169,139 +175,12 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_apply(int V, int J, int F, cons
     }
 }
 
-// workgroup u: listed frame u.  thread i < J: bone i; thread J: the global transform
-__global__ __launch_bounds__(FK_BLOCK) void k_fk_backward(int V, int J, int F, int U, const int32_t* __restrict__ frames_listed,
-                                                          const int32_t* __restrict__ view_rows,
-                                                          const int32_t* __restrict__ frame_of_view, const float* __restrict__ rest,
-                                                          const float* __restrict__ local, const int32_t* __restrict__ parents,
-                                                          const float* __restrict__ base, const float* __restrict__ theta,
-                                                          const float* __restrict__ mask, const float* __restrict__ d_transforms,
-                                                          float* __restrict__ d_theta) {
-    __shared__ float s_L[MGR_MAX_BONES * 16];
-    __shared__ float s_M[MGR_MAX_BONES * 16];
-    __shared__ float s_G[MGR_MAX_BONES * 16];
-    __shared__ float s_A[16];
-    __shared__ float s_dA[16];
-    const int u = blockIdx.x, b = threadIdx.x;
-    const int f = frames_listed[u];
-    float* out = d_theta + (size_t)u * (J + 2) * 3;
-    int shown = 0;                                            // every thread counts the same views: uniform
-    if (f >= 0 && f < F)
-        for (int k = 0; k < V; ++k) shown += (frame_of_view[k] == f && view_rows[k] >= 0) ? 1 : 0;
-    if (shown == 0) {                                         // a frame outside the table or without a view: zeros
-        for (int q = b; q < (J + 2) * 3; q += FK_BLOCK) out[q] = 0.f;
-        return;
-    }
-    const float* th = theta + (size_t)f * (J + 2) * 3;
-    if (b < J) {
-        float a[4][8];
-        bone_invert(rest + (size_t)b * 16, a);
-        float G[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) G[i][j] = 0.f;
-        for (int k = 0; k < V; ++k) {
-            if (frame_of_view[k] != f || view_rows[k] < 0) continue;
-            const float* dT = d_transforms + ((size_t)k * (J + 1) + b) * 16;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc += dT[i * 4 + q] * a[j][4 + q];      // dT inv(rest)^T
-                    G[i][j] += acc;
-                }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s_G[b * 16 + i * 4 + j] = G[i][j];
-        float R[3][3];
-        fk_euler(th + (1 + b) * 3, R);
-        fk_mul_rt(local + (size_t)b * 16, R, 0.f, 0.f, 0.f, s_L + b * 16);
-    } else if (b == J) {
-        const float* t = th + (J + 1) * 3;
-        float R[3][3];
-        fk_euler(th, R);
-        fk_mul_rt(base + (size_t)f * 16, R, t[0], t[1], t[2], s_A);
-    }
-    __syncthreads();
-    if (b < 4) {
-        fk_walk_row(J, b, parents, s_A, s_L, s_M);
-        // row b of the gradients, children before parents: G_parent += G_i L_i^T, dA += G_root L_root^T
-        float dA[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int i = J - 1; i >= 0; --i) {
-            const float* g = s_G + i * 16 + b * 4;
-            const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
-            const float* L = s_L + i * 16;
-            const int p = fk_parent(parents, i);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float up = g0 * L[c * 4] + g1 * L[c * 4 + 1] + g2 * L[c * 4 + 2] + g3 * L[c * 4 + 3];
-                if (p < 0)
-                    dA[c] += up;
-                else
-                    s_G[p * 16 + b * 4 + c] += up;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_dA[b * 4 + c] = dA[c];
-    }
-    __syncthreads();
-    if (b < J) {
-        // Q = the 3x3 block of (M_parent local_i)^T G_i, with A in place of M_parent for a root
-        const int p = fk_parent(parents, b);
-        const float* Mp = p < 0 ? s_A : s_M + p * 16;
-        const float* l = local + (size_t)b * 16;
-        float P[4][3];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                P[r][c] = Mp[r * 4] * l[c] + Mp[r * 4 + 1] * l[4 + c] + Mp[r * 4 + 2] * l[8 + c] + Mp[r * 4 + 3] * l[12 + c];
-        const float* G = s_G + b * 16;
-        float Q[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Q[i][j] = P[0][i] * G[j] + P[1][i] * G[4 + j] + P[2][i] * G[8 + j] + P[3][i] * G[12 + j];
-        float g[3];
-        fk_euler_vjp(th + (1 + b) * 3, Q, g);
-        const float* mk = mask + (1 + b) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[(1 + b) * 3 + c] = mk[c] != 0.f ? g[c] * mk[c] : 0.f;
-    } else if (b == J) {
-        // dC = base^T dA for A = base C, C = [[E(g), t], [0,0,0,1]]
-        const float* bs = base + (size_t)f * 16;
-        float dC[3][4];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dC[i][j] = bs[i] * s_dA[j] + bs[4 + i] * s_dA[4 + j] + bs[8 + i] * s_dA[8 + j] + bs[12 + i] * s_dA[12 + j];
-        float Q[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Q[i][j] = dC[i][j];
-        float g[3];
-        fk_euler_vjp(th, Q, g);
-        const float* mt = mask + (J + 1) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            out[c] = mask[c] != 0.f ? g[c] * mask[c] : 0.f;
-            out[(J + 1) * 3 + c] = mt[c] != 0.f ? dC[c][3] * mt[c] : 0.f;
-        }
-    }
-}
-
 // The terms of mgr_fk_backward_terms and what they read and leave: w_* in double for the values, c_* = (float)(2 w_*) for the
 // gradient.  K = 0 switches the keypoint term off
 struct FkTerms {
     const float* theta_ref;        // (F,J+2,3), read only
     const int32_t* neighbours;     // (F,2) prev, next; outside [0,F): none
-    double* partial;               // (U,3) the listed frames' shares of E_dev, E_smooth, E_kp
+    double* partial;               // (U,3) the listed frames' shares of E_dev, E_smooth, E_kp; (U,4) with E_kp2d
     double w_dev_r, w_smooth_r, w_dev_t, w_smooth_t, w_kp;
     float c_dev_r, c_smooth_r, c_dev_t, c_smooth_t, c_kp;
     int K;
@@ -340,247 +219,6 @@ __device__ __forceinline__ void fk_prior_row(const float* __restrict__ theta, co
     }
 }
 
-// k_fk_backward with the angle priors and the keypoint term (mgr_fk_backward_terms).  A kernel of its own: k_fk_backward keeps its
-// text and with it its bits (moved into a shared body, the compiler fuses other products: pose.hip).  The same sums in the same
-// order around three more barriers: behind the walk thread k < K forms keypoint k, p_k = (M_bone[k] [o_k; 1])[:3], its residual
-// r_k = p_k - y and g_k = (c_kp c) r_k; then thread i < J adds g_k (x) [o_k; 1] of its own keypoints to rows 0..2 of G_i, behind
-// the view sum and in ascending k; then the upward pass and the partials as they were.  The terms do not depend on views: a
-// listed frame inside [0,F) that no position shows runs the whole body on a zero view sum (d_transforms == NULL: every frame).
-// A keypoint is skipped -- exactly 0 in gradient and value, whatever its target holds -- unless its weight is > 0 (a NaN
-// weight skips) and its bone lies in [0,J).  tm.partial[3 u ..] = this frame's shares of E_dev, E_smooth, E_kp in fp64
-__global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms(int V, int J, int F, int U, const int32_t* __restrict__ frames_listed,
-                                                                const int32_t* __restrict__ view_rows,
-                                                                const int32_t* __restrict__ frame_of_view,
-                                                                const float* __restrict__ rest, const float* __restrict__ local,
-                                                                const int32_t* __restrict__ parents, const float* __restrict__ base,
-                                                                const float* __restrict__ theta, const float* __restrict__ mask,
-                                                                const float* __restrict__ d_transforms, float* __restrict__ d_theta,
-                                                                FkTerms tm) {
-    __shared__ float s_L[MGR_MAX_BONES * 16];
-    __shared__ float s_M[MGR_MAX_BONES * 16];
-    __shared__ float s_G[MGR_MAX_BONES * 16];
-    __shared__ float s_A[16];
-    __shared__ float s_dA[16];
-    __shared__ float s_kg[MGR_FK_MAX_KEYPOINTS * 3];          // g_k
-    __shared__ float s_ko[MGR_FK_MAX_KEYPOINTS * 3];          // o_k
-    __shared__ int s_kb[MGR_FK_MAX_KEYPOINTS];                // bone[k], -1: skipped
-    __shared__ double s_kv[MGR_FK_MAX_KEYPOINTS];             // c |r_k|^2
-    __shared__ double s_dev[MGR_MAX_BONES + 1];
-    __shared__ double s_smooth[MGR_MAX_BONES + 1];
-    const int u = blockIdx.x, b = threadIdx.x;
-    const int f = frames_listed[u];
-    const int rowlen = (J + 2) * 3;
-    float* out = d_theta + (size_t)u * rowlen;
-    if (f < 0 || f >= F) {                                    // a frame outside the table: zeros, no share of any value
-        for (int q = b; q < rowlen; q += FK_BLOCK) out[q] = 0.f;
-        if (b < 3) tm.partial[(size_t)u * 3 + b] = 0.0;
-        return;
-    }
-    const bool chain = d_transforms != nullptr;               // uniform
-    const float* th = theta + (size_t)f * rowlen;
-    if (b < J) {
-        float G[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) G[i][j] = 0.f;
-        if (chain) {
-            float a[4][8];
-            bone_invert(rest + (size_t)b * 16, a);
-            for (int k = 0; k < V; ++k) {
-                if (frame_of_view[k] != f || view_rows[k] < 0) continue;
-                const float* dT = d_transforms + ((size_t)k * (J + 1) + b) * 16;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float acc = 0.f;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc += dT[i * 4 + q] * a[j][4 + q];      // dT inv(rest)^T
-                        G[i][j] += acc;
-                    }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s_G[b * 16 + i * 4 + j] = G[i][j];
-        float R[3][3];
-        fk_euler(th + (1 + b) * 3, R);
-        fk_mul_rt(local + (size_t)b * 16, R, 0.f, 0.f, 0.f, s_L + b * 16);
-    } else if (b == J) {
-        const float* t = th + (J + 1) * 3;
-        float R[3][3];
-        fk_euler(th, R);
-        fk_mul_rt(base + (size_t)f * 16, R, t[0], t[1], t[2], s_A);
-    }
-    __syncthreads();
-    if (b < 4) fk_walk_row(J, b, parents, s_A, s_L, s_M);
-    __syncthreads();
-    const int K = tm.K;                                       // 0 .. MGR_FK_MAX_KEYPOINTS = FK_BLOCK: one thread per keypoint
-    if (b < K) {
-        const int bone = tm.kp_bone[b];
-        const float c = tm.kp_weight[(size_t)f * K + b];
-        const bool on = c > 0.f && bone >= 0 && bone < J;     // (a NaN weight compares false)
-        float g[3] = {0.f, 0.f, 0.f};
-        double val = 0.0;
-        const float* o = tm.kp_offset + (size_t)b * 3;
-        const float o0 = o[0], o1 = o[1], o2 = o[2];
-        if (on) {
-            const float* M = s_M + bone * 16;
-            const float* y = tm.kp_target + ((size_t)f * K + b) * 3;
-            const float ck = tm.c_kp * c;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const float p = M[r * 4] * o0 + M[r * 4 + 1] * o1 + M[r * 4 + 2] * o2 + M[r * 4 + 3];
-                const float res = p - y[r];
-                g[r] = ck * res;
-                val += (double)res * (double)res;
-            }
-            val *= (double)c;
-        }
-        s_kb[b] = on ? bone : -1;
-        s_kv[b] = val;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            s_kg[b * 3 + r] = g[r];
-            s_ko[b * 3 + r] = o[r];
-        }
-    }
-    __syncthreads();
-    if (b < J) {
-        for (int k = 0; k < K; ++k) {
-            if (s_kb[k] != b) continue;
-            const float o0 = s_ko[k * 3], o1 = s_ko[k * 3 + 1], o2 = s_ko[k * 3 + 2];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const float g = s_kg[k * 3 + r];
-                s_G[b * 16 + r * 4 + 0] += g * o0;
-                s_G[b * 16 + r * 4 + 1] += g * o1;
-                s_G[b * 16 + r * 4 + 2] += g * o2;
-                s_G[b * 16 + r * 4 + 3] += g;
-            }
-        }
-    }
-    __syncthreads();
-    if (b < 4) {
-        // row b of the gradients, children before parents: G_parent += G_i L_i^T, dA += G_root L_root^T
-        float dA[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int i = J - 1; i >= 0; --i) {
-            const float* g = s_G + i * 16 + b * 4;
-            const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
-            const float* L = s_L + i * 16;
-            const int p = fk_parent(parents, i);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float up = g0 * L[c * 4] + g1 * L[c * 4 + 1] + g2 * L[c * 4 + 2] + g3 * L[c * 4 + 3];
-                if (p < 0)
-                    dA[c] += up;
-                else
-                    s_G[p * 16 + b * 4 + c] += up;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_dA[b * 4 + c] = dA[c];
-    }
-    __syncthreads();
-    // the neighbours of the priors; whether prev is listed is a walk over frames_listed (U is a step's views at most)
-    int prev = -1, next = -1;
-    if (tm.neighbours) {
-        prev = tm.neighbours[2 * (size_t)f];
-        next = tm.neighbours[2 * (size_t)f + 1];
-        if (prev < 0 || prev >= F) prev = -1;
-        if (next < 0 || next >= F) next = -1;
-    }
-    bool prev_listed = false;
-    if (prev >= 0)
-        for (int q = 0; q < U; ++q) prev_listed = prev_listed || frames_listed[q] == prev;
-    const bool prior_r = tm.w_dev_r != 0.0 || tm.w_smooth_r != 0.0, prior_t = tm.w_dev_t != 0.0 || tm.w_smooth_t != 0.0;
-    if (b < J) {
-        // Q = the 3x3 block of (M_parent local_i)^T G_i, with A in place of M_parent for a root
-        const int p = fk_parent(parents, b);
-        const float* Mp = p < 0 ? s_A : s_M + p * 16;
-        const float* l = local + (size_t)b * 16;
-        float P[4][3];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                P[r][c] = Mp[r * 4] * l[c] + Mp[r * 4 + 1] * l[4 + c] + Mp[r * 4 + 2] * l[8 + c] + Mp[r * 4 + 3] * l[12 + c];
-        const float* G = s_G + b * 16;
-        float Q[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Q[i][j] = P[0][i] * G[j] + P[1][i] * G[4 + j] + P[2][i] * G[8 + j] + P[3][i] * G[12 + j];
-        float g[3];
-        fk_euler_vjp(th + (1 + b) * 3, Q, g);
-        double dev = 0.0, smooth = 0.0;
-        if (prior_r) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, 1 + b, !prev_listed, tm.c_dev_r, tm.c_smooth_r, mask, g, dev, smooth);
-        s_dev[b] = tm.w_dev_r * dev;
-        s_smooth[b] = tm.w_smooth_r * smooth;
-        const float* mk = mask + (1 + b) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[(1 + b) * 3 + c] = mk[c] != 0.f ? g[c] * mk[c] : 0.f;
-    } else if (b == J) {
-        // dC = base^T dA for A = base C, C = [[E(g), t], [0,0,0,1]]
-        const float* bs = base + (size_t)f * 16;
-        float dC[3][4];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dC[i][j] = bs[i] * s_dA[j] + bs[4 + i] * s_dA[4 + j] + bs[8 + i] * s_dA[8 + j] + bs[12 + i] * s_dA[12 + j];
-        float Q[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Q[i][j] = dC[i][j];
-        float g[3];
-        fk_euler_vjp(th, Q, g);
-        float gt[3] = {dC[0][3], dC[1][3], dC[2][3]};
-        double dev_r = 0.0, smooth_r = 0.0, dev_t = 0.0, smooth_t = 0.0;
-        if (prior_r) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, 0, !prev_listed, tm.c_dev_r, tm.c_smooth_r, mask, g, dev_r, smooth_r);
-        if (prior_t) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, J + 1, !prev_listed, tm.c_dev_t, tm.c_smooth_t, mask, gt, dev_t, smooth_t);
-        s_dev[J] = tm.w_dev_r * dev_r + tm.w_dev_t * dev_t;
-        s_smooth[J] = tm.w_smooth_r * smooth_r + tm.w_smooth_t * smooth_t;
-        const float* mt = mask + (J + 1) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            out[c] = mask[c] != 0.f ? g[c] * mask[c] : 0.f;
-            out[(J + 1) * 3 + c] = mt[c] != 0.f ? gt[c] * mt[c] : 0.f;
-        }
-    }
-    __syncthreads();
-    // this frame's shares: one thread per term, every sum in ascending index
-    if (b == 0) {
-        double acc = 0.0;
-        for (int i = 0; i <= J; ++i) acc += s_dev[i];
-        tm.partial[(size_t)u * 3] = acc;
-    } else if (b == 1) {
-        double acc = 0.0;
-        for (int i = 0; i <= J; ++i) acc += s_smooth[i];
-        tm.partial[(size_t)u * 3 + 1] = acc;
-    } else if (b == 2) {
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) acc += s_kv[k];
-        tm.partial[(size_t)u * 3 + 2] = tm.w_kp * acc;
-    }
-}
-
-// one workgroup over the (U,3) shares: thread t < 3 adds term t of the listed frames in list order; values[3] = their sum
-__global__ __launch_bounds__(FK_BLOCK) void k_fk_terms_fold(const double* __restrict__ partial, int U, double* __restrict__ values) {
-    __shared__ double s_sum[3];
-    const int t = threadIdx.x;
-    if (t < 3) {
-        double acc = 0.0;
-        for (int u = 0; u < U; ++u) acc += partial[(size_t)u * 3 + t];
-        s_sum[t] = acc;
-        values[t] = acc;
-    }
-    __syncthreads();
-    if (t == 0) values[3] = (s_sum[0] + s_sum[1]) + s_sum[2];
-}
-
 // The 2-D reprojection term of mgr_fk_backward_terms2d beside FkTerms: w in double for the value, c = (float)(2 w) for the
 // gradient; delta / zmin in fp32 as the kernel compares them, delta_d = (double)delta for the value
 struct FkTerms2d {
@@ -594,24 +232,44 @@ struct FkTerms2d {
     int kp3d;                      // the 3-D keypoint term is on (FkTerms::kp_target / kp_weight are read)
 };
 
-// k_fk_backward_terms with the multi-view 2-D keypoint term (mgr_fk_backward_terms2d).  A kernel of its own once more:
-// k_fk_backward and k_fk_backward_terms keep their text and their bits.  The same phases around one more barrier.  The keypoint
-// phase runs on groups = 64 / K lane groups: thread (g, k) forms p_k and walks the cameras c = g, g + groups, ... < C in ascending
-// order: q = P_c [p_k; 1], u = q[:2] / q[2], r = u - t[f,c,k], d = |r|, the Huber factor h, g_u = ((c2d s) h) r,
-// dE/dq = [g_u0 / q2, g_u1 / q2, -(g_u0 u0 + g_u1 u1) / q2], dE/dp = P_c[:, :3]^T dE/dq -- all of it uncontracted -- adding its
-// cameras' dE/dp in that order; behind a barrier thread k < K adds the groups' sums in ascending g -- a fixed tree over camera
-// slices that depends on C and K alone -- behind the 3-D residual part of g_k.  Nothing in LDS is sized by C: projections, targets
-// and weights are read from global memory.  A detection is skipped -- exactly 0 in gradient and value, NaN in dist, its target not
-// read -- unless its weight is > 0 (a NaN weight skips), its bone lies in [0,J) and q2 > zmin.  The output of a frame depends on
-// that frame's inputs alone.  tm.partial[4 u ..] = this frame's shares of E_dev, E_smooth, E_kp, E_kp2d in fp64
-__global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, int F, int U, const int32_t* __restrict__ frames_listed,
-                                                                  const int32_t* __restrict__ view_rows,
-                                                                  const int32_t* __restrict__ frame_of_view,
-                                                                  const float* __restrict__ rest, const float* __restrict__ local,
-                                                                  const int32_t* __restrict__ parents, const float* __restrict__ base,
-                                                                  const float* __restrict__ theta, const float* __restrict__ mask,
-                                                                  const float* __restrict__ d_transforms, float* __restrict__ d_theta,
-                                                                  FkTerms tm, FkTerms2d t2) {
+// Which terms an instantiation of k_fk_backward_t carries: none (mgr_fk_backward), the angle priors and the 3-D keypoints
+// (mgr_fk_backward_terms), or those and the 2-D reprojection (mgr_fk_backward_terms2d)
+constexpr int FK_TERMS_NONE = 0, FK_TERMS_3D = 1, FK_TERMS_2D = 2;
+
+// workgroup u: listed frame u.  thread i < J: bone i; thread J: the global transform.
+//
+// FK_TERMS_NONE: the view sum dT inv(rest)^T into G_i, L_i, the walk down and the walk up by the same four threads with no
+// barrier between, the angle partials.  A frame outside the table or without a view: zeros.  tm and t2 are not read.
+//
+// With terms: the same sums in the same order around more barriers.  Behind the walk down the keypoints form g_k = dE/dp_k (below,
+// per TERMS); then thread i < J adds g_k (x) [o_k; 1] of its own keypoints to rows 0..2 of G_i, behind the view sum and in
+// ascending k; then the upward pass and the partials, the priors added per element behind the partials.  The terms do not depend
+// on views: a listed frame inside [0,F) that no position shows runs the whole body on a zero view sum (d_transforms == NULL:
+// every frame).  The output of a frame depends on that frame's inputs alone.
+// tm.partial[N u ..] = this frame's shares of E_dev, E_smooth, E_kp [, E_kp2d] in fp64, N = 3 or 4.
+//
+// FK_TERMS_3D: thread k < K forms keypoint k, p_k = (M_bone[k] [o_k; 1])[:3], its residual r_k = p_k - y and g_k = (c_kp c) r_k.  A
+// keypoint is skipped -- exactly 0 in gradient and value, whatever its target holds -- unless its weight is > 0 (a NaN weight
+// skips) and its bone lies in [0,J).
+//
+// FK_TERMS_2D: one more barrier.  The keypoint phase runs on groups = 64 / K lane groups: thread (g, k) forms p_k and walks the
+// cameras c = g, g + groups, ... < C in ascending order: q = P_c [p_k; 1], u = q[:2] / q[2], r = u - t[f,c,k], d = |r|, the Huber
+// factor h, g_u = ((c2d s) h) r, dE/dq = [g_u0 / q2, g_u1 / q2, -(g_u0 u0 + g_u1 u1) / q2], dE/dp = P_c[:, :3]^T dE/dq -- all of it
+// uncontracted -- adding its cameras' dE/dp in that order; behind a barrier thread k < K adds the groups' sums in ascending g -- a
+// fixed tree over camera slices that depends on C and K alone -- behind the 3-D residual part of g_k.  Nothing in LDS is sized by
+// C: projections, targets and weights are read from global memory.  A detection is skipped -- exactly 0 in gradient and value,
+// NaN in dist, its target not read -- unless its weight is > 0 (a NaN weight skips), its bone lies in [0,J) and q2 > zmin.
+// t2 is read by FK_TERMS_2D alone
+template <int TERMS>
+__global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_t(int V, int J, int F, int U, const int32_t* __restrict__ frames_listed,
+                                                            const int32_t* __restrict__ view_rows,
+                                                            const int32_t* __restrict__ frame_of_view, const float* __restrict__ rest,
+                                                            const float* __restrict__ local, const int32_t* __restrict__ parents,
+                                                            const float* __restrict__ base, const float* __restrict__ theta,
+                                                            const float* __restrict__ mask, const float* __restrict__ d_transforms,
+                                                            float* __restrict__ d_theta, FkTerms tm, FkTerms2d t2) {
+    constexpr bool ON = TERMS != FK_TERMS_NONE, KP2D = TERMS == FK_TERMS_2D;
+    constexpr int N = KP2D ? 4 : 3;                           // value shares per listed frame
     __shared__ float s_L[MGR_MAX_BONES * 16];
     __shared__ float s_M[MGR_MAX_BONES * 16];
     __shared__ float s_G[MGR_MAX_BONES * 16];
@@ -619,27 +277,38 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, 
     __shared__ float s_dA[16];
     __shared__ float s_kg[MGR_FK_MAX_KEYPOINTS * 3];          // g_k
     __shared__ float s_ko[MGR_FK_MAX_KEYPOINTS * 3];          // o_k
-    __shared__ int s_kb[MGR_FK_MAX_KEYPOINTS];                // bone[k], -1: outside [0,J)
+    __shared__ int s_kb[MGR_FK_MAX_KEYPOINTS];                // bone[k], -1: skipped (3-D) / outside [0,J) (2-D)
     __shared__ double s_kv[MGR_FK_MAX_KEYPOINTS];             // c |r_k|^2
-    __shared__ double s_kv2[MGR_FK_MAX_KEYPOINTS];            // sum_c s rho(d)
-    __shared__ float s_pa[FK_BLOCK * 3];                      // the lane groups' sums of dE/dp
-    __shared__ double s_pv[FK_BLOCK];                         // the lane groups' sums of s rho(d)
+    __shared__ double s_kv2[KP2D ? MGR_FK_MAX_KEYPOINTS : 1]; // sum_c s rho(d)
+    __shared__ float s_pa[KP2D ? FK_BLOCK * 3 : 1];           // the lane groups' sums of dE/dp
+    __shared__ double s_pv[KP2D ? FK_BLOCK : 1];              // the lane groups' sums of s rho(d)
     __shared__ double s_dev[MGR_MAX_BONES + 1];
     __shared__ double s_smooth[MGR_MAX_BONES + 1];
     const int u = blockIdx.x, b = threadIdx.x;
     const int f = frames_listed[u];
     const int rowlen = (J + 2) * 3;
-    const int K = tm.K, C = t2.C;                             // K 1 .. MGR_FK_MAX_KEYPOINTS = FK_BLOCK: one thread per keypoint
-    float* out = d_theta + (size_t)u * rowlen;
-    if (f < 0 || f >= F) {                                    // a frame outside the table: zeros, no share of any value, no distance
+    const int K = tm.K;                                       // 0 (2-D: 1) .. MGR_FK_MAX_KEYPOINTS = FK_BLOCK: one thread per keypoint
+    // (the row offsets as the kernel of each TERMS first had them, a 32-bit row length or 64-bit products throughout: the backend
+    // packs the fp32 sums of the whole body differently behind one and the other, LAB.md)
+    float* out = d_theta + (ON ? (size_t)u * rowlen : (size_t)u * (J + 2) * 3);
+    bool live = f >= 0 && f < F;                              // uniform, as every flag below
+    if constexpr (!ON) {                                      // the chain alone: a frame that no view shows has nothing to carry
+        int shown = 0;
+        if (live)
+            for (int k = 0; k < V; ++k) shown += (frame_of_view[k] == f && view_rows[k] >= 0) ? 1 : 0;
+        live = shown != 0;
+    }
+    if (!live) {                                              // zeros, no share of any value, no distance
         for (int q = b; q < rowlen; q += FK_BLOCK) out[q] = 0.f;
-        if (b < 4) tm.partial[(size_t)u * 4 + b] = 0.0;
-        if (t2.dist && b < K)
-            for (int c = 0; c < C; ++c) t2.dist[((size_t)u * C + c) * K + b] = NAN;
+        if constexpr (ON)
+            if (b < N) tm.partial[(size_t)u * N + b] = 0.0;
+        if constexpr (KP2D)
+            if (t2.dist && b < K)
+                for (int c = 0; c < t2.C; ++c) t2.dist[((size_t)u * t2.C + c) * K + b] = NAN;
         return;
     }
-    const bool chain = d_transforms != nullptr;               // uniform
-    const float* th = theta + (size_t)f * rowlen;
+    const bool chain = !ON || d_transforms != nullptr;        // (with a term on, d_transforms may be NULL)
+    const float* th = theta + (ON ? (size_t)f * rowlen : (size_t)f * (J + 2) * 3);
     if (b < J) {
         float G[4][4];
 #pragma unroll
@@ -678,120 +347,155 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, 
     }
     __syncthreads();
     if (b < 4) fk_walk_row(J, b, parents, s_A, s_L, s_M);
-    __syncthreads();
-    // thread b = (lane group grp, keypoint k): group grp takes the cameras grp, grp + groups, ... in ascending order; the groups'
-    // sums meet in LDS and thread k adds them in ascending group -- one order per (C, K), whatever U and the list hold
-    const int groups = FK_BLOCK / K;                          // >= 1: K <= FK_BLOCK
-    const int grp = b / K, k = b - grp * K;
-    const bool lane_on = grp < groups;
-    int bone = -1;
-    bool bone_ok = false;
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-    float p[3] = {0.f, 0.f, 0.f};
-    if (lane_on) {
-        bone = tm.kp_bone[k];
-        bone_ok = bone >= 0 && bone < J;
-        const float* o = tm.kp_offset + (size_t)k * 3;
-        o0 = o[0], o1 = o[1], o2 = o[2];
-        if (bone_ok) {
-            const float* M = s_M + bone * 16;
+    if constexpr (ON) {      // the keypoints: g_k, then its share of G_bone[k]; without them thread r walks up what it walked down
+        __syncthreads();
+        if constexpr (!KP2D) {
+            if (b < K) {
+                const int bone = tm.kp_bone[b];
+                const float c = tm.kp_weight[(size_t)f * K + b];
+                const bool on = c > 0.f && bone >= 0 && bone < J;     // (a NaN weight compares false)
+                float g[3] = {0.f, 0.f, 0.f};
+                double val = 0.0;
+                const float* o = tm.kp_offset + (size_t)b * 3;
+                const float o0 = o[0], o1 = o[1], o2 = o[2];
+                if (on) {
+                    const float* M = s_M + bone * 16;
+                    const float* y = tm.kp_target + ((size_t)f * K + b) * 3;
+                    const float ck = tm.c_kp * c;
 #pragma unroll
-            for (int r = 0; r < 3; ++r) p[r] = M[r * 4] * o0 + M[r * 4 + 1] * o1 + M[r * 4 + 2] * o2 + M[r * 4 + 3];
-        }
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        double val2 = 0.0;
-        for (int c = grp; c < C; c += groups) {
-            const size_t at = ((size_t)f * C + c) * K + k;
-            const float s = t2.weight[at];
-            float dist = NAN;
-            if (bone_ok && s > 0.f) {                         // (a NaN weight compares false)
-                const float* P = t2.proj + (size_t)c * 12;
-                const float q0 = P[0] * p[0] + P[1] * p[1] + P[2] * p[2] + P[3];
-                const float q1 = P[4] * p[0] + P[5] * p[1] + P[6] * p[2] + P[7];
-                const float q2 = P[8] * p[0] + P[9] * p[1] + P[10] * p[2] + P[11];
-                if (q2 > t2.zmin) {
-#pragma clang fp contract(off)
-                    const float t0 = t2.target[at * 2], t1 = t2.target[at * 2 + 1];
-                    const float u0 = q0 / q2, u1 = q1 / q2;
-                    const float r0 = u0 - t0, r1 = u1 - t1;
-                    const float d = sqrtf(r0 * r0 + r1 * r1);
-                    const bool inside = t2.delta == 0.f || d <= t2.delta;      // (a NaN distance: outside, and h carries it on)
-                    const float h = inside ? 1.f : t2.delta / d;
-                    const float cs = (t2.c * s) * h;
-                    const float gu0 = cs * r0, gu1 = cs * r1;
-                    const float dq0 = gu0 / q2, dq1 = gu1 / q2;
-                    const float dq2 = -((gu0 * u0 + gu1 * u1) / q2);
-                    a0 = a0 + ((P[0] * dq0 + P[4] * dq1) + P[8] * dq2);
-                    a1 = a1 + ((P[1] * dq0 + P[5] * dq1) + P[9] * dq2);
-                    a2 = a2 + ((P[2] * dq0 + P[6] * dq1) + P[10] * dq2);
-                    const double rho = inside ? (double)r0 * (double)r0 + (double)r1 * (double)r1
-                                              : 2.0 * t2.delta_d * (double)d - t2.delta_d * t2.delta_d;
-                    val2 += (double)s * rho;
-                    dist = d;
+                    for (int r = 0; r < 3; ++r) {
+                        const float p = M[r * 4] * o0 + M[r * 4 + 1] * o1 + M[r * 4 + 2] * o2 + M[r * 4 + 3];
+                        const float res = p - y[r];
+                        g[r] = ck * res;
+                        val += (double)res * (double)res;
+                    }
+                    val *= (double)c;
                 }
-            }
-            if (t2.dist) t2.dist[((size_t)u * C + c) * K + k] = dist;
-        }
-        s_pa[b * 3] = a0;
-        s_pa[b * 3 + 1] = a1;
-        s_pa[b * 3 + 2] = a2;
-        s_pv[b] = val2;
-    }
-    __syncthreads();
-    if (b < K) {                                              // (grp = 0, k = b: bone, o and p are this keypoint's)
-        float g[3] = {0.f, 0.f, 0.f};
-        double val = 0.0, val2 = 0.0;
-        if (t2.kp3d && bone_ok) {
-            const float c = tm.kp_weight[(size_t)f * K + b];
-            if (c > 0.f) {                                    // (a NaN weight compares false)
-                const float* y = tm.kp_target + ((size_t)f * K + b) * 3;
-                const float ck = tm.c_kp * c;
+                s_kb[b] = on ? bone : -1;
+                s_kv[b] = val;
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
-                    const float res = p[r] - y[r];
-                    g[r] = ck * res;
-                    val += (double)res * (double)res;
+                    s_kg[b * 3 + r] = g[r];
+                    s_ko[b * 3 + r] = o[r];
                 }
-                val *= (double)c;
             }
-        }
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int q = 0; q < groups; ++q) {
-            const int at = (q * K + b) * 3;
-            a0 = a0 + s_pa[at];
-            a1 = a1 + s_pa[at + 1];
-            a2 = a2 + s_pa[at + 2];
-            val2 += s_pv[q * K + b];
-        }
-        g[0] = g[0] + a0;                                     // the 3-D part first
-        g[1] = g[1] + a1;
-        g[2] = g[2] + a2;
-        s_kb[b] = bone_ok ? bone : -1;
-        s_kv[b] = val;
-        s_kv2[b] = val2;
-        s_kg[b * 3] = g[0];
-        s_kg[b * 3 + 1] = g[1];
-        s_kg[b * 3 + 2] = g[2];
-        s_ko[b * 3] = o0;
-        s_ko[b * 3 + 1] = o1;
-        s_ko[b * 3 + 2] = o2;
-    }
-    __syncthreads();
-    if (b < J) {
-        for (int k = 0; k < K; ++k) {
-            if (s_kb[k] != b) continue;
-            const float o0 = s_ko[k * 3], o1 = s_ko[k * 3 + 1], o2 = s_ko[k * 3 + 2];
+        } else {
+            // thread b = (lane group grp, keypoint k): group grp takes the cameras grp, grp + groups, ... in ascending order; the groups'
+            // sums meet in LDS and thread k adds them in ascending group -- one order per (C, K), whatever U and the list hold
+            const int C = t2.C;
+            const int groups = FK_BLOCK / K;                          // >= 1: K <= FK_BLOCK
+            const int grp = b / K, k = b - grp * K;
+            const bool lane_on = grp < groups;
+            int bone = -1;
+            bool bone_ok = false;
+            float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+            float p[3] = {0.f, 0.f, 0.f};
+            if (lane_on) {
+                bone = tm.kp_bone[k];
+                bone_ok = bone >= 0 && bone < J;
+                const float* o = tm.kp_offset + (size_t)k * 3;
+                o0 = o[0], o1 = o[1], o2 = o[2];
+                if (bone_ok) {
+                    const float* M = s_M + bone * 16;
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const float g = s_kg[k * 3 + r];
-                s_G[b * 16 + r * 4 + 0] += g * o0;
-                s_G[b * 16 + r * 4 + 1] += g * o1;
-                s_G[b * 16 + r * 4 + 2] += g * o2;
-                s_G[b * 16 + r * 4 + 3] += g;
+                    for (int r = 0; r < 3; ++r) p[r] = M[r * 4] * o0 + M[r * 4 + 1] * o1 + M[r * 4 + 2] * o2 + M[r * 4 + 3];
+                }
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+                double val2 = 0.0;
+                for (int c = grp; c < C; c += groups) {
+                    const size_t at = ((size_t)f * C + c) * K + k;
+                    const float s = t2.weight[at];
+                    float dist = NAN;
+                    if (bone_ok && s > 0.f) {                         // (a NaN weight compares false)
+                        const float* P = t2.proj + (size_t)c * 12;
+                        const float q0 = P[0] * p[0] + P[1] * p[1] + P[2] * p[2] + P[3];
+                        const float q1 = P[4] * p[0] + P[5] * p[1] + P[6] * p[2] + P[7];
+                        const float q2 = P[8] * p[0] + P[9] * p[1] + P[10] * p[2] + P[11];
+                        if (q2 > t2.zmin) {
+#pragma clang fp contract(off)
+                            const float t0 = t2.target[at * 2], t1 = t2.target[at * 2 + 1];
+                            const float u0 = q0 / q2, u1 = q1 / q2;
+                            const float r0 = u0 - t0, r1 = u1 - t1;
+                            const float d = sqrtf(r0 * r0 + r1 * r1);
+                            const bool inside = t2.delta == 0.f || d <= t2.delta;      // (a NaN distance: outside, and h carries it on)
+                            const float h = inside ? 1.f : t2.delta / d;
+                            const float cs = (t2.c * s) * h;
+                            const float gu0 = cs * r0, gu1 = cs * r1;
+                            const float dq0 = gu0 / q2, dq1 = gu1 / q2;
+                            const float dq2 = -((gu0 * u0 + gu1 * u1) / q2);
+                            a0 = a0 + ((P[0] * dq0 + P[4] * dq1) + P[8] * dq2);
+                            a1 = a1 + ((P[1] * dq0 + P[5] * dq1) + P[9] * dq2);
+                            a2 = a2 + ((P[2] * dq0 + P[6] * dq1) + P[10] * dq2);
+                            const double rho = inside ? (double)r0 * (double)r0 + (double)r1 * (double)r1
+                                                      : 2.0 * t2.delta_d * (double)d - t2.delta_d * t2.delta_d;
+                            val2 += (double)s * rho;
+                            dist = d;
+                        }
+                    }
+                    if (t2.dist) t2.dist[((size_t)u * C + c) * K + k] = dist;
+                }
+                s_pa[b * 3] = a0;
+                s_pa[b * 3 + 1] = a1;
+                s_pa[b * 3 + 2] = a2;
+                s_pv[b] = val2;
+            }
+            __syncthreads();
+            if (b < K) {                                              // (grp = 0, k = b: bone, o and p are this keypoint's)
+                float g[3] = {0.f, 0.f, 0.f};
+                double val = 0.0, val2 = 0.0;
+                if (t2.kp3d && bone_ok) {
+                    const float c = tm.kp_weight[(size_t)f * K + b];
+                    if (c > 0.f) {                                    // (a NaN weight compares false)
+                        const float* y = tm.kp_target + ((size_t)f * K + b) * 3;
+                        const float ck = tm.c_kp * c;
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) {
+                            const float res = p[r] - y[r];
+                            g[r] = ck * res;
+                            val += (double)res * (double)res;
+                        }
+                        val *= (double)c;
+                    }
+                }
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+                for (int q = 0; q < groups; ++q) {
+                    const int at = (q * K + b) * 3;
+                    a0 = a0 + s_pa[at];
+                    a1 = a1 + s_pa[at + 1];
+                    a2 = a2 + s_pa[at + 2];
+                    val2 += s_pv[q * K + b];
+                }
+                g[0] = g[0] + a0;                                     // the 3-D part first
+                g[1] = g[1] + a1;
+                g[2] = g[2] + a2;
+                s_kb[b] = bone_ok ? bone : -1;
+                s_kv[b] = val;
+                s_kv2[b] = val2;
+                s_kg[b * 3] = g[0];
+                s_kg[b * 3 + 1] = g[1];
+                s_kg[b * 3 + 2] = g[2];
+                s_ko[b * 3] = o0;
+                s_ko[b * 3 + 1] = o1;
+                s_ko[b * 3 + 2] = o2;
             }
         }
+        __syncthreads();
+        if (b < J) {
+            for (int k = 0; k < K; ++k) {
+                if (s_kb[k] != b) continue;
+                const float o0 = s_ko[k * 3], o1 = s_ko[k * 3 + 1], o2 = s_ko[k * 3 + 2];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const float g = s_kg[k * 3 + r];
+                    s_G[b * 16 + r * 4 + 0] += g * o0;
+                    s_G[b * 16 + r * 4 + 1] += g * o1;
+                    s_G[b * 16 + r * 4 + 2] += g * o2;
+                    s_G[b * 16 + r * 4 + 3] += g;
+                }
+            }
+        }
+        __syncthreads();
     }
-    __syncthreads();
     if (b < 4) {
         // row b of the gradients, children before parents: G_parent += G_i L_i^T, dA += G_root L_root^T
         float dA[4] = {0.f, 0.f, 0.f, 0.f};
@@ -815,7 +519,7 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, 
     __syncthreads();
     // the neighbours of the priors; whether prev is listed is a walk over frames_listed (U is a step's views at most)
     int prev = -1, next = -1;
-    if (tm.neighbours) {
+    if (ON && tm.neighbours) {
         prev = tm.neighbours[2 * (size_t)f];
         next = tm.neighbours[2 * (size_t)f + 1];
         if (prev < 0 || prev >= F) prev = -1;
@@ -824,7 +528,7 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, 
     bool prev_listed = false;
     if (prev >= 0)
         for (int q = 0; q < U; ++q) prev_listed = prev_listed || frames_listed[q] == prev;
-    const bool prior_r = tm.w_dev_r != 0.0 || tm.w_smooth_r != 0.0, prior_t = tm.w_dev_t != 0.0 || tm.w_smooth_t != 0.0;
+    const bool prior_r = ON && (tm.w_dev_r != 0.0 || tm.w_smooth_r != 0.0), prior_t = ON && (tm.w_dev_t != 0.0 || tm.w_smooth_t != 0.0);
     if (b < J) {
         // Q = the 3x3 block of (M_parent local_i)^T G_i, with A in place of M_parent for a root
         const int p = fk_parent(parents, b);
@@ -846,8 +550,10 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, 
         fk_euler_vjp(th + (1 + b) * 3, Q, g);
         double dev = 0.0, smooth = 0.0;
         if (prior_r) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, 1 + b, !prev_listed, tm.c_dev_r, tm.c_smooth_r, mask, g, dev, smooth);
-        s_dev[b] = tm.w_dev_r * dev;
-        s_smooth[b] = tm.w_smooth_r * smooth;
+        if constexpr (ON) {
+            s_dev[b] = tm.w_dev_r * dev;
+            s_smooth[b] = tm.w_smooth_r * smooth;
+        }
         const float* mk = mask + (1 + b) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) out[(1 + b) * 3 + c] = mk[c] != 0.f ? g[c] * mk[c] : 0.f;
@@ -870,49 +576,59 @@ __global__ __launch_bounds__(FK_BLOCK) void k_fk_backward_terms2d(int V, int J, 
         double dev_r = 0.0, smooth_r = 0.0, dev_t = 0.0, smooth_t = 0.0;
         if (prior_r) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, 0, !prev_listed, tm.c_dev_r, tm.c_smooth_r, mask, g, dev_r, smooth_r);
         if (prior_t) fk_prior_row(theta, tm.theta_ref, rowlen, f, prev, next, J + 1, !prev_listed, tm.c_dev_t, tm.c_smooth_t, mask, gt, dev_t, smooth_t);
-        s_dev[J] = tm.w_dev_r * dev_r + tm.w_dev_t * dev_t;
-        s_smooth[J] = tm.w_smooth_r * smooth_r + tm.w_smooth_t * smooth_t;
+        if constexpr (ON) {
+            s_dev[J] = tm.w_dev_r * dev_r + tm.w_dev_t * dev_t;
+            s_smooth[J] = tm.w_smooth_r * smooth_r + tm.w_smooth_t * smooth_t;
+        }
         const float* mt = mask + (J + 1) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             out[c] = mask[c] != 0.f ? g[c] * mask[c] : 0.f;
-            out[(J + 1) * 3 + c] = mt[c] != 0.f ? gt[c] * mt[c] : 0.f;
+            // (without a prior on it the translation's gradient is read where it stands, as that kernel first had it: through the
+            // copy the backend selects one product differently)
+            out[(J + 1) * 3 + c] = mt[c] != 0.f ? (ON ? gt[c] : dC[c][3]) * mt[c] : 0.f;
         }
     }
+    if constexpr (!ON) return;                                // (no value, no share)
     __syncthreads();
     // this frame's shares: one thread per term, every sum in ascending index
     if (b == 0) {
         double acc = 0.0;
         for (int i = 0; i <= J; ++i) acc += s_dev[i];
-        tm.partial[(size_t)u * 4] = acc;
+        tm.partial[(size_t)u * N] = acc;
     } else if (b == 1) {
         double acc = 0.0;
         for (int i = 0; i <= J; ++i) acc += s_smooth[i];
-        tm.partial[(size_t)u * 4 + 1] = acc;
+        tm.partial[(size_t)u * N + 1] = acc;
     } else if (b == 2) {
         double acc = 0.0;
         for (int k = 0; k < K; ++k) acc += s_kv[k];
-        tm.partial[(size_t)u * 4 + 2] = tm.w_kp * acc;
-    } else if (b == 3) {
+        tm.partial[(size_t)u * N + 2] = tm.w_kp * acc;
+    } else if (KP2D && b == 3) {
         double acc = 0.0;
         for (int k = 0; k < K; ++k) acc += s_kv2[k];
-        tm.partial[(size_t)u * 4 + 3] = t2.w * acc;
+        tm.partial[(size_t)u * N + 3] = t2.w * acc;
     }
 }
 
-// one workgroup over the (U,4) shares: thread t < 4 adds term t of the listed frames in list order into values[0], [1], [2], [4];
-// values[3] = the sum of the four
-__global__ __launch_bounds__(FK_BLOCK) void k_fk_terms2d_fold(const double* __restrict__ partial, int U, double* __restrict__ values) {
-    __shared__ double s_sum[4];
+// one workgroup over the (U,N) shares, N = 3 or 4: thread t < N adds term t of the listed frames in list order into values[0], [1],
+// [2] and, the fourth, [4]; values[3] = their sum, ((s0 + s1) + s2) [+ s3]
+template <int N>
+__global__ __launch_bounds__(FK_BLOCK) void k_fk_terms_fold_t(const double* __restrict__ partial, int U, double* __restrict__ values) {
+    __shared__ double s_sum[N];
     const int t = threadIdx.x;
-    if (t < 4) {
+    if (t < N) {
         double acc = 0.0;
-        for (int u = 0; u < U; ++u) acc += partial[(size_t)u * 4 + t];
+        for (int u = 0; u < U; ++u) acc += partial[(size_t)u * N + t];
         s_sum[t] = acc;
         values[t < 3 ? t : 4] = acc;
     }
     __syncthreads();
-    if (t == 0) values[3] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+    if (t == 0) {
+        double sum = (s_sum[0] + s_sum[1]) + s_sum[2];
+        if constexpr (N == 4) sum = sum + s_sum[3];
+        values[3] = sum;
+    }
 }
 
 // thread (u, e): element e of the (J+2, 3) row of listed frame u.  pose_adam_one (k_pose_adam's update), rows 0..J at the
@@ -969,8 +685,8 @@ extern "C" int mgr_fk_backward(int V, int J, int F, int U, const int32_t* frames
     hipStream_t stream = (hipStream_t)stream_;
     {
         MGR_PROF("k_fk_backward", stream);
-        hipLaunchKernelGGL(k_fk_backward, dim3(U), dim3(FK_BLOCK), 0, stream, V, J, F, U, frames_listed, view_rows, frame_of_view, rest,
-                           local, parents, base, theta, mask, d_transforms, d_theta);
+        hipLaunchKernelGGL(k_fk_backward_t<FK_TERMS_NONE>, dim3(U), dim3(FK_BLOCK), 0, stream, V, J, F, U, frames_listed, view_rows, frame_of_view, rest,
+                           local, parents, base, theta, mask, d_transforms, d_theta, FkTerms{}, FkTerms2d{});
     }
     MGR_LAUNCH_CHECK("k_fk_backward", stream, 0);
     return MGR_OK;
@@ -1004,6 +720,50 @@ extern "C" size_t mgr_fk_terms_workspace_bytes(int U, int J, int K) {
     return (U < 1 || J < 1) ? 0 : (size_t)U * 3 * sizeof(double);
 }
 
+extern "C" size_t mgr_fk_terms2d_workspace_bytes(int U, int J, int K, int C) {
+    (void)K;      // (the keypoints' and cameras' shares meet inside the workgroup)
+    (void)C;
+    return (U < 1 || J < 1) ? 0 : (size_t)U * 4 * sizeof(double);
+}
+
+// what mgr_fk_backward takes, as the two term entries pass it on
+struct FkChainArgs {
+    int V, J, F, U;
+    const int32_t *frames_listed, *view_rows, *frame_of_view;
+    const float *rest, *local;
+    const int32_t* parents;
+    const float *base, *theta, *mask, *d_transforms;
+    float* d_theta;
+};
+
+// The refusals that the two term entries share, in their order, under the entry's name.  w: w_dev_rot, w_smooth_rot, w_dev_trans,
+// w_smooth_trans, w_kp.  terms: a term is on, so d_transforms may be NULL (no chain part, no views read; V may be 0 then);
+// when: what the entry's message adds to that rule
+static int fk_terms_refuse(const char* name, const char* when, bool terms, const FkChainArgs& a, const double (&w)[5],
+                           const float* theta_ref, const int32_t* neighbours) {
+    for (int i = 0; i < 5; ++i)
+        if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return mgr_fail(MGR_EINVAL, "%s: the weights must be finite and >= 0", name);
+    const bool chain = !terms || a.d_transforms != nullptr;
+    if (a.J < 1 || a.J > MGR_MAX_BONES || a.F < 1 || a.U < 1 || (chain ? a.V < 1 : a.V < 0))
+        return mgr_fail(MGR_EINVAL, "%s: F and U must be at least 1, V too unless d_transforms is NULL%s, J 1 .. MGR_MAX_BONES", name, when);
+    if (!a.frames_listed || !a.rest || !a.local || !a.parents || !a.base || !a.theta || !a.mask || !a.d_theta ||
+        (chain && (!a.view_rows || !a.frame_of_view || !a.d_transforms)))
+        return mgr_fail(MGR_EINVAL, "%s: null pointer", name);
+    if ((long long)a.V * (a.J + 1) > (1ll << 24) || (long long)a.U * (a.J + 2) > (1ll << 24))
+        return mgr_fail(MGR_EINVAL, "%s: V * (J + 1) or U * (J + 2) above 2^24", name);
+    if ((w[0] != 0.0 || w[2] != 0.0) && !theta_ref) return mgr_fail(MGR_EINVAL, "%s: a deviation weight needs theta_ref", name);
+    if ((w[1] != 0.0 || w[3] != 0.0) && !neighbours) return mgr_fail(MGR_EINVAL, "%s: a smoothness weight needs the neighbour table", name);
+    return MGR_OK;
+}
+
+// FkTerms of the weights w (as above): a table whose weights are 0 is not passed on
+static FkTerms fk_terms_of(const double (&w)[5], const float* theta_ref, const int32_t* neighbours, double* partial, int K,
+                           const int32_t* kp_bone, const float* kp_offset, const float* kp_target, const float* kp_weight) {
+    const bool dev = w[0] != 0.0 || w[2] != 0.0, smooth = w[1] != 0.0 || w[3] != 0.0;
+    return FkTerms{dev ? theta_ref : nullptr, smooth ? neighbours : nullptr, partial, w[0], w[1], w[2], w[3], w[4], (float)(2.0 * w[0]),
+                   (float)(2.0 * w[1]), (float)(2.0 * w[2]), (float)(2.0 * w[3]), (float)(2.0 * w[4]), K, kp_bone, kp_offset, kp_target, kp_weight};
+}
+
 extern "C" int mgr_fk_backward_terms(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
                                      const int32_t* frame_of_view, const float* rest, const float* local, const int32_t* parents,
                                      const float* base, const float* theta, const float* mask, const float* d_transforms,
@@ -1011,61 +771,44 @@ extern "C" int mgr_fk_backward_terms(int V, int J, int F, int U, const int32_t* 
                                      double w_smooth_rot, double w_dev_trans, double w_smooth_trans, int K, const int32_t* kp_bone,
                                      const float* kp_offset, const float* kp_target, const float* kp_weight, double w_kp,
                                      double* values, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* name = "mgr_fk_backward_terms";
     const double w[5] = {w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans, w_kp};
-    for (int i = 0; i < 5; ++i)
-        if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
-            return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: the weights must be finite and >= 0");
-    const bool dev = w_dev_rot != 0.0 || w_dev_trans != 0.0, smooth = w_smooth_rot != 0.0 || w_smooth_trans != 0.0, kp = w_kp != 0.0;
-    const bool terms = dev || smooth || kp;
-    const bool chain = !terms || d_transforms != nullptr;      // (with a term on, d_transforms may be NULL: no chain part, no views read)
-    if (J < 1 || J > MGR_MAX_BONES || F < 1 || U < 1 || (chain ? V < 1 : V < 0))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: F and U must be at least 1, V too unless d_transforms is NULL with a term on, J 1 .. MGR_MAX_BONES");
-    if (!frames_listed || !rest || !local || !parents || !base || !theta || !mask || !d_theta || (chain && (!view_rows || !frame_of_view || !d_transforms)))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: null pointer");
-    if ((long long)V * (J + 1) > (1ll << 24) || (long long)U * (J + 2) > (1ll << 24))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: V * (J + 1) or U * (J + 2) above 2^24");
-    if (dev && !theta_ref) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: a deviation weight needs theta_ref");
-    if (smooth && !neighbours) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: a smoothness weight needs the neighbour table");
+    const bool kp = w_kp != 0.0;
+    const bool terms = w_dev_rot != 0.0 || w_dev_trans != 0.0 || w_smooth_rot != 0.0 || w_smooth_trans != 0.0 || kp;
+    const bool chain = !terms || d_transforms != nullptr;
+    const FkChainArgs a = {V, J, F, U, frames_listed, view_rows, frame_of_view, rest, local, parents, base, theta, mask, d_transforms, d_theta};
+    if (const int rc = fk_terms_refuse(name, " with a term on", terms, a, w, theta_ref, neighbours)) return rc;
     if (kp && (K < 1 || K > MGR_FK_MAX_KEYPOINTS))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: the keypoint term needs K 1 .. MGR_FK_MAX_KEYPOINTS");
+        return mgr_fail(MGR_EINVAL, "%s: the keypoint term needs K 1 .. MGR_FK_MAX_KEYPOINTS", name);
     if (kp && (!kp_bone || !kp_offset || !kp_target || !kp_weight))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: the keypoint term needs kp_bone, kp_offset, kp_target and kp_weight");
-    if (terms && (!values || !workspace)) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms: a term needs values and a workspace");
-    if (terms && workspace_bytes < mgr_fk_terms_workspace_bytes(U, J, K))
-        return mgr_fail(MGR_ENOMEM, "mgr_fk_backward_terms: workspace too small");
+        return mgr_fail(MGR_EINVAL, "%s: the keypoint term needs kp_bone, kp_offset, kp_target and kp_weight", name);
+    if (terms && (!values || !workspace)) return mgr_fail(MGR_EINVAL, "%s: a term needs values and a workspace", name);
+    if (terms && workspace_bytes < mgr_fk_terms_workspace_bytes(U, J, K)) return mgr_fail(MGR_ENOMEM, "%s: workspace too small", name);
     hipStream_t stream = (hipStream_t)stream_;
     if (!terms) {      // mgr_fk_backward's own launch; the values of no term are 0
         if (values) MGR_HIP(hipMemsetAsync(values, 0, 4 * sizeof(double), stream));
         {
             MGR_PROF("k_fk_backward", stream);
-            hipLaunchKernelGGL(k_fk_backward, dim3(U), dim3(FK_BLOCK), 0, stream, V, J, F, U, frames_listed, view_rows, frame_of_view, rest,
-                               local, parents, base, theta, mask, d_transforms, d_theta);
+            hipLaunchKernelGGL(k_fk_backward_t<FK_TERMS_NONE>, dim3(U), dim3(FK_BLOCK), 0, stream, V, J, F, U, frames_listed, view_rows, frame_of_view, rest,
+                               local, parents, base, theta, mask, d_transforms, d_theta, FkTerms{}, FkTerms2d{});
         }
         MGR_LAUNCH_CHECK("k_fk_backward", stream, 0);
         return MGR_OK;
     }
     double* partial = (double*)workspace;
-    const FkTerms tm = {dev ? theta_ref : nullptr, smooth ? neighbours : nullptr, partial, w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans,
-                        w_kp, (float)(2.0 * w_dev_rot), (float)(2.0 * w_smooth_rot), (float)(2.0 * w_dev_trans),
-                        (float)(2.0 * w_smooth_trans), (float)(2.0 * w_kp), kp ? K : 0, kp_bone, kp_offset, kp_target, kp_weight};
+    const FkTerms tm = fk_terms_of(w, theta_ref, neighbours, partial, kp ? K : 0, kp_bone, kp_offset, kp_target, kp_weight);
     {
         MGR_PROF("k_fk_backward_terms", stream);
-        hipLaunchKernelGGL(k_fk_backward_terms, dim3(U), dim3(FK_BLOCK), 0, stream, chain ? V : 0, J, F, U, frames_listed, view_rows,
-                           frame_of_view, rest, local, parents, base, theta, mask, d_transforms, d_theta, tm);
+        hipLaunchKernelGGL(k_fk_backward_t<FK_TERMS_3D>, dim3(U), dim3(FK_BLOCK), 0, stream, chain ? V : 0, J, F, U, frames_listed, view_rows,
+                           frame_of_view, rest, local, parents, base, theta, mask, d_transforms, d_theta, tm, FkTerms2d{});
     }
     MGR_LAUNCH_CHECK("k_fk_backward_terms", stream, 0);
     {
         MGR_PROF("k_fk_terms_fold", stream);
-        hipLaunchKernelGGL(k_fk_terms_fold, dim3(1), dim3(FK_BLOCK), 0, stream, partial, U, values);
+        hipLaunchKernelGGL(k_fk_terms_fold_t<3>, dim3(1), dim3(FK_BLOCK), 0, stream, partial, U, values);
     }
     MGR_LAUNCH_CHECK("k_fk_terms_fold", stream, 0);
     return MGR_OK;
-}
-
-extern "C" size_t mgr_fk_terms2d_workspace_bytes(int U, int J, int K, int C) {
-    (void)K;      // (the keypoints' and cameras' shares meet inside the workgroup)
-    (void)C;
-    return (U < 1 || J < 1) ? 0 : (size_t)U * 4 * sizeof(double);
 }
 
 extern "C" int mgr_fk_backward_terms2d(int V, int J, int F, int U, const int32_t* frames_listed, const int32_t* view_rows,
@@ -1077,9 +820,10 @@ extern "C" int mgr_fk_backward_terms2d(int V, int J, int F, int U, const int32_t
                                        const float* kp2d_proj, const float* kp2d_target, const float* kp2d_weight, double w_kp2d,
                                        double delta, double z_min, float* kp2d_dist, double* values, void* workspace,
                                        size_t workspace_bytes, void* stream_) {
+    const char* name = "mgr_fk_backward_terms2d";
     if (!(w_kp2d >= 0.0) || !std::isfinite(w_kp2d) || !(delta >= 0.0) || !std::isfinite(delta))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: w_kp2d and delta must be finite and >= 0");
-    if (!(z_min > 0.0) || !std::isfinite(z_min)) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: z_min must be finite and > 0");
+        return mgr_fail(MGR_EINVAL, "%s: w_kp2d and delta must be finite and >= 0", name);
+    if (!(z_min > 0.0) || !std::isfinite(z_min)) return mgr_fail(MGR_EINVAL, "%s: z_min must be finite and > 0", name);
     hipStream_t stream = (hipStream_t)stream_;
     if (w_kp2d == 0.0) {      // mgr_fk_backward_terms' own path (its refusals, its launches, its bits); no detection is active
         const int rc = mgr_fk_backward_terms(V, J, F, U, frames_listed, view_rows, frame_of_view, rest, local, parents, base, theta, mask,
@@ -1093,45 +837,31 @@ extern "C" int mgr_fk_backward_terms2d(int V, int J, int F, int U, const int32_t
         return MGR_OK;
     }
     const double w[5] = {w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans, w_kp};
-    for (int i = 0; i < 5; ++i)
-        if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
-            return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: the weights must be finite and >= 0");
-    const bool dev = w_dev_rot != 0.0 || w_dev_trans != 0.0, smooth = w_smooth_rot != 0.0 || w_smooth_trans != 0.0, kp = w_kp != 0.0;
+    const bool kp = w_kp != 0.0;
     const bool chain = d_transforms != nullptr;      // (the 2-D term is on: d_transforms may be NULL, no chain part, no views read)
-    if (J < 1 || J > MGR_MAX_BONES || F < 1 || U < 1 || (chain ? V < 1 : V < 0))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: F and U must be at least 1, V too unless d_transforms is NULL, J 1 .. MGR_MAX_BONES");
-    if (!frames_listed || !rest || !local || !parents || !base || !theta || !mask || !d_theta || (chain && (!view_rows || !frame_of_view)))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: null pointer");
-    if ((long long)V * (J + 1) > (1ll << 24) || (long long)U * (J + 2) > (1ll << 24))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: V * (J + 1) or U * (J + 2) above 2^24");
-    if (dev && !theta_ref) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: a deviation weight needs theta_ref");
-    if (smooth && !neighbours) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: a smoothness weight needs the neighbour table");
-    if (C < 1) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: the 2-D keypoint term needs C >= 1 cameras");
-    if (K < 1 || K > MGR_FK_MAX_KEYPOINTS)
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: the keypoint terms need K 1 .. MGR_FK_MAX_KEYPOINTS");
+    const FkChainArgs a = {V, J, F, U, frames_listed, view_rows, frame_of_view, rest, local, parents, base, theta, mask, d_transforms, d_theta};
+    if (const int rc = fk_terms_refuse(name, "", true, a, w, theta_ref, neighbours)) return rc;
+    if (C < 1) return mgr_fail(MGR_EINVAL, "%s: the 2-D keypoint term needs C >= 1 cameras", name);
+    if (K < 1 || K > MGR_FK_MAX_KEYPOINTS) return mgr_fail(MGR_EINVAL, "%s: the keypoint terms need K 1 .. MGR_FK_MAX_KEYPOINTS", name);
     if (!kp_bone || !kp_offset || !kp2d_proj || !kp2d_target || !kp2d_weight)
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: the 2-D keypoint term needs kp_bone, kp_offset, kp2d_proj, kp2d_target and kp2d_weight");
-    if (kp && (!kp_target || !kp_weight))
-        return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: the 3-D keypoint term needs kp_target and kp_weight");
-    if (!values || !workspace) return mgr_fail(MGR_EINVAL, "mgr_fk_backward_terms2d: a term needs values and a workspace");
-    if (workspace_bytes < mgr_fk_terms2d_workspace_bytes(U, J, K, C))
-        return mgr_fail(MGR_ENOMEM, "mgr_fk_backward_terms2d: workspace too small");
+        return mgr_fail(MGR_EINVAL, "%s: the 2-D keypoint term needs kp_bone, kp_offset, kp2d_proj, kp2d_target and kp2d_weight", name);
+    if (kp && (!kp_target || !kp_weight)) return mgr_fail(MGR_EINVAL, "%s: the 3-D keypoint term needs kp_target and kp_weight", name);
+    if (!values || !workspace) return mgr_fail(MGR_EINVAL, "%s: a term needs values and a workspace", name);
+    if (workspace_bytes < mgr_fk_terms2d_workspace_bytes(U, J, K, C)) return mgr_fail(MGR_ENOMEM, "%s: workspace too small", name);
     double* partial = (double*)workspace;
-    const FkTerms tm = {dev ? theta_ref : nullptr, smooth ? neighbours : nullptr, partial, w_dev_rot, w_smooth_rot, w_dev_trans, w_smooth_trans,
-                        w_kp, (float)(2.0 * w_dev_rot), (float)(2.0 * w_smooth_rot), (float)(2.0 * w_dev_trans),
-                        (float)(2.0 * w_smooth_trans), (float)(2.0 * w_kp), K, kp_bone, kp_offset, kp_target, kp_weight};
+    const FkTerms tm = fk_terms_of(w, theta_ref, neighbours, partial, K, kp_bone, kp_offset, kp_target, kp_weight);
     const float delta_f = (float)delta;
     const FkTerms2d t2 = {C, kp2d_proj, kp2d_target, kp2d_weight, kp2d_dist, w_kp2d, (double)delta_f, (float)(2.0 * w_kp2d), delta_f,
                           (float)z_min, kp ? 1 : 0};
     {
         MGR_PROF("k_fk_backward_terms2d", stream);
-        hipLaunchKernelGGL(k_fk_backward_terms2d, dim3(U), dim3(FK_BLOCK), 0, stream, chain ? V : 0, J, F, U, frames_listed, view_rows,
+        hipLaunchKernelGGL(k_fk_backward_t<FK_TERMS_2D>, dim3(U), dim3(FK_BLOCK), 0, stream, chain ? V : 0, J, F, U, frames_listed, view_rows,
                            frame_of_view, rest, local, parents, base, theta, mask, d_transforms, d_theta, tm, t2);
     }
     MGR_LAUNCH_CHECK("k_fk_backward_terms2d", stream, 0);
     {
         MGR_PROF("k_fk_terms2d_fold", stream);
-        hipLaunchKernelGGL(k_fk_terms2d_fold, dim3(1), dim3(FK_BLOCK), 0, stream, partial, U, values);
+        hipLaunchKernelGGL(k_fk_terms_fold_t<4>, dim3(1), dim3(FK_BLOCK), 0, stream, partial, U, values);
     }
     MGR_LAUNCH_CHECK("k_fk_terms2d_fold", stream, 0);
     return MGR_OK;
